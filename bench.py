@@ -7,6 +7,12 @@ BASELINE.json configs[1] per GPU: 8192 synthetic rays (posed pinhole cameras 800
 marching + 3-stage NeuS up-sampling -> fused LoTD(L=16,T=2^19)+2x64 SDF MLP+radiance MLP forward -> compositing ->
 rgb-mse + eikonal loss -> backward (incl. second-order normal terms) -> gradient all-reduce -> Adam, with the
 occupancy-grid refresh every 16 iterations inside the timed region.  Weak scaling: rays per GPU are fixed.
+
+A plain run sets up, warms up, times the K steps and prints the line (``value``, ``ms_per_step`` = the mean timed step).
+``--full`` adds everything else the line can carry: the fp16-vs-oracle rendering check (the run exits non-zero when it
+fails), the side measurements (``variants``, ``with_distant_model``), the CPU baseline, the per-kernel table and, N > 1,
+the exposed all-reduce.  ``--dump-outputs DIR`` writes, after the timed steps, what one step of the timed path computes
+from the state the run started from (``dump_step_outputs``) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -324,6 +330,77 @@ def time_steps(tr, steps, warmup, it):
     return el / steps * 1e3, it
 
 
+FIRST_TIMED_IT = 257       # the timed region starts right after an occupancy refresh (every 16 iterations)
+
+# --dump-outputs: arrays of more elements than this are written as a fixed, seeded sample of their entries (the same indices on
+# every run of the same configuration), so that the files of one run stay within a few MB
+DUMP_SAMPLE = 1 << 18
+DUMP_MAX_BYTES = 64 << 20
+
+
+def step_outputs(tr, loss) -> dict:
+    """What a caller of the timed path holds after a step: the loss ``train_step`` returned, every parameter the step's
+    optimizer update wrote (the f32 master values), the gradient that update applied, and the occupancy values the step's
+    refreshes keep.  -> {name: float32 numpy array}, large arrays sampled (DUMP_SAMPLE)."""
+    names = {id(tr.appear): "appear"}
+    for prefix, mod in (("", tr.model), ("distant_", getattr(tr, "distant_model", None)), ("sky_", getattr(tr, "sky_model", None))):
+        if mod is not None:
+            names.update({id(p): prefix + n.replace(".", "_") for n, p in mod.named_parameters()})
+
+    def host(t):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            flat = flat[idx.to(flat.device)]
+        return flat.float().cpu().numpy()
+
+    out = {"loss": host(loss.reshape(1))}
+    for i, g in enumerate(tr.optim.groups):
+        p = g["p"]
+        name = names.get(id(p), f"group{i}")
+        if name in out:
+            name = f"{name}_group{i}"
+        out[name] = host(p)
+        if p.grad is not None:
+            out["grad_" + name] = host(p.grad)
+    occ = getattr(getattr(tr.model, "accel", None), "occ_val", None)
+    if occ is not None:
+        out["occ_val"] = host(occ)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_MAX_BYTES
+    return out
+
+
+def dump_step_outputs(make_trainer, steps: int, rank: int, dirname: str):
+    """--dump-outputs: one step of the timed path (``train_step`` at the iteration number of the last timed step) on a trainer
+    built afresh by ``make_trainer`` -- the same arguments and seeds as the timed one, i.e. the state the run started from --,
+    run after the timed steps, outside the timed region; rank 0 writes ``step_outputs`` of it to ``dirname``.  As in every timed
+    step, its batch is prefetched on the trainer's side stream and handed over by event.
+    Not the state the timed steps left behind: their gradients are summed with float atomics, whose rounding depends on the order
+    the contributions arrive in, and Adam (near-zero gradients become full steps) and the occupancy thresholds grow it step by
+    step.  Measured on an MI355X, two runs from the same seeded state differ after the last of N steps by (worst array, relative):
+    N = 1: 2e-7, 2: 1e-4, 4: 4e-3, 8: 0.3.  One step from a fixed state is the only step whose outputs agree from run to run up to
+    rounding, so that two builds can be compared output for output.  Every rank takes part (the step's collectives)."""
+    tr = make_trainer()
+    if getattr(tr, "pipeline", False):
+        tr._prefetch()
+    loss = tr.train_step(FIRST_TIMED_IT + steps - 1)
+    if tr.model.device.type == "cuda":
+        torch.cuda.synchronize()
+    if rank == 0:
+        write_outputs(step_outputs(tr, loss), dirname)
+    del tr
+    if torch.cuda.is_available():
+        torch.cuda.empty_cache()
+
+
+def write_outputs(outputs: dict, dirname: str):
+    import numpy as np
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(d / f"{name}.npy", np.ascontiguousarray(arr, dtype=np.float32))
+
+
 def measure_exposed_allreduce(tr, out, steps, it, rank, dev):
     """N > 1: the same steps with the collectives skipped (every rank keeps its local gradients and occupancy values); the
     difference to ``ms_per_step`` is the all-reduce time the overlap could NOT hide.  Replicas diverge from here on --
@@ -346,9 +423,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the API-path / distant-model side measurements")
-    ap.add_argument("--no-parity", action="store_true", help="skip the fp16-vs-oracle rendering check (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline as well: the fp16-vs-oracle rendering check, the side measurements "
+                         "(variants), the CPU baseline, the per-kernel table of an instrumented pass after the timed steps and, "
+                         "N > 1, the exposed all-reduce leg.  A plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what one step of the timed path computes from the state the run started "
+                         "from, at the last timed iteration (its loss, the updated parameters, their gradients, the occupancy "
+                         "values; large arrays as a fixed seeded sample) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-variants", action="store_true", help="--full without the API-path / distant-model side measurements")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the fp16-vs-oracle rendering check")
     ap.add_argument("--rays-per-gpu", type=int, default=None,
                     help="rays per iteration per GPU (8192 = BASELINE configs[1]; the 4- and 8-GPU BASELINE configs draw "
                          "16384 per GPU: 65536 / 4, 131072 / 8)")
@@ -396,14 +481,20 @@ def main():
     if args.rays_per_gpu is None:
         args.rays_per_gpu = RAYS_PER_GPU if args.config == "object" else 16384
     if args.config == "object":
-        tr = build_trainer(dev, rank, world, distant=args.distant, sky=args.sky, sdf_D=args.sdf_depth,
-                           rays_per_gpu=args.rays_per_gpu)
+        def make_trainer():
+            return build_trainer(dev, rank, world, distant=args.distant, sky=args.sky, sdf_D=args.sdf_depth,
+                                 rays_per_gpu=args.rays_per_gpu)
         workload = None
     else:
-        tr = build_config_trainer(args.config, dev, rank, world, args.rays_per_gpu)
+        def make_trainer():
+            return build_config_trainer(args.config, dev, rank, world, args.rays_per_gpu)
         workload = WORKLOADS[args.config]
-    out, it = timed_run(tr, args.steps, args.warmup, rank, world, dev, rays_per_gpu=args.rays_per_gpu, workload=workload)
-    if world > 1:
+    tr = make_trainer()
+    out, it = timed_run(tr, args.steps, args.warmup, rank, world, dev, rays_per_gpu=args.rays_per_gpu, workload=workload,
+                        kernel_table=args.full)
+    if args.dump_outputs:
+        dump_step_outputs(make_trainer, args.steps, rank, args.dump_outputs)
+    if world > 1 and args.full:
         it = measure_exposed_allreduce(tr, out, min(args.steps, 32), it, rank, dev)
     dist_info = distributed_info(world, dev)         # (collective on N > 1: every rank calls it)
     if rank == 0:
@@ -421,7 +512,7 @@ def main():
         out["config"]["sky_model"] = bool(args.sky)
         out["config"]["sdf_mlp"] = f"{args.sdf_depth}x64"
         out["config"]["launch_chain"] = "fused (no autograd engine)" if tr._fused_ok() else "autograd"
-        plain = world == 1 and not args.distant and not args.sky
+        plain = world == 1 and not args.distant and not args.sky and args.full
         if plain and not args.no_parity:
             # the rendering check runs on the state the headline was just measured on, before the side measurements train the
             # model further through other paths
@@ -593,15 +684,23 @@ def main_emulator(args):
     ndist.broadcast_module(m)
     intr, c2w, WH = look_at_cameras(V=4, seed=1, device=dev)
     rays = int(args.rays_per_gpu or 16)
+
+    def make_trainer():
+        m_ = _tiny(dev, seed=42 + rank)
+        ndist.broadcast_module(m_)
+        return RenderTrainer(m_, intr, c2w, WH, num_rays=rays, lr=1e-3, num_uniform=16, rank=rank, world_size=world)
     tr = RenderTrainer(m, intr, c2w, WH, num_rays=rays, lr=1e-3, num_uniform=16, rank=rank, world_size=world)
-    out, it = timed_run(tr, args.steps, args.warmup, rank, world, dev, rays_per_gpu=rays)
+    out, it = timed_run(tr, args.steps, args.warmup, rank, world, dev, rays_per_gpu=rays, kernel_table=args.full)
+    if args.dump_outputs:
+        dump_step_outputs(make_trainer, args.steps, rank, args.dump_outputs)
     import torch.distributed as dist
     if world > 1:          # replicas agree after the all-reduced updates (asserted on every rank) ...
         w = m.sdf_w.detach().clone()
         ws = [torch.zeros_like(w) for _ in range(world)]
         dist.all_gather(ws, w)
         assert all(torch.equal(ws[0], x) for x in ws[1:]), "replicas diverged"
-        it = measure_exposed_allreduce(tr, out, min(args.steps, 2), it, rank, dev)      # ... and diverge from here on
+        if args.full:
+            it = measure_exposed_allreduce(tr, out, min(args.steps, 2), it, rank, dev)      # ... and diverge from here on
     dist_info = distributed_info(world, dev)
     if rank == 0:
         out["distributed"] = dist_info
@@ -666,13 +765,14 @@ def _mo(tr) -> bool:
     return bool(marched_only(tr.model.ray_query_cfg.get("query_param", {})))
 
 
-def timed_run(tr, steps, warmup, rank, world, dev, rays_per_gpu, workload=None):
+def timed_run(tr, steps, warmup, rank, world, dev, rays_per_gpu, workload=None, kernel_table=True):
     """W untimed warm-up steps, then exactly K steps bracketed by barrier + device sync on both sides; the elapsed
-    time is the MAX over ranks; rank 0 returns the JSON record (other ranks None) and the next iteration number."""
+    time is the MAX over ranks; rank 0 returns the JSON record (other ranks None) and the next iteration number.
+    ``kernel_table``: the per-kernel table from an instrumented pass of its own after the timed steps (bench.py --full)."""
     from neuralsim_amd import _lib
     import torch.distributed as dist
     on_gpu = dev.type == "cuda"
-    it0 = 257                      # timed region starts right after an occupancy refresh (every 16 iterations)
+    it0 = FIRST_TIMED_IT
     it = it0 - max(warmup, 1)
     # the warm-up steps run with the same instrumentation as the timed ones (HIP-event pairs around the modelled entry points:
     # their first creations are slow), so the first timed step does not pay for the bench's own timer
@@ -770,7 +870,7 @@ def timed_run(tr, steps, warmup, rank, world, dev, rays_per_gpu, workload=None):
     # the per-kernel table: a short pass with every modelled entry point instrumented, outside the timed region (all ranks)
     n_post = 0
     ksum_post = {}
-    if timer is not None and kt_mode != "full":
+    if timer is not None and kt_mode != "full" and kernel_table:
         n_post = max(1, min(16, steps))
         _lib.TIMER = _lib.KernelTimer(only=KM.keys())
         for _ in range(n_post):
@@ -915,7 +1015,10 @@ def timed_run(tr, steps, warmup, rank, world, dev, rays_per_gpu, workload=None):
                kernels_source=(f"HIP events inside the timed region for the dominant kernel ({dom}: the roofline's live measurement); the "
                                f"other entry points from {n_post} instrumented steps run right after it -- 14 event pairs per step inside "
                                "the timed region cost the step 0.085 ms (NSIM_BENCH_KTIMER=full restores them)") if n_post else
-                              "HIP events inside the timed region for every modelled entry point (NSIM_BENCH_KTIMER=full)",
+                              "HIP events inside the timed region for every modelled entry point (NSIM_BENCH_KTIMER=full)"
+                              if kt_mode == "full" else
+                              (f"HIP events inside the timed region for the dominant kernel ({dom}) only; the table of the other "
+                               "entry points is an instrumented pass of its own after the timed steps (bench.py --full)"),
                # C-ABI entry-point calls of this package per step (each is one kernel launch, three of them two); the ATen /
                # rocprim launches of the host glue (rand, fill, cat, compaction) are on top: profiles/round4_rocprofv3_kernel_stats
                abi_calls_per_step=round(abi_calls / max(1, steps), 1) if abi_calls is not None else None,

@@ -26,6 +26,7 @@ BACKENDS = ["emu", pytest.param("hip", marks=pytest.mark.gpu)]
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
     config.addinivalue_line("markers", "slow: long-running emulator test")
+    config.addinivalue_line("markers", "needs_reference: executes the reference's own sources (emulator backend only)")
 
 
 @pytest.fixture(scope="session")
@@ -76,11 +77,8 @@ def poisoned_empty(monkeypatch, request):
 
 
 def _needs_reference(metafunc) -> bool:
-    """tests that execute the reference's own sources from /root/reference (``needs_reference`` skipif markers)"""
-    for m in metafunc.definition.iter_markers("skipif"):
-        if "/root/reference" in str(m.kwargs.get("reason", "")):
-            return True
-    return False
+    """tests that execute the reference's own sources (marked by ``ref_glue.needs_reference``)"""
+    return metafunc.definition.get_closest_marker("needs_reference") is not None
 
 
 def pytest_generate_tests(metafunc):

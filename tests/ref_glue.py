@@ -20,10 +20,12 @@ glue (``tests/golden/make_renderer_fixture.py`` -> ``tests/golden/renderer_fixtu
 """
 import contextlib
 import importlib.util
+import os
 import sys
 import types
 from pathlib import Path
 
+import pytest
 import torch
 
 REF_ROOT = Path("/root/reference")
@@ -33,8 +35,24 @@ _FILES = {
 }
 
 
+def readable(path) -> bool:
+    """``path`` exists and this user may read it.  (``Path.exists`` raises PermissionError instead of answering False when
+    the tree lies behind a directory the user cannot enter: the skip conditions must not turn into collection errors.)"""
+    try:
+        return Path(path).exists() and os.access(path, os.R_OK)
+    except OSError:
+        return False
+
+
 def reference_available() -> bool:
-    return all((REF_ROOT / f).exists() for f in _FILES.values())
+    return all(readable(REF_ROOT / f) for f in _FILES.values())
+
+
+def needs_reference(available: bool, reason: str):
+    """Decorator of a test that executes the reference's own sources: skipped with ``reason`` where they cannot be read, and
+    marked ``needs_reference`` -- tests/conftest.py gives such a test the emulator backend only."""
+    skip = pytest.mark.skipif(not available, reason=reason)
+    return lambda f: pytest.mark.needs_reference(skip(f))
 
 
 def _stub_module(name, **attrs):

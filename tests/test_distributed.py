@@ -564,7 +564,7 @@ def test_bench_cli_gpus_2_becomes_two_ranks():
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--emulator"],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--emulator", "--full"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT))
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -582,3 +582,26 @@ def test_bench_cli_gpus_2_becomes_two_ranks():
         r3 = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2"], capture_output=True, text=True,
                             timeout=300, env=env, cwd=str(ROOT))
         assert r3.returncode != 0 and "HIP device" in r3.stderr
+
+
+def test_bench_cli_dump_outputs(tmp_path):
+    """``bench.py --dump-outputs DIR`` through the command line (``--emulator``: the host emulator of tests/emu and a tiny model
+    stand in for the GPU): the loss, every parameter and its gradient land as float32 .npy files, and two runs with the same
+    arguments write the same values."""
+    import subprocess
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    dirs = [tmp_path / "run0", tmp_path / "run1"]
+    for d in dirs:
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--emulator",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
+        assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    names = sorted(p.name for p in dirs[0].glob("*.npy"))
+    for n in ("loss.npy", "sdf_w.npy", "grad_sdf_w.npy", "rad_w.npy", "grad_rad_w.npy", "encoding_flattened_params.npy",
+              "grad_encoding_flattened_params.npy", "occ_val.npy"):
+        assert n in names, names
+    assert names == sorted(p.name for p in dirs[1].glob("*.npy"))
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), n
+        np.testing.assert_allclose(a, b, rtol=1e-6, atol=1e-9, err_msg=n)

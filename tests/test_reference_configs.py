@@ -9,8 +9,10 @@ from pathlib import Path
 import pytest
 import torch
 
+import ref_glue
+
 CFG = Path("/root/reference/code_single/configs")
-needs_reference = pytest.mark.skipif(not CFG.exists(), reason="executes the reference's own sources from /root/reference (authoring container only; emulator backend). What it pins is replayed on the GPU box from frozen reference outputs: tests/test_reference_frozen.py, test_reference_glue.py::test_*_fixture")
+needs_reference = ref_glue.needs_reference(ref_glue.readable(CFG), reason="executes the reference's own sources, which only the authoring machine has (emulator backend). What it pins is replayed on the GPU box from frozen reference outputs: tests/test_reference_frozen.py, test_reference_glue.py::test_*_fixture")
 
 
 def _load(rel):

@@ -19,7 +19,7 @@ import torch
 import ref_glue
 
 CFG = Path("/root/reference/code_single/configs")
-needs_reference = pytest.mark.skipif(not (CFG.exists() and ref_glue.reference_available()),
+needs_reference = ref_glue.needs_reference(ref_glue.readable(CFG) and ref_glue.reference_available(),
                                      reason="executes the reference's own sources from /root/reference (authoring container only; "
                                             "emulator backend): the model wrappers / loss modules of app/ cannot travel to the GPU box")
 

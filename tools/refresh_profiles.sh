@@ -10,7 +10,7 @@ mkdir -p $O
 rm -f $O/prof_field_bench.jsonl
 cd /tmp && export TMPDIR=/tmp
 CMD="python $R/bench.py --steps 32 --warmup 16 --no-cpu-baseline --no-variants --no-parity"
-timeout 900 python $R/bench.py > $O/prof_bench.json 2> $O/prof_bench.err
+timeout 900 python $R/bench.py --full > $O/prof_bench.json 2> $O/prof_bench.err
 timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/p_stats -o s -- $CMD > $O/prof_stats_bench.json 2>/tmp/e1.log
 DB=$(find /tmp/p_stats -name "*.db" | head -1)
 python $R/tools/prof_summary.py $DB $O/prof_stats.json

@@ -40,6 +40,9 @@ enum { V_B1 = 0, V_B2, V_WH, V_RB1, V_RB2, V_RB3, V_SCAL, V_COUNT };
 struct FieldLayout {
   int64_t mat[M_COUNT];  // byte offsets
   int64_t vec[V_COUNT];
+  int64_t vend;          // end of the vectors
+  int64_t mat16[4];      // M_W1 .. M_W1T once more as 16-point A fragments (mfma_mlp.h; fp16 mode, <= 16 levels, no
+                         // embedded block: the object shapes of k_field_bwd_h), behind the vectors; empty otherwise
   int64_t total;
   int elt;               // bytes per matrix element (2 | 4)
   int split;             // 1: every matrix is TWO f16 fragment sets, W = hi + lo / SPLIT_LO_SCALE (precision 2)
@@ -70,9 +73,15 @@ static inline FieldLayout field_layout(int precision, int nc = 1) {
     L.vec[v] = off;
     off += 64 * 4;
   }
+  L.vend = off;
+  for (int m = 0; m < 4; ++m) {
+    L.mat16[m] = off;
+    if (precision == 0 && nc == 1) off += (int64_t)mat_uo(m, 1) * mat_ui(m, 1) * 2;
+  }
   L.total = off;
   return L;
 }
+__host__ __device__ inline bool field_has16(const FieldLayout& L) { return L.total > L.vend; }
 
 // flat f32 master-weight layouts (shared with the gradient buffers)
 struct SrcOff {
@@ -205,6 +214,23 @@ __device__ __forceinline__ void field_pack_elem(const FieldLayout& L, const Pack
       case V_SCAL: val = (k == 0) ? sdf_b[o.bh] : 0.f; break;
     }
     ((float*)(wpack + L.vec[v]))[k] = val;
+    return;
+  }
+  // 16-point A fragments of M_W1 .. M_W1T (mfma_mlp.h contract16): element e of lane l of fragment (mo, c) holds
+  // W[16 mo + (l & 15)][32 c + 16 (e >> 2) + 4 (l >> 4) + (e & 3)]
+  int64_t t16 = vtid - (int64_t)V_COUNT * 64;
+  if (!field_has16(L) || t16 < 0) return;
+  for (int m = 0; m < 4; ++m) {
+    const int Uo = dims.uo[m], Ui = dims.ui[m];
+    const int64_t cnt = (int64_t)Uo * Ui;
+    if (t16 < cnt) {
+      const int e = (int)(t16 & 7), lane = (int)((t16 >> 3) & 63), fs = (int)(t16 >> 9);
+      const int nS = Ui / 32, mo = fs / nS, c = fs % nS;
+      const int row = 16 * mo + (lane & 15), col = 32 * c + 16 * (e >> 2) + 4 * (lane >> 4) + (e & 3);
+      ((f16*)(wpack + L.mat16[m]))[t16] = (f16)pack_src(m, row, col, D, F1, dims.E, dims.EB, sdf_w, rad_w);
+      return;
+    }
+    t16 -= cnt;
   }
 }
 
@@ -428,7 +454,7 @@ __device__ __forceinline__ const char* stage_weights(char* smem, const FieldArgs
   if constexpr (PREC != 1) {
     const int64_t m0 = a.lay.mat[first];
     const int64_t m1 = (first + count < M_COUNT) ? a.lay.mat[first + count] : a.lay.vec[0];
-    const int64_t mbytes = m1 - m0, vbytes = a.lay.total - a.lay.vec[0];
+    const int64_t mbytes = m1 - m0, vbytes = a.lay.vend - a.lay.vec[0];
     const f16x8* src = reinterpret_cast<const f16x8*>(a.wpack + m0);
     f16x8* dst = reinterpret_cast<f16x8*>(smem);
     for (int i = threadIdx.x; i < (int)(mbytes >> 4); i += blockDim.x) dst[i] = src[i];
@@ -1636,6 +1662,296 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES) k_field_bwd_j(FieldArgs a) {
   { const int64_t grp = -1; KT(1, 22); }
 }
 
+// ---------------------------------------------------------------------------------- 16-point tiles (mfma_mlp.h)
+// the 16-point fragments of M_W1 .. M_W1T and the per-lane vectors into LDS
+__device__ __forceinline__ const char* stage_weights16(char* smem, const FieldArgs& a, FieldLayout& Lk, int& lds_used) {
+  Lk = a.lay;
+  nsim_prefetch_own_code(a.code_pf, smem);
+  const int64_t m0 = a.lay.mat16[0], mbytes = a.lay.total - m0, vbytes = a.lay.vend - a.lay.vec[0];
+  const f16x8* src = reinterpret_cast<const f16x8*>(a.wpack + m0);
+  f16x8* dst = reinterpret_cast<f16x8*>(smem);
+  for (int i = threadIdx.x; i < (int)(mbytes >> 4); i += blockDim.x) dst[i] = src[i];
+  const f16x8* vsrc = reinterpret_cast<const f16x8*>(a.wpack + a.lay.vec[0]);
+  f16x8* vdst = reinterpret_cast<f16x8*>(smem + mbytes);
+  for (int i = threadIdx.x; i < (int)(vbytes >> 4); i += blockDim.x) vdst[i] = vsrc[i];
+  for (int m = 0; m < 4; ++m) Lk.mat16[m] = a.lay.mat16[m] - m0;
+  for (int v = 0; v < V_COUNT; ++v) Lk.vec[v] = mbytes + (a.lay.vec[v] - a.lay.vec[0]);
+  lds_used = (int)((mbytes + vbytes + 15) & ~15);
+  __syncthreads();
+  return smem;
+}
+static size_t weights16_lds_bytes(const FieldLayout& L) { return (size_t)(((L.total - L.mat16[0]) + (L.vend - L.vec[0]) + 15) & ~15); }
+
+// register k = 4m + r of a 16-point activation (unit 16m + 4g + r) of a per-lane vector stored in the 32-point order
+// [hi][32 (u >> 5) + r' ...]; vb = 32 (g & 1) + 4 (g >> 1)
+__device__ __forceinline__ float vec16(const char* W, const FieldLayout& L, int v, int vb, int k) {
+  return reinterpret_cast<const float*>(W + L.vec[v])[vb + 16 * (k >> 3) + 8 * ((k >> 2) & 1) + (k & 3)];
+}
+
+#define BWD16_PF_BYTES 2048      // per wave: the features of 16 levels x 16 points (f32 pairs)
+
+// k_field_bwd_j<0, SDF_D, 1, 0> on 16-point tiles: the same work (recomputed forward, second-order path, dL/dh and g planes for
+// the scatter, dL/dx, every weight and bias gradient), one wave = 16 points, a workgroup group = 64 points.  Lane (p, g) owns
+// point p and the units 16m + 4g + r, i.e. the levels 8m + 2g + b of the plane image.  Wave w owns the dW1 tiles (w, 0..1) and
+// the dW2 tiles (w, 0..3) in accumulator registers for the whole launch and the bias rows 16w .. 16w + 15 (summed from the
+// A operands it reads anyway).  LDS: 16-point weights + vectors 26 KB, three staging images 24 KB, plane images 8 KB.
+template <int SDF_D>
+__global__ void __launch_bounds__(64 * JOINT_WAVES, 2) k_field_bwd_h(FieldArgs a) {
+  using JT = typename JPlane<0>::T;
+  NSIM_DYN_SMEM(smem);
+  const int lane = nsim_lane(), p = lane & 15, g = lane >> 4;
+  const int wave = (int)(threadIdx.x >> 6);
+  const float beta = a.beta, inv_beta = 1.0f / a.beta;
+  FieldLayout L;
+  int wbytes = 0;
+  const char* W = stage_weights16(smem, a, L, wbytes);
+  char* const stA = smem + wbytes;
+  char* const stB = stA + J16_STAGE_BYTES;
+  char* const stC = stB + J16_STAGE_BYTES;
+  char* const pf = stC + J16_STAGE_BYTES + wave * BWD16_PF_BYTES;
+  const int vb = 32 * (g & 1) + 4 * (g >> 1);
+  f32x4 accW1[2], accW2[4];
+#pragma unroll
+  for (int n = 0; n < 2; ++n) accW1[n] = zero4();
+#pragma unroll
+  for (int n = 0; n < 4; ++n) accW2[n] = zero4();
+  float bs1 = 0.f, bs2 = 0.f, bsh = 0.f, bh = 0.f;
+  const bool do_dw = !(a.ablate & 4);
+
+  const int64_t ntiles = (a.S + 15) / 16;
+  const int64_t ngroups = (ntiles + JOINT_WAVES - 1) / JOINT_WAVES;
+  // the features of a wave's NEXT tile are copied global -> LDS while the group computes: lanes 8k .. 8k + 7 the 128 B of
+  // level 8i + k (rows s0 .. s0 + 15 < PS: the plane pitch is a multiple of 32)
+  auto prefetch_planes = [&](int64_t tile_n) {
+    const int64_t s0 = tile_n * 16;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      nsim_glds16(a.h_pl + ((int64_t)(8 * i + (lane >> 3)) * a.PS + s0) * 2 + 4 * (lane & 7), pf + 1024 * i);
+  };
+  {
+    const int64_t t0 = (int64_t)blockIdx.x * JOINT_WAVES + wave;
+    if (t0 < ntiles) prefetch_planes(t0);
+  }
+  for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+    const int64_t s = (grp * JOINT_WAVES + wave) * 16 + p;      // past the end: an invalid point contributes zeros
+    const bool valid = s < a.S;
+    const int vo = nsim_opaque_zero();
+    const char* Wv = W + vo;
+    float gs = 0.f, gn[3] = {0.f, 0.f, 0.f};
+    float h[8];
+    JPair<JT> Jq[4][3];      // entry 2m + b: the dh/dx of level 8m + 2g + b as stored (three pairs)
+    nsim_wait_vm0();                          // this tile's feature image has landed
+    const int64_t sc = valid ? s : a.S - 1;   // (a point past the end reads the last point's finite values; nothing of it is stored)
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int l = 8 * m + 2 * g + b, r0 = 4 * m + 2 * b;
+        const float* hp = reinterpret_cast<const float*>(pf + 128 * l) + 2 * p;
+        h[r0] = valid ? hp[0] : 0.f;
+        h[r0 + 1] = valid ? hp[1] : 0.f;
+      }
+    nsim_wait_lgkm0();                        // every lane has read the image: the next copy may overwrite it
+    if (valid) {
+      if (a.dsdf) gs = a.dsdf[s];
+      if (a.dnablas) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gn[c] = a.dnablas[3 * s + c];
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int l = 8 * m + 2 * g + b;
+        const JPair<JT>* jp = reinterpret_cast<const JPair<JT>*>(reinterpret_cast<const JT*>(a.J_pl) + ((int64_t)l * a.PS + sc) * 6);
+        Jq[2 * m + b][0] = jp[0];
+        Jq[2 * m + b][1] = jp[1];
+        Jq[2 * m + b][2] = jp[2];
+      }
+    {
+      const int64_t tn = (grp + gridDim.x) * JOINT_WAVES + wave;
+      if (tn < ntiles) prefetch_planes(tn);
+    }
+    // ---- decoder forward (recomputed) and d sdf / d h
+    float a1[16];
+    dense16<4, 2>(a1, W + L.mat16[M_W1], h, true);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) a1[k] = softplus_b(a1[k] + vec16(Wv, L, V_B1, vb, k), beta, inv_beta);
+    float a2[16];
+    float d1[16];      // d sdf / d z1
+    if constexpr (SDF_D == 2) {
+      dense16<4, 4>(a2, W + L.mat16[M_W2], a1, false);
+#pragma unroll
+      for (int k = 0; k < 16; ++k) a2[k] = softplus_b(a2[k] + vec16(Wv, L, V_B2, vb, k), beta, inv_beta);
+      float d2[16];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) d2[k] = sig_from_softplus(a2[k], beta) * vec16(Wv, L, V_WH, vb, k);
+      dense16<4, 4>(d1, W + L.mat16[M_W2T], d2, false);
+#pragma unroll
+      for (int k = 0; k < 16; ++k) d1[k] = sig_from_softplus(a1[k], beta) * d1[k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        a2[k] = a1[k];
+        d1[k] = sig_from_softplus(a1[k], beta) * vec16(Wv, L, V_WH, vb, k);
+      }
+    }
+    {
+      float gg[8];
+      dense16<2, 4>(gg, W + L.mat16[M_W1T], d1, false);
+      if (valid && a.g_pl) {      // hand-off to the scatter kernel: g = d sdf / d h
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            const int l = 8 * m + 2 * g + b, r0 = 4 * m + 2 * b;
+            float* gp = a.g_pl + ((int64_t)l * a.S + s) * 2;
+            gp[0] = gg[r0];
+            gp[1] = gg[r0 + 1];
+          }
+      }
+    }
+    // ======================================================================================= backward
+    float gh[8];      // dL / dg = J . gn
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int r0 = 4 * (e >> 1) + 2 * (e & 1);
+      const float mk = valid ? 1.f : 0.f;
+      gh[r0] = mk * ((float)Jq[e][0].x * gn[0] + (float)Jq[e][0].y * gn[1] + (float)Jq[e][1].x * gn[2]);
+      gh[r0 + 1] = mk * ((float)Jq[e][1].y * gn[0] + (float)Jq[e][2].x * gn[1] + (float)Jq[e][2].y * gn[2]);
+    }
+    // ---- dW1 += d1 (x) gh
+    __syncthreads();                       // the previous group's readers of the staging images are done
+    jstage16<4>(stA, d1, wave);
+    jstage16<2>(stB, gh, wave);
+    __syncthreads();
+    if (do_dw) jdw16_tiles<2>(stA, wave, stB, 0, accW1, nullptr);
+    float dh1[16];  // dL / d d1 = W1 . gh
+    dense16<4, 2>(dh1, W + L.mat16[M_W1], gh, true);
+    float dz1[16], whv[16];
+    if constexpr (SDF_D == 2) {
+      float eh1[16];  // dL / d e1
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const float s1 = sig_from_softplus(a1[k], beta);
+        dz1[k] = dh1[k] * d1[k] * (beta * (1.0f - s1));
+        eh1[k] = dh1[k] * s1;
+      }
+      float d2[16];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) d2[k] = sig_from_softplus(a2[k], beta) * vec16(Wv, L, V_WH, vb, k);
+      // ---- dW2 += d2 (x) eh1
+      __syncthreads();
+      jstage16<4>(stA, d2, wave);
+      jstage16<4>(stB, eh1, wave);
+      __syncthreads();
+      if (do_dw) jdw16_tiles<4>(stA, wave, stB, 0, accW2, nullptr);
+      float dh2[16];  // dL / d d2 = W2 . eh1
+      dense16<4, 4>(dh2, W + L.mat16[M_W2], eh1, true);
+      float dz2[16];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const float s2 = sig_from_softplus(a2[k], beta);
+        const float wh = vec16(Wv, L, V_WH, vb, k);
+        whv[k] = dh2[k] * s2 + gs * a2[k];
+        dz2[k] = gs * wh * s2 + dh2[k] * wh * (beta * s2 * (1.0f - s2));
+      }
+      // ---- dW2 += dz2 (x) a1, d b2 += rowsum(dz2), d wh += rowsum(whv)
+      __syncthreads();
+      jstage16<4>(stA, dz2, wave);
+      jstage16<4>(stB, a1, wave);
+      jstage16<4>(stC, whv, wave);
+      __syncthreads();
+      if (do_dw) {
+        jdw16_tiles<4>(stA, wave, stB, 0, accW2, &bs2);
+        bsh += j16_row_share(stC, wave);
+      }
+      float da1[16];
+      dense16<4, 4>(da1, W + L.mat16[M_W2T], dz2, true);
+#pragma unroll
+      for (int k = 0; k < 16; ++k) dz1[k] = dz1[k] + da1[k] * sig_from_softplus(a1[k], beta);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const float s1 = sig_from_softplus(a1[k], beta);
+        const float wh = vec16(Wv, L, V_WH, vb, k);
+        whv[k] = dh1[k] * s1 + gs * a1[k];
+        dz1[k] = gs * wh * s1 + dh1[k] * wh * (beta * s1 * (1.0f - s1));
+      }
+    }
+    bh += wave_sum(g == 0 ? gs : 0.f);
+    // ---- dW1 += dz1 (x) h, d b1 += rowsum(dz1)  (+ d wh when there is one hidden layer)
+    __syncthreads();
+    jstage16<4>(stA, dz1, wave);
+    jstage16<2>(stB, h, wave);
+    if constexpr (SDF_D == 1) jstage16<4>(stC, whv, wave);
+    __syncthreads();
+    if (do_dw) {
+      jdw16_tiles<2>(stA, wave, stB, 0, accW1, &bs1);
+      if constexpr (SDF_D == 1) bsh += j16_row_share(stC, wave);
+    }
+    float dh[8];
+    dense16<2, 4>(dh, W + L.mat16[M_W1T], dz1, true);
+    if (a.dx) {   // pose refinement: dL/dx += (dh/dx)^T dL/dh  (dh/dx re-read from the planes: this path is rare)
+      float acc[3] = {0.f, 0.f, 0.f};
+      if (valid) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            const int l = 8 * m + 2 * g + b, r0 = 4 * m + 2 * b;
+            float ja[3], jb[3];
+            jload6(reinterpret_cast<const JT*>(a.J_pl) + ((int64_t)l * a.PS + s) * 6, ja, jb);
+#pragma unroll
+            for (int c3 = 0; c3 < 3; ++c3) acc[c3] = acc[c3] + dh[r0] * ja[c3] + dh[r0 + 1] * jb[c3];
+          }
+      }
+#pragma unroll
+      for (int c3 = 0; c3 < 3; ++c3) {
+        acc[c3] = acc[c3] + wave_shfl_xor(acc[c3], 16);
+        acc[c3] = acc[c3] + wave_shfl_xor(acc[c3], 32);
+      }
+      if (valid && g == 0) {
+#pragma unroll
+        for (int c3 = 0; c3 < 3; ++c3) a.dx[3 * s + c3] = a.dx[3 * s + c3] + acc[c3];
+      }
+    }
+    if (valid && a.dh_pl) {      // hand-off to the scatter kernel: dL/dh
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+          const int l = 8 * m + 2 * g + b, r0 = 4 * m + 2 * b;
+          float* dp = a.dh_pl + ((int64_t)l * a.S + s) * 2;
+          dp[0] = dh[r0];
+          dp[1] = dh[r0 + 1];
+        }
+    }
+  }
+  // ---- one flush per wave
+  const int F1 = 2 * a.lotd.num_levels;
+  const SrcOff so = src_off(SDF_D, F1);
+  const int64_t ro = (int64_t)(blockIdx.x & (unsigned)a.rep_mask) * a.rep_stride;      // this workgroup's replica
+#pragma unroll
+  for (int n = 0; n < 2; ++n) jflush16(a.dsdf_w + ro + so.w1, F1, F1, wave, n, accW1[n]);
+  // bias rows 16 wave + p: the four lane groups hold shares over different points
+  bs1 += wave_shfl_xor(bs1, 16);
+  bs1 += wave_shfl_xor(bs1, 32);
+  bsh += wave_shfl_xor(bsh, 16);
+  bsh += wave_shfl_xor(bsh, 32);
+  if constexpr (SDF_D == 2) {
+#pragma unroll
+    for (int n = 0; n < 4; ++n) jflush16(a.dsdf_w + ro + so.w2, 64, 64, wave, n, accW2[n]);
+    bs2 += wave_shfl_xor(bs2, 16);
+    bs2 += wave_shfl_xor(bs2, 32);
+    if (g == 0 && bs2 != 0.f) atomicAdd(&a.dsdf_b[ro + so.b2 + 16 * wave + p], bs2);
+  }
+  if (g == 0 && bs1 != 0.f) atomicAdd(&a.dsdf_b[ro + so.b1 + 16 * wave + p], bs1);
+  if (g == 0 && bsh != 0.f) atomicAdd(&a.dsdf_w[ro + so.wh + 16 * wave + p], bsh);
+  if (lane == 0 && bh != 0.f) atomicAdd(&a.dsdf_b[ro + so.bh], bh);
+}
+
 // No-grad SDF query (all sampling / occupancy-refresh traffic goes through here).  Lean variant of the forward:
 // the gather is split in two phases of 4 levels per lane whose 8 features feed one MFMA K-step each, so only 8
 // features (and 32 corner loads) are live at a time -> ~half the registers of the fused forward -> more waves per
@@ -2645,7 +2961,7 @@ static size_t weights_lds_bytes(const NsimFieldMeta* meta, int first = 0, int co
   if (meta->precision == 1) return 0;
   const FieldLayout L = field_layout(meta->precision, field_ni(meta));
   const int64_t m1 = (first + count < M_COUNT) ? L.mat[first + count] : L.vec[0];
-  return (size_t)(((m1 - L.mat[first]) + (L.total - L.vec[0]) + 15) & ~15);
+  return (size_t)(((m1 - L.mat[first]) + (L.vend - L.vec[0]) + 15) & ~15);
 }
 static size_t stage_bytes(const NsimFieldMeta* meta) {
   return meta->precision == 0 ? stage_bytes_per_wave<0>() : stage_bytes_per_wave<1>();
@@ -2743,7 +3059,7 @@ int nsim_field_pack_weights(const NsimFieldMeta* meta, const float* sdf_w, const
     dims.ui[m] = mat_ui(m, nc);
     total += (int64_t)dims.uo[m] * dims.ui[m];
   }
-  total += (int64_t)V_COUNT * 64;
+  total += (int64_t)V_COUNT * 64 + (L.total - L.vend) / 2;      // (+ the 16-point fragments, f16)
   hipLaunchKernelGGL(k_field_pack, dim3(nsim_blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, L, dims,
                      meta->sdf_D, 2 * meta->lotd.num_levels, sdf_w, sdf_b, rad_w, rad_b, (char*)wpack);
   NSIM_CHECK_LAUNCH();
@@ -2774,6 +3090,7 @@ int nsim_field_pack_weights2(const NsimFieldMeta* meta_a, void* wpack_a, const N
       p.dims[q].ui[m] = mat_ui(m, nc);
       total += (int64_t)p.dims[q].uo[m] * p.dims[q].ui[m];
     }
+    total += (p.L[q].total - p.L[q].vend) / 2;      // (+ the 16-point fragments, f16)
     most = total > most ? total : most;
   }
   p.out[0] = (char*)wpack_a;
@@ -3106,7 +3423,32 @@ static int field_bwd_sdf(const NsimFieldMeta* meta, const void* wpack, const Bwd
   // and no accumulator read-modify-write); forced into 256 registers (two waves per SIMD) it spills 177 and takes 0.275 ms,
   // so the two-hidden-layer instantiation runs one wave per SIMD.  NSIM_SDF_BWD_OLD=1: the round-1 kernel (A/B aid).
   const char* oldp = getenv("NSIM_SDF_BWD_OLD");
-  if (ne || !(oldp && atoi(oldp) == 1)) {
+  const bool old_kernel = oldp && atoi(oldp) == 1;
+  // fp16, <= 16 levels, no embedded block (the object shapes): the 16-point kernel k_field_bwd_h -- 256 registers, 58 KB of LDS,
+  // two workgroups per CU.  NSIM_BWD_TILE=32 (read per launch, A/B aid): the 32-point k_field_bwd_j instead.
+  const char* tile_env = getenv("NSIM_BWD_TILE");
+  if (!old_kernel && meta->precision == 0 && nc == 1 && !ne && field_has16(a.lay) && !(tile_env && atoi(tile_env) == 32)) {
+    const size_t shmem = weights16_lds_bytes(a.lay) + 3 * J16_STAGE_BYTES + JOINT_WAVES * BWD16_PF_BYTES;
+    const int64_t tiles = (S + 15) / 16;
+    int64_t nb = (tiles + JOINT_WAVES - 1) / JOINT_WAVES;
+    const char* gcap = getenv("NSIM_SDF_BWD_GRID");
+    const int64_t cap = gcap ? atoi(gcap) : 512;          // two resident workgroups per CU
+    nb = nb > cap ? cap : (nb < 1 ? 1 : nb);
+    const dim3 grid((unsigned)nb), block(64 * JOINT_WAVES);
+    const SrcOff so = src_off(meta->sdf_D, 2 * meta->lotd.num_levels);
+    int R = 1;
+    float* sc = nb >= grad_replicas_min_wg() ? grad_scratch(stream, so.n_sdf_w + so.n_sdf_b, R) : nullptr;
+    if (sc) {
+      a.dsdf_w = sc; a.dsdf_b = sc + so.n_sdf_w;
+      a.rep_mask = R - 1; a.rep_stride = so.n_sdf_w + so.n_sdf_b;
+    }
+    if (meta->sdf_D == 1) hipLaunchKernelGGL((k_field_bwd_h<1>), grid, block, shmem, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((k_field_bwd_h<2>), grid, block, shmem, (hipStream_t)stream, a);
+    if (sc) grad_scratch_fold(sc, R, so.n_sdf_w, so.n_sdf_b, dsdf_w, dsdf_b, (hipStream_t)stream);
+    NSIM_CHECK_LAUNCH();
+    return 0;
+  }
+  if (ne || !old_kernel) {
     // workgroup-joint weight gradients: weights + three staging areas in LDS, two workgroups per CU
     const size_t row = meta->precision == 0 ? jstage_row_bytes<0>() : jstage_row_bytes<1>();
     // + one 16 KB plane-prefetch buffer per wave in fp16 mode (k_field_bwd_j GLDS)

@@ -388,3 +388,177 @@ __device__ __forceinline__ bool halfwave_run_sum2(int64_t key, bool valid, float
   }
   return valid && ((lane & 31) == 31 || ((heads >> (lane + 1)) & 1ull));
 }
+
+
+// ===================================================================== 16-point tiles (v_mfma_f32_16x16x32_*)
+// Activation-register convention (one wave = 16 points): lane l (p = l & 15, g = l >> 4) owns point p and the units
+// 16m + 4g + r (register 4m + r) of a layer -- the C/D fragment of v_mfma_f32_16x16x32.  The B operand of K-step c is
+// registers 8c .. 8c + 7 as they stand: K index 8g + e <-> unit 16(2c + (e >> 2)) + 4g + (e & 3), and the weight pack (the A
+// operand, field.hip pack16_col) uses the same permutation, so layers chain in registers as in the 32-point convention.  Half
+// the activation registers per lane: the with-grad backward fits 256 registers and runs two waves per SIMD.
+// Weight gradients: the waves of a workgroup stage their activations side by side as [point][unit] rows (one 8-byte store
+// per m-tile and lane) and read them back column-wise with ds_read_b64_tr_b16 (J16_ROW below).
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ f32x4 zero4() {
+  f32x4 z;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) z[r] = 0.f;
+  return z;
+}
+
+// D = A . B + C on v_mfma_f32_16x16x32_{f16,bf16}: A lane l -> row l & 15, B lane l -> col l & 15, K index 8(l >> 4) + e;
+// C/D: col = l & 15, row = 4(l >> 4) + r.  Outside a HIP compile (the host emulator of the tests) the same product is
+// formed from wave_shfl, in the layout the CDNA4 guide states.
+#if defined(__HIP__)
+__device__ __forceinline__ f32x4 mfma_16x16x32_f16(f16x8 a, f16x8 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x4 mfma_16x16x32_bf16(bf16x8 a, bf16x8 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+#else
+template <class V>
+inline f32x4 mfma_16x16x32_portable(V a, V b, f32x4 c) {
+  const int lane = nsim_lane(), col = lane & 15, g = lane >> 4;
+  f32x4 d = c;
+  for (int G = 0; G < 4; ++G) {
+    const V bs = wave_shfl(b, 16 * G + col);
+    for (int r = 0; r < 4; ++r) {
+      const V as = wave_shfl(a, 16 * G + 4 * g + r);
+      float s = 0.f;
+      for (int e = 0; e < 8; ++e) s += (float)as[e] * (float)bs[e];
+      d[r] += s;
+    }
+  }
+  return d;
+}
+inline f32x4 mfma_16x16x32_f16(f16x8 a, f16x8 b, f32x4 c) { return mfma_16x16x32_portable(a, b, c); }
+inline f32x4 mfma_16x16x32_bf16(bf16x8 a, bf16x8 b, f32x4 c) { return mfma_16x16x32_portable(a, b, c); }
+#endif
+
+// ds_read_b64_tr_b16: per group of 16 lanes, lane 4q + p names 4 consecutive 16-bit elements of row q of a 4 x 16 block;
+// lane i of the group receives column i of the 4 rows (row q in element q).  Every lane of the wave must execute it.
+__device__ __forceinline__ bf16x4 lds_read_tr16(const bf16* p) {
+#if defined(__HIP__)
+  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)p);
+#else
+  const int lane = nsim_lane(), G = lane >> 4, i = lane & 15;
+  const unsigned long long me = (unsigned long long)(uintptr_t)p;
+  bf16x4 r;
+  for (int q = 0; q < 4; ++q) {
+    const unsigned long long src = wave_shfl(me, 16 * G + 4 * q + (i >> 2));
+    r[q] = reinterpret_cast<const bf16*>((uintptr_t)src)[i & 3];
+  }
+  return r;
+#endif
+}
+
+// acc[mo] += W16[16 mo.., :] . In^T, In in 16-point register order (NT 16-unit tiles, NT even), scaled by in_scale before
+// the f16 conversion
+template <int MO, int NT>
+__device__ __forceinline__ void contract16(f32x4 (&acc)[MO], const char* wmat, const float (&in)[NT * 4], float in_scale) {
+  static_assert(NT % 2 == 0, "contract16: whole K-steps of 32 inputs");
+  const int lane = nsim_lane();
+  const f16x8* A = reinterpret_cast<const f16x8*>(wmat);
+#pragma unroll
+  for (int c = 0; c < NT / 2; ++c) {
+    f16x8 b;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) b[e] = (f16)(in[8 * c + e] * in_scale);
+#pragma unroll
+    for (int mo = 0; mo < MO; ++mo) acc[mo] = mfma_16x16x32_f16(A[(mo * (NT / 2) + c) * 64 + lane], b, acc[mo]);
+  }
+}
+
+// out[4 mo + r] = (W16 . In^T)[16 mo + 4g + r][pt]   (fp16, dynamic: power-of-two re-scaling of In, as dense)
+template <int MO, int NT>
+__device__ __forceinline__ void dense16(float (&out)[MO * 4], const char* wmat, const float (&in)[NT * 4], bool dynamic) {
+  f32x4 acc[MO];
+#pragma unroll
+  for (int mo = 0; mo < MO; ++mo) acc[mo] = zero4();
+  const float sc = dynamic ? dyn_scale<0, NT * 4>(in) : 1.0f;
+  contract16<MO, NT>(acc, wmat, in, sc);
+  const float inv = 1.0f / sc;
+#pragma unroll
+  for (int mo = 0; mo < MO; ++mo)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) out[mo * 4 + r] = acc[mo][r] * inv;
+}
+
+// ---- LDS staging [point][unit] bf16 for the workgroup-joint weight gradients: J16_PTS rows of 128 bytes (<= 64 units).
+// The 8-byte chunk ch (units 4ch .. 4ch + 3) of row ``row`` sits at chunk ch ^ j16_swz(row): the 16 lanes of a
+// ds_write_b64 (16 consecutive rows, one chunk) hit 16 distinct chunk slots, and each 32-lane half of a transposed read
+// (8 consecutive rows, 4 chunks) covers the 64 banks once -- both conflict-free.
+#define J16_PTS (16 * JOINT_WAVES)
+#define J16_ROW 128
+#define J16_STAGE_BYTES (J16_PTS * J16_ROW)
+
+__device__ __forceinline__ int j16_swz(int row) { return (((row >> 1) & 3) << 2) | (row & 1) | ((row >> 2) & 2); }
+
+// write this wave's 16 points of an activation (NT 16-unit tiles in 16-point register order) into rows 16 wave + p
+template <int NT>
+__device__ __forceinline__ void jstage16(void* st, const float (&v)[NT * 4], int wave) {
+  const int lane = nsim_lane(), p = lane & 15, g = lane >> 4;
+  const int row = 16 * wave + p;
+  char* base = reinterpret_cast<char*>(st) + row * J16_ROW;
+  const int swz = j16_swz(row);
+#pragma unroll
+  for (int m = 0; m < NT; ++m) {
+    bf16x4 w;
+    bf16 b0, b1, b2, b3;
+    nsim_cvt2_bf16(v[4 * m], v[4 * m + 1], b0, b1);
+    nsim_cvt2_bf16(v[4 * m + 2], v[4 * m + 3], b2, b3);
+    w[0] = b0; w[1] = b1; w[2] = b2; w[3] = b3;
+    *reinterpret_cast<bf16x4*>(base + 8 * ((4 * m + g) ^ swz)) = w;
+  }
+}
+
+// the 16x16x32 operand of units 16 t + (l & 15) over K-step c of the staged points: K index 8G + e (G = l >> 4) <-> staged
+// row 32 c + 16 (e >> 2) + 4 G + (e & 3) -- the same for the A and the B side, so the product sums over the points
+__device__ __forceinline__ bf16x8 j16_operand(const void* st, int t, int c) {
+  const int lane = nsim_lane(), G = lane >> 4, q = (lane >> 2) & 3, pc = lane & 3;
+  const char* base = reinterpret_cast<const char*>(st);
+  bf16x8 o;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int row = 32 * c + 16 * h + 4 * G + q;
+    const bf16x4 v = lds_read_tr16(reinterpret_cast<const bf16*>(base + row * J16_ROW + 8 * ((4 * t + pc) ^ j16_swz(row))));
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[4 * h + e] = v[e];
+  }
+  return o;
+}
+
+// acc[n] += A[16 ta + row][:] . B[16 tb_n + col][:]^T over all staged points, tb_n = TB0 + n; rs (optional) += the sum of
+// this lane's share of A's row 16 ta + (l & 15) (summed over the four lane groups at the flush: a bias gradient for free)
+template <int NB>
+__device__ __forceinline__ void jdw16_tiles(const void* stA, int ta, const void* stB, int tb0, f32x4 (&acc)[NB], float* rs) {
+#pragma unroll
+  for (int c = 0; c < J16_PTS / 32; ++c) {
+    const bf16x8 av = j16_operand(stA, ta, c);
+    if (rs) *rs = nsim_bf16x8_sum(av, *rs);
+#pragma unroll
+    for (int n = 0; n < NB; ++n) acc[n] = mfma_16x16x32_bf16(av, j16_operand(stB, tb0 + n, c), acc[n]);
+  }
+}
+
+// the same row share without a product (a staged vector whose gradient is a plain sum over points)
+__device__ __forceinline__ float j16_row_share(const void* st, int t) {
+  float s = 0.f;
+#pragma unroll
+  for (int c = 0; c < J16_PTS / 32; ++c) s = nsim_bf16x8_sum(j16_operand(st, t, c), s);
+  return s;
+}
+
+// flush a 16x16 accumulator tile: dst[(16 to + 4 (l >> 4) + r) * ld + 16 tn + (l & 15)], columns < cols
+__device__ __forceinline__ void jflush16(float* dst, int ld, int cols, int to, int tn, const f32x4& acc) {
+  const int lane = nsim_lane(), col = 16 * tn + (lane & 15);
+  if (col >= cols) return;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = 16 * to + 4 * (lane >> 4) + r;
+    if (acc[r] != 0.f) atomicAdd(&dst[row * ld + col], acc[r]);
+  }
+}

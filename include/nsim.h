@@ -614,6 +614,27 @@ typedef struct {
 int nsim_adam_multi(const NsimAdamTensor* tensors, int n_tensors, float lr, float eps, float grad_scale, int zero_grad,
                     void* stream);
 
+/* ------------------------------------------------------------------------------- marching cubes */
+/* nr3d_lib.graphics.trianglemesh.extract_mesh (code_single/tools/extract_mesh.py:124): the surface {value = level} of a lattice
+ * of SDF values, one z-slab at a time (neuralsim_amd/mesh.py; conventions in csrc/misc.hip).  A slab is lat f32
+ * [nzs + 1][ny][nx] (x fastest), lattice point (i, j, k) at (bx, by, bz) + h (i, j, k0 + k); below / above (may be NULL) are
+ * the single planes next to it.  bpp = ceil(nx ny / 256) blocks per plane.
+ *   count:      cnt_v int32 [(nzs + 1) 2 bpp] (plane k: x/y-edge vertices of its blocks, then z-edge vertices),
+ *               cnt_t int32 [(nzs + 1) bpp] (triangles of the cubes with their origin in the block);
+ *   scan:       both in place -> exclusive offsets; totals int32 [3] = {vertices before plane nzs's x/y edges,
+ *               all vertices of the slab, triangles};
+ *   emit_verts: vid int32 [3][nzs + 1][ny nx] = vbase + slab-local id of the x / y / z edge vertex of every point (-1: none);
+ *               verts / normals f32 [totals[0] (+ plane nzs's x/y vertices when emit_top)][3];
+ *   emit_tris:  faces int32 [totals[2]][3] (global vertex ids from vid). */
+int nsim_mc_count(const float* lat, int64_t nx, int64_t ny, int64_t nzs, float level, int32_t* cnt_v, int32_t* cnt_t,
+                  void* stream);
+int nsim_mc_scan(int32_t* cnt_v, int32_t* cnt_t, int64_t nx, int64_t ny, int64_t nzs, int32_t* totals, void* stream);
+int nsim_mc_emit_verts(const float* lat, const float* below, const float* above, int64_t nx, int64_t ny, int64_t nzs,
+                       float level, float bx, float by, float bz, float h, int64_t k0, int64_t vbase, int emit_top,
+                       const int32_t* off_v, int32_t* vid, float* verts, float* normals, void* stream);
+int nsim_mc_emit_tris(const float* lat, int64_t nx, int64_t ny, int64_t nzs, float level, const int32_t* off_t,
+                      const int32_t* vid, int32_t* faces, void* stream);
+
 /* MFMA layout self-test (tests only): writes D = A(32x16 f16) * B(16x32 f16) with the wrappers used by the
  * field kernels; a, b given in plain row-major. d is 32x32 f32 row-major. */
 int nsim_selftest_mfma(const float* a, const float* b, float* d, int use_f32, void* stream);

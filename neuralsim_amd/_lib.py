@@ -162,6 +162,10 @@ SIGNATURES = {
     "nsim_adam_step": [_P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _F, _I],
     "nsim_adam_multi": [C.POINTER(AdamTensor), _I, _F, _F, _F, _I],
     "nsim_selftest_mfma": [_P, _P, _P, _I],
+    "nsim_mc_count": [_P, _I64, _I64, _I64, _F, _P, _P],
+    "nsim_mc_scan": [_P, _P, _I64, _I64, _I64, _P],
+    "nsim_mc_emit_verts": [_P, _P, _P, _I64, _I64, _I64, _F, _F, _F, _F, _F, _I64, _I64, _I, _P, _P, _P, _P],
+    "nsim_mc_emit_tris": [_P, _I64, _I64, _I64, _F, _P, _P, _P],
 }
 NOSTREAM = {
     "nsim_strerror": ([_I], C.c_char_p),

@@ -1138,8 +1138,14 @@ class LoTDNeuSModel(ModelMixin, nn.Module):
         return self._sdf_query(grid16, wpack, None, rays_o, rays_d, t, ridx, t.shape[0], t.device, goff=goff,
                                n_dev=n_dev, n_add=n_add)
 
-    def forward_sdf_nablas(self, x: torch.Tensor, nablas_has_grad: bool = True) -> Dict[str, torch.Tensor]:
+    def _object_coords(self, x: torch.Tensor, input_normalized: bool) -> torch.Tensor:
+        """``input_normalized=True``: x in [-1, 1]^3 of ``model.space`` -> object coordinates; False: x as given."""
+        return self.space.unnormalize_coords(x) if input_normalized else x
+
+    def forward_sdf_nablas(self, x: torch.Tensor, nablas_has_grad: bool = True, *,
+                           input_normalized: bool = False) -> Dict[str, torch.Tensor]:
         shape = x.shape[:-1]
+        x = self._object_coords(x, input_normalized)
         xf = (x if x.requires_grad else x.detach()).float().reshape(-1, 3).contiguous()   # dL/dx flows when asked for
         sdf, nablas = _FieldFn.apply(self, self._table(), self.sdf_w, self.sdf_b, self.rad_w,
                                      self.rad_b, None, xf, None, None, None, None, False)
@@ -1147,8 +1153,30 @@ class LoTDNeuSModel(ModelMixin, nn.Module):
             nablas = nablas.detach()
         return dict(sdf=sdf.reshape(shape), nablas=nablas.reshape(*shape, 3))
 
-    def forward_sdf(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
-        return dict(sdf=self.forward_sdf_nablas(x, nablas_has_grad=False)["sdf"])
+    def forward_sdf(self, x: torch.Tensor, *, input_normalized: bool = False) -> Dict[str, torch.Tensor]:
+        return dict(sdf=self.forward_sdf_nablas(self._object_coords(x, input_normalized), nablas_has_grad=False)["sdf"])
+
+    def forward(self, x: torch.Tensor, v: torch.Tensor, *, with_rgb: bool = True, with_normal: bool = False,
+                input_normalized: bool = False, h_appear: torch.Tensor = None) -> Dict[str, torch.Tensor]:
+        """The field at free points x [..., 3] seen along directions v [..., 3] (the reference's ``model.forward(x, v,
+        with_rgb=, with_normal=, input_normalized=, h_appear=)``, code_single/tools/extract_mesh.py:109-111) -> dict(sdf, rgb
+        [, nablas]).  The points run through the field forward as zero-length rays ``o = x, d = v, t = 0, ridx = arange``
+        (as ``append_extra_points`` does for the eikonal points); h_appear [n, n_appear] or None as in the ray query."""
+        shape = x.shape[:-1]
+        o = self._object_coords(x, input_normalized).detach().float().reshape(-1, 3).contiguous()
+        d = v.detach().float().reshape(-1, 3).contiguous()
+        n = o.shape[0]
+        t = torch.zeros([n], dtype=torch.float32, device=o.device)
+        ridx = torch.arange(n, device=o.device)
+        ha = h_appear.reshape(n, -1) if h_appear is not None else None
+        outs = _FieldFn.apply(self, self._table(), self.sdf_w, self.sdf_b, self.rad_w, self.rad_b, ha, None, o, d, t, ridx,
+                              bool(with_rgb))
+        ret = dict(sdf=outs[0].reshape(shape))
+        if with_rgb:
+            ret["rgb"] = outs[2].reshape(*shape, 3)
+        if with_normal:
+            ret["nablas"] = outs[1].reshape(*shape, 3)
+        return ret
 
     def sample_pts_uniform(self, num_pts: int, generator=None) -> Dict[str, torch.Tensor]:
         """Random points in the AABB -> forward_sdf_nablas (code_single/tools/train.py:602-613)."""

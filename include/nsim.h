@@ -635,6 +635,33 @@ int nsim_mc_emit_verts(const float* lat, const float* below, const float* above,
 int nsim_mc_emit_tris(const float* lat, int64_t nx, int64_t ny, int64_t nzs, float level, const int32_t* off_t,
                       const int32_t* vid, int32_t* faces, void* stream);
 
+/* --------------------------------------------------------------------------- nearest neighbours */
+/* nr3d_lib.maths.chamfer_distance (code_single/tools/eval_lidar.py:417-421): exact nearest neighbour of every x[i] in y, both f32
+ * [.][3] (neuralsim_amd/pointcloud.py; conventions in csrc/misc.hip).  d2[i] = min_j ((dx dx + dy dy) + dz dz) in f32,
+ * idx[i] = the lowest j that attains it; non-finite points of y are never selected; a non-finite query or an empty y gives
+ * d2 = +inf, idx = -1.  Both paths return the same bits.
+ *   brute:      exhaustive.  qlist (may be NULL: all N queries) = int32 indices of the queries to search, their number read
+ *               from *nq on the device.  nsplit > 1 spreads y over that many workgroups per query block; part_d2 f32 /
+ *               part_idx int32 [nsplit][N] then hold the partial results, combined by a second launch.
+ *   grid_count: hdr int32 [32] (written here: bounding box, cell size and resolution, counters; hdr[7] = the number of queries
+ *               grid_query handed to the exhaustive pass), cell_cnt int32 [max_cells + 1] (points per cell), cell_of / rank
+ *               int32 [M] (cell of every point, -1 when not finite, and its rank inside the cell).  target_occ = the mean
+ *               number of points per occupied cell the cell size aims at.
+ *   grid_scan:  cell_cnt in place -> exclusive offsets.
+ *   grid_fill:  rec [M][4] 16-byte records (x, y, z f32, index int32) of y's finite points in cell order.
+ *   grid_query: rings of cells around each query's cell until the best distance is strictly below the distance to the
+ *               unvisited cells, at most max_rings rings; the queries still open are appended to left_list int32 [N]
+ *               (count in hdr[7]) for nsim_nn_brute(..., qlist = left_list, nq = hdr + 7, ...). */
+int nsim_nn_brute(const float* x, int64_t N, const float* y, int64_t M, const int32_t* qlist, const int32_t* nq, int64_t nsplit,
+                  float* part_d2, int32_t* part_idx, float* d2, int32_t* idx, void* stream);
+int nsim_nn_grid_count(const float* y, int64_t M, float target_occ, int64_t max_cells, int32_t* hdr, int32_t* cell_cnt,
+                       int32_t* cell_of, int32_t* rank, void* stream);
+int nsim_nn_grid_scan(const int32_t* hdr, int32_t* cell_cnt, void* stream);
+int nsim_nn_grid_fill(const float* y, int64_t M, const int32_t* cell_off, const int32_t* cell_of, const int32_t* rank, float* rec,
+                      void* stream);
+int nsim_nn_grid_query(const float* x, int64_t N, const float* rec, const int32_t* cell_off, int32_t* hdr, int max_rings, float* d2,
+                       int32_t* idx, int32_t* left_list, void* stream);
+
 /* MFMA layout self-test (tests only): writes D = A(32x16 f16) * B(16x32 f16) with the wrappers used by the
  * field kernels; a, b given in plain row-major. d is 32x32 f32 row-major. */
 int nsim_selftest_mfma(const float* a, const float* b, float* d, int use_f32, void* stream);

@@ -166,6 +166,11 @@ SIGNATURES = {
     "nsim_mc_scan": [_P, _P, _I64, _I64, _I64, _P],
     "nsim_mc_emit_verts": [_P, _P, _P, _I64, _I64, _I64, _F, _F, _F, _F, _F, _I64, _I64, _I, _P, _P, _P, _P],
     "nsim_mc_emit_tris": [_P, _I64, _I64, _I64, _F, _P, _P, _P],
+    "nsim_nn_brute": [_P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _P],
+    "nsim_nn_grid_count": [_P, _I64, _F, _I64, _P, _P, _P, _P],
+    "nsim_nn_grid_scan": [_P, _P],
+    "nsim_nn_grid_fill": [_P, _I64, _P, _P, _P, _P],
+    "nsim_nn_grid_query": [_P, _I64, _P, _P, _P, _I, _P, _P, _P],
 }
 NOSTREAM = {
     "nsim_strerror": ([_I], C.c_char_p),

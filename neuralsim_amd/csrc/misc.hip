@@ -1,4 +1,5 @@
-// misc.hip -- version / error strings of the C ABI, and marching cubes on slabs of SDF lattices (nsim_mc_*).
+// misc.hip -- version / error strings of the C ABI, marching cubes on slabs of SDF lattices (nsim_mc_*), and exact nearest-neighbour
+// search between point clouds (nsim_nn_*).
 #include "nsim_common.h"
 
 // ------------------------------------------------------------------------------------------------ marching cubes
@@ -404,14 +405,11 @@ __global__ void __launch_bounds__(MC_THREADS) k_mc_count(McSlab s, int32_t* __re
   }
 }
 
-// block 0: exclusive scan of the vertex counts in place (n_v entries; tot[0] = the value at split_v, tot[1] = the total);
-// block 1: of the triangle counts (tot[2] = the total)
-__global__ void __launch_bounds__(MC_SCAN_THREADS) k_mc_scan(int32_t* __restrict__ cnt_v, int64_t n_v, int64_t split_v,
-                                                           int32_t* __restrict__ cnt_t, int64_t n_t, int32_t* __restrict__ tot) {
-  __shared__ int wtot[MC_SCAN_THREADS / 64];
+// exclusive scan of a[0 .. n) in place by one workgroup of MC_SCAN_THREADS threads -> the total (in every thread); the scanned
+// value at index split (if 0 <= split < n) is also written to *at_split.  Shared by k_mc_scan and k_nn_scan.
+__device__ __forceinline__ int block_excl_scan_inplace(int32_t* __restrict__ a, int64_t n, int64_t split, int32_t* at_split,
+                                                       int* wtot) {
   const int tid = threadIdx.x, lane = nsim_lane(), wave = tid >> 6;
-  int32_t* a = blockIdx.x == 0 ? cnt_v : cnt_t;
-  const int64_t n = blockIdx.x == 0 ? n_v : n_t;
   int carry = 0;
   for (int64_t base = 0; base < n; base += (int64_t)MC_SCAN_THREADS * MC_SCAN_PER) {
     const int64_t i0 = base + (int64_t)tid * MC_SCAN_PER;
@@ -438,20 +436,30 @@ __global__ void __launch_bounds__(MC_SCAN_THREADS) k_mc_scan(int32_t* __restrict
       const int64_t i = i0 + q;
       if (i < n) {
         a[i] = run;
-        if (blockIdx.x == 0 && i == split_v) tot[0] = run;
+        if (i == split) *at_split = run;
       }
       run += v[q];
     }
     carry += chunk;
     __syncthreads();
   }
-  if (tid == 0) {
-    if (blockIdx.x == 0) {
+  return carry;
+}
+
+// block 0: exclusive scan of the vertex counts in place (n_v entries; tot[0] = the value at split_v, tot[1] = the total);
+// block 1: of the triangle counts (tot[2] = the total)
+__global__ void __launch_bounds__(MC_SCAN_THREADS) k_mc_scan(int32_t* __restrict__ cnt_v, int64_t n_v, int64_t split_v,
+                                                           int32_t* __restrict__ cnt_t, int64_t n_t, int32_t* __restrict__ tot) {
+  __shared__ int wtot[MC_SCAN_THREADS / 64];
+  if (blockIdx.x == 0) {
+    const int carry = block_excl_scan_inplace(cnt_v, n_v, split_v, &tot[0], wtot);
+    if (threadIdx.x == 0) {
       tot[1] = carry;
-      if (split_v >= n) tot[0] = carry;
-    } else {
-      tot[2] = carry;
+      if (split_v >= n_v) tot[0] = carry;
     }
+  } else {
+    const int carry = block_excl_scan_inplace(cnt_t, n_t, -1, nullptr, wtot);
+    if (threadIdx.x == 0) tot[2] = carry;
   }
 }
 
@@ -634,6 +642,501 @@ int nsim_mc_emit_tris(const float* lat, int64_t nx, int64_t ny, int64_t nzs, flo
 
 }  // extern "C"
 
+// ------------------------------------------------------------------------------------------------ nearest neighbours
+// nr3d_lib.maths.chamfer_distance (code_single/tools/eval_lidar.py:417-421), the kernels behind neuralsim_amd/pointcloud.py.
+//
+// For every query x[i]: d2[i] = min_j nn_dist2(x[i], y[j]) in f32 and idx[i] = the LOWEST j that attains it.  Points of y with a
+// non-finite coordinate are never selected (their distance is inf or NaN, and a candidate replaces the running best only when
+// it compares strictly lower, or equal with a lower index); a query nothing was selected for (non-finite query, empty y, or
+// every distance overflowing) gets d2 = +inf, idx = -1.  Every path goes through nn_dist2 and the same tie rule, so the result
+// is a function of the inputs alone: not of the path, of the order in which points were binned, or of the run.
+//
+// Path a, k_nn_brute: one thread per query, y streamed through LDS in structure-of-arrays tiles of NN_TILE points read as
+// wave-wide broadcasts of 4 points per ds_read_b128.  With nsplit > 1 workgroup (bx, by) searches y's chunk by for the
+// queries of bx and writes a partial (d2, idx); k_nn_combine takes the minimum of the partials in chunk order (chunks ascend
+// in j, so a strict < keeps the lowest index).  With a query list the kernel reads the list's length from device memory and
+// at most NN_LIST_BLOCKS query blocks are launched and stride over it: the leftovers of path b are finished without the host knowing how many there are.
+//
+// Path b, uniform grid over the bounding box of y's finite points, everything on the device:
+//   k_nn_bbox (bounding box and count of the finite points; order-preserving integer encoding of the floats, integer atomic
+//   min) -> k_nn_grid_setup (one thread: cubic cell size and resolution, NnGrid below) -> k_nn_grid_count (cell of every
+//   point; rank inside its cell = the return value of the integer atomic increment of the cell's count) -> k_nn_scan
+//   (exclusive offsets of the cells, x fastest) -> k_nn_grid_fill (records (x, y, z, original index) at offset + rank) ->
+//   k_nn_grid_query.  A point's rank inside its cell depends on the arrival order of the atomics, the results do not: ties
+//   are broken on the original index carried in the record.
+//
+// Cell size: the clouds this is for (LiDAR sweeps, mesh vertices) are surfaces, so a box of n points holds about
+// n h^2 / (e1 e2) points per occupied cell of side h, e1 >= e2 the box's two largest extents:
+// h = sqrt(target_occ e1 e2 / n); from the box VOLUME it would come out far too coarse for a flat cloud (a line: h =
+// target_occ e1 / n).  h then grows by 1.25 until the cell count fits max_cells (the caller's workspace).
+#define NN_THREADS 256
+#define NN_TILE 1024
+#define NN_HDR_INTS 32
+#define NN_COARSE_FACTOR 16.f
+#define NN_LIST_BLOCKS 1024   // at most this many query blocks are launched for a device-side query list (the kernel strides over it)
+
+typedef float nn_f4 __attribute__((ext_vector_type(4)));
+
+// one point of y in cell order: 16 bytes, read whole
+struct alignas(16) NnRec {
+  float x, y, z;
+  int32_t j;   // index in y
+};
+
+// the one distance of every path: f32, (dx dx + dy dy) + dz dz, no contraction (the library is built with -ffp-contract=off)
+__device__ __forceinline__ float nn_dist2(float qx, float qy, float qz, float px, float py, float pz) {
+  const float dx = qx - px, dy = qy - py, dz = qz - pz;
+  return (dx * dx + dy * dy) + dz * dz;
+}
+
+// does candidate (d, j) replace (best, bi)?  false for NaN / inf against the initial (inf, -1)
+__device__ __forceinline__ bool nn_better(float d, int j, float best, int bi) { return d < best || (d == best && j < bi); }
+
+__device__ __forceinline__ bool nn_finite3(float a, float b, float c) { return isfinite(a) && isfinite(b) && isfinite(c); }
+
+// header of the grid workspace (int32 / f32 [NN_HDR_INTS]): written on the device, read by every kernel of path b
+struct NnGrid {
+  uint32_t box[6];   // encoded min x, y, z and complement of the encoded max x, y, z of the finite points (atomic min)
+  int32_t n_finite;  // finite points of y
+  int32_t n_left;    // queries handed to the exhaustive pass
+  int32_t res[3];    // cells per axis
+  int32_t ncells;
+  float bmin[3];
+  float h, inv_h;    // cell side, and the f32 reciprocal every cell coordinate is formed with
+  int32_t n_occ;     // cells that hold at least one point
+  float target_occ;  // the occupancy the cell size aimed at
+  int32_t pad[13];
+};
+static_assert(sizeof(NnGrid) == 4 * NN_HDR_INTS, "NnGrid is the header of the grid workspace");
+
+// order-preserving map of finite floats to uint32
+__device__ __forceinline__ uint32_t nn_enc(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float nn_dec(uint32_t e) {
+  const uint32_t u = (e & 0x80000000u) ? (e & 0x7fffffffu) : ~e;
+  float f;
+  memcpy(&f, &u, 4);
+  return f;
+}
+
+// cell coordinate of p along one axis, in cells, as a float.  Monotone in p (a rounded subtraction and a rounded product with a
+// positive constant are monotone); the cell index is its floor clamped to [0, res - 1].  The points of y and the queries go
+// through this one function: the stopping rule of k_nn_grid_query rests on that.
+__device__ __forceinline__ float nn_cell_coord(float p, float bmin, float inv_h) { return (p - bmin) * inv_h; }
+__device__ __forceinline__ int nn_cell_index(float u, int res) { return (int)fminf(fmaxf(u, 0.f), (float)(res - 1)); }
+
+__global__ void __launch_bounds__(NN_THREADS) k_nn_bbox(const float* __restrict__ y, int64_t M, NnGrid* __restrict__ g) {
+  __shared__ uint32_t sm[NN_THREADS / 64][6];
+  __shared__ int sn[NN_THREADS / 64];
+  uint32_t e[6] = {~0u, ~0u, ~0u, ~0u, ~0u, ~0u};
+  int n = 0;
+  for (int64_t j = (int64_t)blockIdx.x * NN_THREADS + threadIdx.x; j < M; j += (int64_t)gridDim.x * NN_THREADS) {
+    const float p[3] = {y[3 * j], y[3 * j + 1], y[3 * j + 2]};
+    if (!nn_finite3(p[0], p[1], p[2])) continue;
+    ++n;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const uint32_t c = nn_enc(p[a]);
+      e[a] = c < e[a] ? c : e[a];
+      e[3 + a] = ~c < e[3 + a] ? ~c : e[3 + a];
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+      const uint32_t u = wave_shfl_xor(e[a], o);
+      e[a] = u < e[a] ? u : e[a];
+    }
+  }
+  n = wave_sum(n);
+  const int wave = threadIdx.x >> 6;
+  if (nsim_lane() == 0) {
+#pragma unroll
+    for (int a = 0; a < 6; ++a) sm[wave][a] = e[a];
+    sn[wave] = n;
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    uint32_t m = sm[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < NN_THREADS / 64; ++w) m = sm[w][threadIdx.x] < m ? sm[w][threadIdx.x] : m;
+    atomicMin(&g->box[threadIdx.x], m);
+  } else if (threadIdx.x == 6) {
+    int t = 0;
+#pragma unroll
+    for (int w = 0; w < NN_THREADS / 64; ++w) t += sn[w];
+    if (t) atomicAdd(&g->n_finite, t);
+  }
+}
+
+__global__ void __launch_bounds__(64) k_nn_grid_setup(NnGrid* __restrict__ g, float target_occ, int64_t max_cells) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const int n = g->n_finite;
+  float bmin[3] = {0.f, 0.f, 0.f}, e[3] = {0.f, 0.f, 0.f};
+  if (n > 0) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      bmin[a] = nn_dec(g->box[a]);
+      e[a] = nn_dec(~g->box[3 + a]) - bmin[a];
+    }
+  }
+  // the two largest extents
+  const float emax = fmaxf(e[0], fmaxf(e[1], e[2])), emin = fminf(e[0], fminf(e[1], e[2]));
+  const float emid = (e[0] + e[1] + e[2]) - emax - emin;
+  float h = 0.f;
+  if (n > 0 && isfinite(e[0] + e[1] + e[2])) {
+    if (emid > 0.f && emid >= emax * 1e-6f) h = sqrtf(target_occ * (emax / (float)n) * emid);
+    else h = target_occ * emax / (float)n;
+    h = fmaxf(h, emax * (1.f / 1048576.f));   // at most 2^20 cells per axis: cell indices are exact in f32
+  }
+  int res[3] = {1, 1, 1};
+  float inv_h = 1.f;
+  if (h > 0.f && isfinite(h) && isfinite(1.f / h)) {
+    for (int it = 0; it < 256; ++it) {
+      inv_h = 1.f / h;
+      int64_t total = 1;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        res[a] = (int)fminf(e[a] * inv_h, 1048575.f) + 1;
+        total *= res[a];
+      }
+      if (total <= max_cells) break;
+      h *= 1.25f;
+    }
+  } else {
+    h = 1.f;   // no finite point, a single point, or extents that overflow: one cell
+  }
+  if ((int64_t)res[0] * res[1] * res[2] > max_cells || !(inv_h > 0.f) || !isfinite(inv_h)) {
+    res[0] = res[1] = res[2] = 1;
+    h = inv_h = 1.f;
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    g->res[a] = res[a];
+    g->bmin[a] = bmin[a];
+  }
+  g->ncells = res[0] * res[1] * res[2];
+  g->h = h;
+  g->inv_h = inv_h;
+  g->target_occ = target_occ;
+}
+
+__global__ void __launch_bounds__(NN_THREADS) k_nn_grid_count(const float* __restrict__ y, int64_t M, NnGrid* __restrict__ g,
+                                                            int32_t* __restrict__ cell_cnt, int32_t* __restrict__ cell_of,
+                                                            int32_t* __restrict__ rank) {
+  const int64_t j = (int64_t)blockIdx.x * NN_THREADS + threadIdx.x;
+  if (j >= M) return;
+  const float px = y[3 * j], py = y[3 * j + 1], pz = y[3 * j + 2];
+  int c = -1, r = 0;
+  if (nn_finite3(px, py, pz)) {
+    const float ih = g->inv_h;
+    const int cx = nn_cell_index(nn_cell_coord(px, g->bmin[0], ih), g->res[0]);
+    const int cy = nn_cell_index(nn_cell_coord(py, g->bmin[1], ih), g->res[1]);
+    const int cz = nn_cell_index(nn_cell_coord(pz, g->bmin[2], ih), g->res[2]);
+    c = (cz * g->res[1] + cy) * g->res[0] + cx;
+    r = atomicAdd(&cell_cnt[c], 1);
+    if (r == 0) atomicAdd(&g->n_occ, 1);   // exactly one point per occupied cell sees rank 0
+  }
+  cell_of[j] = c;
+  rank[j] = r;
+}
+
+// exclusive offsets of the cells in place; entry ncells (a zero count) becomes the number of finite points
+__global__ void __launch_bounds__(MC_SCAN_THREADS) k_nn_scan(const NnGrid* __restrict__ g, int32_t* __restrict__ cell_cnt) {
+  __shared__ int wtot[MC_SCAN_THREADS / 64];
+  block_excl_scan_inplace(cell_cnt, (int64_t)g->ncells + 1, -1, nullptr, wtot);
+}
+
+__global__ void __launch_bounds__(NN_THREADS) k_nn_grid_fill(const float* __restrict__ y, int64_t M, const int32_t* __restrict__ cell_off,
+                                                           const int32_t* __restrict__ cell_of, const int32_t* __restrict__ rank,
+                                                           NnRec* __restrict__ rec) {
+  const int64_t j = (int64_t)blockIdx.x * NN_THREADS + threadIdx.x;
+  if (j >= M) return;
+  const int c = cell_of[j];
+  if (c < 0) return;
+  NnRec v;
+  v.x = y[3 * j];
+  v.y = y[3 * j + 1];
+  v.z = y[3 * j + 2];
+  v.j = (int32_t)j;
+  rec[cell_off[c] + rank[j]] = v;
+}
+
+__device__ __forceinline__ void nn_scan_records(const NnRec* __restrict__ rec, int p0, int p1, float qx, float qy, float qz, float& best,
+                                                int& bi) {
+  for (int p = p0; p < p1; ++p) {
+    const NnRec v = rec[p];
+    const float d = nn_dist2(qx, qy, qz, v.x, v.y, v.z);
+    if (nn_better(d, v.j, best, bi)) {
+      best = d;
+      bi = v.j;
+    }
+  }
+}
+
+// Lower bound, in cells, of the distance along one axis from the query (cell coordinate u) to any point of y on the far side of
+// the cell plane k (a point whose cell index is >= k when upper, < k when not).
+//
+// Why it is conservative.  Let t = nn_cell_coord(p) for such a point: t >= k (upper; the index is floor(t) clamped from above to
+// res - 1 >= k) or 0 <= t < k (lower).  With a = p - bmin exactly, t = a (1 + d1)(1 + d2) inv_h, |d1|, |d2| <= eps = 2^-24 (one
+// rounded subtraction, one rounded product), so a = t H / ((1 + d1)(1 + d2)) with H = 1 / inv_h, and the same for the query with
+// u, wherever it lies (u < 0 or u > res outside the box).  Hence, upper side,
+//     p - q >= H (t - u) - 2.01 eps H (|t| + |u|) >= H ((k - u) - 2.01 eps (k + |u|))
+// (the middle expression grows with t), and the mirror image on the lower side.  The slack below, 2^-20 (k + |u| + 1), is 8
+// times that plus the rounding of k - u itself; a non-positive or NaN gap (query beyond the plane, or u = +-inf for a query so far
+// away that its coordinate overflows) gives 0: keep searching.
+__device__ __forceinline__ float nn_plane_gap(float u, int k, bool upper) {
+  const float kf = (float)k;
+  const float gap = (upper ? kf - u : u - kf) - 9.5367431640625e-07f * (kf + fabsf(u) + 1.f);
+  return gap > 0.f ? gap : 0.f;
+}
+
+// One thread per query: the cells at Chebyshev distance 0, 1, 2, ... from the query's (clamped) cell, clipped to the grid; a
+// ring's interior rows contribute their two end cells, its border rows a contiguous run of records (x is the fastest cell
+// index).  After ring r every unvisited point lies beyond one of the up to six planes of the visited box that are inside the
+// grid (a clipped side has no cells, hence no points, beyond it -- this is also what makes a query outside y's box safe: its
+// clamped cell sits on the grid's border, the side it lies beyond is clipped from r = 0, and the planes that remain are
+// bounded through nn_plane_gap with the query's true, unclamped coordinate).  So every unvisited point is at least
+// b = h_lo min(gaps) away, h_lo = h (1 - 2^-18) <= 1 / inv_h, and the search stops when best < b b STRICTLY: a point at
+// exactly that distance could tie and carry a lower index.  The factor 1 - 2^-18 also covers the rounding of the computed
+// distances (an unvisited point's computed d2 is at least its true value times 1 - 5 eps, and b b is rounded twice), and b b
+// below 1e-30 counts as 0 (squares that underflow).  All sides clipped: the whole grid was read, done.  A query still open
+// after max_rings rings is appended to left_list (integer atomic; the list's order is arbitrary, its content is not) and
+// finished by k_nn_brute over all of y, which overwrites its outputs.
+__global__ void __launch_bounds__(NN_THREADS) k_nn_grid_query(const float* __restrict__ x, int64_t N, const NnRec* __restrict__ rec,
+                                                            const int32_t* __restrict__ cell_off, NnGrid* __restrict__ g, int max_rings,
+                                                            float* __restrict__ d2, int32_t* __restrict__ idx,
+                                                            int32_t* __restrict__ left_list) {
+  const int64_t i = (int64_t)blockIdx.x * NN_THREADS + threadIdx.x;
+  if (i >= N) return;
+  const float q[3] = {x[3 * i], x[3 * i + 1], x[3 * i + 2]};
+  float best = INFINITY;
+  int bi = -1;
+  bool done = !nn_finite3(q[0], q[1], q[2]) || g->n_finite == 0;
+  // A few far outliers in y blow up the box, the cell budget then forces cells that hold the whole sweep, and walking such a
+  // cell record by record per thread is an exhaustive search without the LDS tiles: when the occupied cells hold more than
+  // NN_COARSE_FACTOR times the occupancy aimed at, every query goes to the tiled exhaustive pass instead.
+  const bool coarse = (float)g->n_finite > NN_COARSE_FACTOR * g->target_occ * (float)g->n_occ;
+  if (!done && coarse) {
+    left_list[atomicAdd(&g->n_left, 1)] = (int32_t)i;
+    done = true;
+  }
+  if (!done) {
+    const int res[3] = {g->res[0], g->res[1], g->res[2]};
+    const float ih = g->inv_h, h_lo = g->h * 0.999996185302734375f;
+    float u[3];
+    int c[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      u[a] = nn_cell_coord(q[a], g->bmin[a], ih);
+      c[a] = nn_cell_index(u[a], res[a]);
+    }
+    for (int r = 0; r <= max_rings && !done; ++r) {
+      int lo[3], hi[3], l[3], m[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        lo[a] = c[a] - r;
+        hi[a] = c[a] + r;
+        l[a] = lo[a] > 0 ? lo[a] : 0;
+        m[a] = hi[a] < res[a] - 1 ? hi[a] : res[a] - 1;
+      }
+      for (int cz = l[2]; cz <= m[2]; ++cz)
+        for (int cy = l[1]; cy <= m[1]; ++cy) {
+          const int row = (cz * res[1] + cy) * res[0];
+          if (cz == lo[2] || cz == hi[2] || cy == lo[1] || cy == hi[1]) {
+            nn_scan_records(rec, cell_off[row + l[0]], cell_off[row + m[0] + 1], q[0], q[1], q[2], best, bi);
+          } else {
+            if (lo[0] >= 0) nn_scan_records(rec, cell_off[row + lo[0]], cell_off[row + lo[0] + 1], q[0], q[1], q[2], best, bi);
+            if (hi[0] < res[0]) nn_scan_records(rec, cell_off[row + hi[0]], cell_off[row + hi[0] + 1], q[0], q[1], q[2], best, bi);
+          }
+        }
+      float gap = INFINITY;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        if (lo[a] >= 1) gap = fminf(gap, nn_plane_gap(u[a], lo[a], false));
+        if (hi[a] + 1 <= res[a] - 1) gap = fminf(gap, nn_plane_gap(u[a], hi[a] + 1, true));
+      }
+      if (gap == INFINITY) {
+        done = true;
+      } else {
+        const float b = gap * h_lo;
+        float b2 = b * b;
+        if (!(b2 > 1e-30f)) b2 = 0.f;
+        done = best < b2;
+      }
+    }
+    if (!done) left_list[atomicAdd(&g->n_left, 1)] = (int32_t)i;
+  }
+  d2[i] = best;
+  idx[i] = bi;
+}
+
+// grid (query blocks, chunks of y).  qlist == NULL: queries 0 .. N - 1; else qlist[0 .. *nq_ptr).
+__global__ void __launch_bounds__(NN_THREADS) k_nn_brute(const float* __restrict__ x, int64_t N, const float* __restrict__ y, int64_t M,
+                                                       const int32_t* __restrict__ qlist, const int32_t* __restrict__ nq_ptr,
+                                                       int64_t chunk, float* __restrict__ part_d2, int32_t* __restrict__ part_idx,
+                                                       float* __restrict__ d2, int32_t* __restrict__ idx) {
+  __shared__ __attribute__((aligned(16))) float sy[3][NN_TILE];
+  int64_t nq = N;
+  if (qlist) {
+    const int64_t n = *nq_ptr;
+    nq = n < N ? n : N;
+  }
+  const int tid = threadIdx.x;
+  // query blocks in a grid-stride loop (block-uniform bounds): a launch for a list of unknown length stays small
+  for (int64_t qblk = blockIdx.x; qblk * NN_THREADS < nq; qblk += gridDim.x) {
+    const int64_t slot = qblk * NN_THREADS + tid;
+    const bool active = slot < nq;
+    const int64_t qi = !active ? 0 : qlist ? qlist[slot] : slot;
+    const float qx = x[3 * qi], qy = x[3 * qi + 1], qz = x[3 * qi + 2];
+    const int64_t j0 = (int64_t)blockIdx.y * chunk, j1 = (j0 + chunk) < M ? (j0 + chunk) : M;
+    float best = INFINITY;
+    int bi = -1;
+    for (int64_t base = j0; base < j1; base += NN_TILE) {
+      __syncthreads();
+      for (int e = tid; e < 3 * NN_TILE; e += NN_THREADS) {   // coalesced [tile][3] -> three rows; NaN beyond the chunk
+        const int64_t ge = 3 * base + e;
+        sy[e % 3][e / 3] = ge < 3 * j1 ? y[ge] : NAN;
+      }
+      __syncthreads();
+      const int64_t left = j1 - base;
+      const int nt = left < NN_TILE ? (int)((left + 3) & ~(int64_t)3) : NN_TILE;
+      for (int t = 0; t < nt; t += 4) {
+        const nn_f4 px = *reinterpret_cast<const nn_f4*>(&sy[0][t]);
+        const nn_f4 py = *reinterpret_cast<const nn_f4*>(&sy[1][t]);
+        const nn_f4 pz = *reinterpret_cast<const nn_f4*>(&sy[2][t]);
+        const float e0 = nn_dist2(qx, qy, qz, px.x, py.x, pz.x), e1 = nn_dist2(qx, qy, qz, px.y, py.y, pz.y);
+        const float e2 = nn_dist2(qx, qy, qz, px.z, py.z, pz.z), e3 = nn_dist2(qx, qy, qz, px.w, py.w, pz.w);
+        const int j = (int)(base + t);
+        // ascending j: a strict < keeps the lowest index (nn_better's rule when j > bi)
+        if (e0 < best) { best = e0; bi = j; }
+        if (e1 < best) { best = e1; bi = j + 1; }
+        if (e2 < best) { best = e2; bi = j + 2; }
+        if (e3 < best) { best = e3; bi = j + 3; }
+      }
+    }
+    if (active) {
+      if (gridDim.y == 1) {
+        d2[qi] = best;
+        idx[qi] = bi;
+      } else {
+        part_d2[(int64_t)blockIdx.y * N + slot] = best;
+        part_idx[(int64_t)blockIdx.y * N + slot] = bi;
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(NN_THREADS) k_nn_combine(int64_t N, const int32_t* __restrict__ qlist, const int32_t* __restrict__ nq_ptr,
+                                                         int nsplit, const float* __restrict__ part_d2,
+                                                         const int32_t* __restrict__ part_idx, float* __restrict__ d2,
+                                                         int32_t* __restrict__ idx) {
+  int64_t nq = N;
+  if (qlist) {
+    const int64_t n = *nq_ptr;
+    nq = n < N ? n : N;
+  }
+  const int64_t slot = (int64_t)blockIdx.x * NN_THREADS + threadIdx.x;
+  if (slot >= nq) return;
+  float best = INFINITY;
+  int bi = -1;
+  for (int s = 0; s < nsplit; ++s) {   // chunks ascend in j
+    const float d = part_d2[(int64_t)s * N + slot];
+    if (d < best) {
+      best = d;
+      bi = part_idx[(int64_t)s * N + slot];
+    }
+  }
+  const int64_t qi = qlist ? qlist[slot] : slot;
+  d2[qi] = best;
+  idx[qi] = bi;
+}
+
+extern "C" {
+
+int nsim_nn_brute(const float* x, int64_t N, const float* y, int64_t M, const int32_t* qlist, const int32_t* nq, int64_t nsplit,
+                  float* part_d2, int32_t* part_idx, float* d2, int32_t* idx, void* stream) {
+  if (N < 0 || M < 0 || nsplit < 1) return 2;
+  if (N >= ((int64_t)1 << 31) - NN_TILE || M >= ((int64_t)1 << 31) - NN_TILE || nsplit > 65535) return 51;
+  if (N == 0) return 0;
+  if (!x || !d2 || !idx || (M > 0 && !y) || (qlist && !nq) || (nsplit > 1 && (!part_d2 || !part_idx))) return 4;
+  // chunks of whole tiles; chunks that would be empty are not launched
+  int64_t chunk = ((M + nsplit - 1) / nsplit + NN_TILE - 1) / NN_TILE * NN_TILE;
+  if (chunk < NN_TILE) chunk = NN_TILE;
+  int64_t ns = (M + chunk - 1) / chunk;
+  if (ns < 1) ns = 1;
+  const unsigned qb = (unsigned)((N + NN_THREADS - 1) / NN_THREADS);
+  const unsigned qbl = (qlist && qb > NN_LIST_BLOCKS) ? NN_LIST_BLOCKS : qb;
+  hipLaunchKernelGGL(k_nn_brute, dim3(qbl, (unsigned)ns), dim3(NN_THREADS), 0, (hipStream_t)stream, x, N, y, M, qlist, nq, chunk, part_d2,
+                     part_idx, d2, idx);
+  NSIM_CHECK_LAUNCH();
+  if (ns > 1) {
+    hipLaunchKernelGGL(k_nn_combine, dim3(qb), dim3(NN_THREADS), 0, (hipStream_t)stream, N, qlist, nq, (int)ns, part_d2, part_idx, d2,
+                       idx);
+    NSIM_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+int nsim_nn_grid_count(const float* y, int64_t M, float target_occ, int64_t max_cells, int32_t* hdr, int32_t* cell_cnt,
+                       int32_t* cell_of, int32_t* rank, void* stream) {
+  if (M < 0) return 2;
+  if (M >= ((int64_t)1 << 31) - NN_TILE || max_cells < 1 || max_cells >= ((int64_t)1 << 30) || !(target_occ > 0.f)) return 51;
+  if (!hdr || !cell_cnt || (M > 0 && (!y || !cell_of || !rank))) return 4;
+  NnGrid* g = reinterpret_cast<NnGrid*>(hdr);
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(hdr, 0, sizeof(NnGrid), st) != hipSuccess) return 1000;
+  if (hipMemsetAsync(hdr, 0xff, 6 * sizeof(uint32_t), st) != hipSuccess) return 1000;
+  if (hipMemsetAsync(cell_cnt, 0, (size_t)(max_cells + 1) * sizeof(int32_t), st) != hipSuccess) return 1000;
+  if (M > 0) {
+    hipLaunchKernelGGL(k_nn_bbox, dim3(nsim_blocks(M, NN_THREADS, 512)), dim3(NN_THREADS), 0, st, y, M, g);
+    NSIM_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(k_nn_grid_setup, dim3(1), dim3(64), 0, st, g, target_occ, max_cells);
+  NSIM_CHECK_LAUNCH();
+  if (M > 0) {
+    hipLaunchKernelGGL(k_nn_grid_count, dim3((unsigned)((M + NN_THREADS - 1) / NN_THREADS)), dim3(NN_THREADS), 0, st, y, M, g, cell_cnt,
+                       cell_of, rank);
+    NSIM_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+int nsim_nn_grid_scan(const int32_t* hdr, int32_t* cell_cnt, void* stream) {
+  if (!hdr || !cell_cnt) return 4;
+  hipLaunchKernelGGL(k_nn_scan, dim3(1), dim3(MC_SCAN_THREADS), 0, (hipStream_t)stream, reinterpret_cast<const NnGrid*>(hdr), cell_cnt);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_nn_grid_fill(const float* y, int64_t M, const int32_t* cell_off, const int32_t* cell_of, const int32_t* rank, float* rec,
+                      void* stream) {
+  if (M < 0) return 2;
+  if (M == 0) return 0;
+  if (!y || !cell_off || !cell_of || !rank || !rec) return 4;
+  hipLaunchKernelGGL(k_nn_grid_fill, dim3((unsigned)((M + NN_THREADS - 1) / NN_THREADS)), dim3(NN_THREADS), 0, (hipStream_t)stream, y, M,
+                     cell_off, cell_of, rank, reinterpret_cast<NnRec*>(rec));
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_nn_grid_query(const float* x, int64_t N, const float* rec, const int32_t* cell_off, int32_t* hdr, int max_rings, float* d2,
+                       int32_t* idx, int32_t* left_list, void* stream) {
+  if (N < 0 || max_rings < 0) return 2;
+  if (N == 0) return 0;
+  if (!x || !rec || !cell_off || !hdr || !d2 || !idx || !left_list) return 4;
+  hipLaunchKernelGGL(k_nn_grid_query, dim3((unsigned)((N + NN_THREADS - 1) / NN_THREADS)), dim3(NN_THREADS), 0, (hipStream_t)stream, x, N,
+                     reinterpret_cast<const NnRec*>(rec), cell_off, reinterpret_cast<NnGrid*>(hdr), max_rings, d2, idx, left_list);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // extern "C"
+
 extern "C" {
 
 int nsim_version(void) { return 100; }
@@ -675,6 +1178,7 @@ const char* nsim_strerror(int code) {
     case 26: return "gradient output pointer is NULL";
     case 37: return "compose collect: at most 64 sources";
     case 50: return "marching cubes: lattice sizes out of range (nx * ny < 2^31, at most 65534 cubes per slab in z)";
+    case 51: return "nearest neighbours: sizes out of range (N, M < 2^31 - 1024, at most 65535 chunks, 1 <= max_cells < 2^30, target occupancy > 0)";
     case 36: return "wide decoder: 0..10 embedding frequencies and at most 128 first-layer inputs (2 num_levels + 3 + 6 n_freq)";
     default: return code >= 1000 ? "HIP launch error (code - 1000 = hipError_t)" : "unknown error";
   }

@@ -507,8 +507,30 @@ class OccGridAccel(nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------- model
+class _QueryCfg(dict):
+    """``model.ray_query_cfg``: a plain dict whose keys can also be set and read as attributes -- the reference's tools write
+    ``model.ray_query_cfg.forward_inv_s = ...`` (code_single/tools/eval.py:219, eval_lidar.py:182) on what is a ConfigDict there."""
+
+    def __getattr__(self, k):
+        try:
+            return self[k]
+        except KeyError:
+            raise AttributeError(k) from None
+
+    def __setattr__(self, k, v):
+        self[k] = v
+
+
 class LoTDNeuSModel(ModelMixin, nn.Module):
     is_ray_query_supported = True
+
+    @property
+    def ray_query_cfg(self):
+        return self._ray_query_cfg
+
+    @ray_query_cfg.setter
+    def ray_query_cfg(self, cfg):
+        self._ray_query_cfg = cfg if isinstance(cfg, _QueryCfg) else _QueryCfg(cfg)
 
     def __init__(self, lod_res: Sequence[int] = None, log2_hashmap_size: int = 19, sdf_D: int = 2, W: int = 64,
                  precision: str = "fp16", softplus_beta: float = 100.0, ln_inv_s_init: float = 0.1,

@@ -45,3 +45,8 @@ def get_transform_np(rot=None, trans=None):
     if trans is not None:
         m[:3, 3] = trans
     return m
+
+
+# ``from nr3d_lib.maths import chamfer_distance`` (code_single/tools/eval_lidar.py:37): per-point chamfer terms of two clouds, on
+# the device (neuralsim_amd/pointcloud.py; Euclidean distances -- a reading of the call site, see that module's docstring)
+from neuralsim_amd.pointcloud import chamfer_distance  # noqa: E402,F401

@@ -25,9 +25,6 @@
 //  * fp16 MFMA operands are re-scaled per tile by an exact power of two (dyn_scale) so that the tiny
 //    upstream gradients of a volume-render loss do not underflow -- no global loss scaler is required;
 //  * PREC=1 selects v_mfma_f32_32x32x2_f32 (exact f32 at the vector rate) for tight parity tests.
-#ifndef NSIM_SCATTER_SCAN_EXIT
-#define NSIM_SCATTER_SCAN_EXIT 1
-#endif
 #include "lotd_dev.h"
 #include "mfma_mlp.h"
 #include "occ_dev.h"
@@ -270,20 +267,9 @@ __device__ __forceinline__ float softplus_exact(float z, float beta, float inv_b
   const float t = nsim_exp2(-fabsf(z) * (beta * NSIM_LOG2E));
   return fmaxf(z, 0.f) + nsim_log2(1.0f + t) * (inv_beta * NSIM_LN2);
 }
-#ifdef NSIM_PROBE_CHEAP_ACT
-// MEASUREMENT AID, never the product build (tools/act_probe.sh): the with-grad decoder kernels with a transcendental-free
-// stand-in of comparable full-rate cost -- the time they lose is the most ANY polynomial activation could win.  The
-// sampling pass (k_field_sdf) keeps the exact form, so the sample sets of a step do not change.
-__device__ __forceinline__ float softplus_b(float z, float beta, float inv_beta) {
-  const float q = fmaxf(0.f, 1.0f - 0.25f * beta * fabsf(z));
-  return fmaxf(z, 0.f) + q * q * (inv_beta * NSIM_LN2);
-}
-__device__ __forceinline__ float sig_from_softplus(float a, float beta) { return fminf(1.0f, 0.72f * a * beta); }
-#else
 __device__ __forceinline__ float softplus_b(float z, float beta, float inv_beta) { return softplus_exact(z, beta, inv_beta); }
 // sigma(beta z) recovered from a = softplus(z):  1 - exp(-beta a)   (abs. error <= 6e-8)
 __device__ __forceinline__ float sig_from_softplus(float a, float beta) { return 1.0f - nsim_exp2(-a * (beta * NSIM_LOG2E)); }
-#endif
 
 __device__ __forceinline__ void sh4_eval(const float d[3], float (&o)[16]) {
   const float x = d[0], y = d[1], z = d[2];
@@ -356,8 +342,10 @@ struct FieldArgs {
   float* occ_val;                                  // no-grad query of a training step: fold f(sdf) into this value grid
   OccDev occ;                                      // ... (update_from_samples_cfg; needs positions in ``x``)
   float occ_inv_s;
-  int ablate;                                      // profiling aid (NSIM_ABLATE): 1 no scatter, 4 no dW products, 8 no dh_appear atomics
-  int code_pf;                                     // bytes of this kernel's own code pulled into L2 by the prologue (stage_weights)
+  int ablate;                                      // always 0 (bit 4 skipped the weight-gradient products, bit 8 the appearance atomics, for profiling);
+  int code_pf;                                     // always 0 (bytes of own code the prologue pulled into L2).  Nothing sets them any more; the kernels
+                                                   // still test them because without the tests the compiler allocates k_field_bwd_j<0,1> 256 + 52 instead
+                                                   // of 246 + 48 registers and spills more in k_field_bwd_j<0,2,2,2> -- to be removed with a GPU measurement
   int rep_mask;                                    // weight-gradient replicas (nsim_set_grad_scratch): workgroup b flushes into
   int64_t rep_stride;                              // copy (b & rep_mask) at + rep_stride floats; 0 / 0 = the caller's buffers
   float *dgrid, *dsdf_w, *dsdf_b, *drad_w, *drad_b, *dh_appear;
@@ -365,84 +353,8 @@ struct FieldArgs {
   int embed_E;                                     // embedded-position inputs of the SDF decoder's first layer (k_field / k_field_bwd_j NE = 2)
 };
 
-// LDS accumulator layouts (floats)
-struct AccOff {
-  int w1, w2, wh, b1, b2, bh, total;
-};
-__host__ __device__ inline AccOff acc_off(int nc = 1) {
-  AccOff a;
-  int o = 0;
-  a.w1 = o; o += 64 * 32 * nc;
-  a.w2 = o; o += 64 * 64;
-  a.wh = o; o += 64;
-  a.b1 = o; o += 64;
-  a.b2 = o; o += 64;
-  a.bh = o; o += 4;
-  a.total = o;
-  return a;
-}
-struct RadAccOff {
-  int r1, r2, r3, rb1, rb2, rb3, total;
-};
-__host__ __device__ inline RadAccOff rad_acc_off() {
-  RadAccOff a;
-  int o = 0;
-  a.r1 = o; o += 64 * 26;
-  a.r2 = o; o += 64 * 64;
-  a.r3 = o; o += 3 * 64;
-  a.rb1 = o; o += 64;
-  a.rb2 = o; o += 64;
-  a.rb3 = o; o += 4;
-  a.total = o;
-  return a;
-}
-
 
 #define FIELD_WAVES 4
-#ifndef NSIM_BWD_DBUF
-#define NSIM_BWD_DBUF 0         // k_field_bwd_j, fp16: 1 = two alternating staging sets for the weight-gradient products (4 instead of 8 barriers
-                                // per group).  Measured null on MI355X (nsim_field_bwd_sdf 0.1208 vs 0.1210 ms, street 0.6419 vs 0.6418;
-                                // gpurun_out/r6_s2_call5) at +36 registers: the barriers are not where the kernel's time goes
-#endif
-#ifndef NSIM_BWD_JDIRECT
-#define NSIM_BWD_JDIRECT 1      // k_field_bwd_j, <= 16 levels, fp16 mode: features through the LDS image, dh/dx as packed pairs straight into registers
-#endif
-#ifndef NSIM_FWD_JPACKED
-#define NSIM_FWD_JPACKED 1      // ... and held there as the packed pairs of the planes until the normals are formed (0: converted at the load)
-#endif
-#ifndef NSIM_FWD_JDIRECT
-#define NSIM_FWD_JDIRECT 1      // k_field MODE 3, <= 16 levels: features through the LDS image, dh/dx straight into registers
-#endif
-
-// Development aid (-DNSIM_KTIME, never in the product build): s_memtime stamps of wave 0 of the first 64 workgroups at
-// phase boundaries of their SECOND group iteration, read back by tools/ktime.py through nsim_debug_ktime.
-#ifdef NSIM_KTIME
-__device__ long long g_ktime[3][64 * 24];
-__device__ long long g_ktime1[3][64 * 24];      // the FIRST group iteration of the same workgroups (cold pass)
-__device__ long long g_kiter[3][64 * 32];       // loop-top stamp of EVERY group iteration (first 32) of the same workgroups
-#define KT(K, i)                                                                                          \
-  if (blockIdx.x < 64 && wave == 0 && lane == 0) {                                                        \
-    if ((i) == 0 && grp >= 0 && (grp - (int64_t)blockIdx.x) / (int64_t)gridDim.x < 32)                    \
-      g_kiter[K][blockIdx.x * 32 + (grp - (int64_t)blockIdx.x) / (int64_t)gridDim.x] =                   \
-          (long long)__builtin_amdgcn_s_memtime();                                                        \
-    if (grp == (int64_t)blockIdx.x + gridDim.x || (i) >= 20)                                              \
-      g_ktime[K][blockIdx.x * 24 + (i)] = (long long)__builtin_amdgcn_s_memtime();                        \
-    else if (grp == (int64_t)blockIdx.x)                                                                  \
-      g_ktime1[K][blockIdx.x * 24 + (i)] = (long long)__builtin_amdgcn_s_memtime();                       \
-  }
-extern "C" int nsim_debug_ktime(long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ktime), sizeof(g_ktime));
-}
-extern "C" int nsim_debug_kiter(long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_kiter), sizeof(g_kiter));
-}
-extern "C" int nsim_debug_ktime1(long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ktime1), sizeof(g_ktime1));
-}
-#else
-#define KT(K, i)
-#endif
-
 // Copy the MFMA fragments a kernel needs into LDS (fp16 mode) and return a layout whose offsets are relative to the
 // LDS copy: matrices [first, first+count) are contiguous in the pack, the per-lane vectors follow.  The f32
 // validation mode reads fragments from global/L2.
@@ -644,24 +556,19 @@ __device__ __forceinline__ void embed_tangent(float* gh, const float (&d)[32], c
 
 template <int PREC>
 __device__ __forceinline__ void radiance_hidden(float (&r1)[32], float (&r2)[32], const float (&rin)[16], const char* W,
-                                                const FieldLayout& L, int hi, const char* WM = nullptr,
-                                                const FieldLayout* LMp = nullptr) {
-  // W / L: per-lane vectors; WM / LM: matrix fragments when they live elsewhere (L2 instead of LDS)
-  const char* Wm = WM ? WM : W;
-  const FieldLayout& LM = LMp ? *LMp : L;
-  dense<PREC, 2, 1>(r1, Wm + LM.mat[M_R1], rin, false);
+                                                const FieldLayout& L, int hi) {
+  dense<PREC, 2, 1>(r1, W + L.mat[M_R1], rin, false);
 #pragma unroll
   for (int k = 0; k < 32; ++k) r1[k] = fmaxf(r1[k] + vecf(W, L, V_RB1, hi, k), 0.f);
-  dense<PREC, 2, 2>(r2, Wm + LM.mat[M_R2], r1, false);
+  dense<PREC, 2, 2>(r2, W + L.mat[M_R2], r1, false);
 #pragma unroll
   for (int k = 0; k < 32; ++k) r2[k] = fmaxf(r2[k] + vecf(W, L, V_RB2, hi, k), 0.f);
 }
 
-// MODE 3: MODE 1 on features / dh-dx planes already gathered level-major by k_lotd_gather_lm<., true> (training).
-// MODE 0: sdf only; MODE 1: sdf + nablas (+ rgb); MODE 2: backward of the SDF branch (gradient w.r.t. grid and
-// decoder weights given dL/dsdf and the TOTAL dL/dnablas, which already includes the radiance net's share).
+// Forward with normals (+ radiance).  MODE 1: gathers the table itself, point-major (queries outside the training step, <= 16
+// levels); MODE 3: on features / dh-dx planes already gathered level-major by k_lotd_gather_lm<., true> (training).
 // NC: 16-level feature chunks of the decoder input (2 for pyramids of 17..32 levels -- the first layer contracts over
-// 64 features; only on the level-major planes, MODE 2 / 3).
+// 64 features; only on the level-major planes, MODE 3).
 // GL2 (MODE 3, NC == 2): the plane image of a tile (1 KB per level of the pyramid) is prefetched into LDS as in the
 // 16-level kernel -- possible while weights + 4 images fit the 160 KB (pyramids of up to 23 levels: the street's 19).
 // NE (MODE 3): 32-input chunks of the embedded-position block behind the feature chunks (0 | 2: NsimFieldMeta.embed_E > 0);
@@ -675,41 +582,13 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES) k_field(FieldArgs a) {
   const float beta = a.beta, inv_beta = 1.0f / a.beta;
   FieldLayout L;
   int wbytes = 0;
-  // fp16 backward: every wave owns a private copy of the weight-gradient accumulators in LDS (plain read-add-write;
-  // LDS float atomics cost ~800 cycles per instruction) and reads the weight fragments from L2 instead of LDS to
-  // make room for the four copies; the f32 validation mode keeps one shared accumulator with atomics.
-  constexpr bool PRIV = (MODE == 2 && PREC == 0);
-  constexpr bool FWD = (MODE == 1 || MODE == 3);          // forward with normals (+ radiance)
-  constexpr bool FROM_PLANES = (MODE == 2 || MODE == 3);  // h / dh-dx come from the level-major planes
+  static_assert(MODE == 1 || MODE == 3, "k_field is the forward; the SDF-branch backward is k_field_bwd_j / k_field_bwd_h");
+  constexpr bool FROM_PLANES = (MODE == 3);  // h / dh-dx come from the level-major planes
   static_assert(NC == 1 || FROM_PLANES, "more than 16 levels: level-major planes only");
   static_assert(NE == 0 || (MODE == 3 && !GL2), "the embedded-position block: forward on the planes (backward: k_field_bwd_j)");
   constexpr int NI = NC + NE;      // 32-input chunks of the first layer
-  // NC == 2: a private accumulator copy is 34 KB -> three waves per workgroup fit the 160 KB of LDS
-  constexpr int NW = (PRIV && NC == 2) ? 3 : FIELD_WAVES;
-  // W / L: per-lane vectors (always LDS in fp16 mode); WM / LM: matrix fragments (LDS, or L2 when PRIV)
-  // MODE 0 / 2 touch only the SDF decoder (W1, W2, W2T, W1T); MODE 1 also the radiance matrices
-  const char* W = stage_weights<PREC>(smem, a, 0, PRIV ? 0 : (FWD ? (NE ? M_R3 + 1 : M_COUNT) : 4), L, wbytes);
-  const char* WM = PRIV ? a.wpack : W;
-  const FieldLayout LM = PRIV ? a.lay : L;
-
-  float* accum = nullptr;
-  char* stA = nullptr;
-  char* stB = nullptr;
-  const AccOff AO = acc_off(NC);
-  constexpr int ACC_BYTES = (((6400 + 2048 * (NC - 1)) * 4 + 15) & ~15);      // >= AO.total floats, one copy
-  if constexpr (MODE == 2) {
-    const int ncopies = PRIV ? NW : 1;
-    accum = reinterpret_cast<float*>(smem + wbytes + (PRIV ? wave * ACC_BYTES : 0));
-    char* stbase = smem + wbytes + ncopies * ACC_BYTES + wave * stage_bytes_per_wave<PREC>();
-    stA = stbase;
-    stB = stbase + stage_bytes_per_wave<PREC>() / 2;
-    if constexpr (PRIV) {
-      for (int i = lane; i < AO.total; i += 64) accum[i] = 0.f;
-    } else {
-      for (int i = threadIdx.x; i < AO.total; i += blockDim.x) accum[i] = 0.f;
-    }
-    __syncthreads();
-  }
+  // matrices (NE: the forward ones only) and per-lane vectors: LDS in fp16 mode
+  const char* W = stage_weights<PREC>(smem, a, 0, NE ? M_R3 + 1 : M_COUNT, L, wbytes);
   const float b_out = reinterpret_cast<const float*>(W + L.vec[V_SCAL])[0];
   const GridRef gref = grid_ref(a.grid);
 
@@ -718,19 +597,19 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES) k_field(FieldArgs a) {
     a.S = sd <= a.S ? sd : 0;
   }
   const int64_t ntiles = (a.S + 31) / 32;
-  const int64_t wstride = (int64_t)gridDim.x * NW;
+  const int64_t wstride = (int64_t)gridDim.x * FIELD_WAVES;
   // MODE 3, <= 16 levels: the planes of the NEXT tile (16 KB: per level 256 B of h and 768 B of dh/dx, each one aligned
   // piece thanks to the 32-point pitch) are copied global -> LDS by 16 global_load_lds_dwordx4 while this tile computes;
   // half of a tile used to be the wait for these reads (all workgroups burst together at one wave per SIMD).
   static_assert(!GL2 || (MODE == 3 && NC == 2), "GL2 is the 17..32-level forward");
   constexpr bool GLDS = (MODE == 3 && (NC == 1 || GL2) && NE == 0);
   const int nlv = a.lotd.num_levels;      // plane levels past it are neither written by the gather nor read here
-  // JDIR (<= 16 levels, NSIM_FWD_JDIRECT): the LDS image holds the FEATURES only (4 KB per wave, 4 copies of 4 levels each);
+  // JDIR (<= 16 levels): the LDS image holds the FEATURES only (4 KB per wave, 4 copies of 4 levels each);
   // dh/dx -- consumed once, at the very end of the tile -- is loaded straight into registers after the image has been
   // read, so its latency hides behind the decoder.  LDS per workgroup 124 KB -> 76 KB: TWO workgroups per CU, two waves per
   // SIMD (the registers, 244 of 512, already allowed it).
-  constexpr bool JDIR = GLDS && NC == 1 && NSIM_FWD_JDIRECT;
-  char* pf = GLDS ? smem + wbytes + wave * (NC == 1 ? (JDIR ? 4096 : 16384) : 1024 * nlv) : nullptr;
+  constexpr bool JDIR = GLDS && NC == 1;
+  char* pf = GLDS ? smem + wbytes + wave * (NC == 1 ? 4096 : 1024 * nlv) : nullptr;
   auto prefetch_planes = [&](int64_t tile_n) {
     const int64_t s0 = tile_n * 32;
     if constexpr (JDIR) {
@@ -750,19 +629,14 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES) k_field(FieldArgs a) {
     }
   };
   if constexpr (GLDS) {
-    const int64_t t0 = (int64_t)blockIdx.x * NW + wave;
+    const int64_t t0 = (int64_t)blockIdx.x * FIELD_WAVES + wave;
     if (t0 < ntiles) prefetch_planes(t0);
   }
-  for (int64_t tile = (int64_t)blockIdx.x * NW + wave; tile < ntiles; tile += wstride) {
-    const int64_t grp = tile / NW;      // (stamps of -DNSIM_KTIME builds: the wave-0 tile sequence of this workgroup)
-    (void)grp;
-    if constexpr (MODE == 2) { KT(1, 0); }
-    if constexpr (MODE == 3) { KT(2, 0); }
+  for (int64_t tile = (int64_t)blockIdx.x * FIELD_WAVES + wave; tile < ntiles; tile += wstride) {
     // JDIR: the point's position / ray / direction (needed by the radiance head only) are requested AFTER the wait for the plane
     // image below -- in front of it that s_waitcnt vmcnt(0) exposed their (dependent: ridx -> rays) latency at the top of every tile
-    constexpr bool JDIR_ = (MODE == 3 && NC == 1 && NE == 0 && NSIM_FWD_JDIRECT);
     TilePoint p;
-    if constexpr (!JDIR_) p = load_point(a, tile, j, FWD);
+    if constexpr (!JDIR) p = load_point(a, tile, j, true);
     const int64_t s = tile * 32 + j;
     const bool valid = s < a.S;
     // ---------------------------------------------------------------- gather (8 of 16 levels per lane)
@@ -772,8 +646,7 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES) k_field(FieldArgs a) {
     float h[16 * NI];                               // [features (16 NC) | embedded position (16 NE)]
     float J[((NC == 1 && NE == 0) || GL2) ? 16 * NC : 1][3];     // NC == 2 without the LDS image (and NE: registers) re-reads dh/dx where it is consumed
     float ed[NE ? 32 : 1];                          // NE: x-derivative of the embedded-position inputs (own axis)
-    constexpr bool JPK = JDIR && NSIM_FWD_JPACKED;
-    JPair<JT> Jq[JPK ? 8 : 1][3];                   // JPK: this lane's (level, point) entries as stored
+    JPair<JT> Jq[JDIR ? 8 : 1][3];                  // JDIR: this lane's (level, point) entries as stored
     if constexpr (JDIR) {
       nsim_wait_vm0();                          // this tile's image has landed
 #pragma unroll
@@ -786,7 +659,7 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES) k_field(FieldArgs a) {
           h[r0 + 1] = valid ? hp[1] : 0.f;
         }
       nsim_wait_lgkm0();                        // every lane has read the image: the next copy may overwrite it
-      p = load_point(a, tile, j, FWD);
+      p = load_point(a, tile, j, true);
       // dh/dx of a point past the end: the last point's (finite values; nothing of such a lane is stored)
       const int64_t sc = valid ? s : a.S - 1;
 #pragma unroll
@@ -794,14 +667,11 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES) k_field(FieldArgs a) {
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
           const int l = 4 * q + 2 * hi + b, r0 = 4 * q + 2 * b;
-          if constexpr (JPK) {      // held as stored -- three packed pairs -- until the normals are formed after the decoder: 24 registers in f16
-            const JPair<JT>* jp = reinterpret_cast<const JPair<JT>*>(reinterpret_cast<const JT*>(a.J_pl) + ((int64_t)l * a.PS + sc) * 6);
-            Jq[2 * q + b][0] = jp[0];
-            Jq[2 * q + b][1] = jp[1];
-            Jq[2 * q + b][2] = jp[2];
-          } else {
-            jload6(reinterpret_cast<const JT*>(a.J_pl) + ((int64_t)l * a.PS + sc) * 6, J[r0], J[r0 + 1]);
-          }
+          // held as stored -- three packed pairs -- until the normals are formed after the decoder: 24 registers in f16
+          const JPair<JT>* jp = reinterpret_cast<const JPair<JT>*>(reinterpret_cast<const JT*>(a.J_pl) + ((int64_t)l * a.PS + sc) * 6);
+          Jq[2 * q + b][0] = jp[0];
+          Jq[2 * q + b][1] = jp[1];
+          Jq[2 * q + b][2] = jp[2];
         }
       if (tile + wstride < ntiles) prefetch_planes(tile + wstride);
     } else if constexpr (GLDS) {
@@ -882,45 +752,39 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES) k_field(FieldArgs a) {
             lotd_load2(gref, (uint32_t)a.lotd.offset[l] + p.goff + 2u * idx, g0, g1);
             f0 = f0 + w * g0;
             f1 = f1 + w * g1;
-            if (MODE >= 1) {
 #pragma unroll
-              for (int c3 = 0; c3 < 3; ++c3) {
-                j0[c3] = j0[c3] + dw[c3] * g0;
-                j1[c3] = j1[c3] + dw[c3] * g1;
-              }
+            for (int c3 = 0; c3 < 3; ++c3) {
+              j0[c3] = j0[c3] + dw[c3] * g0;
+              j1[c3] = j1[c3] + dw[c3] * g1;
             }
           }
           const int r0 = 4 * q + 2 * b;
           h[r0] = f0;
           h[r0 + 1] = f1;
-          if (MODE >= 1) {
 #pragma unroll
-            for (int c3 = 0; c3 < 3; ++c3) {
-              J[r0][c3] = j0[c3] * c.dscale[c3];
-              J[r0 + 1][c3] = j1[c3] * c.dscale[c3];
-            }
-            if (a.h_pl && valid) {
-              float* hp = a.h_pl + ((int64_t)l * a.PS + s) * 2;
-              JT* jp = reinterpret_cast<JT*>(a.J_pl) + ((int64_t)l * a.PS + s) * 6;
-              hp[0] = f0;
-              hp[1] = f1;
-              jstore6(jp, J[r0], J[r0 + 1]);
-            }
+          for (int c3 = 0; c3 < 3; ++c3) {
+            J[r0][c3] = j0[c3] * c.dscale[c3];
+            J[r0 + 1][c3] = j1[c3] * c.dscale[c3];
+          }
+          if (a.h_pl && valid) {
+            float* hp = a.h_pl + ((int64_t)l * a.PS + s) * 2;
+            JT* jp = reinterpret_cast<JT*>(a.J_pl) + ((int64_t)l * a.PS + s) * 6;
+            hp[0] = f0;
+            hp[1] = f1;
+            jstore6(jp, J[r0], J[r0 + 1]);
           }
         }
       }
     }
     if constexpr (NE > 0) embed_eval(a, p.xx, valid, hi, reinterpret_cast<float(&)[32]>(h[16 * NC]), ed);
-    if constexpr (MODE == 2) { KT(1, 1); }
-    if constexpr (MODE == 3) { KT(2, 1); }
     // ---------------------------------------------------------------- SDF decoder forward
     float a1[32];
-    dense<PREC, 2, NI>(a1, WM + LM.mat[M_W1], h, true);
+    dense<PREC, 2, NI>(a1, W + L.mat[M_W1], h, true);
 #pragma unroll
     for (int k = 0; k < 32; ++k) a1[k] = softplus_b(a1[k] + vecf(W, L, V_B1, hi, k), beta, inv_beta);
     float a2[32];  // last hidden activation (== a1 when SDF_D == 1)
     if constexpr (SDF_D == 2) {
-      dense<PREC, 2, 2>(a2, WM + LM.mat[M_W2], a1, false);
+      dense<PREC, 2, 2>(a2, W + L.mat[M_W2], a1, false);
 #pragma unroll
       for (int k = 0; k < 32; ++k) a2[k] = softplus_b(a2[k] + vecf(W, L, V_B2, hi, k), beta, inv_beta);
     } else {
@@ -932,11 +796,6 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES) k_field(FieldArgs a) {
     for (int k = 0; k < 32; ++k) sdf = sdf + vecf(W, L, V_WH, hi, k) * a2[k];
     sdf = sdf + wave_shfl_xor(sdf, 32);
     sdf = sdf + b_out;
-    if constexpr (MODE == 0) {
-      if (valid && hi == 0) a.sdf[s] = sdf;
-      continue;
-    }
-    if constexpr (MODE == 3) { KT(2, 2); }
     // ---------------------------------------------------------------- d sdf / d h  (the "g chain")
     float e1[32];  // d sdf / d a1  (only SDF_D == 2)
     float d1[32];  // d sdf / d z1
@@ -944,7 +803,7 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES) k_field(FieldArgs a) {
       float d2[32];
 #pragma unroll
       for (int k = 0; k < 32; ++k) d2[k] = sig_from_softplus(a2[k], beta) * vecf(W, L, V_WH, hi, k);
-      dense<PREC, 2, 2>(e1, WM + LM.mat[M_W2T], d2, false);
+      dense<PREC, 2, 2>(e1, W + L.mat[M_W2T], d2, false);
 #pragma unroll
       for (int k = 0; k < 32; ++k) d1[k] = sig_from_softplus(a1[k], beta) * e1[k];
     } else {
@@ -955,100 +814,30 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES) k_field(FieldArgs a) {
       }
     }
     float g[16 * NI];
-    dense<PREC, NI, 2>(g, WM + LM.mat[M_W1T], d1, false);
-    if constexpr (FWD) {
-      if constexpr (MODE == 3) { KT(2, 3); }
-      float nab[3];
-      if constexpr (JPK) {
-        float acc[3] = {0.f, 0.f, 0.f};
+    dense<PREC, NI, 2>(g, W + L.mat[M_W1T], d1, false);
+    float nab[3];
+    if constexpr (JDIR) {
+      float acc[3] = {0.f, 0.f, 0.f};
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {      // entry e = 2 q + b: features r0 = 4 q + 2 b (d f0 / dx) and r0 + 1 (d f1 / dx)
-          const int r0 = 4 * (e >> 1) + 2 * (e & 1);
-          acc[0] = acc[0] + g[r0] * (float)Jq[e][0].x + g[r0 + 1] * (float)Jq[e][1].y;
-          acc[1] = acc[1] + g[r0] * (float)Jq[e][0].y + g[r0 + 1] * (float)Jq[e][2].x;
-          acc[2] = acc[2] + g[r0] * (float)Jq[e][1].x + g[r0 + 1] * (float)Jq[e][2].y;
-        }
-#pragma unroll
-        for (int c3 = 0; c3 < 3; ++c3) nab[c3] = acc[c3] + wave_shfl_xor(acc[c3], 32);
-      } else if constexpr ((NC == 1 && NE == 0) || GL2) {
-#pragma unroll
-        for (int c3 = 0; c3 < 3; ++c3) {
-          float acc = 0.f;
-#pragma unroll
-          for (int f = 0; f < 16 * NC; ++f) acc = acc + g[f] * J[f][c3];
-          nab[c3] = acc + wave_shfl_xor(acc, 32);
-        }
-      } else {
-        float acc[3] = {0.f, 0.f, 0.f};
-        if (valid) {
-#pragma unroll
-          for (int m = 0; m < NC; ++m)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-              for (int b = 0; b < 2; ++b) {
-                const int l = 16 * m + 4 * q + 2 * hi + b;
-                const int r0 = 16 * m + 4 * q + 2 * b;
-                if (!LV_OK(l)) continue;
-                float ja[3], jb[3];
-                jload6(reinterpret_cast<const JT*>(a.J_pl) + ((int64_t)l * a.PS + s) * 6, ja, jb);
-#pragma unroll
-                for (int c3 = 0; c3 < 3; ++c3) acc[c3] = acc[c3] + g[r0] * ja[c3] + g[r0 + 1] * jb[c3];
-              }
-        }
-#pragma unroll
-        for (int c3 = 0; c3 < 3; ++c3) nab[c3] = acc[c3] + wave_shfl_xor(acc[c3], 32);
+      for (int e = 0; e < 8; ++e) {      // entry e = 2 q + b: features r0 = 4 q + 2 b (d f0 / dx) and r0 + 1 (d f1 / dx)
+        const int r0 = 4 * (e >> 1) + 2 * (e & 1);
+        acc[0] = acc[0] + g[r0] * (float)Jq[e][0].x + g[r0 + 1] * (float)Jq[e][1].y;
+        acc[1] = acc[1] + g[r0] * (float)Jq[e][0].y + g[r0 + 1] * (float)Jq[e][2].x;
+        acc[2] = acc[2] + g[r0] * (float)Jq[e][1].x + g[r0 + 1] * (float)Jq[e][2].y;
       }
-      if constexpr (NE > 0) {      // the normals' share through the embedded position's own x-derivative
-        float ea[3] = {0.f, 0.f, 0.f};
-        embed_nablas(&g[16 * NC], ed, hi, ea);
 #pragma unroll
-        for (int c3 = 0; c3 < 3; ++c3) nab[c3] = nab[c3] + (ea[c3] + wave_shfl_xor(ea[c3], 32));
+      for (int c3 = 0; c3 < 3; ++c3) nab[c3] = acc[c3] + wave_shfl_xor(acc[c3], 32);
+    } else if constexpr ((NC == 1 && NE == 0) || GL2) {
+#pragma unroll
+      for (int c3 = 0; c3 < 3; ++c3) {
+        float acc = 0.f;
+#pragma unroll
+        for (int f = 0; f < 16 * NC; ++f) acc = acc + g[f] * J[f][c3];
+        nab[c3] = acc + wave_shfl_xor(acc, 32);
       }
-      if constexpr (MODE == 3) { KT(2, 4); }
-      float rgbv[3] = {0.f, 0.f, 0.f};
-      if (a.has_rgb) {
-        float rin[16], r1[32], r2[32];
-        make_rin(rin, p, nab, a.h_appear, hi);
-        radiance_hidden<PREC>(r1, r2, rin, W, L, hi);
-        float o3[16];
-        dense<PREC, 1, 2>(o3, WM + LM.mat[M_R3], r2, false);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {  // rows 0..2 live on the hi == 0 half in registers 0..2
-          const float v = o3[c] + vecf(W, L, V_RB3, hi, c);
-          rgbv[c] = 1.0f / (1.0f + nsim_fast_exp(-v));
-        }
-      }
-      if constexpr (MODE == 3) { KT(2, 5); }
-      if (valid && hi == 0) {
-        a.sdf[s] = sdf;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) a.nablas[3 * s + c] = nab[c];
-        if (a.has_rgb && a.rgb) {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) a.rgb[3 * s + c] = rgbv[c];
-        }
-      }
-      if constexpr (MODE == 3) { KT(2, 6); KT(2, 17); }
-      continue;
-    }
-    // ======================================================================================= backward
-    if constexpr (MODE == 2) {
-      KT(1, 2);
-      float gs = 0.f, gn[3] = {0.f, 0.f, 0.f};
+    } else {
+      float acc[3] = {0.f, 0.f, 0.f};
       if (valid) {
-        if (a.dsdf) gs = a.dsdf[s];
-        if (a.dnablas) {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) gn[c] = a.dnablas[3 * s + c];
-        }
-      }
-      // ------------------------------------------------------------ second-order path through the normals
-      float gh[16 * NC];  // dL / dg
-      if constexpr (NC == 1) {
-#pragma unroll
-        for (int f = 0; f < 16; ++f) gh[f] = J[f][0] * gn[0] + J[f][1] * gn[1] + J[f][2] * gn[2];
-      } else {
 #pragma unroll
         for (int m = 0; m < NC; ++m)
 #pragma unroll
@@ -1057,174 +846,59 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES) k_field(FieldArgs a) {
             for (int b = 0; b < 2; ++b) {
               const int l = 16 * m + 4 * q + 2 * hi + b;
               const int r0 = 16 * m + 4 * q + 2 * b;
-              gh[r0] = gh[r0 + 1] = 0.f;
-              if (valid && LV_OK(l)) {
-                float ja[3], jb[3];
-                jload6(reinterpret_cast<const JT*>(a.J_pl) + ((int64_t)l * a.PS + s) * 6, ja, jb);
-                gh[r0] = ja[0] * gn[0] + ja[1] * gn[1] + ja[2] * gn[2];
-                gh[r0 + 1] = jb[0] * gn[0] + jb[1] * gn[1] + jb[2] * gn[2];
-              }
+              if (!LV_OK(l)) continue;
+              float ja[3], jb[3];
+              jload6(reinterpret_cast<const JT*>(a.J_pl) + ((int64_t)l * a.PS + s) * 6, ja, jb);
+#pragma unroll
+              for (int c3 = 0; c3 < 3; ++c3) acc[c3] = acc[c3] + g[r0] * ja[c3] + g[r0 + 1] * jb[c3];
             }
       }
-      KT(1, 3);
-      float dh1[32];  // dL / d d1  = W1 . gh
-      dense<PREC, 2, NC>(dh1, WM + LM.mat[M_W1], gh, true);
-      KT(1, 4);
-      const bool do_dw = !(a.ablate & 4);
-      if (do_dw) dw_product<PREC, 2, NC, PRIV>(stA, stB, d1, gh, accum + AO.w1, 32 * NC, 64, 32 * NC, nullptr);
-      KT(1, 5);
-      float dz1[32];
-      float whv[32];  // vector-shaped gradient of the SDF head weights
-      if constexpr (SDF_D == 2) {
-        float eh1[32];  // dL / d e1
 #pragma unroll
-        for (int k = 0; k < 32; ++k) {
-          const float s1 = sig_from_softplus(a1[k], beta);
-          dz1[k] = dh1[k] * e1[k] * (beta * s1 * (1.0f - s1));
-          eh1[k] = dh1[k] * s1;
-        }
-        float d2[32];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) d2[k] = sig_from_softplus(a2[k], beta) * vecf(W, L, V_WH, hi, k);
-        KT(1, 6);
-        if (do_dw) dw_product<PREC, 2, 2, PRIV>(stA, stB, d2, eh1, accum + AO.w2, 64, 64, 64, nullptr);
-        KT(1, 7);
-        float dh2[32];  // dL / d d2 = W2 . eh1
-        dense<PREC, 2, 2>(dh2, WM + LM.mat[M_W2], eh1, true);
-        float dz2[32];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) {
-          const float s2 = sig_from_softplus(a2[k], beta);
-          const float wh = vecf(W, L, V_WH, hi, k);
-          whv[k] = dh2[k] * s2 + gs * a2[k];
-          dz2[k] = gs * wh * s2 + dh2[k] * wh * (beta * s2 * (1.0f - s2));
-        }
-        KT(1, 8);
-        if (do_dw) dw_product<PREC, 2, 2, PRIV>(stA, stB, dz2, a1, accum + AO.w2, 64, 64, 64, accum + AO.b2);
-        KT(1, 9);
-        float da1[32];
-        dense<PREC, 2, 2>(da1, WM + LM.mat[M_W2T], dz2, true);
-        KT(1, 10);
-#pragma unroll
-        for (int k = 0; k < 32; ++k) dz1[k] = dz1[k] + da1[k] * sig_from_softplus(a1[k], beta);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 32; ++k) {
-          const float s1 = sig_from_softplus(a1[k], beta);
-          const float wh = vecf(W, L, V_WH, hi, k);
-          whv[k] = dh1[k] * s1 + gs * a1[k];
-          dz1[k] = gs * wh * s1 + dh1[k] * wh * (beta * s1 * (1.0f - s1));
-        }
-      }
-      KT(1, 11);
-      if (do_dw) rowsum_acc<PREC, 2, PRIV>(stA, whv, accum + AO.wh, 64);
-      KT(1, 12);
-      {
-        float v = (hi == 0) ? gs : 0.f;
-        v = wave_sum(v);
-        if (lane == 0 && v != 0.f) {
-          if constexpr (PRIV) accum[AO.bh] = accum[AO.bh] + v;
-          else atomicAdd(&accum[AO.bh], v);
-        }
-      }
-      if (do_dw) dw_product<PREC, 2, NC, PRIV>(stA, stB, dz1, h, accum + AO.w1, 32 * NC, 64, 32 * NC, accum + AO.b1);
-      KT(1, 13);
-      float dh[16 * NC];
-      dense<PREC, NC, 2>(dh, WM + LM.mat[M_W1T], dz1, true);
-      KT(1, 14);
-      if (a.dx) {   // pose refinement: dL/dx += (dh/dx)^T dL/dh  (dh/dx re-read from the planes: this path is rare)
-        float acc[3] = {0.f, 0.f, 0.f};
-        if (valid) {
-#pragma unroll
-          for (int m = 0; m < NC; ++m)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-              for (int b = 0; b < 2; ++b) {
-                const int l = 16 * m + 4 * q + 2 * hi + b;
-                const int r0 = 16 * m + 4 * q + 2 * b;
-                if (!LV_OK(l)) continue;
-                float ja[3], jb[3];
-                jload6(reinterpret_cast<const JT*>(a.J_pl) + ((int64_t)l * a.PS + s) * 6, ja, jb);
-#pragma unroll
-                for (int c3 = 0; c3 < 3; ++c3) acc[c3] = acc[c3] + dh[r0] * ja[c3] + dh[r0 + 1] * jb[c3];
-              }
-        }
-#pragma unroll
-        for (int c3 = 0; c3 < 3; ++c3) acc[c3] = acc[c3] + wave_shfl_xor(acc[c3], 32);
-        if (valid && hi == 0) {
-#pragma unroll
-          for (int c3 = 0; c3 < 3; ++c3) a.dx[3 * s + c3] = a.dx[3 * s + c3] + acc[c3];
-        }
-      }
-      // ------------------------------------------------------------ hand-off to the scatter kernel
-      // dL/dh and g = d sdf/d h as level-major planes + the total dL/dnablas per sample; k_lotd_scatter turns
-      // them into grid gradients at full occupancy (it is bound by the atomic unit, not by this kernel's MFMA chain)
-      if (valid && a.dh_pl) {
-#pragma unroll
-        for (int m = 0; m < NC; ++m)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-#pragma unroll
-          for (int b = 0; b < 2; ++b) {
-            const int l = 16 * m + 4 * q + 2 * hi + b;
-            const int r0 = 16 * m + 4 * q + 2 * b;
-            if (!LV_OK(l)) continue;             // the scatter reads the planes of real levels only
-            float* dp = a.dh_pl + ((int64_t)l * a.S + s) * 2;
-            float* gp = a.g_pl + ((int64_t)l * a.S + s) * 2;
-            dp[0] = dh[r0];
-            dp[1] = dh[r0 + 1];
-            gp[0] = g[r0];
-            gp[1] = g[r0 + 1];
-          }
-        }
-      }
-      KT(1, 15);
-      KT(1, 16);
-      KT(1, 17);
+      for (int c3 = 0; c3 < 3; ++c3) nab[c3] = acc[c3] + wave_shfl_xor(acc[c3], 32);
     }
-  }
-
-  if constexpr (MODE == 2) {
-    __syncthreads();
-    const int F1 = 2 * a.lotd.num_levels;
-    const SrcOff so = src_off(SDF_D, F1);
-    for (int i = threadIdx.x; i < AO.total; i += blockDim.x) {
-      float v;
-      if constexpr (PRIV) {      // sum the four private copies
-        const float* a0 = reinterpret_cast<const float*>(smem + wbytes);
-        v = 0.f;
+    if constexpr (NE > 0) {      // the normals' share through the embedded position's own x-derivative
+      float ea[3] = {0.f, 0.f, 0.f};
+      embed_nablas(&g[16 * NC], ed, hi, ea);
 #pragma unroll
-        for (int w = 0; w < NW; ++w) v += a0[w * (ACC_BYTES / 4) + i];
-      } else {
-        v = accum[i];
+      for (int c3 = 0; c3 < 3; ++c3) nab[c3] = nab[c3] + (ea[c3] + wave_shfl_xor(ea[c3], 32));
+    }
+    float rgbv[3] = {0.f, 0.f, 0.f};
+    if (a.has_rgb) {
+      float rin[16], r1[32], r2[32];
+      make_rin(rin, p, nab, a.h_appear, hi);
+      radiance_hidden<PREC>(r1, r2, rin, W, L, hi);
+      float o3[16];
+      dense<PREC, 1, 2>(o3, W + L.mat[M_R3], r2, false);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {  // rows 0..2 live on the hi == 0 half in registers 0..2
+        const float v = o3[c] + vecf(W, L, V_RB3, hi, c);
+        rgbv[c] = 1.0f / (1.0f + nsim_fast_exp(-v));
       }
-      if (v == 0.f) continue;
-      float* dst = nullptr;
-      if (i < AO.w2) {           // accumulator rows are 32 NC wide, the parameter rows F1 (<= 32 NC) wide
-        const int row = (i - AO.w1) / (32 * NC), col = (i - AO.w1) % (32 * NC);
-        dst = col < F1 ? a.dsdf_w + so.w1 + row * F1 + col : nullptr;
-      } else if (i < AO.wh) dst = (SDF_D == 2) ? a.dsdf_w + so.w2 + (i - AO.w2) : nullptr;
-      else if (i < AO.b1) dst = a.dsdf_w + so.wh + (i - AO.wh);
-      else if (i < AO.b2) dst = a.dsdf_b + so.b1 + (i - AO.b1);
-      else if (i < AO.bh) dst = (SDF_D == 2) ? a.dsdf_b + so.b2 + (i - AO.b2) : nullptr;
-      else dst = (i == AO.bh) ? a.dsdf_b + so.bh : nullptr;
-      if (dst) atomicAdd(dst, v);
+    }
+    if (valid && hi == 0) {
+      a.sdf[s] = sdf;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) a.nablas[3 * s + c] = nab[c];
+      if (a.has_rgb && a.rgb) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a.rgb[3 * s + c] = rgbv[c];
+      }
     }
   }
 }
 
-// Backward of the SDF branch (the work of k_field<., ., 2>) with workgroup-joint weight gradients (mfma_mlp.h): per group of
+// Backward of the SDF branch (gradient w.r.t. the decoder weights, and dL/dh + g = d sdf / d h as planes for the table scatter, given
+// dL/dsdf and the TOTAL dL/dnablas, which already includes the radiance net's share) with workgroup-joint weight gradients (mfma_mlp.h): per group of
 // 4 x 32 points the waves stage the operands of the four weight-gradient products side by side; wave w owns the dW2 tile
 // (w >> 1, w & 1) and the dW1 tile w & 1 over the point half w >> 1, both in MFMA accumulator registers for the whole
 // launch; bias / head-weight sums are one register each.  LDS: W1, W2, W2T, W1T + vectors (26 KB) + staging 192 rows
-// (51 KB) = 77 KB -> two workgroups per CU.  J (dh/dx, 48 registers in k_field) is consumed straight from its loads
+// (51 KB) = 77 KB -> two workgroups per CU.  J (dh/dx) is consumed straight from its loads
 // into dL/dg, h is re-read for the last product, g leaves for the scatter as soon as it exists: the live set fits
-// 256 registers = two waves per SIMD (k_field<0,2,2>: 468 registers, 145 KB LDS -> one wave per SIMD).
+// 256 registers = two waves per SIMD (the per-wave LDS accumulators it replaced: 468 registers, 145 KB LDS -> one wave per SIMD).
 // NC = 2 (17..32 levels, the street pyramids): the first layer contracts over two 16-level chunks, dW1 is 64 x 64 -> wave w
 // owns its tile (w >> 1, w & 1) over all 128 points like dW2; h / dL/dg / g / dL/dh are 32 wide; dh/dx is consumed
 // straight from its loads (never held: 96 registers), the next group's features are prefetched into registers (the LDS
-// image of a 32-level tile would be 32 KB per wave).  Round 3: k_field<0,1,2,2> 1.76 ms -> this kernel on the street step.
+// image of a 32-level tile would be 32 KB per wave).  Round 3: the per-wave-accumulator kernel 1.76 ms -> this kernel on the street step.
 // NE = 2 (NsimFieldMeta.embed_E > 0): the embedded-position block as two more 32-input chunks of the first layer -- its values
 // and x-derivative are regenerated from the sample positions, its columns of dW1 are more accumulator tiles (column tiles are
 // dealt in PAIRS: wave w owns tile (w >> 1, 2 p + (w & 1)) of pair p over all 128 points; an odd last column tile is split by point
@@ -1241,21 +915,19 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES) k_field_bwd_j(FieldArgs a) {
   const float beta = a.beta, inv_beta = 1.0f / a.beta;
   FieldLayout L;
   int wbytes = 0;
-  { const int64_t grp = -1; KT(1, 23); }
   const char* W = stage_weights<PREC>(smem, a, 0, 4, L, wbytes);
-  // Staging set = A (64 rows) + B (32 NI, at least 64) + C (64).  DB (fp16 mode without the embedded block: LDS allows it): TWO sets
-  // used alternately by the group's weight-gradient products, so only the barrier between a product's writers and its readers
-  // remains -- the set a product writes was last read two products ago, and every wave passed the barrier in between after
-  // its reads (8 -> 4 barriers per group of 128 points; at one wave per SIMD a barrier costs the waves' drift).
-  constexpr bool DB = NSIM_BWD_DBUF && PREC == 0 && NE == 0 && (NC == 2 || NSIM_BWD_JDIRECT);
+  // Staging set = A (64 rows) + B (32 NI, at least 64) + C (64), one barrier in front of every product's writers and one behind.
+  // (Two alternating sets -- 4 instead of 8 barriers per group -- measured null at +36 registers: nsim_field_bwd_sdf 0.1208 vs
+  // 0.1210 ms, street 0.6419 vs 0.6418; the barriers are not where the kernel's time goes.)
   constexpr int SET_ROWS = 128 + (NI > 2 ? 32 * NI : 64);
   char* const st0 = smem + wbytes;
-  auto set_base = [&](int k) -> char* { return st0 + (DB ? (k & 1) * SET_ROWS * jstage_row_bytes<PREC>() : 0); };
   char* stA = st0;
   char* stB = stA + 64 * jstage_row_bytes<PREC>();
   char* stC = stB + (NI > 2 ? 32 * NI : 64) * jstage_row_bytes<PREC>();
-  auto use_set = [&](int k) {
-    stA = set_base(k);
+  // (re-derived in front of every product, as when two sets alternated: spelled as constants, the compiler folds the staging
+  // address arithmetic differently and the f32 forms of this kernel spill up to 9 more registers)
+  auto restage = [&]() {
+    stA = st0;
     stB = stA + 64 * jstage_row_bytes<PREC>();
     stC = stB + (NI > 2 ? 32 * NI : 64) * jstage_row_bytes<PREC>();
   };
@@ -1276,7 +948,6 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES) k_field_bwd_j(FieldArgs a) {
 
   const int64_t ntiles = (a.S + 31) / 32;
   const int64_t ngroups = (ntiles + JOINT_WAVES - 1) / JOINT_WAVES;
-  { const int64_t grp = -1; KT(1, 20); }
   // Software pipeline over the plane reads (512 B per point, the only bulk HBM traffic of this kernel): the features of
   // the NEXT group are requested while this group computes, and dh/dx -- needed only after the recomputed forward -- is
   // requested before it, so that the bursts of all workgroups no longer alternate with their compute phases.
@@ -1298,30 +969,18 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES) k_field_bwd_j(FieldArgs a) {
         }
       }
   };
-  // fp16 mode: the whole 16 KB plane image of a wave's NEXT tile (h and dh/dx) is copied global -> LDS while the group
-  // computes (as in k_field MODE 3); f32 validation mode (its f32 staging leaves no LDS for it) prefetches h into registers
+  // fp16 mode, <= 16 levels: the feature image of a wave's NEXT tile (4 KB: 4 copies of 4 levels each, 256 B per level) is copied
+  // global -> LDS while the group computes (as in k_field MODE 3); dh/dx -- consumed once, for dL/dg = J . gn, AFTER the recomputed
+  // forward -- is loaded as packed pairs straight from the planes at the top of a group: 24 registers (f16) instead of 48 converted
+  // floats live across the forward, no LDS round trip, the loads fly under the forward.  f32 validation mode (its f32 staging
+  // leaves no LDS for the image) prefetches h into registers.
   constexpr bool GLDS = (PREC == 0 && NC == 1 && NE == 0);
-  char* pf = GLDS ? st0 + (DB ? 2 : 1) * SET_ROWS * jstage_row_bytes<PREC>() + wave * (NSIM_BWD_JDIRECT ? 4096 : 16384) : nullptr;
-  // BJD: the image holds the FEATURES only (4 copies of 4 levels each, 256 B per level); dh/dx -- consumed once, for dL/dg = J . gn,
-  // AFTER the recomputed forward -- is loaded as packed pairs straight from the planes at the top of a group: 24 registers
-  // (f16) instead of 48 converted floats live across the forward, no LDS round trip, the loads fly under the forward
-  constexpr bool BJD = GLDS && NSIM_BWD_JDIRECT;
+  char* pf = GLDS ? st0 + SET_ROWS * jstage_row_bytes<PREC>() + wave * 4096 : nullptr;
   auto prefetch_planes = [&](int64_t tile_n) {
     const int64_t s0 = tile_n * 32;
-    if constexpr (BJD) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i)      // lanes 16 k .. 16 k + 15: the 256 B of level 4 i + k
-        nsim_glds16(a.h_pl + ((int64_t)(4 * i + (lane >> 4)) * a.PS + s0) * 2 + 4 * (lane & 15), pf + 1024 * i);
-      return;
-    }
-#pragma unroll
-    for (int l = 0; l < 16; ++l) {
-      // 16 bytes per lane: lanes 0..15 the 256 B of features, the next 48 (f32) | 24 (f16) lanes the tile's dh/dx
-      constexpr int JL = 16 / (int)sizeof(JT);      // dh/dx elements per lane
-      const void* src = lane < 16 ? (const void*)(a.h_pl + ((int64_t)l * a.PS + s0) * 2 + 4 * lane)
-                                  : (const void*)(reinterpret_cast<const JT*>(a.J_pl) + ((int64_t)l * a.PS + s0) * 6 + JL * (lane - 16));
-      if (lane < 16 + 192 / JL) nsim_glds16(src, pf + 1024 * l);
-    }
+    for (int i = 0; i < 4; ++i)      // lanes 16 k .. 16 k + 15: the 256 B of level 4 i + k
+      nsim_glds16(a.h_pl + ((int64_t)(4 * i + (lane >> 4)) * a.PS + s0) * 2 + 4 * (lane & 15), pf + 1024 * i);
   };
   float hn[16 * NC];
   if constexpr (GLDS) {
@@ -1331,7 +990,6 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES) k_field_bwd_j(FieldArgs a) {
     load_h_at(hn, ((int64_t)blockIdx.x * JOINT_WAVES + wave) * 32 + j);
   }
   for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
-    KT(1, 0);
     const int64_t s = (grp * JOINT_WAVES + wave) * 32 + j;      // past the end: an invalid point contributes zeros
     const bool valid = s < a.S;
     // the per-lane bias / head vectors are re-read from LDS where they are used: an address the compiler cannot prove
@@ -1348,13 +1006,13 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES) k_field_bwd_j(FieldArgs a) {
         }
       }
     };
-    // BJD: the upstream gradients are requested AFTER the wait for the plane image below -- issued in front of it, that
+    // GLDS: the upstream gradients are requested AFTER the wait for the plane image below -- issued in front of it, that
     // s_waitcnt vmcnt(0) exposed their full memory latency at the top of every group (s_memtime: 4.4 k of 27 k ticks per group)
-    if constexpr (!(PREC == 0 && NC == 1 && NE == 0 && NSIM_BWD_JDIRECT)) load_upstream();
+    if constexpr (!GLDS) load_upstream();
     // ---- dL/dg = J . gn (second-order path through the normals) and the features, from the level-major planes
     float h[16 * NI];                   // [features | embedded position]
-    float Jr[(NC == 1 && !BJD) ? 16 : 1][3];      // dh/dx of this group (NC == 2 / BJD: consumed straight from its loads, below)
-    JPair<JT> Jq[BJD ? 8 : 1][3];                 // BJD: the (level, point) entries of this lane as stored (three pairs each)
+    float Jr[(NC == 1 && !GLDS) ? 16 : 1][3];     // dh/dx of this group (NC == 2 / GLDS: consumed straight from its loads, below)
+    JPair<JT> Jq[GLDS ? 8 : 1][3];                // GLDS: the (level, point) entries of this lane as stored (three pairs each)
     float gh[16 * NI];                  // dL / dg = J . gn
     if constexpr (NE > 0) {             // the block's values and its tangent along dL/dnablas, from the sample position
       const TilePoint tp = load_point(a, grp * JOINT_WAVES + wave, j, false);
@@ -1362,7 +1020,7 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES) k_field_bwd_j(FieldArgs a) {
       embed_eval(a, tp.xx, valid, hi, reinterpret_cast<float(&)[32]>(h[16 * NC]), ed);
       embed_tangent(&gh[16 * NC], ed, gn, hi);
     }
-    if constexpr (BJD) {
+    if constexpr (GLDS) {
       nsim_wait_vm0();                          // this tile's feature image has landed
       const int64_t sc = valid ? s : a.S - 1;   // (a point past the end reads the last point's finite values; nothing of it is stored)
 #pragma unroll
@@ -1386,29 +1044,6 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES) k_field_bwd_j(FieldArgs a) {
           Jq[2 * q + b][1] = jp[1];
           Jq[2 * q + b][2] = jp[2];
         }
-      const int64_t tn = (grp + gridDim.x) * JOINT_WAVES + wave;
-      if (tn < ntiles) prefetch_planes(tn);
-    } else if constexpr (GLDS) {
-      nsim_wait_vm0();                          // this tile's image has landed
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-          const int l = 4 * q + 2 * hi + b, r0 = 4 * q + 2 * b;
-          const float* hp = reinterpret_cast<const float*>(pf + 1024 * l) + 2 * j;
-          const JT* jp = reinterpret_cast<const JT*>(pf + 1024 * l + 256) + 6 * j;
-          const bool lv = valid && LV_OK(l);
-          h[r0] = lv ? hp[0] : 0.f;
-          h[r0 + 1] = lv ? hp[1] : 0.f;
-          float ja[3], jb[3];
-          jload6(jp, ja, jb);
-#pragma unroll
-          for (int c3 = 0; c3 < 3; ++c3) {
-            Jr[r0][c3] = lv ? ja[c3] : 0.f;
-            Jr[r0 + 1][c3] = lv ? jb[c3] : 0.f;
-          }
-        }
-      nsim_wait_lgkm0();                        // every lane has read the image: the next copy may overwrite it
       const int64_t tn = (grp + gridDim.x) * JOINT_WAVES + wave;
       if (tn < ntiles) prefetch_planes(tn);
     } else if constexpr (NC == 2) {
@@ -1446,7 +1081,6 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES) k_field_bwd_j(FieldArgs a) {
         }
       load_h_at(hn, ((grp + gridDim.x) * JOINT_WAVES + wave) * 32 + j);      // next group's features (zeros past the end)
     }
-    KT(1, 1);
     // ---- decoder forward (recomputed) and d sdf / d h
     float a1[32];
     dense<PREC, 2, NI>(a1, W + L.mat[M_W1], h, true);
@@ -1490,7 +1124,7 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES) k_field_bwd_j(FieldArgs a) {
       }
     }
     // ======================================================================================= backward
-    if constexpr (BJD) {
+    if constexpr (GLDS) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) {      // entry e = 2 q + b holds features r0 = 4 q + 2 b (d f0 / dx) and r0 + 1 (d f1 / dx)
         const int r0 = 4 * (e >> 1) + 2 * (e & 1);
@@ -1503,18 +1137,14 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES) k_field_bwd_j(FieldArgs a) {
       for (int f = 0; f < 16; ++f) gh[f] = Jr[f][0] * gn[0] + Jr[f][1] * gn[1] + Jr[f][2] * gn[2];
     }
     // ---- dW1 += d1 (x) gh
-    KT(1, 2);
-    use_set(0);
-    if constexpr (!DB) __syncthreads();
-    KT(1, 3);                              // the previous group's readers of the staging areas are done
+    restage();
+    __syncthreads();                       // the previous group's readers of the staging areas are done
     jstage<PREC, 2, SP>(stA, d1, wave);
     jstage<PREC, NI, SP>(stB, gh, wave);
     __syncthreads();
     if (do_dw) dw1_tiles(stA, stB);
-    KT(1, 4);
     float dh1[32];  // dL / d d1 = W1 . gh
     dense<PREC, 2, NI>(dh1, W + L.mat[M_W1], gh, true);
-    KT(1, 5);
     float dz1[32], whv[32];
     if constexpr (SDF_D == 2) {
       float eh1[32];  // dL / d e1
@@ -1528,15 +1158,12 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES) k_field_bwd_j(FieldArgs a) {
 #pragma unroll
       for (int k = 0; k < 32; ++k) d2[k] = sig_from_softplus(a2[k], beta) * vecf(Wv, L, V_WH, hi, k);
       // ---- dW2 += d2 (x) eh1
-      KT(1, 6);
-      use_set(1);
-      if constexpr (!DB) __syncthreads();
-      KT(1, 7);
+      restage();
+      __syncthreads();
       jstage<PREC, 2, SP>(stA, d2, wave);
       jstage<PREC, 2, SP>(stB, eh1, wave);
       __syncthreads();
       if (do_dw) accW2 = jdw_tile<PREC>(stA, wave >> 1, stB, wave & 1, accW2);
-      KT(1, 8);
       float dh2[32];  // dL / d d2 = W2 . eh1
       dense<PREC, 2, 2>(dh2, W + L.mat[M_W2], eh1, true);
       float dz2[32];
@@ -1548,10 +1175,8 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES) k_field_bwd_j(FieldArgs a) {
         dz2[k] = gs * wh * s2 + dh2[k] * wh * (beta * s2 * (1.0f - s2));
       }
       // ---- dW2 += dz2 (x) a1, d b2 += rowsum(dz2), d wh += rowsum(whv)
-      KT(1, 9);
-      use_set(0);
-      if constexpr (!DB) __syncthreads();
-      KT(1, 10);
+      restage();
+      __syncthreads();
       jstage<PREC, 2, SP>(stA, dz2, wave);
       jstage<PREC, 2, SP>(stB, a1, wave);
       jstage<PREC, 2, SP>(stC, whv, wave);
@@ -1561,7 +1186,6 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES) k_field_bwd_j(FieldArgs a) {
         bs2 += jrow_sum<PREC>(stA, 64, wave);
         bsh += jrow_sum<PREC>(stC, 64, wave);
       }
-      KT(1, 11);
       float da1[32];
       dense<PREC, 2, 2>(da1, W + L.mat[M_W2T], dz2, true);
 #pragma unroll
@@ -1580,10 +1204,8 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES) k_field_bwd_j(FieldArgs a) {
       bh += wave_sum(v);
     }
     // ---- dW1 += dz1 (x) h, d b1 += rowsum(dz1)  (+ d wh when there is one hidden layer)
-    KT(1, 12);
-    use_set(1);
-    if constexpr (!DB) __syncthreads();
-    KT(1, 13);
+    restage();
+    __syncthreads();
     jstage<PREC, 2, SP>(stA, dz1, wave);
     jstage<PREC, NI, SP>(stB, h, wave);
     if constexpr (SDF_D == 1) jstage<PREC, 2, SP>(stC, whv, wave);
@@ -1593,10 +1215,8 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES) k_field_bwd_j(FieldArgs a) {
       bs1 += jrow_sum<PREC>(stA, 64, wave);
       if constexpr (SDF_D == 1) bsh += jrow_sum<PREC>(stC, 64, wave);
     }
-    KT(1, 14);
     float dh[16 * NC];
     dense<PREC, NC, 2>(dh, W + L.mat[M_W1T], dz1, true);
-    KT(1, 15);
     if (a.dx) {   // pose refinement: dL/dx += (dh/dx)^T dL/dh  (dh/dx re-read from the planes: this path is rare)
       float acc[3] = {0.f, 0.f, 0.f};
       if (valid) {
@@ -1635,10 +1255,7 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES) k_field_bwd_j(FieldArgs a) {
           dp[1] = dh[r0 + 1];
         }
     }
-    KT(1, 16);
-    KT(1, 17);
   }
-  { const int64_t grp = -1; KT(1, 21); }
   // ---- one flush per wave
   const int F1 = 2 * a.lotd.num_levels, FIN = F1 + (NE ? a.embed_E : 0);      // W1 rows: [features (F1) | embedded position]
   const SrcOff so = src_off(SDF_D, FIN);
@@ -1659,7 +1276,6 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES) k_field_bwd_j(FieldArgs a) {
   if (bs1 != 0.f) atomicAdd(&a.dsdf_b[ro + so.b1 + lane], bs1);
   if (bsh != 0.f) atomicAdd(&a.dsdf_w[ro + so.wh + lane], bsh);
   if (lane == 0 && bh != 0.f) atomicAdd(&a.dsdf_b[ro + so.bh], bh);
-  { const int64_t grp = -1; KT(1, 22); }
 }
 
 // ---------------------------------------------------------------------------------- 16-point tiles (mfma_mlp.h)
@@ -1960,9 +1576,6 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES, 2) k_field_bwd_h(FieldArgs a
 #ifndef NSIM_SDF_MIN_WAVES
 #define NSIM_SDF_MIN_WAVES 2
 #endif
-#ifndef NSIM_SDF_NBUF
-#define NSIM_SDF_NBUF 1      // LDS plane images per wave of the sampling decoder (<= 16 levels); 2 = double-buffered (measured: 0.0387 vs 0.0372 ms)
-#endif
 // Level-major gather of the no-grad SDF query (sampling pass, occupancy refresh): every wave owns GLM_PTS x 64 points
 // and walks the 16 levels in the same order as every other wave of the launch, so at any moment the chip reads ONE
 // level's table (<= 2 MB for T = 2^19), which stays resident in each XCD's 4 MB L2 -- the point-major fused kernel
@@ -1973,31 +1586,17 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES, 2) k_field_bwd_h(FieldArgs a
 // Measured ceiling (tools/gather_bench.hip): a random 4-byte gather retires 267 G lines/s from an L2-resident 2 MB
 // table (= the 34 TB/s aggregate L2->L1 rate at 128 B per miss) but only 65-120 G/s from an 8-32 MB one.
 // WJ = true (with-grad forward of the training step): writes the f32 planes h [16][S][2] and dh/dx [16][S][2][3] that
-// the decoder kernels (k_field MODE 3 forward, MODE 2 backward) read -- the same split, so the 6.7 k-instruction
-// forward no longer carries the gather's address registers (it spilled 440 B per lane).
-#ifndef GLM_PTS
-#define GLM_PTS 2      // points per lane of the no-grad forms (round 6: 4 -> 2, nsim_lotd_gather_lm 0.0608 -> 0.0593 ms per launch over two
-#endif                 // alternated runs each, gpurun_out/r6_s2_call15; 1 point and / or the operand tables: the same within noise)
-#ifndef GLM_PTS_WJ
-#define GLM_PTS_WJ 1      // points per lane of the with-grad form (eight accumulators per point: f, dh/dx): one -- 57 registers, eight
-                          // waves per SIMD -- with the slot tables below: nsim_field_fwd 0.1200 -> 0.1131 ms on the bench step (4 points:
-                          // 96 registers, five waves; 2 points 0.1161, 2 + tables 0.1154, 3 + tables 0.1192; gpurun_out/r6_s2_call13)
-#endif
-#ifndef NSIM_GATHER_WJ_WAVES
-#define NSIM_GATHER_WJ_WAVES 1   // WJ (with-grad planes): waves per SIMD the register allocation must leave room for (A/B knob of the slot tables)
-#endif
-#ifndef NSIM_GATHER_SLOTS_WJ
-#define NSIM_GATHER_SLOTS_WJ 1   // ... for the with-grad form only: that form is VALU-heavy enough (dh/dx) for the tables to pay once its
-                                 // register count no longer costs waves
-#endif
-#ifndef NSIM_GATHER_SLOTS
-#define NSIM_GATHER_SLOTS 0      // 1: the parity enumeration through per-axis operand tables (lotd_slots, ~30 % fewer VALU operations per level) instead
-                                 // of runtime corner indices.  Measured null on MI355X (gpurun_out/r6_s2_call7: nsim_lotd_gather_lm 0.0603 -> 0.0599 ms,
-                                 // the with-grad gather inside nsim_field_fwd +1.5 % at 99 registers / four waves or 96 + 20 B scratch): the
-                                 // gathers wait on L2 requests, not on the VALU
-#endif
+// the decoder kernels (k_field MODE 3 forward, k_field_bwd_j / k_field_bwd_h backward) read -- the same split, so the
+// 6.7 k-instruction forward no longer carries the gather's address registers (it spilled 440 B per lane).
+// Points per lane of the no-grad forms: 2 (round 6: 4 -> 2, nsim_lotd_gather_lm 0.0608 -> 0.0593 ms per launch; 1 point and / or the
+// operand tables: the same within noise -- the gathers wait on L2 requests, not on the VALU) ...
+constexpr int GLM_PTS = 2;
+// ... and of the with-grad form (eight accumulators per point: f, dh/dx): one -- 57 registers, eight waves per SIMD -- with the
+// per-axis operand tables of lotd_dev.h (that form is VALU-heavy enough for them to pay): nsim_field_fwd 0.1200 -> 0.1131 ms on
+// the bench step (4 points: 96 registers, five waves; 2 points 0.1161, 2 + tables 0.1154, 3 + tables 0.1192)
+constexpr int GLM_PTS_WJ = 1;
 template <int PREC, bool WJ>
-__global__ void __launch_bounds__(64, WJ ? NSIM_GATHER_WJ_WAVES : 1) k_lotd_gather_lm(FieldArgs a) {
+__global__ void __launch_bounds__(64, 1) k_lotd_gather_lm(FieldArgs a) {
   using JT = typename JPlane<PREC>::T;      // element type of the dh/dx planes (WJ)
   // points per lane.  (Round 5: 1 / 2 points per lane for launches of <= 98 k / 196 k points -- four times the waves for the
   // small up-sampling draws -- measured nothing: 0.0643-0.0658 against 0.0651-0.0666 ms per launch, profiles/round5_gather_ab.txt)
@@ -2057,8 +1656,8 @@ __global__ void __launch_bounds__(64, WJ ? NSIM_GATHER_WJ_WAVES : 1) k_lotd_gath
 #pragma unroll
         for (int c3 = 0; c3 < 3; ++c3) j0[q][c3] = j1[q][c3] = 0.f;
       }
-      // slots by vertex parity (lotd_dev.h): through per-axis operand tables (SLOTS) or runtime corner indices
-      constexpr bool SLOTS = NSIM_GATHER_SLOTS || (WJ && NSIM_GATHER_SLOTS_WJ);
+      // slots by vertex parity (lotd_dev.h): through per-axis operand tables (with-grad form) or runtime corner indices
+      constexpr bool SLOTS = WJ;
       const LotdSlots SL = lotd_slots(c);
       const int pm = lotd_slot_mask(c);
       if (l < a.lotd.n_active)
@@ -2105,9 +1704,6 @@ __global__ void __launch_bounds__(64, WJ ? NSIM_GATHER_WJ_WAVES : 1) k_lotd_gath
           JT* jp = reinterpret_cast<JT*>(a.J_pl) + ep * 6;
           hp[0] = f0[q];
           hp[1] = f1[q];
-#ifdef NSIM_PROBE_GATHER_NOJ      // timing probe (wrong results): the dh/dx stores dropped but for an impossible case
-          if (f0[q] == 123.456f)
-#endif
           jstore6(jp, j0[q], j1[q]);
         } else if constexpr (PREC == 0) {
           union {
@@ -2132,14 +1728,13 @@ static void launch_gather_lm(const FieldArgs& a, int64_t S, hipStream_t stream) 
   hipLaunchKernelGGL((k_lotd_gather_lm<PREC, WJ>), gg, dim3(64), 0, stream, a);
 }
 
-// GL (PLANES only): the tile's plane image -- per level 32 points x (f16x2 | f32x2) = 128 B | 256 B, one aligned piece
+// PLANES: the tile's plane image -- per level 32 points x (f16x2 | f32x2) = 128 B | 256 B, one aligned piece
 // thanks to the 32-point pitch -- is copied global -> LDS (global_load_lds_dwordx4: 8 | 4 levels per instruction) one tile
-// AHEAD, double-buffered for <= 16 levels (2 x 4 KB per wave), single-buffered above (8 KB): without it a tile began with
-// eight dependent-on-nothing but unhidden plane reads per K-step at two waves per SIMD (round 4; the with-grad decoders got
-// the same treatment in round 2).  NSIM_SDF_GLDS=0 launches the GL = false form.
-template <int PREC, int SDF_D, bool PLANES, int NC = 1, bool GL = false>
+// AHEAD into one buffer per wave (2 | 4 KB for <= 16 levels, twice that above; a second, alternating buffer measured
+// 0.0387 vs 0.0372 ms): without it a tile began with eight dependent-on-nothing but unhidden plane reads per K-step at
+// two waves per SIMD (round 4; the with-grad decoders got the same treatment in round 2).
+template <int PREC, int SDF_D, bool PLANES, int NC = 1>
 __global__ void __launch_bounds__(64 * FIELD_WAVES, NSIM_SDF_MIN_WAVES) k_field_sdf(FieldArgs a) {
-  static_assert(!GL || PLANES, "the LDS image is an image of the level-major planes");
   NSIM_DYN_SMEM(smem);
   const int lane = nsim_lane(), j = lane & 31, hi = lane >> 5;
   const int wave = (int)(threadIdx.x >> 6);
@@ -2156,14 +1751,13 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES, NSIM_SDF_MIN_WAVES) k_field_
   }
   const int64_t ntiles = (Sv + 31) / 32;
   const int64_t wstride = (int64_t)gridDim.x * FIELD_WAVES;
-  // ---- LDS image of the planes (GL)
+  // ---- LDS image of the planes (PLANES)
   constexpr int LV_BYTES = PREC == 0 ? 128 : 256;               // one level of one tile
   constexpr int LV_PER_COPY = 1024 / LV_BYTES;                  // levels per global_load_lds_dwordx4 (64 lanes x 16 B)
   constexpr int IMG_BYTES = 16 * NC * LV_BYTES;
-  constexpr int NBUF = NC == 1 ? NSIM_SDF_NBUF : 1;
   const int lv_used = NC == 1 ? 16 : ((a.lotd.num_levels + 7) & ~7);       // (wave-uniform) levels the K-steps read
-  char* img = GL ? smem + wbytes + wave * (NBUF * IMG_BYTES) : nullptr;
-  auto prefetch_planes = [&](int64_t tile_n, int buf) {
+  char* img = PLANES ? smem + wbytes + wave * IMG_BYTES : nullptr;
+  auto prefetch_planes = [&](int64_t tile_n) {
     const int64_t s0 = tile_n * 32;
     const int sub = lane / (64 / LV_PER_COPY), part = lane % (64 / LV_PER_COPY);
 #pragma unroll
@@ -2171,13 +1765,12 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES, NSIM_SDF_MIN_WAVES) k_field_
       if (NC == 2 && k * LV_PER_COPY >= lv_used) continue;
       const int l = k * LV_PER_COPY + sub;
       const char* src = reinterpret_cast<const char*>(a.feat_pl) + ((int64_t)l * a.PS + s0) * (LV_BYTES / 32) + 16 * part;
-      nsim_glds16(src, img + buf * IMG_BYTES + 1024 * k);
+      nsim_glds16(src, img + 1024 * k);
     }
   };
-  int buf = 0;
-  if constexpr (GL) {
+  if constexpr (PLANES) {
     const int64_t t0 = (int64_t)blockIdx.x * FIELD_WAVES + wave;
-    if (t0 < ntiles) prefetch_planes(t0, 0);
+    if (t0 < ntiles) prefetch_planes(t0);
   }
   for (int64_t tile = (int64_t)blockIdx.x * FIELD_WAVES + wave; tile < ntiles; tile += wstride) {
     TilePoint p;
@@ -2188,15 +1781,7 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES, NSIM_SDF_MIN_WAVES) k_field_
       p = load_point(a, tile, j, false);
       p.valid = p.valid && p.s < Sv;            // (a device-side point count below the capacity: round 5)
     }
-    const char* cur = nullptr;
-    if constexpr (GL) {
-      nsim_wait_vm0();                          // this tile's image has landed
-      cur = img + buf * IMG_BYTES;
-      if constexpr (NBUF == 2) {                // the next tile's image goes to the other buffer while this one is read
-        if (tile + wstride < ntiles) prefetch_planes(tile + wstride, buf ^ 1);
-        buf ^= 1;
-      }
-    }
+    if constexpr (PLANES) nsim_wait_vm0();      // this tile's image has landed
     f32x16 acc[2] = {zero16(), zero16()};
     f32x16 accc[PREC == 2 ? 2 : 1];            // split mode: the hi.lo + lo.hi correction, in units of 1 / SPLIT_LO_SCALE
     if constexpr (PREC == 2) accc[0] = accc[1] = zero16();
@@ -2208,7 +1793,7 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES, NSIM_SDF_MIN_WAVES) k_field_
       if (NC == 2 && lb >= ((a.lotd.num_levels + 7) & ~7)) continue;
       float f8[8];
       f16x8 bvp;
-      if constexpr (GL) {
+      if constexpr (PLANES) {
         // from the LDS image; lanes past the valid points read whatever the pitch padding holds: zeroed (their columns of
         // the products are discarded, but nothing non-finite is fed to the matrix cores)
 #pragma unroll
@@ -2221,35 +1806,14 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES, NSIM_SDF_MIN_WAVES) k_field_
                 uint32_t u;
                 f16 h[2];
               } cv;
-              cv.u = reinterpret_cast<const uint32_t*>(cur + LV_BYTES * l)[j];
+              cv.u = reinterpret_cast<const uint32_t*>(img + LV_BYTES * l)[j];
               if (!p.valid) cv.u = 0u;
               bvp[4 * qq + 2 * b] = cv.h[0];
               bvp[4 * qq + 2 * b + 1] = cv.h[1];
             } else {
-              const float* ip = reinterpret_cast<const float*>(cur + LV_BYTES * l) + 2 * j;
+              const float* ip = reinterpret_cast<const float*>(img + LV_BYTES * l) + 2 * j;
               f8[4 * qq + 2 * b] = p.valid ? ip[0] : 0.f;
               f8[4 * qq + 2 * b + 1] = p.valid ? ip[1] : 0.f;
-            }
-          }
-      } else if constexpr (PLANES) {
-        // features were gathered level-major by k_lotd_gather_lm (fp16 mode: already scaled by SDF_H_SCALE)
-#pragma unroll
-        for (int qq = 0; qq < 2; ++qq)
-#pragma unroll
-          for (int b = 0; b < 2; ++b) {
-            const int l = lb + 4 * qq + 2 * hi + b;
-            const int64_t e = (int64_t)l * a.PS + (p.valid ? p.s : 0);
-            if constexpr (PREC == 0) {
-              union {
-                uint32_t u;
-                f16 h[2];
-              } cv;
-              cv.u = reinterpret_cast<const uint32_t*>(a.feat_pl)[e];
-              bvp[4 * qq + 2 * b] = cv.h[0];
-              bvp[4 * qq + 2 * b + 1] = cv.h[1];
-            } else {
-              f8[4 * qq + 2 * b] = reinterpret_cast<const float*>(a.feat_pl)[2 * e];
-              f8[4 * qq + 2 * b + 1] = reinterpret_cast<const float*>(a.feat_pl)[2 * e + 1];
             }
           }
       } else {
@@ -2318,9 +1882,9 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES, NSIM_SDF_MIN_WAVES) k_field_
             acc[mo] = mfma_32x32x2_f32(A[(mo * 16 * NC + 8 * rb + e) * 64 + lane], f8[e], acc[mo]);
       }
     }
-    if constexpr (GL && NBUF == 1) {            // one buffer: every lane has read the image, the next copy may overwrite it
+    if constexpr (PLANES) {                     // every lane has read the image, the next copy may overwrite it
       nsim_wait_lgkm0();
-      if (tile + wstride < ntiles) prefetch_planes(tile + wstride, 0);
+      if (tile + wstride < ntiles) prefetch_planes(tile + wstride);
     }
     const float inv_h = PREC != 1 ? 1.0f / SDF_H_SCALE : 1.0f;
     float sdf = 0.f;
@@ -2426,8 +1990,8 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES, NSIM_SDF_MIN_WAVES) k_field_
 // that idles during the product.  LDS: the six weight matrices (34.5 KB) + one staging area (34.8 KB) = 69 KB -> two
 // workgroups per CU, two waves per SIMD (round 1's per-wave LDS accumulators: 141 KB, one).
 // Measured (MI355X, 274 k points): 0.208 ms in round 1 -> 0.162 ms with this structure -> 0.104 ms once the per-sample
-// appearance-code atomics were summed per ray inside the wave (they had been 80 % of a group's time: s_memtime stamps,
-// tools/ktime.py); the round-1 structure with the same atomics fix measured 0.100 ms -- the atomics were the bound.
+// appearance-code atomics were summed per ray inside the wave (they had been 80 % of a group's time by s_memtime stamps);
+// the round-1 structure with the same atomics fix measured 0.100 ms -- the atomics were the bound.
 template <int PREC>
 __global__ void __launch_bounds__(64 * JOINT_WAVES, PREC == 0 ? 2 : 1) k_rad_bwd_j(FieldArgs a) {
   NSIM_DYN_SMEM(smem);
@@ -2435,7 +1999,6 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES, PREC == 0 ? 2 : 1) k_rad_bwd
   const int wave = (int)(threadIdx.x >> 6);
   FieldLayout L;
   int wbytes;
-  { const int64_t grp = -1; KT(0, 23); }
   const char* W = stage_weights<PREC>(smem, a, M_R1, 6, L, wbytes);
   char* stA = smem + wbytes;
   char* stB = stA + 64 * jstage_row_bytes<PREC>();
@@ -2450,9 +2013,7 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES, PREC == 0 ? 2 : 1) k_rad_bwd
 
   const int64_t ntiles = (a.S + 31) / 32;
   const int64_t ngroups = (ntiles + JOINT_WAVES - 1) / JOINT_WAVES;
-  { const int64_t grp = -1; KT(0, 20); }
   for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
-    KT(0, 0);
     const int64_t tile = grp * JOINT_WAVES + wave;          // may lie past the end: all its points are invalid (zeros)
     const TilePoint p = load_point(a, tile, j, true);
     const int64_t s = p.s;
@@ -2468,9 +2029,7 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES, PREC == 0 ? 2 : 1) k_rad_bwd
     }
     float rin[16], r1[32], r2[32];
     make_rin(rin, p, nab, a.h_appear, hi);
-    KT(0, 1);
     radiance_hidden<PREC>(r1, r2, rin, W, L, hi);
-    KT(0, 2);
     float dout[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) dout[r] = 0.f;
@@ -2486,49 +2045,35 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES, PREC == 0 ? 2 : 1) k_rad_bwd
 #pragma unroll
     for (int r = 0; r < 16; ++r) douts[r] = dout[r] * sc;
     // ---- dR3 += dout (x) r2, d rb3 += rowsum(dout)
-    KT(0, 3);
     __syncthreads();                              // the previous group's readers of the staging area are done
-    KT(0, 4);
     jstage<PREC, 1>(stA, dout, wave);
     jstage<PREC, 2>(stB, r2, wave);
     if constexpr (RIN_EARLY) jstage<PREC, 1>(stC, rin, wave);      // (its readers of the previous group passed the barrier above)
-    KT(0, 5);
     __syncthreads();
-    KT(0, 6);
     if (wave < 2) accX = jdw_tile<PREC>(stA, 0, stB, wave, accX);
     bs3 += jrow_sum<PREC>(stA, 3, wave);
-    KT(0, 7);
     float dr2s[32];
     dense<PREC, 2, 1>(dr2s, W + L.mat[M_R3T], douts, false);
 #pragma unroll
     for (int k = 0; k < 32; ++k) dr2s[k] = r2[k] > 0.f ? dr2s[k] : 0.f;
     // ---- dR2 += dr2 (x) r1, d rb2 += rowsum(dr2)      (dr2 = dr2s / sc, formed where it is staged)
-    KT(0, 8);
     __syncthreads();
-    KT(0, 9);
     jstage_scaled<PREC, 2>(stA, dr2s, inv_sc, wave);
     jstage<PREC, 2>(stB, r1, wave);
-    KT(0, 10);
     __syncthreads();
-    KT(0, 11);
     accR2 = jdw_tile<PREC>(stA, wave >> 1, stB, wave & 1, accR2);
     bs2 += jrow_sum<PREC>(stA, 64, wave);
-    KT(0, 12);
     float dr1s[32];
     dense<PREC, 2, 2>(dr1s, W + L.mat[M_R2T], dr2s, false);
 #pragma unroll
     for (int k = 0; k < 32; ++k) dr1s[k] = r1[k] > 0.f ? dr1s[k] : 0.f;
     // ---- dR1 += dr1 (x) rin, d rb1 += rowsum(dr1)
-    KT(0, 13);
     __syncthreads();
-    KT(0, 14);
     jstage_scaled<PREC, 2>(stA, dr1s, inv_sc, wave);
     if constexpr (!RIN_EARLY) jstage<PREC, 1>(stB, rin, wave);
     __syncthreads();
-    KT(0, 15);
     if (wave >= 2) accX = jdw_tile<PREC>(stA, wave - 2, RIN_EARLY ? stC : stB, 0, accX);
     bs1 += jrow_sum<PREC>(stA, 64, wave);
-    KT(0, 16);
     float din[16];
     dense<PREC, 1, 2>(din, W + L.mat[M_R1T], dr1s, false);
 #pragma unroll
@@ -2575,9 +2120,7 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES, PREC == 0 ? 2 : 1) k_rad_bwd
         atomicAdd(dst + 1, c1);
       }
     }
-    KT(0, 17);
   }
-  { const int64_t grp = -1; KT(0, 21); }
   // ---- one flush per wave
   const SrcOff so = src_off(1);
   const int64_t ro = (int64_t)(blockIdx.x & (unsigned)a.rep_mask) * a.rep_stride;      // this workgroup's replica
@@ -2587,7 +2130,6 @@ __global__ void __launch_bounds__(64 * JOINT_WAVES, PREC == 0 ? 2 : 1) k_rad_bwd
   if (bs1 != 0.f) atomicAdd(&a.drad_b[ro + so.rb1 + lane], bs1);
   if (bs2 != 0.f) atomicAdd(&a.drad_b[ro + so.rb2 + lane], bs2);
   if (lane < 3 && bs3 != 0.f) atomicAdd(&a.drad_b[ro + so.rb3 + lane], bs3);
-  { const int64_t grp = -1; KT(0, 22); }
 }
 
 // ------------------------------------------------------------------------------------ grid scatter
@@ -2610,26 +2152,21 @@ struct ScatterArgs {
   float* dgrid;
   int dedup_max_res;
   int level_begin;      // this launch covers levels [level_begin, level_begin + gridDim.y)
-  int parity_slots;     // the eight vertices of a cell are enumerated by the PARITY of their coordinates (round 6, default on)
 };
 
-// CONSEC (default since round 6; NSIM_SCATTER_GROUP=0: the strided form of rounds 1-5): which 16 samples of the wave's 64 share
-// one atomic instruction.  The atomic unit retires one request per distinct 64-byte sector per wave instruction at ~21 G/s, and
-// lanes of one instruction on the SAME address are separate requests (profiles/round4_atomic_line_bench.txt,
-// profiles/round6_atomic_conflict_bench.txt) -- so a launch costs the number of such requests, which tools/scatter_sector_model.py
-// counts on a dumped step's sample set (25.1 modelled, 24.9 measured per point for the rounds 1-5 kernel).  Issue I of the quad
-// transposition used to take the samples 4q + I (a DPP quad broadcast); it now takes the 16 CONSECUTIVE samples 16 I + q (six
-// ds_bpermute per issue): neighbours on a ray, whose vertex rows share sectors.  On its own that measured nothing (neighbouring
-// cells share VERTICES, i.e. addresses: 0.376 ms either way); with the parity slots below, which fold the shared vertices
-// first, it is worth another 8 %.  MI355X, bench step / street step (profiles/round6_scatter_requests.json):
-//     slots by corner offset, strided issue (rounds 1-5)   0.376 ms   3.32 ms    25.1 / 43.5 requests per point (model)
-//     parity slots, strided issue                           0.309      2.84       20.4 / 37.5
-//     parity slots, consecutive issue (default)             0.286      2.47       17.8 / 32.4
+// Which 16 samples of the wave's 64 share one atomic instruction.  The atomic unit retires one request per distinct 64-byte sector
+// per wave instruction at ~21 G/s, and lanes of one instruction on the SAME address are separate requests
+// (profiles/round4_atomic_line_bench.txt, profiles/round6_atomic_conflict_bench.txt) -- so a launch costs the number of such requests,
+// which tools/scatter_sector_model.py counts on a dumped step's sample set.  Issue I of the quad transposition takes the 16
+// CONSECUTIVE samples 16 I + q (six ds_bpermute per issue): neighbours on a ray, whose vertex rows share sectors; the parity slots
+// below fold the vertices neighbouring cells share first.  MI355X, bench step / street step (profiles/round6_scatter_requests.json):
+//     slots by corner offset, issue I = samples 4q + I (rounds 1-5)   0.376 ms   3.32 ms    25.1 / 43.5 requests per point (model)
+//     parity slots, issue I = samples 4q + I                          0.309      2.84       20.4 / 37.5
+//     parity slots, consecutive issue (this kernel)                   0.286      2.47       17.8 / 32.4
 #ifndef NSIM_SCATTER_MIN_WAVES
 #define NSIM_SCATTER_MIN_WAVES 5      // waves per SIMD the register allocation leaves room for: 98 -> 96 registers, five waves instead of
                                       // four (MI355X, bench step: 0.2865 -> 0.2811 ms; 6 -- 80 registers + 64 B scratch -- 0.328 ms)
 #endif
-template <bool CONSEC>
 __global__ void __launch_bounds__(256, NSIM_SCATTER_MIN_WAVES) k_lotd_scatter(ScatterArgs a) {
   const int lane = nsim_lane();
   const int l = a.level_begin + (int)blockIdx.y;
@@ -2667,7 +2204,7 @@ __global__ void __launch_bounds__(256, NSIM_SCATTER_MIN_WAVES) k_lotd_scatter(Sc
     const LotdCell c = lotd_cell(xx, R, a.lotd);
     const float q0[3] = {g0 * gn[0] * c.dscale[0], g0 * gn[1] * c.dscale[1], g0 * gn[2] * c.dscale[2]};
     const float q1[3] = {g1 * gn[0] * c.dscale[0], g1 * gn[1] * c.dscale[1], g1 * gn[2] * c.dscale[2]};
-    const int px0 = a.parity_slots ? (c.c0[0] & 1) : 0, py0 = a.parity_slots ? (c.c0[1] & 1) : 0, pz0 = a.parity_slots ? (c.c0[2] & 1) : 0;
+    const int px0 = c.c0[0] & 1, py0 = c.c0[1] & 1, pz0 = c.c0[2] & 1;
 #pragma unroll
     for (int yz = 0; yz < 4; ++yz) {
       uint32_t idx[2];
@@ -2699,8 +2236,8 @@ __global__ void __launch_bounds__(256, NSIM_SCATTER_MIN_WAVES) k_lotd_scatter(Sc
 #pragma unroll
           for (int d = 1; d < 64; d <<= 1) {
             // (wave-uniform early exit: no run of this slot reaches d lanes back -- at the fine levels runs are 1-3 lanes long
-            // and two of the six rounds do all the work; -DNSIM_SCATTER_SCAN_EXIT=0 keeps all six)
-            if (NSIM_SCATTER_SCAN_EXIT && !wave_ballot(lane - d >= run_start)) break;
+            // and two of the six rounds do all the work)
+            if (!wave_ballot(lane - d >= run_start)) break;
             const float o0 = wave_shfl(v0[dx], lane - d), o1 = wave_shfl(v1[dx], lane - d);
             if (lane - d >= run_start) {
               v0[dx] += o0;
@@ -2710,36 +2247,17 @@ __global__ void __launch_bounds__(256, NSIM_SCATTER_MIN_WAVES) k_lotd_scatter(Sc
           emit[dx] = valid && (lane == 63 || ((heads >> (lane + 1)) & 1ull));  // last lane of the run
         }
       }
-#define NSIM_QUAD_ISSUE(I)                                                                                   \
-  {                                                                                                          \
-    const uint32_t i0 = quad_bcast<I>(idx[0]), i1 = quad_bcast<I>(idx[1]);                                   \
-    const float a0 = quad_bcast<I>(v0[0]), a1 = quad_bcast<I>(v1[0]);                                        \
-    const float b0 = quad_bcast<I>(v0[1]), b1 = quad_bcast<I>(v1[1]);                                        \
-    const int e0 = quad_bcast<I>((int)emit[0]), e1 = quad_bcast<I>((int)emit[1]);                            \
-    const uint32_t ii = rq < 2 ? i0 : i1;                                                                    \
-    const float vv = rq == 0 ? a0 : (rq == 1 ? a1 : (rq == 2 ? b0 : b1));                                    \
-    const int ee = rq < 2 ? e0 : e1;                                                                         \
-    if (ee) atomicAdd(base + 2 * (int64_t)ii + (rq & 1), vv);                                                \
-  }
-      if constexpr (CONSEC) {
-        const uint32_t k0 = emit[0] ? idx[0] : 0xffffffffu, k1 = emit[1] ? idx[1] : 0xffffffffu;
+      const uint32_t k0 = emit[0] ? idx[0] : 0xffffffffu, k1 = emit[1] ? idx[1] : 0xffffffffu;
 #pragma unroll
-        for (int I = 0; I < 4; ++I) {
-          const int src = 16 * I + (lane >> 2);
-          const uint32_t i0 = wave_shfl(k0, src), i1 = wave_shfl(k1, src);
-          const float a0 = wave_shfl(v0[0], src), a1 = wave_shfl(v1[0], src);
-          const float b0 = wave_shfl(v0[1], src), b1 = wave_shfl(v1[1], src);
-          const uint32_t ii = rq < 2 ? i0 : i1;
-          const float vv = rq == 0 ? a0 : (rq == 1 ? a1 : (rq == 2 ? b0 : b1));
-          if (ii != 0xffffffffu) atomicAdd(base + 2 * (int64_t)ii + (rq & 1), vv);
-        }
-      } else {
-        NSIM_QUAD_ISSUE(0)
-        NSIM_QUAD_ISSUE(1)
-        NSIM_QUAD_ISSUE(2)
-        NSIM_QUAD_ISSUE(3)
+      for (int I = 0; I < 4; ++I) {
+        const int src = 16 * I + (lane >> 2);
+        const uint32_t i0 = wave_shfl(k0, src), i1 = wave_shfl(k1, src);
+        const float a0 = wave_shfl(v0[0], src), a1 = wave_shfl(v1[0], src);
+        const float b0 = wave_shfl(v0[1], src), b1 = wave_shfl(v1[1], src);
+        const uint32_t ii = rq < 2 ? i0 : i1;
+        const float vv = rq == 0 ? a0 : (rq == 1 ? a1 : (rq == 2 ? b0 : b1));
+        if (ii != 0xffffffffu) atomicAdd(base + 2 * (int64_t)ii + (rq & 1), vv);
       }
-#undef NSIM_QUAD_ISSUE
     }
   }
 }
@@ -2871,7 +2389,7 @@ static int field_meta_check_full(const NsimFieldMeta* m) {
 
 // ------------------------------------------------------------------------------------ weight-gradient replicas
 // The joint backward kernels end with every workgroup adding its partial weight gradients into the SAME ~6 k floats.
-// 256-512 same-address atomics per address serialise in L2 at ~0.1 us each: s_memtime stamps (tools/ktime.py, round 3)
+// 256-512 same-address atomics per address serialise in L2 at ~0.1 us each: s_memtime stamps (round 3)
 // show the last group of the radiance backward waiting ~55 us of a 100 us launch behind that storm.  With a caller-owned,
 // zeroed scratch registered for the stream (nsim_set_grad_scratch), workgroup b flushes into replica b % R instead and a
 // small second launch folds the R copies into the caller's gradient buffers (and zeroes the scratch again).
@@ -2944,14 +2462,12 @@ static FieldArgs field_args(const NsimFieldMeta* meta) {
   a.lay = field_layout(meta->precision, field_ni(meta));
   a.embed_E = meta->embed_E;
   a.beta = meta->softplus_beta > 0.f ? meta->softplus_beta : 1e30f;      // (<= 0: relu, see softplus_exact)
-  static const int code_pf = getenv("NSIM_CODE_PREFETCH") ? atoi(getenv("NSIM_CODE_PREFETCH")) : 0;
-  a.code_pf = code_pf;
   return a;
 }
 
-static unsigned field_grid(int64_t S, int64_t max_blocks, int waves = FIELD_WAVES) {
+static unsigned field_grid(int64_t S, int64_t max_blocks) {
   const int64_t tiles = (S + 31) / 32;
-  int64_t b = (tiles + waves - 1) / waves;
+  int64_t b = (tiles + FIELD_WAVES - 1) / FIELD_WAVES;
   if (b > max_blocks) b = max_blocks;
   if (b < 1) b = 1;
   return (unsigned)b;
@@ -2963,20 +2479,10 @@ static size_t weights_lds_bytes(const NsimFieldMeta* meta, int first = 0, int co
   const int64_t m1 = (first + count < M_COUNT) ? L.mat[first + count] : L.vec[0];
   return (size_t)(((m1 - L.mat[first]) + (L.vend - L.vec[0]) + 15) & ~15);
 }
-static size_t stage_bytes(const NsimFieldMeta* meta) {
-  return meta->precision == 0 ? stage_bytes_per_wave<0>() : stage_bytes_per_wave<1>();
-}
-
-// waves per workgroup of k_field<., ., MODE, NC> (see NW in the kernel)
-static int field_waves(const NsimFieldMeta* meta, int mode) {
-  return (mode == 2 && meta->precision == 0 && field_nc(meta->lotd.num_levels) == 2) ? 3 : FIELD_WAVES;
-}
-
 template <int MODE>
 static int field_launch(const NsimFieldMeta* meta, const FieldArgs& a, size_t shmem, int64_t max_blocks,
                         hipStream_t stream, bool gl2 = false) {
-  const int nw = field_waves(meta, MODE);
-  const dim3 grid(field_grid(a.S, max_blocks, nw)), block(64 * nw);
+  const dim3 grid(field_grid(a.S, max_blocks)), block(64 * FIELD_WAVES);
   const int key = meta->precision * 2 + (meta->sdf_D - 1);
   if (field_ne(meta)) {      // embedded-position block behind the features: the forward on the planes only
     if constexpr (MODE == 3) {
@@ -3005,7 +2511,7 @@ static int field_launch(const NsimFieldMeta* meta, const FieldArgs& a, size_t sh
         return 0;
       }
     }
-    if constexpr (MODE == 2 || MODE == 3) {
+    if constexpr (MODE == 3) {
       switch (key) {
         case 0: hipLaunchKernelGGL((k_field<0, 1, MODE, 2>), grid, block, shmem, stream, a); break;
         case 1: hipLaunchKernelGGL((k_field<0, 2, MODE, 2>), grid, block, shmem, stream, a); break;
@@ -3028,14 +2534,8 @@ static int field_launch(const NsimFieldMeta* meta, const FieldArgs& a, size_t sh
   return 0;
 }
 
-static int bwd_ablate() {
-  const char* ab = getenv("NSIM_ABLATE");
-  return ab ? atoi(ab) : 0;
-}
-
-// persistent grids: the packed weights (58 KB) are staged into LDS once per workgroup
+// persistent grid of the point-major forward: the packed weights (58 KB) are staged into LDS once per workgroup
 #define FIELD_GRID_FWD 1024
-#define FIELD_GRID_BWD 256      // one resident workgroup per CU (LDS-limited): persistent waves amortise the accumulator flush
 
 extern "C" {
 
@@ -3214,17 +2714,11 @@ int nsim_field_sdf(const NsimFieldMeta* meta, const void* grid_f16, const void* 
   size_t shmem = weights_lds_bytes(meta, 0, 2);
   const int key = meta->precision * 2 + (meta->sdf_D - 1);
   // (split precision without planes -- the fused point-major form -- exists for <= 16 levels since round 5: small launches)
-  static const bool sdf_glds = !(getenv("NSIM_SDF_GLDS") && atoi(getenv("NSIM_SDF_GLDS")) == 0);
   const int nc = field_nc(meta->lotd.num_levels);
-  const bool gl = sdf_glds && feat_scratch;
-  if (gl)     // the LDS plane image(s) of every wave behind the weights: 2 x (2 | 4) KB for <= 16 levels, 1 x (4 | 8) KB above
-    shmem = ((shmem + 15) & ~(size_t)15) + (size_t)FIELD_WAVES * (nc == 1 ? NSIM_SDF_NBUF : 1) * 16 * nc * (meta->precision == 0 ? 128 : 256);
+  if (feat_scratch)     // the LDS plane image of every wave behind the weights: (2 | 4) KB for <= 16 levels, (4 | 8) KB above
+    shmem = ((shmem + 15) & ~(size_t)15) + (size_t)FIELD_WAVES * 16 * nc * (meta->precision == 0 ? 128 : 256);
   hipStream_t st = (hipStream_t)stream;
-#define NSIM_SDF_LAUNCH(P, D, N)                                                                                  \
-  do {                                                                                                            \
-    if (gl) hipLaunchKernelGGL((k_field_sdf<P, D, true, N, true>), grid, block, shmem, st, a);                    \
-    else hipLaunchKernelGGL((k_field_sdf<P, D, true, N, false>), grid, block, shmem, st, a);                      \
-  } while (0)
+#define NSIM_SDF_LAUNCH(P, D, N) hipLaunchKernelGGL((k_field_sdf<P, D, true, N>), grid, block, shmem, st, a)
   if (nc == 2) {
     if (!feat_scratch) return 33;     // more than 16 levels: level-major path only
     switch (key) {
@@ -3284,9 +2778,8 @@ int nsim_field_fwd(const NsimFieldMeta* meta, const void* grid_f16, const void* 
   a.sdf = sdf; a.nablas = nablas; a.rgb = rgb;
   a.h_pl = h_planes; a.J_pl = J_planes;
   a.has_rgb = rgb ? 1 : 0;
-  static const bool fused = getenv("NSIM_FWD_FUSED") && atoi(getenv("NSIM_FWD_FUSED")) == 1;
   if (!grid_f16 && !h_planes) return 4;
-  if (h_planes && (!grid_f16 || !fused || n_dev || field_nc(meta->lotd.num_levels) == 2)) {      // training: level-major gather into the planes, then the decoders on the planes
+  if (h_planes) {      // training: level-major gather into the planes, then the decoders on the planes
     if (grid_f16) {      // (NULL: the caller's encoding has filled the planes already -- nsim_permuto_gather)
       deal_levels(meta, a);
       if (meta->precision == 0) launch_gather_lm<0, true>(a, S, (hipStream_t)stream);
@@ -3296,27 +2789,26 @@ int nsim_field_fwd(const NsimFieldMeta* meta, const void* grid_f16, const void* 
         return 0;
       }
     }
-    // <= 16 levels: + one 16 KB plane-prefetch buffer per wave (k_field GLDS); 17..32 levels, fp16: 1 KB per level and wave
-    // where that still fits the 160 KB of a CU (NSIM_FWD_GL2=0: the direct-load kernel)
+    // <= 16 levels: + one 4 KB feature image per wave (k_field JDIR); 17..32 levels, fp16: a plane image of 1 KB per level and wave
+    // where that still fits the 160 KB of a CU (otherwise, and in f32 mode: the direct-load kernel)
     size_t wl = weights_lds_bytes(meta);
     if (meta->precision != 0) wl = 0;
     if (field_ne(meta))      // the forward matrices only, no plane image: 66 KB (<= 16 levels) -> two workgroups per CU
       return field_launch<3>(meta, a, weights_lds_bytes(meta, 0, M_R3 + 1), 512, (hipStream_t)stream, false);
-    size_t pf_bytes = field_nc(meta->lotd.num_levels) == 1 ? (size_t)FIELD_WAVES * (NSIM_FWD_JDIRECT ? 4096 : 16384) : 0;
+    size_t pf_bytes = field_nc(meta->lotd.num_levels) == 1 ? (size_t)FIELD_WAVES * 4096 : 0;
     bool gl2 = false;
     if (field_nc(meta->lotd.num_levels) == 2 && meta->precision == 0) {
-      static const bool gl2_on = !(getenv("NSIM_FWD_GL2") && atoi(getenv("NSIM_FWD_GL2")) == 0);
       const size_t img = (size_t)FIELD_WAVES * 1024 * meta->lotd.num_levels;
-      if (gl2_on && wl + img <= 160 * 1024) {
+      if (wl + img <= 160 * 1024) {
         gl2 = true;
         pf_bytes = img;
       }
     }
-    // persistent workgroups: with the plane-prefetch buffers one workgroup fits a CU (124 KB of LDS), 1024 of them ran as
+    // persistent workgroups: with the whole plane image one workgroup fits a CU (124 KB of LDS), 1024 of them ran as
     // four rounds that each staged the weights and took a cold first tile (s_memtime stamps: 22.5 k vs 16.7 k ticks) --
-    // one round of 256: 0.197 -> 0.189 ms per 0.31 M points (gather included); the 17..32-level kernel fits two per CU
+    // one round of 256: 0.197 -> 0.189 ms per 0.31 M points (gather included); the other forms fit two per CU
     static const int fwd_grid_env = getenv("NSIM_FWD_GRID") ? atoi(getenv("NSIM_FWD_GRID")) : 0;
-    const int fwd_grid = fwd_grid_env > 0 ? fwd_grid_env : ((pf_bytes && !(NSIM_FWD_JDIRECT && !gl2)) ? 256 : 512);
+    const int fwd_grid = fwd_grid_env > 0 ? fwd_grid_env : (gl2 ? 256 : 512);
     return field_launch<3>(meta, a, wl + pf_bytes, fwd_grid, (hipStream_t)stream, gl2);
   }
   if (field_ne(meta)) return 36;      // the embedded-position block exists on the level-major path (h_planes / J_planes) only
@@ -3361,7 +2853,6 @@ int nsim_field_bwd_rad(const NsimFieldMeta* meta, const void* wpack, const float
   a.drad_w = drad_w; a.drad_b = drad_b; a.dh_appear = dh_appear;
   a.dx = dx; a.dv = dv;
   a.has_rgb = 1;
-  a.ablate = bwd_ablate();
   const int64_t tiles = (S + 31) / 32;
   // workgroup-joint weight gradients: weights + one staging area in LDS, two workgroups per CU
   const size_t row = meta->precision == 0 ? jstage_row_bytes<0>() : jstage_row_bytes<1>();
@@ -3416,18 +2907,11 @@ static int field_bwd_sdf(const NsimFieldMeta* meta, const void* wpack, const Bwd
   a.dh_pl = dh_planes; a.g_pl = g_planes;
   a.dsdf_w = dsdf_w; a.dsdf_b = dsdf_b;
   a.dx = dx;
-  a.ablate = bwd_ablate();
-  const int nc = field_nc(meta->lotd.num_levels), nw = field_waves(meta, 2);
-  // 16-level pyramids: the workgroup-joint kernel (k_field_bwd_j).  Measured on 278 k points (MI355X): k_field<0,2,2>
-  // 0.232 ms -> 0.176 ms (weights in LDS instead of L2 reads -- the recomputed forward alone was 35 % of a tile --
-  // and no accumulator read-modify-write); forced into 256 registers (two waves per SIMD) it spills 177 and takes 0.275 ms,
-  // so the two-hidden-layer instantiation runs one wave per SIMD.  NSIM_SDF_BWD_OLD=1: the round-1 kernel (A/B aid).
-  const char* oldp = getenv("NSIM_SDF_BWD_OLD");
-  const bool old_kernel = oldp && atoi(oldp) == 1;
+  const int nc = field_nc(meta->lotd.num_levels);
   // fp16, <= 16 levels, no embedded block (the object shapes): the 16-point kernel k_field_bwd_h -- 256 registers, 58 KB of LDS,
-  // two workgroups per CU.  NSIM_BWD_TILE=32 (read per launch, A/B aid): the 32-point k_field_bwd_j instead.
+  // two workgroups per CU.  NSIM_BWD_TILE=32 (read per launch): the 32-point k_field_bwd_j instead, the reference of its tests.
   const char* tile_env = getenv("NSIM_BWD_TILE");
-  if (!old_kernel && meta->precision == 0 && nc == 1 && !ne && field_has16(a.lay) && !(tile_env && atoi(tile_env) == 32)) {
+  if (meta->precision == 0 && nc == 1 && !ne && field_has16(a.lay) && !(tile_env && atoi(tile_env) == 32)) {
     const size_t shmem = weights16_lds_bytes(a.lay) + 3 * J16_STAGE_BYTES + JOINT_WAVES * BWD16_PF_BYTES;
     const int64_t tiles = (S + 15) / 16;
     int64_t nb = (tiles + JOINT_WAVES - 1) / JOINT_WAVES;
@@ -3448,55 +2932,49 @@ static int field_bwd_sdf(const NsimFieldMeta* meta, const void* wpack, const Bwd
     NSIM_CHECK_LAUNCH();
     return 0;
   }
-  if (ne || !old_kernel) {
-    // workgroup-joint weight gradients: weights + three staging areas in LDS, two workgroups per CU
-    const size_t row = meta->precision == 0 ? jstage_row_bytes<0>() : jstage_row_bytes<1>();
-    // + one 16 KB plane-prefetch buffer per wave in fp16 mode (k_field_bwd_j GLDS)
-    const int ni = nc + ne;      // staging: A 64 rows, B 32 ni (>= 64) rows, C 64 rows
-    const bool dbuf = NSIM_BWD_DBUF && meta->precision == 0 && !ne && (nc == 2 || NSIM_BWD_JDIRECT);      // (DB in the kernel)
-    const size_t shmem = weights_lds_bytes(meta, 0, 4) + (dbuf ? 2 : 1) * (128 + (ni > 2 ? 32 * ni : 64)) * row +
-                         (meta->precision == 0 && nc == 1 && !ne ? (size_t)JOINT_WAVES * (NSIM_BWD_JDIRECT ? 4096 : 16384) : 0);
-    const int64_t tiles = (S + 31) / 32;
-    int64_t nb = (tiles + JOINT_WAVES - 1) / JOINT_WAVES;
-    const char* gcap = getenv("NSIM_SDF_BWD_GRID");
-    const int64_t cap = gcap ? atoi(gcap) : 256;          // one resident workgroup per CU (register-limited)
-    nb = nb > cap ? cap : (nb < 1 ? 1 : nb);
-    const dim3 grid((unsigned)nb), block(64 * JOINT_WAVES);
-    const SrcOff so = src_off(meta->sdf_D, 2 * meta->lotd.num_levels + meta->embed_E);
-    int R = 1;
-    float* sc = nb >= grad_replicas_min_wg() ? grad_scratch(stream, so.n_sdf_w + so.n_sdf_b, R) : nullptr;
-    if (sc) {
-      a.dsdf_w = sc; a.dsdf_b = sc + so.n_sdf_w;
-      a.rep_mask = R - 1; a.rep_stride = so.n_sdf_w + so.n_sdf_b;
-    }
-    switch ((ne ? 8 : 0) + (nc - 1) * 4 + meta->precision * 2 + (meta->sdf_D - 1)) {
-      case 8: hipLaunchKernelGGL((k_field_bwd_j<0, 1, 1, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
-      case 9: hipLaunchKernelGGL((k_field_bwd_j<0, 2, 1, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
-      case 10: hipLaunchKernelGGL((k_field_bwd_j<1, 1, 1, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
-      case 11: hipLaunchKernelGGL((k_field_bwd_j<1, 2, 1, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
-      case 12: hipLaunchKernelGGL((k_field_bwd_j<0, 1, 2, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
-      case 13: hipLaunchKernelGGL((k_field_bwd_j<0, 2, 2, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
-      case 14: hipLaunchKernelGGL((k_field_bwd_j<1, 1, 2, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
-      case 15: hipLaunchKernelGGL((k_field_bwd_j<1, 2, 2, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
-      case 0: hipLaunchKernelGGL((k_field_bwd_j<0, 1>), grid, block, shmem, (hipStream_t)stream, a); break;
-      case 1: hipLaunchKernelGGL((k_field_bwd_j<0, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
-      case 2: hipLaunchKernelGGL((k_field_bwd_j<1, 1>), grid, block, shmem, (hipStream_t)stream, a); break;
-      case 3: hipLaunchKernelGGL((k_field_bwd_j<1, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
-      case 4: hipLaunchKernelGGL((k_field_bwd_j<0, 1, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
-      case 5: hipLaunchKernelGGL((k_field_bwd_j<0, 2, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
-      case 6: hipLaunchKernelGGL((k_field_bwd_j<1, 1, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
-      case 7: hipLaunchKernelGGL((k_field_bwd_j<1, 2, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
-    }
-    if (sc) grad_scratch_fold(sc, R, so.n_sdf_w, so.n_sdf_b, dsdf_w, dsdf_b, (hipStream_t)stream);
-    NSIM_CHECK_LAUNCH();
-    return 0;
+  // Every other shape: the 32-point workgroup-joint kernel k_field_bwd_j (weights + one staging set in LDS).  Measured on 278 k
+  // points (MI355X) against per-wave LDS accumulators: 0.232 ms -> 0.176 ms (weights in LDS instead of L2 reads -- the recomputed
+  // forward alone was 35 % of a tile -- and no accumulator read-modify-write); forced into 256 registers (two waves per SIMD) it
+  // spills 177 and takes 0.275 ms, so the two-hidden-layer instantiation runs one wave per SIMD.
+  const size_t row = meta->precision == 0 ? jstage_row_bytes<0>() : jstage_row_bytes<1>();
+  const int ni = nc + ne;      // staging: A 64 rows, B 32 ni (>= 64) rows, C 64 rows
+  // + one 4 KB feature image per wave in fp16 mode, <= 16 levels (k_field_bwd_j GLDS)
+  const size_t shmem = weights_lds_bytes(meta, 0, 4) + (128 + (ni > 2 ? 32 * ni : 64)) * row +
+                       (meta->precision == 0 && nc == 1 && !ne ? (size_t)JOINT_WAVES * 4096 : 0);
+  const int64_t tiles = (S + 31) / 32;
+  int64_t nb = (tiles + JOINT_WAVES - 1) / JOINT_WAVES;
+  const char* gcap = getenv("NSIM_SDF_BWD_GRID");
+  const int64_t cap = gcap ? atoi(gcap) : 256;          // one resident workgroup per CU (register-limited)
+  nb = nb > cap ? cap : (nb < 1 ? 1 : nb);
+  const dim3 grid((unsigned)nb), block(64 * JOINT_WAVES);
+  const SrcOff so = src_off(meta->sdf_D, 2 * meta->lotd.num_levels + meta->embed_E);
+  int R = 1;
+  float* sc = nb >= grad_replicas_min_wg() ? grad_scratch(stream, so.n_sdf_w + so.n_sdf_b, R) : nullptr;
+  if (sc) {
+    a.dsdf_w = sc; a.dsdf_b = sc + so.n_sdf_w;
+    a.rep_mask = R - 1; a.rep_stride = so.n_sdf_w + so.n_sdf_b;
   }
-  // NSIM_SDF_BWD_OLD=1 (A/B aid): the round-1 kernel; more than 16 levels: fp16: one private accumulator copy per wave +
-  // staging, weights from L2; f32: staged weights + one shared accumulator
-  const size_t acc_bytes = ((6400 + 2048 * (nc - 1)) * 4 + 15) & ~15;
-  const size_t shmem = meta->precision == 0 ? weights_lds_bytes(meta, 0, 0) + nw * acc_bytes + nw * stage_bytes(meta)
-                                            : weights_lds_bytes(meta, 0, 4) + acc_bytes + FIELD_WAVES * stage_bytes(meta);
-  return field_launch<2>(meta, a, shmem, FIELD_GRID_BWD, (hipStream_t)stream);
+  switch ((ne ? 8 : 0) + (nc - 1) * 4 + meta->precision * 2 + (meta->sdf_D - 1)) {
+    case 8: hipLaunchKernelGGL((k_field_bwd_j<0, 1, 1, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 9: hipLaunchKernelGGL((k_field_bwd_j<0, 2, 1, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 10: hipLaunchKernelGGL((k_field_bwd_j<1, 1, 1, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 11: hipLaunchKernelGGL((k_field_bwd_j<1, 2, 1, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 12: hipLaunchKernelGGL((k_field_bwd_j<0, 1, 2, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 13: hipLaunchKernelGGL((k_field_bwd_j<0, 2, 2, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 14: hipLaunchKernelGGL((k_field_bwd_j<1, 1, 2, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 15: hipLaunchKernelGGL((k_field_bwd_j<1, 2, 2, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 0: hipLaunchKernelGGL((k_field_bwd_j<0, 1>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 1: hipLaunchKernelGGL((k_field_bwd_j<0, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 2: hipLaunchKernelGGL((k_field_bwd_j<1, 1>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 3: hipLaunchKernelGGL((k_field_bwd_j<1, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 4: hipLaunchKernelGGL((k_field_bwd_j<0, 1, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 5: hipLaunchKernelGGL((k_field_bwd_j<0, 2, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 6: hipLaunchKernelGGL((k_field_bwd_j<1, 1, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 7: hipLaunchKernelGGL((k_field_bwd_j<1, 2, 2>), grid, block, shmem, (hipStream_t)stream, a); break;
+  }
+  if (sc) grad_scratch_fold(sc, R, so.n_sdf_w, so.n_sdf_b, dsdf_w, dsdf_b, (hipStream_t)stream);
+  NSIM_CHECK_LAUNCH();
+  return 0;
 }
 
 extern "C" {
@@ -3532,7 +3010,6 @@ int nsim_lotd_scatter(const NsimLotdMeta* meta, const float* x, const float* ray
   if (!x && !(rays_o && rays_d && t && ridx)) return 24;
   if (!dh_planes || !g_planes || !dgrid) return 28;
   if (ray_goff && !ridx) return 29;
-  if (bwd_ablate() & 1) return 0;
   ScatterArgs sa;
   sa.lotd = lotd_dev(meta);
   sa.x = x; sa.rays_o = rays_o; sa.rays_d = rays_d; sa.t = t; sa.ridx = ridx;
@@ -3543,17 +3020,10 @@ int nsim_lotd_scatter(const NsimLotdMeta* meta, const float* x, const float* ray
   sa.dedup_max_res = 1 << 30;   // every level (compressed query mode keeps neighbouring fine samples: 0.345 -> 0.319 ms; it was 600 for the un-compressed mode)
   const char* e = getenv("NSIM_DEDUP_MAX_RES");
   if (e) sa.dedup_max_res = atoi(e);
-  const char* ep = getenv("NSIM_SCATTER_PARITY");      // 0: slots by corner offset, as rounds 1-5 (A/B aid)
-  sa.parity_slots = !(ep && atoi(ep) == 0);
   const int64_t chunks = (S + 63) / 64;
   sa.level_begin = level_begin;
   const dim3 grid(nsim_blocks(chunks, 4, 4096), level_count);
-  const char* eg = getenv("NSIM_SCATTER_GROUP");       // (read per launch: A/B runs flip it inside one process)
-  const bool consec = !(eg && atoi(eg) == 0);
-  if (consec)
-    hipLaunchKernelGGL(k_lotd_scatter<true>, grid, dim3(256), 0, (hipStream_t)stream, sa);
-  else
-    hipLaunchKernelGGL(k_lotd_scatter<false>, grid, dim3(256), 0, (hipStream_t)stream, sa);
+  hipLaunchKernelGGL(k_lotd_scatter, grid, dim3(256), 0, (hipStream_t)stream, sa);
   NSIM_CHECK_LAUNCH();
   return 0;
 }

@@ -8,9 +8,6 @@
 // code_single/configs/object_centric/lotd_neus.dtu.230814.yaml:186-247).  Executable spec: oracle/distant.py.
 // Same register-resident transposed-MFMA scheme as field.hip (mfma_mlp.h); no second-order terms are needed here
 // (the distant model has ``use_nablas: false``).
-#ifndef NSIM_SCATTER_SCAN_EXIT
-#define NSIM_SCATTER_SCAN_EXIT 1
-#endif
 #include "mfma_mlp.h"
 #include <stdlib.h>
 
@@ -769,14 +766,12 @@ struct Scatter4Args {
   int64_t S;
   const float* dh_pl;
   float* dgrid;
-  int dedup_max_rw;
-  int parity_slots;
+  int dedup_max_rw;     // 1 << 30: every level is folded (3.62 -> 1.73 ms per 0.52 M shell points; levels with Rw <= 16 / 64 only: 2.07 / 1.76)
+  int parity_slots;     // 1.  Both stay run-time values: as constants the kernel needs 87-88 instead of 86 registers
 };
 
-// CONSEC (default since round 6, NSIM_SCATTER_GROUP=0: off): issue I of the quad transposition carries the 16 consecutive shells
-// 16 I + q instead of the shells 4q + I; with the parity slots (NSIM_SCATTER_PARITY) the street step's 4-D scatter went
-// 2.15 -> 1.99 (parity slots) -> 1.74 ms (+ consecutive issue), see k_lotd_scatter in field.hip
-template <bool CONSEC>
+// Issue I of the quad transposition carries the 16 consecutive shells 16 I + q (not the shells 4q + I); with the parity slots
+// the street step's 4-D scatter went 2.15 -> 1.99 (parity slots) -> 1.74 ms (+ consecutive issue), see k_lotd_scatter in field.hip
 __global__ void __launch_bounds__(256) k_lotd4_scatter(Scatter4Args a) {
   const int lane = nsim_lane();
   const int l = blockIdx.y;
@@ -828,8 +823,8 @@ __global__ void __launch_bounds__(256) k_lotd4_scatter(Scatter4Args a) {
 #pragma unroll
           for (int d = 1; d < 64; d <<= 1) {
             // (wave-uniform early exit: no run of this slot reaches d lanes back -- at the fine levels runs are 1-3 lanes long
-            // and two of the six rounds do all the work; -DNSIM_SCATTER_SCAN_EXIT=0 keeps all six)
-            if (NSIM_SCATTER_SCAN_EXIT && !wave_ballot(lane - d >= run_start)) break;
+            // and two of the six rounds do all the work)
+            if (!wave_ballot(lane - d >= run_start)) break;
             const float o0 = wave_shfl(v0[dx], lane - d), o1 = wave_shfl(v1[dx], lane - d);
             if (lane - d >= run_start) {
               v0[dx] += o0;
@@ -839,36 +834,17 @@ __global__ void __launch_bounds__(256) k_lotd4_scatter(Scatter4Args a) {
           emit[dx] = valid && (lane == 63 || ((heads >> (lane + 1)) & 1ull));   // last lane of the run
         }
       }
-#define NSIM_QUAD4(I)                                                                                      \
-  {                                                                                                        \
-    const uint32_t i0 = quad_bcast<I>(idx[0]), i1 = quad_bcast<I>(idx[1]);                                 \
-    const float a0 = quad_bcast<I>(v0[0]), a1 = quad_bcast<I>(v1[0]);                                      \
-    const float b0 = quad_bcast<I>(v0[1]), b1 = quad_bcast<I>(v1[1]);                                      \
-    const int e0 = quad_bcast<I>(emit[0]), e1 = quad_bcast<I>(emit[1]);                                    \
-    const uint32_t ii = rq < 2 ? i0 : i1;                                                                  \
-    const float vv = rq == 0 ? a0 : (rq == 1 ? a1 : (rq == 2 ? b0 : b1));                                  \
-    const int ee = rq < 2 ? e0 : e1;                                                                       \
-    if (ee) atomicAdd(base + 2 * (int64_t)ii + (rq & 1), vv);                                              \
-  }
-      if constexpr (CONSEC) {
-        const uint32_t k0 = emit[0] ? idx[0] : 0xffffffffu, k1 = emit[1] ? idx[1] : 0xffffffffu;
+      const uint32_t k0 = emit[0] ? idx[0] : 0xffffffffu, k1 = emit[1] ? idx[1] : 0xffffffffu;
 #pragma unroll
-        for (int I = 0; I < 4; ++I) {
-          const int src = 16 * I + (lane >> 2);
-          const uint32_t i0 = wave_shfl(k0, src), i1 = wave_shfl(k1, src);
-          const float a0 = wave_shfl(v0[0], src), a1 = wave_shfl(v1[0], src);
-          const float b0 = wave_shfl(v0[1], src), b1 = wave_shfl(v1[1], src);
-          const uint32_t ii = rq < 2 ? i0 : i1;
-          const float vv = rq == 0 ? a0 : (rq == 1 ? a1 : (rq == 2 ? b0 : b1));
-          if (ii != 0xffffffffu) atomicAdd(base + 2 * (int64_t)ii + (rq & 1), vv);
-        }
-      } else {
-        NSIM_QUAD4(0)
-        NSIM_QUAD4(1)
-        NSIM_QUAD4(2)
-        NSIM_QUAD4(3)
+      for (int I = 0; I < 4; ++I) {
+        const int src = 16 * I + (lane >> 2);
+        const uint32_t i0 = wave_shfl(k0, src), i1 = wave_shfl(k1, src);
+        const float a0 = wave_shfl(v0[0], src), a1 = wave_shfl(v1[0], src);
+        const float b0 = wave_shfl(v0[1], src), b1 = wave_shfl(v1[1], src);
+        const uint32_t ii = rq < 2 ? i0 : i1;
+        const float vv = rq == 0 ? a0 : (rq == 1 ? a1 : (rq == 2 ? b0 : b1));
+        if (ii != 0xffffffffu) atomicAdd(base + 2 * (int64_t)ii + (rq & 1), vv);
       }
-#undef NSIM_QUAD4
     }
   }
 }
@@ -967,8 +943,7 @@ int nsim_distant_fwd(const NsimDistantMeta* meta, const void* grid_f16, const vo
   a.u4 = u4; a.rays_d = rays_d; a.h_appear = h_appear;
   a.S = S; a.K = K;
   a.sigma = sigma; a.rgb = rgb; a.h_pl = h_planes;
-  static const bool fused_gather = getenv("NSIM_DISTANT_FUSED_GATHER") && atoi(getenv("NSIM_DISTANT_FUSED_GATHER")) == 1;
-  if (h_planes && !fused_gather) {        // training: the table reads as their own level-major launch, decoders on the planes
+  if (h_planes) {        // training: the table reads as their own level-major launch, decoders on the planes
     Gather4Args g;
     g.lotd = a.lotd;
     g.grid = a.grid;
@@ -1034,16 +1009,10 @@ int nsim_lotd4_scatter(const NsimLotd4Meta* meta, const float* u4, const uint8_t
   Scatter4Args sa;
   sa.lotd = lotd4_dev(meta);
   sa.u4 = u4; sa.valid = valid; sa.S = S; sa.dh_pl = dh_planes; sa.dgrid = dgrid;
-  sa.dedup_max_rw = 1 << 30;      // every level: 3.62 -> 1.73 ms per 0.52 M shell points (levels with Rw <= 16 / 64 only: 2.07 / 1.76)
-  if (const char* e = getenv("NSIM_DEDUP4_MAX_RW")) sa.dedup_max_rw = atoi(e);
-  const char* ep = getenv("NSIM_SCATTER_PARITY");
-  sa.parity_slots = !(ep && atoi(ep) == 0);
+  sa.dedup_max_rw = 1 << 30;
+  sa.parity_slots = 1;
   const dim3 grid(nsim_blocks((S + 63) / 64, 4, 4096), meta->num_levels);
-  const char* eg = getenv("NSIM_SCATTER_GROUP");
-  if (!(eg && atoi(eg) == 0))
-    hipLaunchKernelGGL(k_lotd4_scatter<true>, grid, dim3(256), 0, (hipStream_t)stream, sa);
-  else
-    hipLaunchKernelGGL(k_lotd4_scatter<false>, grid, dim3(256), 0, (hipStream_t)stream, sa);
+  hipLaunchKernelGGL(k_lotd4_scatter, grid, dim3(256), 0, (hipStream_t)stream, sa);
   NSIM_CHECK_LAUNCH();
   return 0;
 }

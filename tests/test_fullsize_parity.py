@@ -319,7 +319,7 @@ def _api_path_body(precision, compressed, encoding):
         assert rec["fix_grad_" + k] < gtol, (k, rec["fix_grad_" + k])
     if not e2e_tight:
         # random cotangents: f32 = the exact-f32 kernels, fp16 = f16 MFMA operands / f16 tables.  Measured over three fresh
-        # device pre-trainings (tools/r6_ab1.sh): f32 <= 3.6e-6 on two fields and 8.8e-4 (radiance weights; a field with
+        # device pre-trainings on an MI355X: f32 <= 3.6e-6 on two fields and 8.8e-4 (radiance weights; a field with
         # normals of magnitude ~10, see gtol above) on the third; fp16 <= 1.4e-2 (radiance weights), <= 3e-3 table / decoder
         for k in ("grid", "sdf_w", "sdf_b", "rad_w", "rad_b"):
             assert rec["rnd_grad_" + k] < (5e-3 if precision == "f32" else 5e-2), (k, rec["rnd_grad_" + k])

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Per-kernel timing of the field kernels on one fixed render batch (8192 rays of the bench workload), with the
-NSIM_ABLATE / NSIM_DEDUP_MAX_RES profiling knobs of csrc/field.hip.  Development aid, not part of the product."""
+NSIM_DEDUP_MAX_RES knob of the table scatter (csrc/field.hip).  Development aid, not part of the product."""
 import os
 import sys
 from pathlib import Path
@@ -16,11 +16,9 @@ def main():
     dev = torch.device("cuda", 0)
     tr = bench.build_trainer(dev, 0, 1)
     xy, fidx, gt = tr.sample_batch()
-    variants = [("full", {}), ("no-scatter", {"NSIM_ABLATE": "1"}), ("no-dW", {"NSIM_ABLATE": "4"}),
-                ("no-scatter,no-dW", {"NSIM_ABLATE": "5"}), ("no-dedup", {"NSIM_DEDUP_MAX_RES": "0"}),
-                ("dedup-all", {"NSIM_DEDUP_MAX_RES": "4096"})]
+    variants = [("full", {}), ("no-dedup", {"NSIM_DEDUP_MAX_RES": "0"}), ("dedup-all", {"NSIM_DEDUP_MAX_RES": "4096"})]
     for name, env in variants:
-        for k in ("NSIM_ABLATE", "NSIM_DEDUP_MAX_RES"):
+        for k in ("NSIM_DEDUP_MAX_RES",):
             os.environ.pop(k, None)
         os.environ.update(env)
         for rep in range(3):
@@ -44,7 +42,7 @@ if __name__ == "__main__" and "--lotd" not in sys.argv:
 def lotd_standalone():
     """How fast is the un-fused, high-occupancy gather / scatter (csrc/lotd.hip) on the same sample set?"""
     dev = torch.device("cuda", 0)
-    for k in ("NSIM_ABLATE", "NSIM_DEDUP_MAX_RES"):
+    for k in ("NSIM_DEDUP_MAX_RES",):
         os.environ.pop(k, None)
     tr = bench.build_trainer(dev, 0, 1)
     xy, fidx, gt = tr.sample_batch()

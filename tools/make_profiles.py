@@ -161,16 +161,15 @@ def main():
           f"(MI355X, {TAG}; 12 steps; ATen kernels left out: they are dominated by the one-off dataset synthesis of the set-up)",
           f"{TAG}_street_rocprofv3_kernel_stats.txt", own_only=True)
     for src, dst in (("prof_distant_bench.json", f"{TAG}_bench_n1_distant.json"), ("prof_street_bench.json", f"{TAG}_bench_n1_street.json"),
-                     ("prof_scatter_levels.json", f"{TAG}_scatter_levels.json"), ("prof_distant_pmc_sq.json", f"{TAG}_distant_pmc_sq.json"),
-                     ("prof_distant_fusedgather.json", f"{TAG}_bench_n1_distant_fused_gather.json")):
+                     ("prof_scatter_levels.json", f"{TAG}_scatter_levels.json"), ("prof_distant_pmc_sq.json", f"{TAG}_distant_pmc_sq.json")):
         f = G / src
         if f.exists():
             txt = f.read_text().strip()
             try:
-                (P / dst).write_text(json.dumps(json.loads(txt.splitlines()[-1] if src.endswith("bench.json") or "fusedgather" in src else txt), indent=1))
+                (P / dst).write_text(json.dumps(json.loads(txt.splitlines()[-1] if src.endswith("bench.json") else txt), indent=1))
             except Exception:
                 (P / dst).write_text(txt)
-    for src, dst in (("prof_ktime.txt", f"{TAG}_ktime_timelines.txt"), ("prof_field_bench.jsonl", f"{TAG}_field_bench.jsonl"),
+    for src, dst in (("prof_field_bench.jsonl", f"{TAG}_field_bench.jsonl"),
                      ("prof_bench_noreplicas.json", f"{TAG}_bench_n1_no_grad_replicas.json"),
                      ("prof_distant_lmgather.json", f"{TAG}_bench_n1_distant_noprofiler.json")):
         f = G / src

@@ -35,11 +35,8 @@ timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/p_street -o s -- $SCMD > $O
 python $R/tools/prof_summary.py $(find /tmp/p_street -name "*.db" | head -1) $O/prof_street_stats.json
 [ "${NSIM_PROFILE_EXTRAS:-0}" = "1" ] || exit 0      # the round-3 A/B legs below only on request
 timeout 300 python $R/tools/scatter_levels.py $O/prof_scatter_levels.json > /dev/null 2>&1
-# fused 4-D gather A/B WITHOUT a profiler on either side
+# the distant model WITHOUT a profiler
 timeout 300 python $R/bench.py --distant --steps 16 --warmup 8 --no-cpu-baseline --no-variants --no-parity > $O/prof_distant_lmgather.json 2>/dev/null
-NSIM_DISTANT_FUSED_GATHER=1 timeout 300 python $R/bench.py --distant --steps 16 --warmup 8 --no-cpu-baseline --no-variants --no-parity > $O/prof_distant_fusedgather.json 2>/dev/null
-# per-iteration s_memtime timelines of the decoder kernels (a -DNSIM_KTIME build next to the product library, if present)
-[ -f $R/neuralsim_amd/csrc/_probe/libnsim_hip_ktime.so ] && (cd $R && timeout 300 python tools/ktime.py > $O/prof_ktime.txt 2>/dev/null)
 # flush storm A/B: direct weight-gradient flush vs replicas, same command
 NSIM_GRAD_REPLICAS=1 timeout 300 $CMD > $O/prof_bench_noreplicas.json 2>/dev/null
 # per-entry-point times of a with-grad query: object / street / permuto shapes

@@ -59,7 +59,7 @@ def model(u, lod_res, T, group="strided", dedup=True, cross=False, slots="offset
     slots: 'offset' -- slot (dx, yz) holds the corner c0 + (dx, yz & 1, yz >> 1) (the kernel of rounds 1-5) | 'parity' -- slot
     (dx, yz) holds the vertex whose coordinates have those parities (round 6: a vertex shared by neighbouring cells keeps its slot,
     so the per-slot run merge folds it);  group: 'strided' (issue I = lanes 4q + I) | 'consecutive' (issue I = lanes 16 I + q:
-    NSIM_SCATTER_GROUP=1);  dedup: runs of equal vertex index on consecutive lanes of a slot are summed by shuffles first (the
+    the kernels' form);  dedup: runs of equal vertex index on consecutive lanes of a slot are summed by shuffles first (the
     kernel does);  cross ('offset' slots only): fold a sample's x + 1 corner into the next sample's x corner when they are the same
     vertex;  entry_bytes: 8 = two f32 per vertex (the kernel), 4 = a packed 2-byte pair per vertex (global_atomic_pk_add_*)."""
     S = u.shape[0]
@@ -132,8 +132,8 @@ def main():
                      ("corner-offset slots, consecutive issue", dict(group="consecutive")),
                      ("corner-offset slots, consecutive issue + cross-corner fold", dict(group="consecutive", cross=True)),
                      ("corner-offset slots, packed 2-byte pair per vertex (pk_add)", dict(entry_bytes=4)),
-                     ("PARITY slots, strided issue (round 6 kernel, default)", dict(slots="parity")),
-                     ("PARITY slots, consecutive issue (NSIM_SCATTER_GROUP=1)", dict(slots="parity", group="consecutive")),
+                     ("PARITY slots, strided issue", dict(slots="parity")),
+                     ("PARITY slots, consecutive issue (the kernels)", dict(slots="parity", group="consecutive")),
                      ("PARITY slots, consecutive issue, packed 2-byte pair per vertex", dict(slots="parity", group="consecutive", entry_bytes=4))):
         lv = model(u, lod_res, T, **kw)
         tot = sum(v["requests"] for v in lv)

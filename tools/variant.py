@@ -2,7 +2,7 @@
 """Development aid: build / run the bench on a VARIANT of the HIP library compiled with extra -D flags (A/B of compile-time
 tunables on one GPU box in one gpurun call).  The product library is untouched; variants live under csrc/_probe/<name>/.
 
-    python tools/variant.py build NAME "-DNSIM_SDF_NBUF=1 ..." [file.hip ...]   # here (hipcc cross-compiles); default: field.hip
+    python tools/variant.py build NAME "-DNSIM_SDF_MIN_WAVES=3 ..." [file.hip ...]   # here (hipcc cross-compiles); default: field.hip
     python tools/variant.py run NAME [bench args]                                  # on the GPU box
 """
 import os

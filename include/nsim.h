@@ -379,6 +379,22 @@ int nsim_field_sdf(const NsimFieldMeta* meta, const void* grid_f16, const void* 
                    const float* rays_o, const float* rays_d, const float* t, const int64_t* ridx,
                    const int64_t* ray_goff, int64_t S, const int64_t* n_dev, int64_t n_add, float* sdf,
                    const void* feat_planes, float* occ_val, const NsimOccMeta* occ_meta, float occ_inv_s, void* stream);
+/* Sphere tracing of R rays against the SDF (``query_mode: sphere_trace`` + ``model.tracer.trace``: the library's
+ * csrc/sphere_trace extension behind app/visualizer/gui_runner_single_cuboid.py:76-104 and
+ * code_single/tools/inspect_rendering.py:71-73,262-287; its source is absent, the semantics are fixed in DESIGN sec. 7).
+ * One persistent launch; the SDF is the fused point-major query of nsim_field_sdf (same meta / grid / weight pack, <= 16
+ * levels), empty space is skipped on the marching lattice of nsim_march_* with jitter 0 (bits / meta / step / max_steps as
+ * there).  Per ray, from t = near: [skip to the next occupied lattice point, OUT if none] -> s = sdf(o + t d), n_steps += 1
+ * -> HIT if s <= hit_threshold -> t += max(distance_scale s, min_step) -> OUT if t > far -> ALIVE if n_steps == max_iters.
+ * Outputs by ray: status (0 ALIVE, 1 HIT, 2 OUT; inspect_rendering.py:285), n_steps, and (t_out, sdf_out) = depth and value of
+ * the ray's LAST query -- the hit point of a HIT ray; (near, NaN) for a ray that never queried.  Results do not depend on
+ * the schedule.  workspace: nsim_sphere_trace_workspace_bytes() bytes of device memory, contents irrelevant (the ray cursor). */
+int64_t nsim_sphere_trace_workspace_bytes(void);
+int nsim_sphere_trace(const NsimFieldMeta* meta, const void* grid_f16, const void* wpack, const float* rays_o,
+                      const float* rays_d, const float* near, const float* far, int64_t R, const uint32_t* occ_bits,
+                      const NsimOccMeta* occ_meta, float march_step, int max_steps, float distance_scale, float min_step,
+                      float hit_threshold, int max_iters, float* t_out, float* sdf_out, uint8_t* status_out,
+                      int32_t* n_steps_out, void* workspace, void* stream);
 /* Level-major LoTD gather of the no-grad query (the encoding half of forward_sdf): feat_planes [NLP][P] (NLP = 16 for <= 16 levels, 32 above;
  * P = NSIM_PLANE_PITCH(S): a 32-point tile of a level is one aligned 128 B | 256 B piece, which nsim_field_sdf copies
  * straight into LDS, global_load_lds_dwordx4, one tile ahead) of

@@ -123,6 +123,8 @@ SIGNATURES = {
     "nsim_lotd_bwd": [_P, _P, _P, C.POINTER(LotdMeta), _I64, _P],
     "nsim_field_pack_weights": [C.POINTER(FieldMeta), _P, _P, _P, _P, _P],
     "nsim_field_sdf": [C.POINTER(FieldMeta), _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, C.POINTER(OccMeta), _F],
+    "nsim_sphere_trace": [C.POINTER(FieldMeta), _P, _P, _P, _P, _P, _P, _I64, _P, C.POINTER(OccMeta), _F, _I, _F, _F, _F, _I, _P,
+                          _P, _P, _P, _P],
     "nsim_lotd_gather_lm": [C.POINTER(FieldMeta), _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P],
     "nsim_field_fwd": [C.POINTER(FieldMeta), _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64],
     "nsim_compose_collect_sort": [_P, _I, _P, _I64, _P],
@@ -177,6 +179,7 @@ NOSTREAM = {
     "nsim_version": ([], _I),
     "nsim_field_wpack_bytes": ([C.POINTER(FieldMeta)], _I64),
     "nsim_jplane_elem_bytes": ([C.POINTER(FieldMeta)], _I),
+    "nsim_sphere_trace_workspace_bytes": ([], _I64),
     "nsim_distant_wpack_bytes": ([C.POINTER(DistantMeta)], _I64),
     "nsim_sky_wpack_bytes": ([C.POINTER(SkyMeta)], _I64),
     "nsim_sky_plane_pitch": ([_I64], _I64),

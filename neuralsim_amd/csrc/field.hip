@@ -1728,6 +1728,177 @@ static void launch_gather_lm(const FieldArgs& a, int64_t S, hipStream_t stream) 
   hipLaunchKernelGGL((k_lotd_gather_lm<PREC, WJ>), gg, dim3(64), 0, stream, a);
 }
 
+// The three pieces of the point-major no-grad query, shared by k_field_sdf and k_sphere_trace (a point is one MFMA column:
+// its SDF does not depend on the other 31 points of the tile).
+// (1) the 8 features of one first-layer K-step -- levels lb + 4 qq + 2 hi + b -- gathered from the table at p.xx
+__device__ __forceinline__ void sdf_gather8(const FieldArgs& a, const GridRef& gref, const TilePoint& p, int lb, int hi,
+                                            float (&f8)[8]) {
+#pragma unroll
+  for (int qq = 0; qq < 2; ++qq) {
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int l = lb + 4 * qq + 2 * hi + b;
+      const LotdRes R = a.lotd.res[l];
+      const LotdCell c = lotd_cell(p.xx, R, a.lotd);
+      float f0 = 0.f, f1 = 0.f;
+      const int pm = lotd_slot_mask(c);
+      if (l < a.lotd.n_active)
+#pragma unroll
+      for (int slot = 0; slot < 8; ++slot) {
+        const int corner = slot ^ pm;
+        float w, dw[3];
+        lotd_corner_w(c, corner, w, dw);
+        const uint32_t idx = lotd_index(c.c0[0] + (corner & 1), c.c0[1] + ((corner >> 1) & 1),
+                                        c.c0[2] + ((corner >> 2) & 1), R, a.lotd.type[l], a.lotd.size[l]);
+        float g0, g1;
+        lotd_load2(gref, (uint32_t)a.lotd.offset[l] + p.goff + 2u * idx, g0, g1);
+        f0 = f0 + w * g0;
+        f1 = f1 + w * g1;
+      }
+      f8[4 * qq + 2 * b] = f0;
+      f8[4 * qq + 2 * b + 1] = f1;
+    }
+  }
+}
+
+// (2) one K-step of the first layer: acc += W1[:, K-step rb] . features (HAVE_BV, fp16 mode: ``bvp`` holds them converted)
+template <int PREC, int NC, bool HAVE_BV>
+__device__ __forceinline__ void sdf_layer1_step(const char* W, const FieldLayout& L, int rb, int lane, const float (&f8)[8],
+                                                const f16x8& bvp, f32x16 (&acc)[2], f32x16 (&accc)[PREC == 2 ? 2 : 1]) {
+  constexpr bool PLANES = HAVE_BV;
+  if constexpr (PREC == 0) {
+    f16x8 bv;
+    if constexpr (PLANES) {
+      bv = bvp;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) bv[e] = (f16)f16_sat(f8[e] * SDF_H_SCALE);
+    }
+    const f16x8* A = reinterpret_cast<const f16x8*>(W + L.mat[M_W1]);
+#pragma unroll
+    for (int mo = 0; mo < 2; ++mo) acc[mo] = mfma_32x32x16_f16(A[(mo * 2 * NC + rb) * 64 + lane], bv, acc[mo]);
+  } else if constexpr (PREC == 2) {
+    f16x8 bh, bl;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      f16 h_, l_;
+      split_f16(f8[e] * SDF_H_SCALE, h_, l_);
+      bh[e] = h_;
+      bl[e] = l_;
+    }
+    const f16x8* Ah = reinterpret_cast<const f16x8*>(W + L.mat[M_W1]);
+    const f16x8* Al = Ah + 64 * 4 * NC;           // lo fragments follow the [64 x 32 NC] hi ones
+#pragma unroll
+    for (int mo = 0; mo < 2; ++mo) {
+      const int fi = (mo * 2 * NC + rb) * 64 + lane;
+      acc[mo] = mfma_32x32x16_f16(Ah[fi], bh, acc[mo]);
+      accc[mo] = mfma_32x32x16_f16(Ah[fi], bl, accc[mo]);
+      accc[mo] = mfma_32x32x16_f16(Al[fi], bh, accc[mo]);
+    }
+  } else {
+    const float* A = reinterpret_cast<const float*>(W + L.mat[M_W1]);
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+#pragma unroll
+      for (int mo = 0; mo < 2; ++mo)
+        acc[mo] = mfma_32x32x2_f32(A[(mo * 16 * NC + 8 * rb + e) * 64 + lane], f8[e], acc[mo]);
+  }
+}
+
+// (3) first-layer accumulators -> SDF: activation, second layer (SDF_D == 2), head, the sum over the two lane halves
+template <int PREC, int SDF_D>
+__device__ __forceinline__ float sdf_decode(const char* W, const FieldLayout& L, f32x16 (&acc)[2],
+                                            f32x16 (&accc)[PREC == 2 ? 2 : 1], int hi, int lane, float beta, float inv_beta,
+                                            float b_out) {
+  const float inv_h = PREC != 1 ? 1.0f / SDF_H_SCALE : 1.0f;
+  float sdf = 0.f;
+  if constexpr (PREC == 2) {
+#pragma unroll
+    for (int mo = 0; mo < 2; ++mo)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[mo][r] = acc[mo][r] + accc[mo][r] * (1.0f / SPLIT_LO_SCALE);
+  }
+  if constexpr (PREC == 2 && SDF_D == 2) {
+    // second layer on split operands: activations and weights as hi + lo, three MFMAs per K-step
+    f16x8 bqh[4], bql[4];
+#pragma unroll
+    for (int mo = 0; mo < 2; ++mo)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        f16 h_, l_;
+        split_f16(softplus_exact(acc[mo][r] * inv_h + vecf(W, L, V_B1, hi, mo * 16 + r), beta, inv_beta), h_, l_);
+        bqh[2 * mo + (r >> 3)][r & 7] = h_;
+        bql[2 * mo + (r >> 3)][r & 7] = l_;
+      }
+    const f16x8* A2h = reinterpret_cast<const f16x8*>(W + L.mat[M_W2]);
+    const f16x8* A2l = A2h + 64 * 8;                 // [64 x 64] hi fragments: 8 per lane
+#pragma unroll
+    for (int mo = 0; mo < 2; ++mo) {
+      f32x16 acc2 = zero16(), acc2c = zero16();
+#pragma unroll
+      for (int st = 0; st < 4; ++st) {
+        const int fi = (mo * 4 + st) * 64 + lane;
+        acc2 = mfma_32x32x16_f16(A2h[fi], bqh[st], acc2);
+        acc2c = mfma_32x32x16_f16(A2h[fi], bql[st], acc2c);
+        acc2c = mfma_32x32x16_f16(A2l[fi], bqh[st], acc2c);
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        sdf = sdf + vecf(W, L, V_WH, hi, mo * 16 + r) *
+                        softplus_exact(acc2[r] + acc2c[r] * (1.0f / SPLIT_LO_SCALE) + vecf(W, L, V_B2, hi, mo * 16 + r), beta,
+                                   inv_beta);
+    }
+  } else if constexpr (PREC == 2) {
+#pragma unroll
+    for (int mo = 0; mo < 2; ++mo)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        sdf = sdf + vecf(W, L, V_WH, hi, mo * 16 + r) *
+                        softplus_exact(acc[mo][r] * inv_h + vecf(W, L, V_B1, hi, mo * 16 + r), beta, inv_beta);
+  } else if constexpr (PREC == 0 && SDF_D == 2) {
+    // register-lean second layer: layer-1 activations are packed to f16 B fragments at once (16 VGPRs), each
+    // output M-tile is consumed by the head dot-product as soon as its four MFMAs retire
+    f16x8 bq[4];
+#pragma unroll
+    for (int mo = 0; mo < 2; ++mo)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        bq[2 * mo + (r >> 3)][r & 7] =
+            (f16)softplus_exact(acc[mo][r] * inv_h + vecf(W, L, V_B1, hi, mo * 16 + r), beta, inv_beta);
+    const f16x8* A2 = reinterpret_cast<const f16x8*>(W + L.mat[M_W2]);
+#pragma unroll
+    for (int mo = 0; mo < 2; ++mo) {
+      f32x16 acc2 = zero16();
+#pragma unroll
+      for (int st = 0; st < 4; ++st) acc2 = mfma_32x32x16_f16(A2[(mo * 4 + st) * 64 + lane], bq[st], acc2);
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        sdf = sdf + vecf(W, L, V_WH, hi, mo * 16 + r) *
+                        softplus_exact(acc2[r] + vecf(W, L, V_B2, hi, mo * 16 + r), beta, inv_beta);
+    }
+  } else {
+    float a1[32];
+#pragma unroll
+    for (int mo = 0; mo < 2; ++mo)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        a1[mo * 16 + r] = softplus_exact(acc[mo][r] * inv_h + vecf(W, L, V_B1, hi, mo * 16 + r), beta, inv_beta);
+    if constexpr (SDF_D == 2) {
+      float a2[32];
+      dense<PREC, 2, 2>(a2, W + L.mat[M_W2], a1, false);
+#pragma unroll
+      for (int k = 0; k < 32; ++k)
+        sdf = sdf + vecf(W, L, V_WH, hi, k) * softplus_exact(a2[k] + vecf(W, L, V_B2, hi, k), beta, inv_beta);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 32; ++k) sdf = sdf + vecf(W, L, V_WH, hi, k) * a1[k];
+    }
+  }
+  sdf = sdf + wave_shfl_xor(sdf, 32);
+  sdf = sdf + b_out;
+  return sdf;
+}
+
 // PLANES: the tile's plane image -- per level 32 points x (f16x2 | f32x2) = 128 B | 256 B, one aligned piece
 // thanks to the 32-point pitch -- is copied global -> LDS (global_load_lds_dwordx4: 8 | 4 levels per instruction) one tile
 // AHEAD into one buffer per wave (2 | 4 KB for <= 16 levels, twice that above; a second, alternating buffer measured
@@ -1817,166 +1988,156 @@ __global__ void __launch_bounds__(64 * FIELD_WAVES, NSIM_SDF_MIN_WAVES) k_field_
             }
           }
       } else {
-#pragma unroll
-      for (int qq = 0; qq < 2; ++qq) {
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-          const int l = lb + 4 * qq + 2 * hi + b;
-          const LotdRes R = a.lotd.res[l];
-          const LotdCell c = lotd_cell(p.xx, R, a.lotd);
-          float f0 = 0.f, f1 = 0.f;
-          const int pm = lotd_slot_mask(c);
-          if (l < a.lotd.n_active)
-#pragma unroll
-          for (int slot = 0; slot < 8; ++slot) {
-            const int corner = slot ^ pm;
-            float w, dw[3];
-            lotd_corner_w(c, corner, w, dw);
-            const uint32_t idx = lotd_index(c.c0[0] + (corner & 1), c.c0[1] + ((corner >> 1) & 1),
-                                            c.c0[2] + ((corner >> 2) & 1), R, a.lotd.type[l], a.lotd.size[l]);
-            float g0, g1;
-            lotd_load2(gref, (uint32_t)a.lotd.offset[l] + p.goff + 2u * idx, g0, g1);
-            f0 = f0 + w * g0;
-            f1 = f1 + w * g1;
-          }
-          f8[4 * qq + 2 * b] = f0;
-          f8[4 * qq + 2 * b + 1] = f1;
-        }
+        sdf_gather8(a, gref, p, lb, hi, f8);
       }
-      }
-      if constexpr (PREC == 0) {
-        f16x8 bv;
-        if constexpr (PLANES) {
-          bv = bvp;
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) bv[e] = (f16)f16_sat(f8[e] * SDF_H_SCALE);
-        }
-        const f16x8* A = reinterpret_cast<const f16x8*>(W + L.mat[M_W1]);
-#pragma unroll
-        for (int mo = 0; mo < 2; ++mo) acc[mo] = mfma_32x32x16_f16(A[(mo * 2 * NC + rb) * 64 + lane], bv, acc[mo]);
-      } else if constexpr (PREC == 2) {
-        f16x8 bh, bl;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          f16 h_, l_;
-          split_f16(f8[e] * SDF_H_SCALE, h_, l_);
-          bh[e] = h_;
-          bl[e] = l_;
-        }
-        const f16x8* Ah = reinterpret_cast<const f16x8*>(W + L.mat[M_W1]);
-        const f16x8* Al = Ah + 64 * 4 * NC;           // lo fragments follow the [64 x 32 NC] hi ones
-#pragma unroll
-        for (int mo = 0; mo < 2; ++mo) {
-          const int fi = (mo * 2 * NC + rb) * 64 + lane;
-          acc[mo] = mfma_32x32x16_f16(Ah[fi], bh, acc[mo]);
-          accc[mo] = mfma_32x32x16_f16(Ah[fi], bl, accc[mo]);
-          accc[mo] = mfma_32x32x16_f16(Al[fi], bh, accc[mo]);
-        }
-      } else {
-        const float* A = reinterpret_cast<const float*>(W + L.mat[M_W1]);
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-#pragma unroll
-          for (int mo = 0; mo < 2; ++mo)
-            acc[mo] = mfma_32x32x2_f32(A[(mo * 16 * NC + 8 * rb + e) * 64 + lane], f8[e], acc[mo]);
-      }
+      sdf_layer1_step<PREC, NC, PLANES>(W, L, rb, lane, f8, bvp, acc, accc);
     }
     if constexpr (PLANES) {                     // every lane has read the image, the next copy may overwrite it
       nsim_wait_lgkm0();
       if (tile + wstride < ntiles) prefetch_planes(tile + wstride);
     }
-    const float inv_h = PREC != 1 ? 1.0f / SDF_H_SCALE : 1.0f;
-    float sdf = 0.f;
-    if constexpr (PREC == 2) {
-#pragma unroll
-      for (int mo = 0; mo < 2; ++mo)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mo][r] = acc[mo][r] + accc[mo][r] * (1.0f / SPLIT_LO_SCALE);
-    }
-    if constexpr (PREC == 2 && SDF_D == 2) {
-      // second layer on split operands: activations and weights as hi + lo, three MFMAs per K-step
-      f16x8 bqh[4], bql[4];
-#pragma unroll
-      for (int mo = 0; mo < 2; ++mo)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          f16 h_, l_;
-          split_f16(softplus_exact(acc[mo][r] * inv_h + vecf(W, L, V_B1, hi, mo * 16 + r), beta, inv_beta), h_, l_);
-          bqh[2 * mo + (r >> 3)][r & 7] = h_;
-          bql[2 * mo + (r >> 3)][r & 7] = l_;
-        }
-      const f16x8* A2h = reinterpret_cast<const f16x8*>(W + L.mat[M_W2]);
-      const f16x8* A2l = A2h + 64 * 8;                 // [64 x 64] hi fragments: 8 per lane
-#pragma unroll
-      for (int mo = 0; mo < 2; ++mo) {
-        f32x16 acc2 = zero16(), acc2c = zero16();
-#pragma unroll
-        for (int st = 0; st < 4; ++st) {
-          const int fi = (mo * 4 + st) * 64 + lane;
-          acc2 = mfma_32x32x16_f16(A2h[fi], bqh[st], acc2);
-          acc2c = mfma_32x32x16_f16(A2h[fi], bql[st], acc2c);
-          acc2c = mfma_32x32x16_f16(A2l[fi], bqh[st], acc2c);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          sdf = sdf + vecf(W, L, V_WH, hi, mo * 16 + r) *
-                          softplus_exact(acc2[r] + acc2c[r] * (1.0f / SPLIT_LO_SCALE) + vecf(W, L, V_B2, hi, mo * 16 + r), beta,
-                                     inv_beta);
-      }
-    } else if constexpr (PREC == 2) {
-#pragma unroll
-      for (int mo = 0; mo < 2; ++mo)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          sdf = sdf + vecf(W, L, V_WH, hi, mo * 16 + r) *
-                          softplus_exact(acc[mo][r] * inv_h + vecf(W, L, V_B1, hi, mo * 16 + r), beta, inv_beta);
-    } else if constexpr (PREC == 0 && SDF_D == 2) {
-      // register-lean second layer: layer-1 activations are packed to f16 B fragments at once (16 VGPRs), each
-      // output M-tile is consumed by the head dot-product as soon as its four MFMAs retire
-      f16x8 bq[4];
-#pragma unroll
-      for (int mo = 0; mo < 2; ++mo)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          bq[2 * mo + (r >> 3)][r & 7] =
-              (f16)softplus_exact(acc[mo][r] * inv_h + vecf(W, L, V_B1, hi, mo * 16 + r), beta, inv_beta);
-      const f16x8* A2 = reinterpret_cast<const f16x8*>(W + L.mat[M_W2]);
-#pragma unroll
-      for (int mo = 0; mo < 2; ++mo) {
-        f32x16 acc2 = zero16();
-#pragma unroll
-        for (int st = 0; st < 4; ++st) acc2 = mfma_32x32x16_f16(A2[(mo * 4 + st) * 64 + lane], bq[st], acc2);
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          sdf = sdf + vecf(W, L, V_WH, hi, mo * 16 + r) *
-                          softplus_exact(acc2[r] + vecf(W, L, V_B2, hi, mo * 16 + r), beta, inv_beta);
-      }
-    } else {
-      float a1[32];
-#pragma unroll
-      for (int mo = 0; mo < 2; ++mo)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          a1[mo * 16 + r] = softplus_exact(acc[mo][r] * inv_h + vecf(W, L, V_B1, hi, mo * 16 + r), beta, inv_beta);
-      if constexpr (SDF_D == 2) {
-        float a2[32];
-        dense<PREC, 2, 2>(a2, W + L.mat[M_W2], a1, false);
-#pragma unroll
-        for (int k = 0; k < 32; ++k)
-          sdf = sdf + vecf(W, L, V_WH, hi, k) * softplus_exact(a2[k] + vecf(W, L, V_B2, hi, k), beta, inv_beta);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 32; ++k) sdf = sdf + vecf(W, L, V_WH, hi, k) * a1[k];
-      }
-    }
-    sdf = sdf + wave_shfl_xor(sdf, 32);
-    sdf = sdf + b_out;
+    const float sdf = sdf_decode<PREC, SDF_D>(W, L, acc, accc, hi, lane, beta, inv_beta, b_out);
     if (p.valid && hi == 0) a.sdf[p.s] = sdf;
     if (a.occ_val) {      // the 32 points of the tile are the hi == 0 lanes (neighbouring samples of a ray)
       const bool ok = p.valid && hi == 0;
       occ_collect_wave(a.occ_val, a.occ, ok, ok ? a.x[3 * p.s] : 0.f, ok ? a.x[3 * p.s + 1] : 0.f, ok ? a.x[3 * p.s + 2] : 0.f,
                        sdf, a.occ_inv_s);
+    }
+  }
+}
+
+// Sphere tracing (``query_mode: sphere_trace``), one persistent launch: every wave owns one MFMA tile of 32 rays (a ray is
+// the column j = lane & 31; both lane halves carry the same per-ray state and each gathers its half of the levels, as in
+// k_field_sdf).  Per iteration: x = o + t d, the point-major gather + decoder above, then per lane
+//   HIT if sdf <= hit_threshold;  t' = t + max(distance_scale sdf, min_step);  OUT if not t' <= far;  ALIVE if that was query
+//   number max_iters;  otherwise t = t', moved on to the next occupied point of the marching lattice when it lies in an
+//   unoccupied voxel (OUT when there is none) -- no SDF query is spent on empty space.
+// Lanes whose ray has finished take fresh rays from ONE device-side cursor (wave ballot + one atomicAdd per refill), so the
+// tiles stay full while the live set shrinks.  The cursor is the only state workgroups share: nobody waits for anybody, a
+// workgroup that starts after the cursor has run dry simply exits; the loop ends after at most max_iters queries per ray.
+// Results are written by ray index and a ray's trajectory is a function of the ray alone (one MFMA column), so they do not
+// depend on which wave traced it or next to whom.
+struct TraceArgs {
+  const float *rays_o, *rays_d, *near, *far;
+  int64_t R;
+  const uint32_t* occ_bits;
+  OccDev occ;
+  float march_step;
+  int max_steps;
+  float distance_scale, min_step, hit_threshold;
+  int max_iters;
+  float *t_out, *sdf_out;
+  uint8_t* status_out;
+  int32_t* n_steps_out;
+  int* cursor;
+};
+
+// step 1 of the tracer: t stays if its voxel is occupied, otherwise it moves to the smallest lattice point > t in an
+// occupied voxel (march_test: the points and the bitfield read of nsim_march_*, jitter 0); false = there is none
+__device__ __forceinline__ bool trace_skip_empty(const MarchRay& m, const OccDev& occ, const uint32_t* bits, float step,
+                                                 float& t) {
+  int64_t flat;
+  if (occ_voxel(occ, m.o[0] + t * m.d[0], m.o[1] + t * m.d[1], m.o[2] + t * m.d[2], flat) &&
+      ((bits[flat >> 5] >> (flat & 31)) & 1u))
+    return true;
+  float kf = floorf((t - m.near) / step) - 1.0f;      // an estimate from below of the first k with t_k > t
+  kf = fminf(fmaxf(kf, 0.f), (float)m.K);
+  int k = (int)kf;
+  while (k < m.K && !(m.near + ((float)k + m.jit) * step > t)) ++k;
+  for (; k < m.K; ++k) {
+    float tk;
+    if (march_test(m, occ, bits, k, step, tk)) {
+      t = tk;
+      return true;
+    }
+    if (!(tk < m.far)) break;
+  }
+  return false;
+}
+
+#define TRACE_ALIVE 0
+#define TRACE_HIT 1
+#define TRACE_OUT 2
+
+template <int PREC, int SDF_D>
+__global__ void __launch_bounds__(64 * FIELD_WAVES, NSIM_SDF_MIN_WAVES) k_sphere_trace(FieldArgs a, TraceArgs tr) {
+  NSIM_DYN_SMEM(smem);
+  const int lane = nsim_lane(), j = lane & 31, hi = lane >> 5;
+  const float beta = a.beta, inv_beta = 1.0f / a.beta;
+  FieldLayout L;
+  int wbytes;
+  const char* W = stage_weights<PREC>(smem, a, 0, 2, L, wbytes);   // W1, W2 only
+  const float b_out = reinterpret_cast<const float*>(W + L.vec[V_SCAL])[0];
+  const GridRef gref = grid_ref(a.grid);
+  MarchRay m = MarchRay();
+  int64_t ray = -1;                   // the ray of this column, -1: none
+  float t = 0.f, s_last = 0.f;
+  int n = 0;
+  bool dry = false;                   // (wave-uniform) the cursor has passed R
+  // (t_out, sdf_out) = the ray's last query; a ray that never queried keeps t = near and gets a NaN
+  auto finish = [&](int status) {
+    if (hi == 0) {
+      tr.t_out[ray] = t;
+      tr.sdf_out[ray] = n > 0 ? s_last : __builtin_nanf("");
+      tr.status_out[ray] = (uint8_t)status;
+      tr.n_steps_out[ray] = n;
+    }
+    ray = -1;
+  };
+  for (;;) {
+    // ---- refill: free columns take the next rays of the cursor; a fresh ray that finds no occupied point is OUT at once
+    // and frees its column again, so this repeats until the tile is full or the cursor is dry
+    for (;;) {
+      const uint32_t free_m = (uint32_t)wave_ballot(ray < 0);        // (the low half: one bit per column)
+      if (free_m == 0u || dry) break;
+      const int cnt = __popc(free_m);
+      int base = 0;
+      if (lane == 0) base = atomicAdd(tr.cursor, cnt);
+      base = wave_shfl(base, 0);
+      if ((int64_t)base + cnt >= tr.R) dry = true;
+      if (ray < 0) {
+        const int64_t r = (int64_t)base + __popc(free_m & ((1u << j) - 1u));
+        if (r < tr.R) {
+          ray = r;
+          m = march_load(tr.rays_o, tr.rays_d, tr.near, tr.far, nullptr, r, tr.march_step, tr.max_steps);
+          m.jit = 0.f;
+          t = m.near;
+          n = 0;
+          if (!(m.near <= m.far) || !trace_skip_empty(m, tr.occ, tr.occ_bits, tr.march_step, t)) finish(TRACE_OUT);
+        }
+      }
+    }
+    if (wave_ballot(ray >= 0) == 0ull) break;
+    // ---- query
+    TilePoint p;
+    p.valid = ray >= 0;
+    p.goff = 0u;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) p.xx[c] = p.valid ? m.o[c] + t * m.d[c] : 0.f;
+    f32x16 acc[2] = {zero16(), zero16()};
+    f32x16 accc[PREC == 2 ? 2 : 1];
+    if constexpr (PREC == 2) accc[0] = accc[1] = zero16();
+#pragma unroll 1
+    for (int rb = 0; rb < 2; ++rb) {
+      float f8[8];
+      f16x8 bvp;
+      sdf_gather8(a, gref, p, 8 * rb, hi, f8);
+      sdf_layer1_step<PREC, 1, false>(W, L, rb, lane, f8, bvp, acc, accc);
+    }
+    const float sdf = sdf_decode<PREC, SDF_D>(W, L, acc, accc, hi, lane, beta, inv_beta, b_out);
+    // ---- advance
+    if (ray >= 0) {
+      s_last = sdf;
+      ++n;
+      if (sdf <= tr.hit_threshold) {
+        finish(TRACE_HIT);
+      } else {
+        float tn = t + fmaxf(tr.distance_scale * sdf, tr.min_step);
+        if (!(tn <= m.far)) finish(TRACE_OUT);
+        else if (n >= tr.max_iters) finish(TRACE_ALIVE);
+        else if (!trace_skip_empty(m, tr.occ, tr.occ_bits, tr.march_step, tn)) finish(TRACE_OUT);
+        else t = tn;
+      }
     }
   }
 }
@@ -2534,6 +2695,34 @@ static int field_launch(const NsimFieldMeta* meta, const FieldArgs& a, size_t sh
   return 0;
 }
 
+// Workgroups of a persistent launch: as many as the device keeps resident (CU count x the kernel's occupancy at this
+// block size and LDS demand, asked of the runtime once per kernel and device), at most ``want``.
+template <class K>
+static int resident_workgroups(K kernel, int block, size_t shmem, int64_t want) {
+#ifdef __HIPCC__
+  struct Slot {
+    const void* fn;
+    int dev, n;
+  };
+  static Slot cache[32];
+  static int ncache = 0;
+  const int dev = current_device();
+  int n = 0;
+  for (int i = 0; i < ncache; ++i)
+    if (cache[i].fn == (const void*)kernel && cache[i].dev == dev) n = cache[i].n;
+  if (n == 0) {
+    int cus = 0, per_cu = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) return -1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, shmem) != hipSuccess || per_cu < 1) return -1;
+    n = cus * per_cu;
+    if (ncache < 32) cache[ncache++] = Slot{(const void*)kernel, dev, n};
+  }
+#else       // a host build without the HIP runtime (the tests' emulator): workgroups run one after another there -- two, so
+  int n = 2;  // that a workgroup also meets a cursor that another one has run dry
+#endif
+  return (int)(want < n ? (want < 1 ? 1 : want) : n);
+}
+
 // persistent grid of the point-major forward: the packed weights (58 KB) are staged into LDS once per workgroup
 #define FIELD_GRID_FWD 1024
 
@@ -2749,6 +2938,60 @@ int nsim_field_sdf(const NsimFieldMeta* meta, const void* grid_f16, const void* 
       case 5: hipLaunchKernelGGL((k_field_sdf<2, 2, false>), grid, block, shmem, (hipStream_t)stream, a); break;
     }
   }
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int64_t nsim_sphere_trace_workspace_bytes(void) { return 64; }
+
+int nsim_sphere_trace(const NsimFieldMeta* meta, const void* grid_f16, const void* wpack, const float* rays_o,
+                      const float* rays_d, const float* near, const float* far, int64_t R, const uint32_t* occ_bits,
+                      const NsimOccMeta* occ_meta, float march_step, int max_steps, float distance_scale, float min_step,
+                      float hit_threshold, int max_iters, float* t_out, float* sdf_out, uint8_t* status_out,
+                      int32_t* n_steps_out, void* workspace, void* stream) {
+  const int rc = field_meta_check(meta);
+  if (rc) return rc;
+  if (field_ne(meta)) return 36;
+  if (field_nc(meta->lotd.num_levels) == 2) return 33;      // the point-major gather exists for <= 16 levels
+  if (R < 0) return 2;
+  if (R == 0) return 0;
+  if (R >= ((int64_t)1 << 30) || max_iters < 1 || !(min_step > 0.f)) return 52;
+  if (!occ_meta || !occ_bits || !(march_step > 0.f) || max_steps < 0) return 5;
+  if (!(rays_o && rays_d && near && far && grid_f16 && wpack)) return 24;
+  if (!(t_out && sdf_out && status_out && n_steps_out && workspace)) return 4;
+  FieldArgs a = field_args(meta);
+  a.grid = (const f16*)grid_f16;
+  a.wpack = (const char*)wpack;
+  TraceArgs tr;
+  tr.rays_o = rays_o; tr.rays_d = rays_d; tr.near = near; tr.far = far;
+  tr.R = R;
+  tr.occ_bits = occ_bits;
+  tr.occ = occ_dev(occ_meta);
+  tr.march_step = march_step; tr.max_steps = max_steps;
+  tr.distance_scale = distance_scale; tr.min_step = min_step; tr.hit_threshold = hit_threshold;
+  tr.max_iters = max_iters;
+  tr.t_out = t_out; tr.sdf_out = sdf_out; tr.status_out = status_out; tr.n_steps_out = n_steps_out;
+  tr.cursor = (int*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(workspace, 0, 64, st) != hipSuccess) return 1000;
+  const size_t shmem = weights_lds_bytes(meta, 0, 2);
+  const dim3 block(64 * FIELD_WAVES);
+  const int64_t want = (R + 32 * FIELD_WAVES - 1) / (32 * FIELD_WAVES);      // one tile of rays per wave at least
+#define NSIM_TRACE_LAUNCH(P, D)                                                              \
+  {                                                                                          \
+    const int nb = resident_workgroups(k_sphere_trace<P, D>, 64 * FIELD_WAVES, shmem, want); \
+    if (nb < 1) return 53;                                                                   \
+    hipLaunchKernelGGL((k_sphere_trace<P, D>), dim3((unsigned)nb), block, shmem, st, a, tr); \
+  }
+  switch (meta->precision * 2 + (meta->sdf_D - 1)) {
+    case 0: NSIM_TRACE_LAUNCH(0, 1) break;
+    case 1: NSIM_TRACE_LAUNCH(0, 2) break;
+    case 2: NSIM_TRACE_LAUNCH(1, 1) break;
+    case 3: NSIM_TRACE_LAUNCH(1, 2) break;
+    case 4: NSIM_TRACE_LAUNCH(2, 1) break;
+    case 5: NSIM_TRACE_LAUNCH(2, 2) break;
+  }
+#undef NSIM_TRACE_LAUNCH
   NSIM_CHECK_LAUNCH();
   return 0;
 }

@@ -64,3 +64,38 @@ __device__ __forceinline__ void occ_collect_wave(float* __restrict__ val, const 
   memcpy(&iv, &v, 4);
   atomicMax((int*)val + flat, iv);
 }
+
+// ------------------------------------------------------------------------------------------ marching lattice
+// t_k = near + (k + jitter) * step, k < K = clamp(ceil((far - near) / step), 0, max_steps), t_k < far: the samples of
+// nsim_march_* (sampling.hip) and the empty-space skip of nsim_sphere_trace (field.hip) test the same points the same way.
+struct MarchRay {
+  float o[3], d[3], near, far, jit;
+  int K;
+};
+
+__device__ __forceinline__ MarchRay march_load(const float* rays_o, const float* rays_d, const float* near,
+                                               const float* far, const float* jitter, int64_t r, float step,
+                                               int max_steps) {
+  MarchRay m;
+  for (int a = 0; a < 3; ++a) {
+    m.o[a] = rays_o[3 * r + a];
+    m.d[a] = rays_d[3 * r + a];
+  }
+  m.near = near[r];
+  m.far = far[r];
+  m.jit = jitter ? jitter[r] : 0.5f;
+  float kf = ceilf((m.far - m.near) / step);
+  kf = fminf(fmaxf(kf, 0.f), (float)max_steps);
+  m.K = (int)kf;
+  return m;
+}
+
+__device__ __forceinline__ bool march_test(const MarchRay& m, const OccDev& occ, const uint32_t* bits, int k,
+                                           float step, float& t) {
+  t = m.near + ((float)k + m.jit) * step;
+  if (k >= m.K || !(t < m.far)) return false;
+  const float px = m.o[0] + t * m.d[0], py = m.o[1] + t * m.d[1], pz = m.o[2] + t * m.d[2];
+  int64_t flat;
+  if (!occ_voxel(occ, px, py, pz, flat)) return false;
+  return (bits[flat >> 5] >> (flat & 31)) & 1u;
+}

@@ -69,6 +69,7 @@ class BatchedRaysMixin:
     tables: table + occupancy offsets per pair) and the batched permutohedral model (one table, a latent per pair:
     fields/batched_permuto_neus.py).  The model provides ``ins_inds_per_batch`` (the condition) and
     ``_pair_extras(ins [R], which [R]) -> dict`` merged into the tested-rays dict of the single-model ``ray_query``."""
+    _sphere_trace_ok = False        # query_mode: sphere_trace traces one instance (no per-ray table / occupancy offsets)
 
     # ------------------------------------------------------------------ batched rays (buffer_compose_renderer.py:222-265)
     def batched_ray_test(self, rays_o: torch.Tensor, rays_d: torch.Tensor, near=None, far=None, compact_batch=True,

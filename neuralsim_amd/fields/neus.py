@@ -70,6 +70,9 @@ def append_extra_points(model, rays_o, rays_d, t, ridx, h_appear, extra_x):
     return rays_o, rays_d, t, ridx, h_appear
 
 
+QUERY_MODES = ("march_occ_multi_upsample", "march_occ_multi_upsample_compressed", "sphere_trace")
+
+
 def fine_list(qp: dict):
     """``num_fine`` per up-sampling stage.  A list names the stages (``num_fine [8, 8, 32]`` with ``upsample_inv_s_factors [1, 4,
     16]``, lotd_neus.dtu.230814.yaml:150-152); the multi-object configs give ONE number next to two factors (``num_fine: 16,
@@ -1577,9 +1580,15 @@ class LoTDNeuSModel(ModelMixin, nn.Module):
 
     def ray_query(self, *, ray_input: dict = None, ray_tested: dict, config, return_buffer: bool = True,
                   return_details: bool = False, render_per_obj_individual: bool = False) -> Dict:
-        """``query_mode = march_occ_multi_upsample`` (single_volume_renderer.py:244-246)."""
+        """``query_mode = march_occ_multi_upsample[_compressed]`` (single_volume_renderer.py:244-246) | ``sphere_trace``
+        (inspect_rendering.py:98-109; ``_ray_query_sphere_trace``)."""
         cfg = dict(config)
         qp = dict(cfg.get("query_param", self.ray_query_cfg.get("query_param", {})))
+        mode = cfg.get("query_mode", self.ray_query_cfg.get("query_mode", "march_occ_multi_upsample"))
+        if mode not in QUERY_MODES:
+            raise ValueError(f"query_mode={mode!r}: this model knows {', '.join(QUERY_MODES)}")
+        if mode == "sphere_trace":
+            return self._ray_query_sphere_trace(ray_input, ray_tested, cfg, qp, return_details, render_per_obj_individual)
         with_rgb = cfg.get("with_rgb", True)
         with_normal = cfg.get("with_normal", False)
         if cfg.get("with_feature_dim", 0):          # ``n_extra_feat_from_output`` is 0 in every config of the hot path
@@ -1616,7 +1625,6 @@ class LoTDNeuSModel(ModelMixin, nn.Module):
         # built now, and ``_compress`` calls ``spec_launch`` -- gather + decoders at a CAPACITY, point count read on the
         # device -- before the host waits for the size of the kept set (see ``_compress``; NSIM_SPEC_FORWARD=0: off)
         spec = None
-        mode = cfg.get("query_mode", self.ray_query_cfg.get("query_mode", "march_occ_multi_upsample"))
         if (_SPEC_FORWARD and type(self) is LoTDNeuSModel and mode.endswith("_compressed") and torch.is_grad_enabled()
                 and self.encoding.flattened_params.requires_grad and not (o_g.requires_grad or d_g.requires_grad)):
             M = int(extra_x.shape[0]) if extra_x is not None else 0
@@ -1703,4 +1711,89 @@ class LoTDNeuSModel(ModelMixin, nn.Module):
             # the model's space (x = o + near d).  (Implementation in the absent nr3d_lib: semantics fixed here.)
             x_near = (o + ray_tested["near"].float()[:, None] * d).detach()
             ret.setdefault("details", {})["near_sdf"] = self.forward_sdf_nablas(x_near, nablas_has_grad=False)["sdf"]
+        return ret
+
+    # ------------------------------------------------------------------ sphere tracing
+    _sphere_trace_ok = True         # (the permutohedral and the batched models: not yet)
+
+    @property
+    def tracer(self):
+        """``obj.model.tracer`` (inspect_rendering.py:262): fields/sphere_trace.py."""
+        tr = self.__dict__.get("_tracer")
+        if tr is None:
+            from .sphere_trace import SphereTracer
+            tr = SphereTracer(self)
+            object.__setattr__(self, "_tracer", tr)
+        return tr
+
+    @torch.no_grad()
+    def _ray_query_sphere_trace(self, ray_input, ray_tested: dict, cfg: dict, qp: dict, return_details: bool,
+                                render_per_obj_individual: bool) -> Dict:
+        """``query_mode = sphere_trace``: surface rendering.  The tested rays are traced to their first surface point (one
+        persistent launch, fields/sphere_trace.py) and the volume buffer holds exactly ONE sample per hit ray, at the hit depth,
+        with ``opacity_alpha = 1`` -- so the renderers' compositing returns that sample's colour, depth and normal.  ``sdf``,
+        ``nablas`` (, ``rgb``) of the sample come from the with-grad-capable query at the hit points, without gradient: the mode is
+        evaluation-only.  One host read (the number of hit rays)."""
+        from .sphere_trace import HIT, trace_params
+        if not self._sphere_trace_ok:
+            raise NotImplementedError(f"query_mode='sphere_trace': not implemented for {type(self).__name__}")
+        prm = trace_params(qp)
+        with_rgb, with_normal = cfg.get("with_rgb", True), cfg.get("with_normal", False)
+        if cfg.get("with_feature_dim", 0):
+            raise NotImplementedError("with_feature_dim > 0: the decoders of this model emit no extra feature channels")
+        R = ray_tested["num_rays"]
+        dev = ray_tested["rays_inds"].device
+        n_all = None
+        if render_per_obj_individual and ray_input is not None and ray_input.get("rays_o") is not None:
+            n_all = int(ray_input["rays_o"].shape[0])
+        want_render = render_per_obj_individual or cfg.get("_render", False)
+        ret = dict()
+
+        def empty(details):
+            ret["volume_buffer"] = dict(type="empty")
+            if want_render:
+                z = lambda *sh: torch.zeros([n_all or 0, *sh], dtype=torch.float32, device=dev)      # noqa: E731
+                ret["rendered"] = dict(mask_volume=z(), depth_volume=z())
+                if with_rgb:
+                    ret["rendered"]["rgb_volume"] = z(3)
+                if with_normal or cfg.get("_render", False):
+                    ret["rendered"]["normals_volume"] = z(3)
+            if return_details:
+                ret["details"] = details
+            return ret
+        if R == 0:
+            return empty(dict())
+        tracer = self.tracer
+        o, d, near, far = tracer._rays(ray_tested)
+        march = tracer._march_cfg(qp)
+        if tracer.use_kernel:
+            res = tracer.trace_kernel(o, d, near, far, prm, march=march)
+        else:
+            res = tracer.trace_replay(o, d, near, far, prm, march=march)
+        details = dict(status=res["status"], n_steps=res["n_steps"], t=res["t"], sdf_nograd=res["sdf"])
+        idx = (res["status"] == HIT).nonzero()[:, 0]        # host read: the number of hit rays
+        H = int(idx.shape[0])
+        if H == 0:
+            return empty(details)
+        t = res["t"][idx].contiguous()
+        h_appear = ray_tested.get("rays_h_appear", None)
+        outs = _FieldFn.apply(self, self._table(), self.sdf_w, self.sdf_b, self.rad_w, self.rad_b,
+                              h_appear if with_rgb else None, None, o, d, t, idx, bool(with_rgb), None, None, None)
+        sdf, nablas = outs[0], outs[1]
+        pi = torch.stack([torch.arange(H, device=dev), torch.ones([H], dtype=torch.long, device=dev)], dim=-1)
+        alpha = torch.ones([H], dtype=torch.float32, device=dev)
+        self._rays_sel = idx
+        vb = dict(type="packed", rays_inds_hit=ray_tested["rays_inds"][idx], pack_infos_hit=pi, t=t, opacity_alpha=alpha,
+                  nablas=nablas, sdf=sdf)
+        if with_rgb:
+            vb["rgb"] = outs[2]
+        ret["volume_buffer"] = vb
+        if want_render:
+            ret["rendered"] = volume_integration(alpha, t, vb.get("rgb"), nablas if (with_normal or cfg.get("_render", False)) else None,
+                                                 pi, cfg.get("depth_use_normalized_vw", True),
+                                                 rays_inds=vb["rays_inds_hit"] if n_all is not None else None, num_rays=n_all)
+            ret["rendered"].pop("vw", None)
+            ret["rendered"].pop("trans", None)
+        if return_details:
+            ret["details"] = details
         return ret

@@ -98,6 +98,7 @@ class PermutoNeuSModel(LoTDNeuSModel):
     ``z_dim`` > 0: ``set_condition(z)`` with z [R_or_1, z_dim] makes every ray (or all of them) carry a latent that is
     concatenated to the position (GenerativePermutoConcat); ``z`` rides along ``ridx`` inside the kernels."""
     planes_always = True
+    _sphere_trace_ok = False        # query_mode: sphere_trace steps on the LoTD point-major query (fields/neus.py)
 
     def __init__(self, permuto_auto_compute_cfg: Optional[dict] = None, z_dim: int = 0, param_bound: float = 1e-4,
                  seed: int = 42, device=None, **kw):

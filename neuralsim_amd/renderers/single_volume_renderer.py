@@ -18,6 +18,7 @@ There is no Scene graph here: the model is passed directly (the reference looks 
 ``scene.get_drawable_groups_by_class_name``), rays are expected in the model's object space.
 """
 import os
+from collections.abc import Mapping
 from typing import Callable, Dict, List, Optional
 
 import torch
@@ -111,7 +112,10 @@ class SingleVolumeRenderer(nn.Module):
         ray_query_config.update({k: v for k, v in config.items()})
         ray_query_config.update(with_rgb=with_rgb, with_normal=with_normal)
         for k, v in (bypass_ray_query_cfg or {}).items():
-            ray_query_config[k] = v
+            if k == config.get("main_class_name", "Main") and isinstance(v, Mapping):
+                ray_query_config.update(v)          # the reference's per-class form {class_name: {key: value}} (:241-242)
+            else:
+                ray_query_config[k] = v
         cr_ret = model.ray_query(ray_input=cr_ray_input, ray_tested=cr_ray_tested, config=ray_query_config,
                                  return_buffer=True, return_details=return_details,
                                  render_per_obj_individual=render_per_obj_individual)

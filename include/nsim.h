@@ -592,6 +592,24 @@ int nsim_rows_scatter_add(const float* g, const int64_t* idx, int64_t n, int C, 
  * (the free points a training step appends to its rays carry no appearance code) -- out [n + tail, C]. */
 int nsim_rows_gather(const float* table, const int64_t* idx, int64_t n, int C, int64_t rows, int64_t tail, float* out,
                      void* stream);
+/* The SDF curvature regulariser (PermutoSDF, Rosu & Behnke 2023): the pointwise part of ``model.get_sdf_curvature_1d(net_x,
+ * nablas, eps=)``, app/loss/sdf_curvature.py:69,75 (the method itself lives in the absent nr3d_lib; semantics: DESIGN.md sec. 7).
+ *   curv_shift:     x_out = clamp(x + eps (n^ x r^), aabb_lo, aabb_hi) with n^ = nablas / max(|nablas|, 1e-12), r^ = dirs
+ *                   normalised alike; the cross product is NOT renormalised.  aabb_lo / aabb_hi: 3 device floats each.
+ *   curv_angle_fwd: curv[i] = acos(clamp(n0^ . n1^, -(1 - 1e-6), 1 - 1e-6)) / pi      (the bound as its nearest f32)
+ *   curv_angle_bwd: dn0 / dn1 [n,3] (either may be NULL) from gcurv [n], recomputed from n0, n1 -- the forward's output is not
+ *                   read, so the caller may modify it in place (``curvature.clamp_max_(0.5)``, sdf_curvature.py:42).  Zero where
+ *                   the clamp is active and for a vector shorter than 1e-12.
+ *   curv_loss_fwd:  out[0] += mean(min(curv_i, clamp_max)) in one launch (out zeroed by the caller, as eikonal_loss_fwd)
+ *   curv_loss_bwd:  its gradient given gout [1]; dn0 / dn1 as above. */
+int nsim_curv_shift(const float* nablas, const float* x, const float* dirs, const float* aabb_lo, const float* aabb_hi,
+                    float eps, int64_t n, float* x_out, void* stream);
+int nsim_curv_angle_fwd(const float* n0, const float* n1, int64_t n, float* curv, void* stream);
+int nsim_curv_angle_bwd(const float* n0, const float* n1, const float* gcurv, int64_t n, float* dn0, float* dn1,
+                        void* stream);
+int nsim_curv_loss_fwd(const float* n0, const float* n1, int64_t n, float clamp_max, float* out, void* stream);
+int nsim_curv_loss_bwd(const float* n0, const float* n1, int64_t n, float clamp_max, const float* gout, float* dn0,
+                       float* dn1, void* stream);
 /* The loss head of one training step in a single launch (the reference's total = mse + w (eikonal(render samples) +
  * eikonal(uniform points)), code_single/tools/train.py:1411-1423 with app/loss/photometric.py + eikonal.py):
  *   acc[0] += mse(pred, gt) over n_img floats; acc[1] += eikonal(nablas[:S]); acc[2] += eikonal(nablas[S:S+M]);

@@ -153,6 +153,11 @@ SIGNATURES = {
     "nsim_sky_bwd": [C.POINTER(SkyMeta), _P, _P, _P, _I64, _P, _P, _P, _P, _P],
     "nsim_eikonal_loss_fwd": [_P, _I64, _P],
     "nsim_eikonal_loss_bwd": [_P, _I64, _P, _P],
+    "nsim_curv_shift": [_P, _P, _P, _P, _P, _F, _I64, _P],
+    "nsim_curv_angle_fwd": [_P, _P, _I64, _P],
+    "nsim_curv_angle_bwd": [_P, _P, _P, _I64, _P, _P],
+    "nsim_curv_loss_fwd": [_P, _P, _I64, _F, _P],
+    "nsim_curv_loss_bwd": [_P, _P, _I64, _F, _P, _P, _P],
     "nsim_mse_loss_fwd": [_P, _P, _I64, _P],
     "nsim_train_loss_head": [_P, _P, _I64, _P, _I64, _I64, _F, _P, _P, _P],
     "nsim_mse_loss_bwd": [_P, _P, _I64, _P, _P],

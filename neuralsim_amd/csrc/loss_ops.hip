@@ -3,6 +3,9 @@
 //   * eikonal: mean((|nablas| - 1)^2)                 (app/loss/eikonal.py:96-105 with safe_mse off, alpha_reg_zero 0)
 //   * photometric mse: mean((pred - gt)^2)            (app/loss/photometric.py:88-146, fn_type mse, no mask)
 //   * rows_scatter_add: d embed[idx[i], :] += g[i, :]  (app/models/scene/image_embeddings.py:23-80: ``embed[fidx]``)
+//   * sdf curvature: acos(n0^ . n1^) / pi of the nablas at a point and at its tangentially shifted neighbour, the shift
+//     itself, and mean(min(curvature, clamp_max))     (model.get_sdf_curvature_1d + SDFCurvatureRegLoss.fn,
+//     app/loss/sdf_curvature.py:42,69,75; the regulariser of PermutoSDF, Rosu & Behnke 2023)
 // The reference evaluates these with a handful of torch ops each; here one launch per direction, because at 8192
 // rays per iteration the step is bounded by launch count, not by bytes.
 #include "nsim_common.h"
@@ -178,6 +181,130 @@ __global__ void __launch_bounds__(LOSS_BLOCK) k_gather_rays(const float* __restr
   far_out[i] = far[r];
 }
 
+// ---------------------------------------------------------------------------------------------- sdf curvature
+// A lane owns one point: its three floats are one 12-byte load (the wave reads 768 contiguous bytes, every byte of every cache
+// line it touches is used), as k_eikonal_* read their nablas.  Plain f32, no LDS beyond the block reduction.
+#define CURV_MAX_BLOCKS 2048          // elementwise kernels: 8 blocks per CU, the rest by grid stride
+#define CURV_NORM_MIN 1e-12f          // n^ = n / max(|n|, 1e-12); a shorter vector gets NO gradient (departs from F.normalize)
+#define CURV_DOT_MAX 0x1.ffffdep-1f   // f32(1 - 1e-6) = 1 - 1.0133e-6: the clamp of the dot product
+#define CURV_AT_DOT_MAX 0x1.db2614p-12f   // f32(acos( CURV_DOT_MAX) / pi) = 4.5313715e-4
+#define CURV_AT_DOT_MIN 0x1.ffc49cp-1f    // f32(acos(-CURV_DOT_MAX) / pi) = 1 - 4.5313715e-4
+#define CURV_ANGLE_MIN 0x1.752e52p-10f     // f32(acos(CURV_DOT_MAX)) = 1.4235723e-3 rad
+#define CURV_PI 3.14159265358979f
+
+struct CurvUnit {
+  float x, y, z, len;
+};
+
+__device__ __forceinline__ CurvUnit curv_unit(const float* __restrict__ v, int64_t i) {
+  const float a = v[3 * i], b = v[3 * i + 1], c = v[3 * i + 2];
+  CurvUnit u;
+  u.len = sqrtf(a * a + b * b + c * c);
+  const float inv = 1.0f / fmaxf(u.len, CURV_NORM_MIN);
+  u.x = a * inv;
+  u.y = b * inv;
+  u.z = c * inv;
+  return u;
+}
+
+// curvature of one pair of normalised vectors and d curvature / d dot (0 where the clamp of the dot product is active -- there the
+// curvature is one of two constants).  The ONE angle function of the elementwise and the fused kernels.
+// The angle is taken as atan2(|n0^ x n1^|, |n0^ . n1^|), not as acos of the dot product: just inside the clamp d acos / d dot is
+// 1 / sqrt(2e-6) = 700, which turns the 6e-8 rounding of an f32 dot product near 1 into 1.3e-5 of curvature per ulp; the cross
+// product keeps its relative precision down to the clamp angle (1.4e-3 rad), so does the gradient's 1 / sin.
+__device__ __forceinline__ float curv_angle(const CurvUnit& u0, const CurvUnit& u1, float* dot_out, float* dcurv_ddot) {
+  const float dot = u0.x * u1.x + u0.y * u1.y + u0.z * u1.z;
+  *dot_out = dot;
+  *dcurv_ddot = 0.f;
+  if (u0.len < CURV_NORM_MIN || u1.len < CURV_NORM_MIN) {
+    // a vector below the norm floor is not a unit vector: the formula as it stands, acos(clamp(dot)) / pi (|dot| < 1 here)
+    if (dot >= CURV_DOT_MAX) return CURV_AT_DOT_MAX;
+    if (dot <= -CURV_DOT_MAX) return CURV_AT_DOT_MIN;
+    *dcurv_ddot = -1.0f / (CURV_PI * sqrtf((1.0f - dot) * (1.0f + dot)));
+    return acosf(dot) / CURV_PI;
+  }
+  const float cx = u0.y * u1.z - u0.z * u1.y, cy = u0.z * u1.x - u0.x * u1.z, cz = u0.x * u1.y - u0.y * u1.x;
+  const float sn = sqrtf(cx * cx + cy * cy + cz * cz);
+  const float th = atan2f(sn, fabsf(dot));            // angle to the nearer of +-n1^, in [0, pi/2]
+  if (th <= CURV_ANGLE_MIN) return dot > 0.f ? CURV_AT_DOT_MAX : CURV_AT_DOT_MIN;
+  *dcurv_ddot = -1.0f / (CURV_PI * sn);
+  const float c = th / CURV_PI;
+  return dot >= 0.f ? c : 1.0f - c;
+}
+
+// d n [3] = k (d dot / d n) with d dot / d n = (other^ - dot n^) / |n| through the normalisation; 0 below CURV_NORM_MIN
+__device__ __forceinline__ void curv_store_grad(float* __restrict__ dn, int64_t i, float k, float dot, const CurvUnit& u,
+                                                const CurvUnit& o) {
+  const float s = u.len >= CURV_NORM_MIN ? k / u.len : 0.f;
+  dn[3 * i] = s * (o.x - dot * u.x);
+  dn[3 * i + 1] = s * (o.y - dot * u.y);
+  dn[3 * i + 2] = s * (o.z - dot * u.z);
+}
+
+// x_out = clamp(x + eps (n^ x r^), aabb): the tangential neighbour the second query runs at (|shift| = eps sin(n^, r^) <= eps)
+__global__ void __launch_bounds__(LOSS_BLOCK) k_curv_shift(const float* __restrict__ nab, const float* __restrict__ x,
+                                                           const float* __restrict__ dirs, const float* __restrict__ lo,
+                                                           const float* __restrict__ hi, float eps, int64_t n,
+                                                           float* __restrict__ x_out) {
+  const float lx = lo[0], ly = lo[1], lz = lo[2], hx = hi[0], hy = hi[1], hz = hi[2];
+  for (int64_t i = (int64_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * LOSS_BLOCK) {
+    const CurvUnit u = curv_unit(nab, i), r = curv_unit(dirs, i);
+    const float tx = u.y * r.z - u.z * r.y, ty = u.z * r.x - u.x * r.z, tz = u.x * r.y - u.y * r.x;
+    x_out[3 * i] = fminf(fmaxf(x[3 * i] + eps * tx, lx), hx);
+    x_out[3 * i + 1] = fminf(fmaxf(x[3 * i + 1] + eps * ty, ly), hy);
+    x_out[3 * i + 2] = fminf(fmaxf(x[3 * i + 2] + eps * tz, lz), hz);
+  }
+}
+
+__global__ void __launch_bounds__(LOSS_BLOCK) k_curv_angle_fwd(const float* __restrict__ n0, const float* __restrict__ n1,
+                                                               int64_t n, float* __restrict__ curv) {
+  for (int64_t i = (int64_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * LOSS_BLOCK) {
+    float dot, dc;
+    curv[i] = curv_angle(curv_unit(n0, i), curv_unit(n1, i), &dot, &dc);
+  }
+}
+
+// recomputes the dot product from the inputs (the forward's output is the caller's to modify in place); dn0 / dn1 may be NULL
+__global__ void __launch_bounds__(LOSS_BLOCK) k_curv_angle_bwd(const float* __restrict__ n0, const float* __restrict__ n1,
+                                                               const float* __restrict__ gcurv, int64_t n,
+                                                               float* __restrict__ dn0, float* __restrict__ dn1) {
+  for (int64_t i = (int64_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * LOSS_BLOCK) {
+    const CurvUnit u0 = curv_unit(n0, i), u1 = curv_unit(n1, i);
+    float dot, dc;
+    curv_angle(u0, u1, &dot, &dc);
+    const float k = gcurv[i] * dc;
+    if (dn0) curv_store_grad(dn0, i, k, dot, u0, u1);
+    if (dn1) curv_store_grad(dn1, i, k, dot, u1, u0);
+  }
+}
+
+__global__ void __launch_bounds__(LOSS_BLOCK) k_curv_loss_fwd(const float* __restrict__ n0, const float* __restrict__ n1,
+                                                              int64_t n, float inv_n, float clamp_max,
+                                                              float* __restrict__ out) {
+  float acc = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * LOSS_BLOCK) {
+    float dot, dc;
+    acc += fminf(curv_angle(curv_unit(n0, i), curv_unit(n1, i), &dot, &dc), clamp_max);
+  }
+  block_sum_atomic(acc, inv_n, out);
+}
+
+// d mean(min(curvature, clamp_max)): the min passes the gradient where curvature <= clamp_max (torch's clamp_max_)
+__global__ void __launch_bounds__(LOSS_BLOCK) k_curv_loss_bwd(const float* __restrict__ n0, const float* __restrict__ n1,
+                                                              int64_t n, float inv_n, float clamp_max,
+                                                              const float* __restrict__ gout, float* __restrict__ dn0,
+                                                              float* __restrict__ dn1) {
+  const float g = gout[0] * inv_n;
+  for (int64_t i = (int64_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * LOSS_BLOCK) {
+    const CurvUnit u0 = curv_unit(n0, i), u1 = curv_unit(n1, i);
+    float dot, dc;
+    const float c = curv_angle(u0, u1, &dot, &dc);
+    const float k = c <= clamp_max ? g * dc : 0.f;
+    if (dn0) curv_store_grad(dn0, i, k, dot, u0, u1);
+    if (dn1) curv_store_grad(dn1, i, k, dot, u1, u0);
+  }
+}
+
 static inline dim3 loss_grid(int64_t n) {
   int64_t b = nsim_blocks(n, LOSS_BLOCK);
   return dim3((unsigned)(b > LOSS_MAX_BLOCKS ? LOSS_MAX_BLOCKS : b));
@@ -222,6 +349,65 @@ int nsim_mse_loss_bwd(const float* pred, const float* gt, int64_t n, const float
   if (!dpred || !gout) return 26;
   hipLaunchKernelGGL(k_mse_bwd, dim3(nsim_blocks(n, LOSS_BLOCK)), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, pred, gt, n,
                      1.0f / (float)n, gout, dpred);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+static inline dim3 curv_grid(int64_t n) {
+  return dim3(nsim_blocks(n, LOSS_BLOCK, CURV_MAX_BLOCKS));
+}
+
+// x_out [n,3] = clamp(x + eps (nablas^ x dirs^), aabb_lo, aabb_hi); aabb_lo / aabb_hi: 3 device floats each
+int nsim_curv_shift(const float* nablas, const float* x, const float* dirs, const float* aabb_lo, const float* aabb_hi,
+                    float eps, int64_t n, float* x_out, void* stream) {
+  if (n < 0) return 2;
+  if (n == 0) return 0;
+  if (!nablas || !x || !dirs || !aabb_lo || !aabb_hi || !x_out) return 4;
+  hipLaunchKernelGGL(k_curv_shift, curv_grid(n), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, nablas, x, dirs, aabb_lo, aabb_hi,
+                     eps, n, x_out);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_curv_angle_fwd(const float* n0, const float* n1, int64_t n, float* curv, void* stream) {
+  if (n < 0) return 2;
+  if (n == 0) return 0;
+  if (!n0 || !n1 || !curv) return 4;
+  hipLaunchKernelGGL(k_curv_angle_fwd, curv_grid(n), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, n0, n1, n, curv);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+// dn0 / dn1 [n,3]: either may be NULL (gradient not wanted)
+int nsim_curv_angle_bwd(const float* n0, const float* n1, const float* gcurv, int64_t n, float* dn0, float* dn1,
+                        void* stream) {
+  if (n < 0) return 2;
+  if (n == 0 || (!dn0 && !dn1)) return 0;
+  if (!n0 || !n1 || !gcurv) return 26;
+  hipLaunchKernelGGL(k_curv_angle_bwd, curv_grid(n), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, n0, n1, gcurv, n, dn0, dn1);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+// out[0] must be zero on entry; out[0] += mean(min(curvature_i, clamp_max))
+int nsim_curv_loss_fwd(const float* n0, const float* n1, int64_t n, float clamp_max, float* out, void* stream) {
+  if (n < 0) return 2;
+  if (!out) return 4;
+  if (n == 0) return 0;
+  if (!n0 || !n1) return 4;
+  hipLaunchKernelGGL(k_curv_loss_fwd, loss_grid(n), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, n0, n1, n, 1.0f / (float)n,
+                     clamp_max, out);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_curv_loss_bwd(const float* n0, const float* n1, int64_t n, float clamp_max, const float* gout, float* dn0,
+                       float* dn1, void* stream) {
+  if (n < 0) return 2;
+  if (n == 0 || (!dn0 && !dn1)) return 0;
+  if (!n0 || !n1 || !gout) return 26;
+  hipLaunchKernelGGL(k_curv_loss_bwd, curv_grid(n), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, n0, n1, n, 1.0f / (float)n,
+                     clamp_max, gout, dn0, dn1);
   NSIM_CHECK_LAUNCH();
   return 0;
 }

@@ -71,6 +71,12 @@ class BatchedRaysMixin:
     ``_pair_extras(ins [R], which [R]) -> dict`` merged into the tested-rays dict of the single-model ``ray_query``."""
     _sphere_trace_ok = False        # query_mode: sphere_trace traces one instance (no per-ray table / occupancy offsets)
 
+    def get_sdf_curvature_1d(self, x, nablas, eps: float = 1.0e-4, **kw):
+        """SDFCurvatureRegLoss (app/loss/sdf_curvature.py:69,75) passes neither ``bidx`` nor ``ins_ind``: the second query has no
+        instance to run on."""
+        raise NotImplementedError(f"{type(self).__name__}.get_sdf_curvature_1d: the call carries no instance index; the SDF "
+                                  f"curvature regulariser is built for LoTDNeuSModel and PermutoNeuSModel")
+
     # ------------------------------------------------------------------ batched rays (buffer_compose_renderer.py:222-265)
     def batched_ray_test(self, rays_o: torch.Tensor, rays_d: torch.Tensor, near=None, far=None, compact_batch=True,
                          **extra) -> Dict:

@@ -1229,6 +1229,36 @@ class LoTDNeuSModel(ModelMixin, nn.Module):
         ret["net_x"] = x
         return ret
 
+    def _curvature_neighbours(self, x: torch.Tensor, nablas: torch.Tensor, eps: float, dirs: torch.Tensor = None,
+                              generator=None) -> torch.Tensor:
+        """x' = clamp(x + eps (n^ x r^), aabb) [n, 3], one launch (``nsim_curv_shift``): every point moved in its tangent plane
+        along a random direction.  A constant of the step -- no gradient flows through the shift."""
+        xf = x.detach().float().reshape(-1, 3).contiguous()
+        nf = nablas.detach().float().reshape(-1, 3).contiguous()
+        if dirs is None:
+            dirs = torch.randn(xf.shape, dtype=torch.float32, device=xf.device, generator=generator)
+        df = dirs.detach().float().reshape(-1, 3).contiguous()
+        assert nf.shape == xf.shape and df.shape == xf.shape
+        aabb = self.accel.aabb
+        x2 = torch.empty_like(xf)
+        _lib.call("nsim_curv_shift", _lib.ptr(nf), _lib.ptr(xf), _lib.ptr(df), _lib.ptr(aabb[0]), _lib.ptr(aabb[1]), float(eps),
+                  xf.shape[0], _lib.ptr(x2))
+        return x2
+
+    def get_sdf_curvature_1d(self, x: torch.Tensor, nablas: torch.Tensor, eps: float = 1.0e-4, *, dirs: torch.Tensor = None,
+                             generator=None) -> torch.Tensor:
+        """``model.get_sdf_curvature_1d(net_x, nablas, eps=)`` of SDFCurvatureRegLoss (app/loss/sdf_curvature.py:69,75), the
+        regulariser of PermutoSDF (Rosu & Behnke 2023): the angle, as a fraction of pi, between the normal at x and the normal at
+        a neighbour ``eps sin(n^, r^)`` away in the tangent plane, r^ random (``dirs`` [..., 3], or ``torch.randn`` from
+        ``generator``).  x [..., 3] in object coordinates (the ``net_x`` of ``sample_pts_uniform`` / the volume buffer), nablas
+        [..., 3] -> [...] f32, safe to modify in place.  Gradients reach ``nablas`` and, through the second with-grad query, the
+        parameters; the neighbour itself is a constant.  (The method lives in the absent nr3d_lib: semantics fixed in DESIGN.md
+        sec. 7.)"""
+        from ..losses import sdf_curvature
+        x2 = self._curvature_neighbours(x, nablas, eps, dirs, generator)
+        nablas2 = self.forward_sdf_nablas(x2)["nablas"]
+        return sdf_curvature(nablas, nablas2.reshape(nablas.shape))
+
     # ------------------------------------------------------------------ rays
     @staticmethod
     def convert_rays_in_node(rays_o, rays_d, rotation: torch.Tensor, translation: torch.Tensor, scale=1.0):
@@ -1695,6 +1725,10 @@ class LoTDNeuSModel(ModelMixin, nn.Module):
                   nablas=nablas, sdf=sdf)
         if with_rgb:
             vb["rgb"] = rgb
+        if qp.get("with_net_x", False):
+            # a key of this package: the sample positions in object coordinates, read by SDFCurvatureRegLoss
+            # (app/loss/sdf_curvature.py:75 ``volume_buffer['net_x']``)
+            vb["net_x"] = o[ridx] + t.detach()[:, None] * d[ridx]
         ret["volume_buffer"] = vb
         if render_per_obj_individual or cfg.get("_render", False):
             ret["rendered"] = volume_integration(alpha, t, rgb, nablas if (with_normal or cfg.get("_render", False)) else None,
@@ -1787,6 +1821,8 @@ class LoTDNeuSModel(ModelMixin, nn.Module):
                   nablas=nablas, sdf=sdf)
         if with_rgb:
             vb["rgb"] = outs[2]
+        if qp.get("with_net_x", False):
+            vb["net_x"] = o[idx] + t[:, None] * d[idx]
         ret["volume_buffer"] = vb
         if want_render:
             ret["rendered"] = volume_integration(alpha, t, vb.get("rgb"), nablas if (with_normal or cfg.get("_render", False)) else None,

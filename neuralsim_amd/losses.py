@@ -1,5 +1,6 @@
 """Fused evaluations of the losses the object-centric training step puts on the path's outputs
-and the appearance-embedding lookup.  The reference writes these as a few torch ops each (app/loss/eikonal.py:96-105,
+and the appearance-embedding lookup, and the pointwise part of the SDF curvature regulariser (app/loss/sdf_curvature.py:42,69,75).
+The reference writes these as a few torch ops each (app/loss/eikonal.py:96-105,
 app/loss/photometric.py:88-146, app/models/scene/image_embeddings.py:23-80); values and gradients are identical, the
 launch count is not (one kernel per direction)."""
 import torch
@@ -28,6 +29,71 @@ class _EikonalFn(torch.autograd.Function):
 def eikonal_loss(nablas: torch.Tensor) -> torch.Tensor:
     """mean((|nablas| - 1)^2) -- ``EikonalLoss.fn(nablas).mean()`` with the defaults (no noise, plain mse)."""
     return _EikonalFn.apply(nablas)
+
+
+def _rows3(t: torch.Tensor, name: str) -> torch.Tensor:
+    _lib.require_device(t, name)
+    return t.detach().float().reshape(-1, 3).contiguous()
+
+
+class _CurvatureFn(torch.autograd.Function):
+    """Saves its INPUTS only: the backward recomputes the angle, so the returned tensor -- a fresh buffer, never a view -- may be
+    modified in place (``curvature.clamp_max_(0.5)``, app/loss/sdf_curvature.py:42)."""
+
+    @staticmethod
+    def forward(ctx, n0, n1):
+        a, b = _rows3(n0, "n0"), _rows3(n1, "n1")
+        out = torch.empty(n0.shape[:-1], dtype=torch.float32, device=a.device)
+        _lib.call("nsim_curv_angle_fwd", _lib.ptr(a), _lib.ptr(b), a.shape[0], _lib.ptr(out))
+        ctx.save_for_backward(a, b)
+        ctx.shapes = (n0.shape, n1.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        d0 = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        d1 = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        _lib.call("nsim_curv_angle_bwd", _lib.ptr(a), _lib.ptr(b), _lib.ptr(g.float().reshape(-1).contiguous()), a.shape[0],
+                  _lib.ptr(d0), _lib.ptr(d1))
+        return (d0.reshape(ctx.shapes[0]) if d0 is not None else None, d1.reshape(ctx.shapes[1]) if d1 is not None else None)
+
+
+def sdf_curvature(n0: torch.Tensor, n1: torch.Tensor) -> torch.Tensor:
+    """``acos(clamp(n0^ . n1^, -(1 - 1e-6), 1 - 1e-6)) / pi`` per point, n^ = n / max(|n|, 1e-12): the angle between the nablas at a
+    point and at its neighbour as a fraction of pi (n0, n1 [..., 3] -> [...]; the pointwise part of
+    ``model.get_sdf_curvature_1d``).  Gradients to both; exactly zero where the clamp is active and for a vector
+    shorter than 1e-12 (``F.normalize`` would hand back 1e12 x there)."""
+    assert n0.shape == n1.shape and n0.shape[-1] == 3
+    return _CurvatureFn.apply(n0, n1)
+
+
+class _CurvatureLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, n0, n1, clamp_max):
+        a, b = _rows3(n0, "n0"), _rows3(n1, "n1")
+        out = _lib.zeros([], device=a.device)
+        _lib.call("nsim_curv_loss_fwd", _lib.ptr(a), _lib.ptr(b), a.shape[0], float(clamp_max), _lib.ptr(out))
+        ctx.save_for_backward(a, b)
+        ctx.shapes, ctx.clamp_max = (n0.shape, n1.shape), float(clamp_max)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        d0 = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        d1 = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        _lib.call("nsim_curv_loss_bwd", _lib.ptr(a), _lib.ptr(b), a.shape[0], ctx.clamp_max, _lib.ptr(g.float().reshape(1).contiguous()),
+                  _lib.ptr(d0), _lib.ptr(d1))
+        return (d0.reshape(ctx.shapes[0]) if d0 is not None else None, d1.reshape(ctx.shapes[1]) if d1 is not None else None,
+                None)
+
+
+def sdf_curvature_loss(n0: torch.Tensor, n1: torch.Tensor, clamp_max: float = 0.5) -> torch.Tensor:
+    """``mean(min(sdf_curvature(n0, n1), clamp_max))`` -- ``SDFCurvatureRegLoss.fn`` (app/loss/sdf_curvature.py:42) on the
+    curvature of ``sdf_curvature``, one launch per direction."""
+    assert n0.shape == n1.shape and n0.shape[-1] == 3
+    return _CurvatureLossFn.apply(n0, n1, clamp_max)
 
 
 class _MseFn(torch.autograd.Function):

@@ -20,7 +20,7 @@ from .fields.neus import LoTDNeuSModel, volume_integration, append_extra_points,
 from .graphics.cameras import selected_rays
 from .optim import FusedAdam
 _PREFETCH_HANDOFF = os.environ.get("NSIM_PREFETCH_HANDOFF", "1") == "1"
-from .losses import eikonal_loss, mse_loss, embedding_lookup, mono_depth_loss, mono_normal_loss
+from .losses import eikonal_loss, mse_loss, embedding_lookup, mono_depth_loss, mono_normal_loss, sdf_curvature_loss
 
 
 class RenderTrainer:
@@ -31,7 +31,8 @@ class RenderTrainer:
                  target_sphere_radius: Optional[float] = None, pipeline: bool = True,
                  pose_refine: Optional[dict] = None, c2w_true=None, fused_step: Optional[bool] = None,
                  distortion: Optional[torch.Tensor] = None, target_images: Optional[torch.Tensor] = None,
-                 mono: Optional[dict] = None, rgb_fn: str = "mse", lidar: Optional[dict] = None):
+                 mono: Optional[dict] = None, rgb_fn: str = "mse", lidar: Optional[dict] = None, w_curvature: float = 0.0,
+                 curvature_eps: float = 1.0e-4):
         """pose_refine: ``dict(lr=1e-4, start_it=500)`` -- per-frame pose corrections (an axis-angle rotation and a
         translation, ``c2w' = [R Exp(w) | T + dT]``) trained through the rays from ``start_it`` on, standing in for the
         reference's ``LearnableParams`` (withmask_withlidar_joint.240219.yaml:338-352; the parametrisation of the
@@ -50,7 +51,12 @@ class RenderTrainer:
         (0 = no return), num_rays=8192, w_depth=0.02, w_los=0.1, epsilon=1.5, discard_toofar=80)`` -- a batch of lidar
         beams rendered with ``with_rgb=False`` (no radiance network), l1 depth loss on the returns + the line-of-sight
         term of ``neus_unisim`` (squared visibility weights further than epsilon from the return), own backward and
-        optimizer step, as in the reference's loop (train.py:1540-1590)."""
+        optimizer step, as in the reference's loop (train.py:1540-1590).
+        w_curvature, curvature_eps: the SDF curvature regulariser of PermutoSDF (app/loss/sdf_curvature.py, ``fn`` :42 on
+        ``model.get_sdf_curvature_1d`` :69) on the ``num_uniform`` uniform points, ``w_curvature * mean(min(curvature, 0.5))``
+        with neighbours ``curvature_eps`` away, reported as ``loss_parts['loss_curvature']``.  With ``w_curvature > 0`` the step
+        takes the generic autograd path (one more with-grad query of the uniform points; the fused launch chain does not carry
+        the term); with 0 nothing changes."""
         self.model = model
         self.target_images, self.mono, self.rgb_fn = target_images, (dict(mono) if mono else None), rgb_fn
         self.lidar = dict(lidar) if lidar else None
@@ -100,6 +106,8 @@ class RenderTrainer:
             self.pose_optim = torch.optim.Adam([self.pose_delta], lr=float(self.pose_refine.get("lr", 1e-4)))
         self.num_rays = num_rays             # rays per rank per iteration (weak scaling, as the reference's DDP)
         self.w_eikonal, self.num_uniform = w_eikonal, num_uniform
+        self.w_curvature, self.curvature_eps = float(w_curvature), float(curvature_eps)
+        self.loss_parts: Dict[str, torch.Tensor] = {}      # the terms of the last autograd-path step (detached device scalars)
         self.near, self.far, self.perturb = near, far, perturb
         self.rank, self.world_size = rank, world_size
         dev = model.device
@@ -233,7 +241,7 @@ class RenderTrainer:
         plain = type(m) is LoTDNeuSModel or (type(m).__name__ == "PermutoNeuSModel" and getattr(m, "z_dim", 0) == 0)
         return (self.fused_step and plain and not getattr(m, "pos_embed_E", 0) and self.distant_model is None and self.sky_model is None
                 and not self.pose_refine_active() and getattr(m, "_ctrl_mix", 0.0) == 0.0 and self.mono is None
-                and self.rgb_fn == "mse")
+                and self.rgb_fn == "mse" and self.w_curvature <= 0.0)
 
     def _train_render_fused(self, batch: dict) -> Optional[torch.Tensor]:
         """render + loss + backward of one prefetched batch WITHOUT the autograd engine: the launches the autograd path
@@ -567,7 +575,7 @@ class RenderTrainer:
             if self.mono.get("patch_hw"):
                 n_p = self.mono["patch_hw"][0] * self.mono["patch_hw"][1]
                 loss_rgb = loss_rgb + w_d * mono_depth_loss(r_["depth_volume"][:n_p], aux["depth"][:n_p], occupied[:n_p])
-        eik = None
+        eik, curv = None, None
         cr_vb = ret["raw_per_obj_model"]["main"]["volume_buffer"]
         if cr_vb["type"] != "empty":
             eik = eikonal_loss(cr_vb["nablas"])
@@ -578,10 +586,17 @@ class RenderTrainer:
                 uni = self.model.sample_pts_uniform(self.num_uniform, generator=self.gen)
             e2 = eikonal_loss(uni["nablas"])
             eik = e2 if eik is None else eik + e2
+            if self.w_curvature > 0:
+                m = self.model
+                x2 = m._curvature_neighbours(uni["net_x"], uni["nablas"], self.curvature_eps, generator=self.gen)
+                curv = sdf_curvature_loss(uni["nablas"], m.forward_sdf_nablas(x2)["nablas"])
         if eik is None:
             eik = torch.zeros([], device=gt.device)
         # (``torch.add(a, b, alpha=w)``: a + w b as ONE launch forward and one backward)
-        return torch.add(loss_rgb, eik, alpha=self.w_eikonal), dict(loss_rgb=loss_rgb.detach(), loss_eikonal=eik.detach())
+        total, parts = torch.add(loss_rgb, eik, alpha=self.w_eikonal), dict(loss_rgb=loss_rgb.detach(), loss_eikonal=eik.detach())
+        if curv is not None:
+            total, parts["loss_curvature"] = torch.add(total, curv, alpha=self.w_curvature), curv.detach()
+        return total, parts
 
     # ------------------------------------------------------------------ lidar step (street configs)
     def sample_lidar_batch(self):
@@ -699,8 +714,9 @@ class RenderTrainer:
             ret = self.render(xy, fidx, extra_pts=x_uni, batch=batch)
             uni = None
             if x_uni is not None and "extra_pts" not in ret["raw_per_obj_model"]["main"]:     # no ray hit anything
-                uni = model.forward_sdf_nablas(x_uni)
+                uni = dict(model.forward_sdf_nablas(x_uni), net_x=x_uni)
             loss, parts = self.loss(ret, gt, uni, aux=batch.get("aux") if batch is not None else self._last_aux)
+            self.loss_parts = parts
             self.optim.zero_grad()
             if refine:
                 self.pose_optim.zero_grad(set_to_none=True)

@@ -551,6 +551,58 @@ int nsim_distant_bwd(const NsimDistantMeta* meta, const void* wpack, const float
 int nsim_lotd4_scatter(const NsimLotd4Meta* meta, const float* u4, const uint8_t* valid, int64_t S,
                        const float* dh_planes, float* dgrid, void* stream);
 
+/* ------------------------------------------------ close-range NGP NeRF (LoTDNeRFObj / LoTDNeRFStreet: LoTDNeRFModel) */
+/* InstantNGP + UrbanNeRF (docs/methods/ngp_lidar.md; code_single/configs/waymo/ngp_withlidar.230814.yaml:100-158; wrappers
+ * app/models/single/nerf.py:33-143).  The implementation is in the absent nr3d_lib: semantics fixed in DESIGN sec. 7.
+ *   encoding_cfg (yaml :103-118): the 3-D LoTD pyramid, <= 16 levels x 2 features, gathered LEVEL-MAJOR by the existing entry
+ *     points (nsim_field_fwd with wpack == NULL for a with-grad query, nsim_lotd_gather_lm on an f32 meta otherwise) into
+ *     h_planes [16][P][2] f32; ``anneal_cfg{type: hardmask}``: lotd.n_active_levels (masked levels are neither read nor given
+ *     a gradient).
+ *   density_decoder_cfg{D: 1, W: 64, output_activation{trunc_exp, offset: -1}} + extra_pos_embed_cfg{identity} +
+ *     n_extra_feat_from_output: 31 (yaml :119-128): [h (2 num_levels) | x_n (3)] -> 64 (relu) -> 32 (linear), x_n = the
+ *     AABB-normalised position 2 (x * x_scale + x_shift) - 1; output 0 = raw, sigma = exp(raw - 1), outputs 1..31 = geometry
+ *     feature.  den_w = [W1 (64 x (2 num_levels + 3)), W2 (32 x 64)] row-major, den_b = [64, 32].
+ *   radiance_decoder_cfg{use_pos: false, use_view_dirs: true, use_nablas: false, dir_embed_cfg{spherical, 4}, D: 2, W: 64}
+ *     (yaml :129-137): [geo (31) | SH-4 of the normalised rays_d (16) | h_appear (n_appear = 0 | 4)] -> 64 -> 64 (relu) -> 3
+ *     (sigmoid).  rad_w = [Q1 (64 x (47 + n_appear)), Q2 (64 x 64), Q3 (3 x 64)], rad_b = [64, 64, 3]. */
+typedef struct NsimNgpMeta {
+  NsimLotdMeta lotd;     /* 1..16 levels */
+  int32_t precision;     /* 0: fp16 MFMA, 1: exact f32 MFMA */
+  int32_t n_appear;      /* radiance_decoder_cfg.n_appear_embedding: 0 or 4 */
+} NsimNgpMeta;
+/* MFMA-fragment pack of the f32 master weights (once per optimizer step), as nsim_distant_pack_weights. */
+int64_t nsim_ngp_wpack_bytes(const NsimNgpMeta* meta);
+int nsim_ngp_pack_weights(const NsimNgpMeta* meta, const float* den_w, const float* den_b, const float* rad_w,
+                          const float* rad_b, void* wpack, void* stream);
+/* Fused decoders over the feature planes (pitch plane_pitch; 0 = NSIM_PLANE_PITCH(S)) of S points x [S,3] or
+ * rays_o[ridx] + t rays_d[ridx] (``ray_query_cfg{query_mode: march_occ}``, yaml :153-158: the samples of nsim_march_*).
+ * Writes sigma [S], alpha [S] = 1 - exp(-sigma step) (may be NULL) and rgb [S,3].  rgb == NULL: the density decoder alone
+ * (lidar rays -- with_rgb=False --, the occupancy refresh, sample_pts_uniform); rays_d / ridx are then not needed with x. */
+int nsim_ngp_fwd(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* x,
+                 const float* rays_o, const float* rays_d, const float* t, const int64_t* ridx, const float* h_appear,
+                 int64_t S, float step, float* sigma, float* alpha, float* rgb, void* stream);
+/* Backward on the saved planes and forward outputs: dsigma / dalpha [S], drgb [S,3] (each may be NULL; drgb == NULL skips the
+ * radiance decoder, drad_w / drad_b are then untouched).  Accumulates dden_w / dden_b / drad_w / drad_b (layouts above; through
+ * the replicas of nsim_set_grad_scratch when a scratch of 16 x 12288 floats is registered), dh_appear [R,4] (may be NULL)
+ * and writes dh_planes [16][S][2] (may be NULL) for nsim_lotd_scatter (g_planes = gn = NULL).  trunc_exp: d sigma / d raw =
+ * exp(min(raw - 1, 15)).  The rays get no gradient. */
+int nsim_ngp_bwd(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* x,
+                 const float* rays_o, const float* rays_d, const float* t, const int64_t* ridx, const float* h_appear,
+                 int64_t S, float step, const float* sigma_fwd, const float* rgb_fwd, const float* dsigma,
+                 const float* dalpha, const float* drgb, float* dh_planes, float* dden_w, float* dden_b, float* drad_w,
+                 float* drad_b, float* dh_appear, void* stream);
+/* ``accel_cfg{type: occ_grid, occ_thre, occ_thre_consider_mean, ema_decay, update_from_net_cfg, update_from_samples_cfg: {}}``
+ * of a density field (yaml :138-152): the value grid holds densities.  update: val = max(val * decay, sigma(p)) over pts [n,3];
+ * collect (a training step's own samples: x [n,3] or rays + t + ridx): the max-fold without decay; pack_bits_mean: a voxel is
+ * occupied when val > thre, thre = consider_mean ? min(occ_thre, mean(val)) : occ_thre, the mean taken on the device.
+ * workspace: 65 floats, contents irrelevant; workspace[64] receives the threshold used. */
+int nsim_occ_update_density(float* val, int64_t nvox, float decay, const float* pts, const float* sigma, int64_t n,
+                            const NsimOccMeta* meta, void* stream);
+int nsim_occ_collect_density(float* val, const float* x, const float* rays_o, const float* rays_d, const float* t,
+                             const int64_t* ridx, const float* sigma, int64_t n, const NsimOccMeta* meta, void* stream);
+int nsim_occ_pack_bits_mean(const float* val, int64_t nvox, float occ_thre, int consider_mean, float* workspace,
+                            uint32_t* bits, void* stream);
+
 /* ------------------------------------------------------------------------------- sky MLP (row a16) */
 /* ``SimpleSky`` (app/models/env/sky.py:16-51) as configured by the street configs
  * (code_single/configs/waymo/streetsurf/withmask_withlidar_joint.240219.yaml:312-322): sinusoidal embedding of the

@@ -41,6 +41,10 @@ class DistantMeta(C.Structure):
     _fields_ = [("lotd", Lotd4Meta), ("precision", C.c_int32)]
 
 
+class NgpMeta(C.Structure):        # include/nsim.h NsimNgpMeta
+    _fields_ = [("lotd", LotdMeta), ("precision", C.c_int32), ("n_appear", C.c_int32)]
+
+
 class SkyMeta(C.Structure):
     _fields_ = [("n_frequencies", C.c_int32), ("n_appear", C.c_int32), ("precision", C.c_int32)]
 
@@ -148,6 +152,12 @@ SIGNATURES = {
     "nsim_distant_fwd": [C.POINTER(DistantMeta), _P, _P, _P, _P, _P, _I64, _I, _P, _P, _P],
     "nsim_distant_bwd": [C.POINTER(DistantMeta), _P, _P, _P, _P, _P, _P, _P, _I64, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "nsim_lotd4_scatter": [C.POINTER(Lotd4Meta), _P, _P, _I64, _P, _P],
+    "nsim_ngp_pack_weights": [C.POINTER(NgpMeta), _P, _P, _P, _P, _P],
+    "nsim_ngp_fwd": [C.POINTER(NgpMeta), _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _F, _P, _P, _P],
+    "nsim_ngp_bwd": [C.POINTER(NgpMeta), _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _F] + [_P] * 11,
+    "nsim_occ_update_density": [_P, _I64, _F, _P, _P, _I64, C.POINTER(OccMeta)],
+    "nsim_occ_collect_density": [_P, _P, _P, _P, _P, _P, _P, _I64, C.POINTER(OccMeta)],
+    "nsim_occ_pack_bits_mean": [_P, _I64, _F, _I, _P, _P],
     "nsim_sky_pack_weights": [C.POINTER(SkyMeta), _P, _P, _P],
     "nsim_sky_fwd": [C.POINTER(SkyMeta), _P, _P, _P, _I64, _P, _P],
     "nsim_sky_bwd": [C.POINTER(SkyMeta), _P, _P, _P, _I64, _P, _P, _P, _P, _P],
@@ -186,6 +196,7 @@ NOSTREAM = {
     "nsim_jplane_elem_bytes": ([C.POINTER(FieldMeta)], _I),
     "nsim_sphere_trace_workspace_bytes": ([], _I64),
     "nsim_distant_wpack_bytes": ([C.POINTER(DistantMeta)], _I64),
+    "nsim_ngp_wpack_bytes": ([C.POINTER(NgpMeta)], _I64),
     "nsim_sky_wpack_bytes": ([C.POINTER(SkyMeta)], _I64),
     "nsim_sky_plane_pitch": ([_I64], _I64),
 }
@@ -318,8 +329,8 @@ def _marshal(args):
 
 
 _GRAD_SCRATCH = {}
-_GRAD_SCRATCH_USERS = ("nsim_field_bwd_rad", "nsim_field_bwd_sdf")
-GRAD_SCRATCH_FLOATS = 16 * 8448       # 16 replicas of the largest decoder gradient (64 x 64 + 64 x 64 + 64 + 129 floats)
+_GRAD_SCRATCH_USERS = ("nsim_field_bwd_rad", "nsim_field_bwd_sdf", "nsim_ngp_bwd")
+GRAD_SCRATCH_FLOATS = 16 * 12288      # 16 replicas of the largest decoder gradient (nsim_ngp_bwd: both decoders, 12067 floats)
 
 
 def ensure_grad_scratch(device):

@@ -2612,9 +2612,23 @@ static float* grad_scratch(void* stream, int64_t n, int& R) {
   return nullptr;
 }
 
+// the same scratch for the backward launches of other translation units (nerf_field.hip: nsim_ngp_bwd), NULL when the launch
+// is too small for a storm (nb workgroups) or nothing large enough is registered
+extern "C" float* nsim_grad_scratch_acquire(void* stream, int64_t n, int64_t nb, int* R) {
+  if (nb < grad_replicas_min_wg()) return nullptr;
+  return grad_scratch(stream, n, *R);
+}
+
 static void grad_scratch_fold(float* sc, int R, int64_t n_w, int64_t n_b, float* dst_w, float* dst_b, hipStream_t stream) {
   const int64_t n = n_w + n_b;
   hipLaunchKernelGGL(k_rep_reduce, dim3(nsim_blocks(n, 256)), dim3(256), 0, stream, sc, R, n, n_w, dst_w, dst_b, n);
+}
+
+// ... and its fold for a sub-range [sc, sc + n_w + n_b) of replicas that lie ``stride`` floats apart
+extern "C" void nsim_grad_scratch_fold(float* sc, int R, int64_t stride, int64_t n_w, int64_t n_b, float* dst_w, float* dst_b,
+                                       void* stream) {
+  const int64_t n = n_w + n_b;
+  hipLaunchKernelGGL(k_rep_reduce, dim3(nsim_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, sc, R, stride, n_w, dst_w, dst_b, n);
 }
 
 static FieldArgs field_args(const NsimFieldMeta* meta) {

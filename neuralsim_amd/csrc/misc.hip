@@ -1181,6 +1181,8 @@ const char* nsim_strerror(int code) {
     case 51: return "nearest neighbours: sizes out of range (N, M < 2^31 - 1024, at most 65535 chunks, 1 <= max_cells < 2^30, target occupancy > 0)";
     case 52: return "sphere trace: fewer than 2^30 rays, max_march_iters >= 1 and min_step > 0";
     case 53: return "sphere trace: the runtime reports no resident workgroup for the kernel (CU count / occupancy query)";
+    case 38: return "the close-range NeRF decoders take 1..16 LoTD levels (<= 32 input features)";
+    case 39: return "n_appear must be 0 or 4";
     case 36: return "wide decoder: 0..10 embedding frequencies and at most 128 first-layer inputs (2 num_levels + 3 + 6 n_freq)";
     default: return code >= 1000 ? "HIP launch error (code - 1000 = hipError_t)" : "unknown error";
   }

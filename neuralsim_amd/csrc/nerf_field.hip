@@ -9,6 +9,7 @@
 // Same register-resident transposed-MFMA scheme as field.hip (mfma_mlp.h); no second-order terms are needed here
 // (the distant model has ``use_nablas: false``).
 #include "mfma_mlp.h"
+#include "lotd_dev.h"
 #include <stdlib.h>
 
 #define D4_MAX_LEVELS 16
@@ -849,6 +850,509 @@ __global__ void __launch_bounds__(256) k_lotd4_scatter(Scatter4Args a) {
   }
 }
 
+// ================================================================================== close-range NGP NeRF
+// ``LoTDNeRFModel`` (app/models/single/nerf.py:33-143 LoTDNeRFObj / LoTDNeRFStreet; config
+// code_single/configs/waymo/ngp_withlidar.230814.yaml:100-158): 3-D LoTD features (gathered level-major by field.hip) ->
+// density decoder [h (F <= 32) | x_n (3)] -> 64 (relu) -> 32 (linear): output 0 = raw density (sigma = exp(raw - 1)),
+// outputs 1..31 = geometry feature -> radiance decoder [geo (31) | SH-4 (16) | h_appear (0 | 4)] -> 64 -> 64 -> 3 (sigmoid).
+// Same 32-point register-resident transposed-MFMA scheme as k_nerf above.  The three-position block of the first density
+// layer is a rank-3 update on the VALU in f32 (forward) and a 3-column weight-gradient product (backward): it never
+// enters an MFMA chunk, so 2 num_levels = 32 needs no second 32-input chunk and x_n is not rounded to fp16.
+#include "occ_dev.h"
+
+enum { G_D1 = 0, G_D2, G_Q1, G_Q2, G_Q3, G_D1T, G_D2T, G_Q3T, G_Q2T, G_Q1T, G_MCOUNT };
+enum { GV_DB1 = 0, GV_DX0, GV_DX1, GV_DX2, GV_DB2, GV_RB1, GV_RB2, GV_RB3, GV_COUNT };
+static const int kGUo[G_MCOUNT] = {64, 32, 64, 64, 32, 32, 64, 64, 64, 64};
+static const int kGUi[G_MCOUNT] = {32, 64, 64, 64, 64, 64, 32, 32, 64, 64};
+
+// pack: [vectors | forward matrices | transposed matrices] -- the forward stages [0, fwd_end) into LDS, the fp16 backward
+// the vectors alone
+struct NgpLayout {
+  int64_t mat[G_MCOUNT], vec[GV_COUNT], fwd_end, total;
+  int elt;
+};
+static inline NgpLayout ngp_layout(int precision) {
+  NgpLayout L;
+  L.elt = precision == 0 ? 2 : 4;
+  int64_t off = 0;
+  for (int v = 0; v < GV_COUNT; ++v) {
+    L.vec[v] = off;
+    off += 64 * 4;
+  }
+  L.fwd_end = 0;
+  for (int m = 0; m < G_MCOUNT; ++m) {
+    L.mat[m] = off;
+    off += (int64_t)kGUo[m] * kGUi[m] * L.elt;
+    if (m == G_Q3) L.fwd_end = off;
+  }
+  L.total = off;
+  return L;
+}
+
+// radiance input slot (0..63) -> column of the [64 x (31 + 16 + NA)] first radiance layer, or -1.  Slot 0 is the raw
+// density (not an input of the radiance net), slots 1..31 the geometry feature, 32..47 SH-4, 48..51 the appearance code.
+__host__ __device__ inline int ngp_q1_col(int slot, int NA) {
+  if (slot < 1) return -1;
+  if (slot < 32) return slot - 1;
+  if (slot < 48) return 31 + (slot - 32);
+  if (slot < 52) return NA == 4 ? 47 + (slot - 48) : -1;
+  return -1;
+}
+
+__device__ __forceinline__ float ngp_src(int mat, int row, int col, int F, int NA, const float* den_w, const float* rad_w) {
+  const int FI = F + 3, K1 = 47 + NA;
+  const int d2 = 64 * FI, q2 = 64 * K1, q3 = q2 + 4096;
+  switch (mat) {
+    case G_D1: return col < F ? den_w[row * FI + col] : 0.f;
+    case G_D1T: return row < F ? den_w[col * FI + row] : 0.f;
+    case G_D2: return den_w[d2 + row * 64 + col];
+    case G_D2T: return den_w[d2 + col * 64 + row];
+    case G_Q1: { const int c = ngp_q1_col(col, NA); return c >= 0 ? rad_w[row * K1 + c] : 0.f; }
+    case G_Q1T: { const int c = ngp_q1_col(row, NA); return c >= 0 ? rad_w[col * K1 + c] : 0.f; }
+    case G_Q2: return rad_w[q2 + row * 64 + col];
+    case G_Q2T: return rad_w[q2 + col * 64 + row];
+    case G_Q3: return row < 3 ? rad_w[q3 + row * 64 + col] : 0.f;
+    case G_Q3T: return col < 3 ? rad_w[q3 + col * 64 + row] : 0.f;
+  }
+  return 0.f;
+}
+
+struct NgpDims {
+  int uo[G_MCOUNT], ui[G_MCOUNT];
+};
+
+__global__ void __launch_bounds__(256) k_ngp_pack(NgpLayout L, NgpDims dims, int F, int NA, const float* __restrict__ den_w,
+                                                   const float* __restrict__ den_b, const float* __restrict__ rad_w,
+                                                   const float* __restrict__ rad_b, char* __restrict__ wpack) {
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t base = 0;
+  for (int m = 0; m < G_MCOUNT; ++m) {
+    const int Uo = dims.uo[m], Ui = dims.ui[m];
+    const int64_t cnt = (int64_t)Uo * Ui;
+    if (tid >= base && tid < base + cnt) {
+      const int64_t k = tid - base;
+      if (L.elt == 2) {
+        const int e = (int)(k & 7), lane = (int)((k >> 3) & 63), fs = (int)(k >> 9);
+        const int nS = Ui / 16, mo = fs / nS, s = fs % nS;
+        const int row = 32 * mo + (lane & 31), col = 16 * s + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
+        ((f16*)(wpack + L.mat[m]))[k] = (f16)ngp_src(m, row, col, F, NA, den_w, rad_w);
+      } else {
+        const int lane = (int)(k & 63), fr = (int)(k >> 6), r = fr & 15, fm = fr >> 4;
+        const int nMi = Ui / 32, mo = fm / nMi, mi = fm % nMi;
+        ((float*)(wpack + L.mat[m]))[k] = ngp_src(m, 32 * mo + (lane & 31), unit_of(mi, r, lane >> 5), F, NA, den_w, rad_w);
+      }
+      return;
+    }
+    base += cnt;
+  }
+  const int64_t vtid = tid - base;
+  if (vtid >= 0 && vtid < (int64_t)GV_COUNT * 64) {
+    const int v = (int)(vtid >> 6), k = (int)(vtid & 63);
+    const int hi = k >> 5, m = (k >> 4) & 1, r = k & 15, u = unit_of(m, r, hi);
+    const int FI = F + 3;
+    float val = 0.f;
+    switch (v) {
+      case GV_DB1: val = den_b[u]; break;
+      case GV_DX0: val = den_w[u * FI + F]; break;
+      case GV_DX1: val = den_w[u * FI + F + 1]; break;
+      case GV_DX2: val = den_w[u * FI + F + 2]; break;
+      case GV_DB2: val = u < 32 ? den_b[64 + u] : 0.f; break;
+      case GV_RB1: val = rad_b[u]; break;
+      case GV_RB2: val = rad_b[64 + u]; break;
+      case GV_RB3: val = u < 3 ? rad_b[128 + u] : 0.f; break;
+    }
+    ((float*)(wpack + L.vec[v]))[k] = val;
+  }
+}
+
+struct NgpArgs {
+  NgpLayout lay;
+  int F, NL, n_active, NA;                // features = 2 NL; levels >= n_active are masked (hardmask annealing)
+  float xs[3], xb[3];                     // u = x * xs + xb in [0,1]; x_n = 2 u - 1
+  const char* wpack;
+  const float *x, *rays_o, *rays_d, *t;   // points: x [S,3], or rays_o[ridx] + t rays_d[ridx]
+  const int64_t* ridx;
+  const float* h_appear;                  // [R,4] or NULL
+  int64_t S, PS;                          // points; pitch of h_pl
+  float step;                             // alpha = 1 - exp(-sigma step)
+  const float* h_pl;                      // [16][PS][2] gathered features
+  float *sigma, *alpha, *rgb;             // forward outputs (rgb NULL: density only)
+  const float *sigma_fwd, *rgb_fwd;       // saved forward outputs
+  const float *dsigma, *dalpha, *drgb;    // upstream (each may be NULL)
+  float* dh_pl;                           // [16][S][2] hand-off to nsim_lotd_scatter (may be NULL)
+  float* dst[4];                          // dden_w, dden_b, drad_w, drad_b -- or replica 0 of the registered scratch
+  int64_t rep_stride;                     // floats between replicas (workgroup b adds into replica b & rep_mask)
+  int rep_mask;
+  float* dh_appear;
+};
+
+#define NGP_WAVES 4
+#define NGP_WAVES_BWD 2       // the weight-gradient accumulators are 51.6 KB per private copy: two fit next to the staging
+
+__device__ __forceinline__ float ngp_vec(const char* WV, const NgpLayout& L, int v, int hi, int k) {
+  return reinterpret_cast<const float*>(WV + L.vec[v])[hi * 32 + k];
+}
+
+struct NgpPoint {
+  int64_t s, ray;
+  bool valid;
+  float xn[3], vd[3], ha[4];
+};
+__device__ __forceinline__ NgpPoint ngp_point(const NgpArgs& a, int64_t tile, int j, bool with_rad) {
+  NgpPoint p;
+  p.s = tile * 32 + j;
+  p.valid = p.s < a.S;
+  p.ray = 0;
+  p.xn[0] = p.xn[1] = p.xn[2] = 0.f;
+  p.vd[0] = p.vd[1] = 0.f;
+  p.vd[2] = 1.f;
+  p.ha[0] = p.ha[1] = p.ha[2] = p.ha[3] = 0.f;
+  if (p.valid) {
+    p.ray = a.ridx ? a.ridx[p.s] : p.s;
+    float xx[3];
+    if (a.x) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) xx[c] = a.x[3 * p.s + c];
+    } else {
+      const float tt = a.t[p.s];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) xx[c] = a.rays_o[3 * p.ray + c] + tt * a.rays_d[3 * p.ray + c];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) p.xn[c] = 2.0f * (xx[c] * a.xs[c] + a.xb[c]) - 1.0f;
+    if (with_rad) {
+      float d[3], n2 = 0.f;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        d[c] = a.rays_d[3 * p.ray + c];
+        n2 = n2 + d[c] * d[c];
+      }
+      const float inv = n2 > 0.f ? 1.0f / sqrtf(n2) : 0.f;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) p.vd[c] = d[c] * inv;
+      if (a.h_appear && a.NA == 4) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) p.ha[c] = a.h_appear[4 * p.ray + c];
+      }
+    }
+  }
+  return p;
+}
+
+// BWD = 0: sigma / alpha / rgb.  BWD = 1: recomputes the activations from the saved feature planes and accumulates the
+// weight gradients (per-wave private LDS accumulators in fp16 mode, as k_nerf), dh planes, dh_appear.
+template <int PREC, int BWD>
+__global__ void __launch_bounds__(64 * (BWD ? NGP_WAVES_BWD : NGP_WAVES)) k_ngp(NgpArgs a) {
+  NSIM_DYN_SMEM(smem);
+  constexpr bool PRIV = (PREC == 0 && BWD);
+  constexpr int NW = BWD ? NGP_WAVES_BWD : NGP_WAVES;
+  const int lane = nsim_lane(), j = lane & 31, hi = lane >> 5;
+  const int wave = (int)(threadIdx.x >> 6);
+  const NgpLayout& L = a.lay;
+  const bool with_rad = BWD ? (a.drgb != nullptr) : (a.rgb != nullptr);
+  // ---- weights: fp16 stages the vectors (+ the forward matrices in the forward) into LDS; f32 reads the pack from L2
+  const char* W = a.wpack;        // base the vectors AND matrices are addressed from
+  const char* WM = a.wpack;
+  int wbytes = 0;
+  if constexpr (PREC == 0) {
+    const int64_t nbytes = BWD ? L.mat[0] : L.fwd_end;
+    const int n16 = (int)((nbytes + 15) >> 4);
+    const f16x8* src = reinterpret_cast<const f16x8*>(a.wpack);
+    f16x8* dst = reinterpret_cast<f16x8*>(smem);
+    for (int i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
+    wbytes = n16 << 4;
+    __syncthreads();
+    W = smem;
+    if constexpr (!BWD) WM = smem;
+  }
+  constexpr int A_D1 = 0, A_DX = 2048, A_DB1 = A_DX + 192, A_D2 = A_DB1 + 64, A_DB2 = A_D2 + 2048, A_Q1 = A_DB2 + 32,
+                A_Q2 = A_Q1 + 4096, A_Q3 = A_Q2 + 4096, A_RB1 = A_Q3 + 192, A_RB2 = A_RB1 + 64, A_RB3 = A_RB2 + 64,
+                A_TOTAL = A_RB3 + 4;
+  constexpr int ACC_BYTES = (A_TOTAL * 4 + 15) & ~15;
+  float* accum = nullptr;
+  char* stA = nullptr;
+  char* stB = nullptr;
+  if constexpr (BWD) {
+    accum = reinterpret_cast<float*>(smem + wbytes + (PRIV ? wave * ACC_BYTES : 0));
+    char* stbase = smem + wbytes + (PRIV ? NW : 1) * ACC_BYTES + wave * stage_bytes_per_wave<PREC>();
+    stA = stbase;
+    stB = stbase + stage_bytes_per_wave<PREC>() / 2;
+    if constexpr (PRIV) {
+      for (int i = lane; i < A_TOTAL; i += 64) accum[i] = 0.f;
+    } else {
+      for (int i = threadIdx.x; i < A_TOTAL; i += blockDim.x) accum[i] = 0.f;
+    }
+    __syncthreads();
+  }
+  const int64_t ntiles = (a.S + 31) / 32;
+  const int64_t wstride = (int64_t)gridDim.x * NW;
+  for (int64_t tile = (int64_t)blockIdx.x * NW + wave; tile < ntiles; tile += wstride) {
+    const NgpPoint p = ngp_point(a, tile, j, with_rad);
+    const int64_t s = p.s;
+    // -------------------------------------------------------------- features from the level-major planes
+    float h[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int l = 4 * q + 2 * hi + b;
+        float f0 = 0.f, f1 = 0.f;
+        if (p.valid && l < a.n_active) {      // (masked and padding levels: zero features, their planes are never read)
+          const float* hp = a.h_pl + ((int64_t)l * a.PS + s) * 2;
+          f0 = hp[0];
+          f1 = hp[1];
+        }
+        h[4 * q + 2 * b] = f0;
+        h[4 * q + 2 * b + 1] = f1;
+      }
+    }
+    // -------------------------------------------------------------- density decoder
+    float a1[32];
+    dense<PREC, 2, 1>(a1, WM + L.mat[G_D1], h, true);
+#pragma unroll
+    for (int k = 0; k < 32; ++k) {
+      float z = a1[k] + ngp_vec(W, L, GV_DB1, hi, k);
+      z = z + ngp_vec(W, L, GV_DX0, hi, k) * p.xn[0];
+      z = z + ngp_vec(W, L, GV_DX1, hi, k) * p.xn[1];
+      z = z + ngp_vec(W, L, GV_DX2, hi, k) * p.xn[2];
+      a1[k] = fmaxf(z, 0.f);
+    }
+    float rin[32];      // [0,16): density outputs (slot 0 = raw, zeroed: not a radiance input), [16,32): SH / appearance
+    {
+      float o16[16];
+      dense<PREC, 1, 2>(o16, WM + L.mat[G_D2], a1, true);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) rin[r] = o16[r] + ngp_vec(W, L, GV_DB2, hi, r);
+    }
+    if constexpr (!BWD) {
+      const float raw = wave_shfl(rin[0], j);       // unit 0 lives in register 0 of the lower half-wave
+      const float sg = expf(raw - 1.0f);
+      if (p.valid && hi == 0) {
+        a.sigma[s] = sg;
+        if (a.alpha) a.alpha[s] = 1.0f - expf(-sg * a.step);
+      }
+    }
+    if (hi == 0) rin[0] = 0.f;
+    float r1[32], r2[32];
+    if (with_rad) {
+      nerf_rin_tail(rin, p.vd, p.ha, hi);
+      dense<PREC, 2, 2>(r1, WM + L.mat[G_Q1], rin, true);
+#pragma unroll
+      for (int k = 0; k < 32; ++k) r1[k] = fmaxf(r1[k] + ngp_vec(W, L, GV_RB1, hi, k), 0.f);
+      dense<PREC, 2, 2>(r2, WM + L.mat[G_Q2], r1, false);
+#pragma unroll
+      for (int k = 0; k < 32; ++k) r2[k] = fmaxf(r2[k] + ngp_vec(W, L, GV_RB2, hi, k), 0.f);
+    }
+    if constexpr (!BWD) {
+      if (with_rad) {
+        float o3[16];
+        dense<PREC, 1, 2>(o3, WM + L.mat[G_Q3], r2, false);
+        if (p.valid && hi == 0) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) a.rgb[3 * s + c] = 1.0f / (1.0f + nsim_fast_exp(-(o3[c] + ngp_vec(W, L, GV_RB3, hi, c))));
+        }
+      }
+    }
+    if constexpr (BWD) {
+      float dO[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dO[r] = 0.f;
+      if (with_rad) {
+        float gr[3] = {0.f, 0.f, 0.f}, rgbv[3] = {0.f, 0.f, 0.f};
+        if (p.valid) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            gr[c] = a.drgb[3 * s + c];
+            rgbv[c] = a.rgb_fwd[3 * s + c];
+          }
+        }
+        float dout[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dout[r] = 0.f;
+        if (hi == 0) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) dout[c] = gr[c] * rgbv[c] * (1.0f - rgbv[c]);
+        }
+        dw_product<PREC, 1, 2, PRIV>(stA, stB, dout, r2, accum + A_Q3, 64, 3, 64, accum + A_RB3);
+        float dr2[32];
+        dense<PREC, 2, 1>(dr2, WM + L.mat[G_Q3T], dout, true);
+#pragma unroll
+        for (int k = 0; k < 32; ++k) dr2[k] = r2[k] > 0.f ? dr2[k] : 0.f;
+        dw_product<PREC, 2, 2, PRIV>(stA, stB, dr2, r1, accum + A_Q2, 64, 64, 64, accum + A_RB2);
+        float dr1[32];
+        dense<PREC, 2, 2>(dr1, WM + L.mat[G_Q2T], dr2, true);
+#pragma unroll
+        for (int k = 0; k < 32; ++k) dr1[k] = r1[k] > 0.f ? dr1[k] : 0.f;
+        dw_product<PREC, 2, 2, PRIV>(stA, stB, dr1, rin, accum + A_Q1, 64, 64, 64, accum + A_RB1);
+        float din[32];
+        dense<PREC, 2, 2>(din, WM + L.mat[G_Q1T], dr1, true);
+        // appearance slots 48..51 = second M-tile local 16..19 (lower half-wave, registers 8..11); one atomic per ray and
+        // channel: the samples of a ray are neighbouring lanes
+        if (a.dh_appear && a.NA == 4) {
+          float c0 = din[16 + 8], c1 = din[16 + 9], c2 = din[16 + 10], c3 = din[16 + 11];
+          const bool v = p.valid && hi == 0;
+          const bool last = halfwave_run_sum2(p.ray, v, c0, c1);
+          halfwave_run_sum2(p.ray, v, c2, c3);
+          if (last) {
+            float* dst = a.dh_appear + 4 * p.ray;
+            atomicAdd(dst, c0);
+            atomicAdd(dst + 1, c1);
+            atomicAdd(dst + 2, c2);
+            atomicAdd(dst + 3, c3);
+          }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dO[r] = din[r];      // geometry feature (slot 0: the packed row is zero)
+      }
+      // ---- sigma = exp(raw - 1): d raw = (d sigma + d alpha step exp(-sigma step)) exp(min(raw - 1, 15))
+      if (hi == 0) {
+        float g = 0.f;
+        if (p.valid) {
+          const float sg = a.sigma_fwd[s];
+          if (a.dsigma) g = g + a.dsigma[s];
+          if (a.dalpha) g = g + a.dalpha[s] * (a.step * expf(-sg * a.step));
+          g = g * fminf(sg, 3269017.3724721107f);       // exp(15)
+        }
+        dO[0] = g;
+      }
+      dw_product<PREC, 1, 2, PRIV>(stA, stB, dO, a1, accum + A_D2, 64, 32, 64, accum + A_DB2);
+      float da[32];
+      dense<PREC, 2, 1>(da, WM + L.mat[G_D2T], dO, true);
+#pragma unroll
+      for (int k = 0; k < 32; ++k) da[k] = a1[k] > 0.f ? da[k] : 0.f;
+      dw_product<PREC, 2, 1, PRIV>(stA, stB, da, h, accum + A_D1, 32, 64, 32, accum + A_DB1);
+      {
+        float xt[16];     // the position block as an input tile: units 0..2 = registers 0..2 of the lower half-wave
+#pragma unroll
+        for (int r = 0; r < 16; ++r) xt[r] = (hi == 0 && r < 3) ? p.xn[r < 3 ? r : 0] : 0.f;
+        dw_product<PREC, 2, 1, PRIV>(stA, stB, da, xt, accum + A_DX, 3, 64, 3, nullptr);
+      }
+      if (a.dh_pl) {
+        float dh[16];
+        dense<PREC, 1, 2>(dh, WM + L.mat[G_D1T], da, true);
+        if (p.valid) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+              const int l = 4 * q + 2 * hi + b;
+              if (l >= a.NL) continue;                      // (the scatter reads the pyramid's own levels only)
+              const bool on = l < a.n_active;
+              float* dp = a.dh_pl + ((int64_t)l * a.S + s) * 2;
+              dp[0] = on ? dh[4 * q + 2 * b] : 0.f;
+              dp[1] = on ? dh[4 * q + 2 * b + 1] : 0.f;
+            }
+          }
+        }
+      }
+    }
+  }
+  if constexpr (BWD) {
+    __syncthreads();
+    const int F = a.F, FI = a.F + 3, K1 = 47 + a.NA;
+    const int64_t rep = (int64_t)(blockIdx.x & (unsigned)a.rep_mask) * a.rep_stride;
+    for (int i = threadIdx.x; i < A_TOTAL; i += blockDim.x) {
+      float v;
+      if constexpr (PRIV) {
+        constexpr int ACC_FLOATS = ACC_BYTES / 4;
+        const float* a0 = reinterpret_cast<const float*>(smem + wbytes);
+        v = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) v += a0[w * ACC_FLOATS + i];
+      } else {
+        v = accum[i];
+      }
+      if (v == 0.f) continue;
+      int d = -1;
+      int64_t off = 0;
+      if (i < A_DX) {
+        const int row = i >> 5, col = i & 31;
+        if (col < F) { d = 0; off = row * FI + col; }
+      } else if (i < A_DB1) {
+        const int k = i - A_DX;
+        d = 0; off = (k / 3) * FI + F + (k % 3);
+      } else if (i < A_D2) { d = 1; off = i - A_DB1; }
+      else if (i < A_DB2) { d = 0; off = 64 * FI + (i - A_D2); }
+      else if (i < A_Q1) { d = 1; off = 64 + (i - A_DB2); }
+      else if (i < A_Q2) {
+        const int row = (i - A_Q1) >> 6, c = ngp_q1_col((i - A_Q1) & 63, a.NA);
+        if (c >= 0) { d = 2; off = row * K1 + c; }
+      } else if (i < A_Q3) { d = 2; off = 64 * K1 + (i - A_Q2); }
+      else if (i < A_RB1) { d = 2; off = 64 * K1 + 4096 + (i - A_Q3); }
+      else if (i < A_RB2) { d = 3; off = i - A_RB1; }
+      else if (i < A_RB3) { d = 3; off = 64 + (i - A_RB2); }
+      else if (i - A_RB3 < 3) { d = 3; off = 128 + (i - A_RB3); }
+      if (d >= 0) atomicAdd(a.dst[d] + rep + off, v);
+    }
+  }
+}
+
+// ----------------------------------------------------------------------------------------- density occupancy
+// ``accel_cfg{type: occ_grid}`` of a density field (ngp_withlidar.230814.yaml:138-152; no ``occ_val_fn_cfg``: the value IS
+// the density): val[voxel(p)] = max(val[voxel(p)], sigma(p)).  sigma >= 0: the integer atomicMax on the bit pattern is
+// exact (occ_dev.h: occ_max_wave).
+__global__ void __launch_bounds__(256) k_occ_max_density(float* __restrict__ val, const float* __restrict__ x,
+                                                          const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                          const float* __restrict__ t, const int64_t* __restrict__ ridx,
+                                                          const float* __restrict__ sigma, int64_t n, OccDev m) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool ok = i < n;
+  float px = 0.f, py = 0.f, pz = 0.f, v = 0.f;
+  if (ok) {
+    if (x) {
+      px = x[3 * i]; py = x[3 * i + 1]; pz = x[3 * i + 2];
+    } else {
+      const int64_t r = ridx[i];
+      const float tt = t[i];
+      px = rays_o[3 * r] + tt * rays_d[3 * r];
+      py = rays_o[3 * r + 1] + tt * rays_d[3 * r + 1];
+      pz = rays_o[3 * r + 2] + tt * rays_d[3 * r + 2];
+    }
+    v = fmaxf(sigma[i], 0.f);
+    if (!(v == v)) v = 0.f;
+  }
+  occ_max_wave(val, m, ok, px, py, pz, v);
+}
+
+__global__ void __launch_bounds__(256) k_occ_scale(float* __restrict__ val, int64_t n, float decay) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) val[i] = val[i] * decay;
+}
+
+// partial sums of the value grid: block b -> part[b] (fixed grid, fixed order: the threshold is reproducible)
+#define OCC_MEAN_BLOCKS 64
+__global__ void __launch_bounds__(256) k_occ_partial_sum(const float* __restrict__ val, int64_t nvox, float* __restrict__ part) {
+  __shared__ float sh[4];
+  float s = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvox; i += (int64_t)gridDim.x * blockDim.x) s += val[i];
+  s = wave_sum(s);
+  if (nsim_lane() == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+// thre = min(occ_thre, mean(val)) (``occ_thre_consider_mean``) from the partial sums; bits; thre_out[0] = the threshold used
+__global__ void __launch_bounds__(256) k_occ_pack_bits_mean(const float* __restrict__ val, int64_t nvox, float occ_thre,
+                                                             int consider_mean, const float* __restrict__ part,
+                                                             uint32_t* __restrict__ bits, float* __restrict__ thre_out) {
+  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  float thre = occ_thre;
+  if (consider_mean) {
+    float s = 0.f;
+    for (int b = 0; b < OCC_MEAN_BLOCKS; ++b) s += part[b];
+    thre = fminf(occ_thre, s / (float)nvox);
+  }
+  if (w == 0 && thre_out) thre_out[0] = thre;
+  const int64_t nwords = (nvox + 31) / 32;
+  if (w >= nwords) return;
+  uint32_t b = 0;
+  for (int k = 0; k < 32; ++k) {
+    const int64_t v = w * 32 + k;
+    if (v < nvox && val[v] > thre) b |= (1u << k);
+  }
+  bits[w] = b;
+}
+
 // ================================================================================== C ABI
 static int nerf_meta_check(const NsimDistantMeta* m) {
   if (!m) return 20;
@@ -1013,6 +1517,187 @@ int nsim_lotd4_scatter(const NsimLotd4Meta* meta, const float* u4, const uint8_t
   sa.parity_slots = 1;
   const dim3 grid(nsim_blocks((S + 63) / 64, 4, 4096), meta->num_levels);
   hipLaunchKernelGGL(k_lotd4_scatter, grid, dim3(256), 0, (hipStream_t)stream, sa);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+
+// ------------------------------------------------------------------------------ close-range NGP NeRF (LoTDNeRFModel)
+static int ngp_meta_check(const NsimNgpMeta* m) {
+  if (!m) return 20;
+  const int rc = lotd_meta_check(&m->lotd);
+  if (rc) return rc;
+  if (m->lotd.num_levels > 16) return 38;
+  if (m->precision != 0 && m->precision != 1) return 23;
+  if (m->n_appear != 0 && m->n_appear != 4) return 39;
+  return 0;
+}
+
+static NgpArgs ngp_args(const NsimNgpMeta* meta) {
+  NgpArgs a = NgpArgs();
+  const LotdDev d = lotd_dev(&meta->lotd);
+  a.lay = ngp_layout(meta->precision);
+  a.NL = meta->lotd.num_levels;
+  a.F = 2 * a.NL;
+  a.n_active = d.n_active;
+  a.NA = meta->n_appear;
+  for (int c = 0; c < 3; ++c) {
+    a.xs[c] = d.xs[c];
+    a.xb[c] = d.xb[c];
+  }
+  return a;
+}
+
+// the replica scratch of nsim_set_grad_scratch (field.hip), for a launch of nb workgroups adding n floats
+float* nsim_grad_scratch_acquire(void* stream, int64_t n, int64_t nb, int* R);
+void nsim_grad_scratch_fold(float* sc, int R, int64_t stride, int64_t n_w, int64_t n_b, float* dst_w, float* dst_b, void* stream);
+
+int64_t nsim_ngp_wpack_bytes(const NsimNgpMeta* meta) {
+  if (ngp_meta_check(meta)) return -1;
+  return ngp_layout(meta->precision).total;
+}
+
+int nsim_ngp_pack_weights(const NsimNgpMeta* meta, const float* den_w, const float* den_b, const float* rad_w,
+                          const float* rad_b, void* wpack, void* stream) {
+  const int rc = ngp_meta_check(meta);
+  if (rc) return rc;
+  if (!den_w || !den_b || !rad_w || !rad_b || !wpack) return 4;
+  const NgpLayout L = ngp_layout(meta->precision);
+  NgpDims dims;
+  int64_t total = 0;
+  for (int m = 0; m < G_MCOUNT; ++m) {
+    dims.uo[m] = kGUo[m];
+    dims.ui[m] = kGUi[m];
+    total += (int64_t)kGUo[m] * kGUi[m];
+  }
+  total += (int64_t)GV_COUNT * 64;
+  hipLaunchKernelGGL(k_ngp_pack, dim3(nsim_blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, L, dims,
+                     2 * meta->lotd.num_levels, meta->n_appear, den_w, den_b, rad_w, rad_b, (char*)wpack);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_ngp_fwd(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* x,
+                 const float* rays_o, const float* rays_d, const float* t, const int64_t* ridx, const float* h_appear,
+                 int64_t S, float step, float* sigma, float* alpha, float* rgb, void* stream) {
+  const int rc = ngp_meta_check(meta);
+  if (rc) return rc;
+  if (S <= 0) return 0;
+  if (!wpack || !sigma) return 4;
+  if (!h_planes) return 28;
+  if (!x && !(rays_o && rays_d && t && ridx)) return 24;
+  if (rgb && !(rays_d && ridx)) return 25;
+  NgpArgs a = ngp_args(meta);
+  a.wpack = (const char*)wpack;
+  a.h_pl = h_planes;
+  a.PS = plane_pitch > 0 ? plane_pitch : NSIM_PLANE_PITCH(S);
+  a.x = x; a.rays_o = rays_o; a.rays_d = rays_d; a.t = t; a.ridx = ridx; a.h_appear = h_appear;
+  a.S = S; a.step = step;
+  a.sigma = sigma; a.alpha = alpha; a.rgb = rgb;
+  const size_t shmem = meta->precision == 0 ? (size_t)((a.lay.fwd_end + 15) & ~15) : 0;
+  const int64_t tiles = (S + 31) / 32;
+  int64_t nb = (tiles + NGP_WAVES - 1) / NGP_WAVES;
+  nb = nb > 512 ? 512 : (nb < 1 ? 1 : nb);       // persistent workgroups: 31 KB of LDS each, two per CU
+  const dim3 grid((unsigned)nb), block(64 * NGP_WAVES);
+  if (meta->precision == 0) hipLaunchKernelGGL((k_ngp<0, 0>), grid, block, shmem, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((k_ngp<1, 0>), grid, block, shmem, (hipStream_t)stream, a);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_ngp_bwd(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* x,
+                 const float* rays_o, const float* rays_d, const float* t, const int64_t* ridx, const float* h_appear,
+                 int64_t S, float step, const float* sigma_fwd, const float* rgb_fwd, const float* dsigma,
+                 const float* dalpha, const float* drgb, float* dh_planes, float* dden_w, float* dden_b, float* drad_w,
+                 float* drad_b, float* dh_appear, void* stream) {
+  const int rc = ngp_meta_check(meta);
+  if (rc) return rc;
+  if (S <= 0) return 0;
+  if (!wpack || !h_planes || !sigma_fwd) return 28;
+  if (!x && !(rays_o && rays_d && t && ridx)) return 24;
+  if (drgb && !(rays_d && ridx && rgb_fwd)) return 25;
+  if (!dden_w || !dden_b || (drgb && (!drad_w || !drad_b))) return 26;
+  NgpArgs a = ngp_args(meta);
+  a.wpack = (const char*)wpack;
+  a.h_pl = h_planes;
+  a.PS = plane_pitch > 0 ? plane_pitch : NSIM_PLANE_PITCH(S);
+  a.x = x; a.rays_o = rays_o; a.rays_d = rays_d; a.t = t; a.ridx = ridx; a.h_appear = h_appear;
+  a.S = S; a.step = step;
+  a.sigma_fwd = sigma_fwd; a.rgb_fwd = rgb_fwd;
+  a.dsigma = dsigma; a.dalpha = dalpha; a.drgb = drgb;
+  a.dh_pl = dh_planes;
+  a.dh_appear = dh_appear;
+  const bool priv = meta->precision == 0;
+  const size_t st = priv ? stage_bytes_per_wave<0>() : stage_bytes_per_wave<1>();
+  const size_t acc = (12900 * 4 + 15) & ~15;
+  const size_t vec_bytes = (size_t)((a.lay.mat[0] + 15) & ~15);
+  const size_t shmem = priv ? vec_bytes + NGP_WAVES_BWD * acc + NGP_WAVES_BWD * st : acc + NGP_WAVES_BWD * st;
+  const int64_t tiles = (S + 31) / 32;
+  int64_t nb = (tiles + NGP_WAVES_BWD - 1) / NGP_WAVES_BWD;
+  nb = nb > 256 ? 256 : (nb < 1 ? 1 : nb);       // one workgroup per CU (125 KB of LDS)
+  const int FI = 2 * meta->lotd.num_levels + 3, K1 = 47 + meta->n_appear;
+  const int64_t n[4] = {64 * FI + 2048, 96, drgb ? 64 * K1 + 4096 + 192 : 0, drgb ? 131 : 0};
+  const int64_t n_all = n[0] + n[1] + n[2] + n[3];
+  int R = 1;
+  float* sc = nsim_grad_scratch_acquire(stream, n_all, nb, &R);
+  if (sc) {        // workgroup b adds into replica b % R of the registered scratch; k_ngp_fold sums them up
+    a.dst[0] = sc; a.dst[1] = sc + n[0]; a.dst[2] = sc + n[0] + n[1]; a.dst[3] = sc + n[0] + n[1] + n[2];
+    a.rep_stride = n_all;
+    a.rep_mask = R - 1;
+  } else {
+    a.dst[0] = dden_w; a.dst[1] = dden_b; a.dst[2] = drad_w; a.dst[3] = drad_b;
+    a.rep_stride = 0;
+    a.rep_mask = 0;
+  }
+  const dim3 grid((unsigned)nb), block(64 * NGP_WAVES_BWD);
+  if (priv) hipLaunchKernelGGL((k_ngp<0, 1>), grid, block, shmem, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((k_ngp<1, 1>), grid, block, shmem, (hipStream_t)stream, a);
+  NSIM_CHECK_LAUNCH();
+  if (sc) {      // the replicas of [den_w | den_b] and of [rad_w | rad_b] folded by field.hip's reduction (which zeroes them again)
+    nsim_grad_scratch_fold(sc, R, n_all, n[0], n[1], dden_w, dden_b, stream);
+    if (drgb) nsim_grad_scratch_fold(sc + n[0] + n[1], R, n_all, n[2], n[3], drad_w, drad_b, stream);
+    NSIM_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+int nsim_occ_update_density(float* val, int64_t nvox, float decay, const float* pts, const float* sigma, int64_t n,
+                            const NsimOccMeta* meta, void* stream) {
+  if (nvox <= 0) return 0;
+  if (!meta || !val) return 5;
+  hipLaunchKernelGGL(k_occ_scale, dim3(nsim_blocks(nvox, 256)), dim3(256), 0, (hipStream_t)stream, val, nvox, decay);
+  NSIM_CHECK_LAUNCH();
+  if (n <= 0) return 0;
+  if (!pts || !sigma) return 4;
+  hipLaunchKernelGGL(k_occ_max_density, dim3(nsim_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, val, pts,
+                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const int64_t*)nullptr, sigma, n,
+                     occ_dev(meta));
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_occ_collect_density(float* val, const float* x, const float* rays_o, const float* rays_d, const float* t,
+                             const int64_t* ridx, const float* sigma, int64_t n, const NsimOccMeta* meta, void* stream) {
+  if (n <= 0) return 0;
+  if (!meta || !val) return 5;
+  if (!sigma) return 4;
+  if (!x && !(rays_o && rays_d && t && ridx)) return 24;
+  hipLaunchKernelGGL(k_occ_max_density, dim3(nsim_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, val, x, rays_o,
+                     rays_d, t, ridx, sigma, n, occ_dev(meta));
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_occ_pack_bits_mean(const float* val, int64_t nvox, float occ_thre, int consider_mean, float* workspace,
+                            uint32_t* bits, void* stream) {
+  if (nvox <= 0) return 0;
+  if (!val || !bits || !workspace) return 4;
+  if (consider_mean) {
+    hipLaunchKernelGGL(k_occ_partial_sum, dim3(OCC_MEAN_BLOCKS), dim3(256), 0, (hipStream_t)stream, val, nvox, workspace);
+    NSIM_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(k_occ_pack_bits_mean, dim3(nsim_blocks((nvox + 31) / 32, 256)), dim3(256), 0, (hipStream_t)stream, val,
+                     nvox, occ_thre, consider_mean, workspace, bits, workspace + OCC_MEAN_BLOCKS);
   NSIM_CHECK_LAUNCH();
   return 0;
 }

@@ -28,14 +28,14 @@ __device__ __forceinline__ bool occ_voxel(const OccDev& m, float px, float py, f
   return inside;
 }
 
-// val[voxel(p)] = max(val[voxel(p)], 4 sig(s sdf)(1 - sig(s sdf))) for the lanes with ``ok`` (all 64 lanes call).
+// val[voxel(p)] = max(val[voxel(p)], v) for the lanes with ``ok`` (all 64 lanes call), v >= 0.
 // Consecutive samples of a ray share voxels (64^3 grid: ~6 marching steps per voxel) and most values do not exceed what
 // the grid already holds: same-address atomics are separate requests that serialise in L2, so (1) equal voxels of
 // neighbouring lanes are max-reduced inside the wave and only the last lane of a run goes on, (2) it skips the atomic
-// when a plain read already shows a value >= its own (the grid only grows between refreshes).  f(sdf) >= 0: the integer
+// when a plain read already shows a value >= its own (the grid only grows between refreshes).  v >= 0: the integer
 // atomicMax on the bit pattern is exact.
-__device__ __forceinline__ void occ_collect_wave(float* __restrict__ val, const OccDev& m, bool ok, float px, float py,
-                                                 float pz, float sdf, float inv_s) {
+__device__ __forceinline__ void occ_max_wave(float* __restrict__ val, const OccDev& m, bool ok, float px, float py,
+                                             float pz, float v_in) {
   const int lane = nsim_lane();
   int64_t flat = -1 - lane;
   float v = 0.f;
@@ -44,8 +44,7 @@ __device__ __forceinline__ void occ_collect_wave(float* __restrict__ val, const 
     ok = occ_voxel(m, px, py, pz, f);
     if (ok) {
       flat = f;
-      const float s = 1.0f / (1.0f + expf(-sdf * inv_s));
-      v = 4.0f * s * (1.0f - s);
+      v = v_in;
     }
   }
   const int64_t pk = wave_shfl(flat, lane - 1);
@@ -63,6 +62,17 @@ __device__ __forceinline__ void occ_collect_wave(float* __restrict__ val, const 
   int iv;
   memcpy(&iv, &v, 4);
   atomicMax((int*)val + flat, iv);
+}
+
+// the SDF-derived occupancy value 4 sig(s sdf)(1 - sig(s sdf)) (``occ_val_fn_cfg{type: sdf, inv_s}``) folded the same way
+__device__ __forceinline__ void occ_collect_wave(float* __restrict__ val, const OccDev& m, bool ok, float px, float py,
+                                                 float pz, float sdf, float inv_s) {
+  float v = 0.f;
+  if (ok) {
+    const float s = 1.0f / (1.0f + expf(-sdf * inv_s));
+    v = 4.0f * s * (1.0f - s);
+  }
+  occ_max_wave(val, m, ok, px, py, pz, v);
 }
 
 // ------------------------------------------------------------------------------------------ marching lattice

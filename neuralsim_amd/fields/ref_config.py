@@ -265,3 +265,91 @@ def distant_native_kwargs(params: dict) -> Dict:
     if "max_steps" in mc:
         kw["max_steps"] = int(mc["max_steps"])
     return kw
+
+
+NERF_REFERENCE_KEYS = {"dtype", "encoding_cfg", "extra_pos_embed_cfg", "density_decoder_cfg", "radiance_decoder_cfg",
+                       "n_extra_feat_from_output", "use_tcnn_backend", "accel_cfg", "ray_query_cfg", "precision"}
+
+
+def validate_nerf_params(params: dict) -> Dict:
+    """Reference ``model_params`` of the close-range ``LoTDNeRFModel`` (waymo/ngp_withlidar.230814.yaml:101-158) -> the
+    settings ``fields/nerf.py`` builds from.  Every option the kernels of csrc/nerf_field.hip do not cover raises
+    ``NotImplementedError`` naming the key."""
+    p = dict(params)
+    unknown = set(p) - NERF_REFERENCE_KEYS
+    if unknown:
+        raise TypeError(f"LoTDNeRFModel: unexpected model_params {sorted(unknown)}")
+    if p.get("use_tcnn_backend", False):
+        _unsupported("use_tcnn_backend", True, "there is no tiny-cuda-nn here; the decoders are HIP MFMA kernels")
+    out: Dict = dict(precision=p.get("precision") or _precision(p.get("dtype", "half")))
+    enc = dict(p.get("encoding_cfg") or {})
+    if int(enc.get("input_ch", 3)) != 3:
+        _unsupported("encoding_cfg.input_ch", enc.get("input_ch"), "the close-range model encodes (x, y, z)")
+    ac = dict(enc.get("lotd_auto_compute_cfg") or dict(type="ngp", target_num_params=32 * 2 ** 20, min_res=16,
+                                                        log2_hashmap_size=20))
+    if ac.get("type", "ngp") not in ("ngp", "gen_ngp"):
+        _unsupported("encoding_cfg.lotd_auto_compute_cfg.type", ac.get("type"), "ngp and gen_ngp are built")
+    if int(ac.get("n_feats", 2)) != 2:
+        _unsupported("lotd_auto_compute_cfg.n_feats", ac.get("n_feats"), "2 features per level")
+    if ac.get("type", "ngp") == "ngp":        # the decoders read at most 32 features: the pyramid stops at 16 levels
+        ac["max_num_levels"] = min(int(ac.get("max_num_levels") or 16), 16)
+    elif int(ac.get("num_levels", 16)) > 16:
+        _unsupported("lotd_auto_compute_cfg.num_levels", ac.get("num_levels"), "at most 16 levels (32 decoder input features)")
+    out["auto"] = ac
+    out["cuboid"] = bool(enc.get("lotd_use_cuboid", False))
+    pi = dict(enc.get("param_init_cfg") or {})
+    if pi.get("type", "uniform_to_type") != "uniform_to_type":
+        _unsupported("encoding_cfg.param_init_cfg.type", pi.get("type"), "uniform_to_type")
+    out["param_bound"] = float(pi.get("bound", 1e-4))
+    an = enc.get("anneal_cfg")
+    out["anneal"] = None
+    if an is not None:
+        if an.get("type", "hardmask") != "hardmask":
+            _unsupported("encoding_cfg.anneal_cfg.type", an.get("type"), "hardmask level annealing is built")
+        out["anneal"] = dict(start_it=int(an.get("start_it", 0)), stop_it=int(an.get("stop_it", 1000)),
+                             start_level=int(an.get("start_level", 2)))
+    if (p.get("extra_pos_embed_cfg") or {}).get("type", "identity") != "identity":
+        _unsupported("extra_pos_embed_cfg.type", p["extra_pos_embed_cfg"]["type"], "identity (the position itself)")
+    dd = dict(p.get("density_decoder_cfg") or {})
+    _check_decoder("density_decoder_cfg", dd, {1})
+    oa = dd.get("output_activation") or dict(type="trunc_exp", offset=-1)
+    oa = dict(type=oa) if isinstance(oa, str) else dict(oa)
+    if oa.get("type") != "trunc_exp" or float(oa.get("offset", -1)) != -1.0:
+        _unsupported("density_decoder_cfg.output_activation", oa, "trunc_exp with offset -1 is what the kernels evaluate")
+    if int(p.get("n_extra_feat_from_output", 31)) != 31:
+        _unsupported("n_extra_feat_from_output", p.get("n_extra_feat_from_output"), "31 geometry features next to sigma")
+    rd = dict(p.get("radiance_decoder_cfg") or {})
+    _check_decoder("radiance_decoder_cfg", rd, {2})
+    if rd.get("use_pos", False):
+        _unsupported("radiance_decoder_cfg.use_pos", True, "the radiance kernel has no position input")
+    if rd.get("use_nablas", False):
+        _unsupported("radiance_decoder_cfg.use_nablas", True, "a density field has no normals here")
+    de = dict(rd.get("dir_embed_cfg") or dict(type="spherical", degree=4))
+    if not rd.get("use_view_dirs", True) or de.get("type") != "spherical" or int(de.get("degree", 4)) != 4:
+        _unsupported("radiance_decoder_cfg.dir_embed_cfg", de, "view directions enter through spherical harmonics of degree 4")
+    out["n_appear"] = int(rd.get("n_appear_embedding", 0) or 0)
+    if out["n_appear"] not in (0, 4):
+        _unsupported("radiance_decoder_cfg.n_appear_embedding", rd.get("n_appear_embedding"), "0 or 4 appearance channels")
+    acc = _plain(dict(p.get("accel_cfg") or {}))
+    if acc.get("type", "occ_grid") != "occ_grid":
+        _unsupported("accel_cfg.type", acc.get("type"), "occ_grid")
+    if acc.get("occ_val_fn_cfg") is not None:
+        _unsupported("accel_cfg.occ_val_fn_cfg", acc["occ_val_fn_cfg"], "the occupancy value of a density field is the density")
+    ic = acc.get("init_cfg") or {}
+    if ic.get("mode", "constant") != "constant":
+        _unsupported("accel_cfg.init_cfg.mode", ic.get("mode"), "constant")
+    if acc.get("update_from_samples_cfg"):
+        _unsupported("accel_cfg.update_from_samples_cfg", acc["update_from_samples_cfg"], "{} (every sample is used)")
+    if "resolution" not in acc:
+        acc["resolution"] = [64, 64, 64]
+    out["accel_cfg"] = acc
+    rq = _plain(p.get("ray_query_cfg") or dict(query_mode="march_occ", query_param=dict(march_cfg=dict(step_size=0.1, max_steps=4096))))
+    if rq.get("query_mode", "march_occ") != "march_occ":
+        _unsupported("ray_query_cfg.query_mode", rq.get("query_mode"), "march_occ")
+    out["ray_query_cfg"] = rq
+    return out
+
+
+def nerf_lod_res(cfgd: dict, aabb) -> Tuple[list, int]:
+    """The 3-D pyramid of a validated NeRF block: ``lod_res_from_encoding_cfg`` on its (level-capped) auto-compute block."""
+    return lod_res_from_encoding_cfg(dict(lotd_auto_compute_cfg=cfgd["auto"], lotd_use_cuboid=cfgd["cuboid"]), aabb)

@@ -1,0 +1,427 @@
+"""Close-range LoTD NeRF model (InstantNGP + UrbanNeRF, waymo/ngp_withlidar.230814.yaml): the fused density / radiance
+decoders of csrc/nerf_field.hip (nsim_ngp_fwd / nsim_ngp_bwd), the density occupancy grid and the host model
+(neuralsim_amd/fields/nerf.py) against the restatement tests/nerf_ref.py."""
+import copy
+
+import pytest
+import torch
+
+import nerf_ref as nr
+from oracle import render as orr
+from util import leaf, look_at_cameras, rel_l2
+
+AABB = torch.tensor([[-1.0, -1, -1], [1.0, 1, 1]])
+RES = [8, 8, 8]
+STEP, MAX_STEPS, N = 0.09, 64, 21
+
+
+def yaml_params(levels=6, n_appear=0, dtype="float", **over):
+    """The ``model_params`` block of ngp_withlidar.230814.yaml:101-158 with the sizes overridden down."""
+    p = dict(
+        dtype=dtype,
+        encoding_cfg=dict(input_ch=3, lotd_use_cuboid=False,
+                          lotd_auto_compute_cfg=dict(type="ngp", target_num_params=2 ** 30, min_res=4, n_feats=2,
+                                                     log2_hashmap_size=9, max_num_levels=levels),
+                          param_init_cfg=dict(type="uniform_to_type", bound=1.0e-4)),
+        extra_pos_embed_cfg=dict(type="identity"),
+        density_decoder_cfg=dict(type="mlp", D=1, W=64, output_activation=dict(type="trunc_exp", offset=-1)),
+        n_extra_feat_from_output=31,
+        radiance_decoder_cfg=dict(use_pos=False, use_view_dirs=True, use_nablas=False, dir_embed_cfg=dict(type="spherical", degree=4),
+                                  D=2, W=64, n_appear_embedding=n_appear),
+        accel_cfg=dict(type="occ_grid", resolution=RES, occ_thre_consider_mean=True, occ_thre=0.5, ema_decay=0.95,
+                       init_cfg=dict(mode="constant", constant_value=1.0e-2), update_from_net_cfg=dict(num_steps=1, num_pts=1024),
+                       update_from_samples_cfg={}, n_steps_between_update=16, n_steps_warmup=256),
+        ray_query_cfg=dict(query_mode="march_occ", query_param=dict(march_cfg=dict(step_size=STEP, max_steps=MAX_STEPS))))
+    p.update(over)
+    return p
+
+
+def pattern():
+    """hand-set 8^3 occupancy: the voxels with (i + j + k) % 3 == 0, storage order x fastest"""
+    v = torch.arange(RES[0] * RES[1] * RES[2])
+    i, j, k = v % RES[0], (v // RES[0]) % RES[1], v // (RES[0] * RES[1])
+    return (i + j + k) % 3 == 0
+
+
+def build(backend, levels=6, n_appear=0, precision="f32", seed=11):
+    from neuralsim_amd.fields.nerf import LoTDNeRFModel
+    m = LoTDNeRFModel(**yaml_params(levels, n_appear, dtype={"f32": "float", "fp16": "half"}[precision]))
+    cfg = m.encoding.cfg
+    assert cfg.num_levels == levels and "Dense" in cfg.lod_types and "Hash" in cfg.lod_types
+    p = nr.make_nerf_params(cfg.lod_res, 9, n_appear=n_appear, seed=seed)
+    assert p.spec.n_params == cfg.n_params
+    with torch.no_grad():
+        m.encoding.flattened_params.copy_(p.grid)
+        m.den_w.copy_(torch.cat([w.reshape(-1) for w in p.den_w]))
+        m.den_b.copy_(torch.cat(p.den_b))
+        m.rad_w.copy_(torch.cat([w.reshape(-1) for w in p.rad_w]))
+        m.rad_b.copy_(torch.cat(p.rad_b))
+    m = m.to(backend)
+    occ = pattern()
+    m.accel.occ_val.copy_(occ.float().to(backend))
+    m.accel.pack_bits()
+    return m, p, occ
+
+
+_RAYS = {}
+
+
+def rays():
+    """N = 21 rays, every fourth shifted to miss the box; computed once."""
+    if not _RAYS:
+        g = torch.Generator().manual_seed(1)
+        intr, c2w, WH = look_at_cameras(V=3, seed=2)
+        o, d = orr.pinhole_rays(torch.rand(N, 2, generator=g) * 0.6 + 0.2, torch.randint(0, 3, (N,), generator=g), intr, c2w, WH)
+        o[::4] += torch.tensor([0.0, 3.0, 0.0])
+        near, far, hit = orr.aabb_ray_test(o, d, AABB[0], AABB[1], 0.01, None)
+        occ = pattern()
+        assert 0 < int(hit.sum()) < N and 0.1 < float(occ.float().mean()) < 0.6
+        t, ridx, counts, pi = nr.march(o[hit], d[hit], near[hit], far[hit], torch.zeros(int(hit.sum())), occ, AABB, RES, STEP,
+                                       MAX_STEPS)
+        assert t.shape[0] % 32 != 0 and int(counts.max()) <= 40 and t.shape[0] > 64
+        _RAYS.update(o=o, d=d, hit=hit, t=t, ridx=ridx, counts=counts, ha=torch.randn(N, 4, generator=g) * 0.3,
+                     wa=torch.randn(t.shape[0], generator=g), wr=torch.randn(t.shape[0], 3, generator=g))
+    return _RAYS
+
+
+def run_query(m, backend, ha=None, **cfg):
+    r = rays()
+    dv = lambda t: t.to(backend).contiguous()      # noqa: E731
+    kw = dict(rays_h_appear=ha) if ha is not None else {}
+    tested = m.ray_test(dv(r["o"]), dv(r["d"]), near=0.01, **kw)
+    ret = m.ray_query(ray_tested=tested, config=dict(cfg), return_details=True)
+    return tested, ret
+
+
+def flat_grads(p):
+    return dict(grid=p.grid.grad, den_w=torch.cat([w.grad.reshape(-1) for w in p.den_w]), den_b=torch.cat([b.grad for b in p.den_b]),
+                rad_w=torch.cat([w.grad.reshape(-1) for w in p.rad_w]), rad_b=torch.cat([b.grad for b in p.rad_b]))
+
+
+def scene(backend, distant=True, sky=True):
+    """The model (6 levels, 4 appearance channels, f32) as the close-range object of tests/renderer_scenario.py's scene dict,
+    with that file's distant model and sky behind it: shared by tests/test_nerf_reference.py and the frozen replay below."""
+    from oracle import distant as od
+    from renderer_scenario import build_scenario
+    s = build_scenario("main_distant_sky_train", backend)
+    m, p, _ = build(backend, 6, 4, "f32")
+    r = rays()
+    dv = lambda t: t.to(backend).contiguous()      # noqa: E731
+    s.update(model=m, p=p, rays_o=dv(r["o"]), rays_d=dv(r["d"]), h_appear=dv(r["ha"]), N=N, distant=distant, sky=sky)
+    s["pd"] = od.make_distant_params(od.make_ngp4d_spec(target_num_params=2 ** 14, min_res_xyz=3, min_res_w=2, log2_hashmap_size=10),
+                                     grid_bound=0.5)
+    if not distant:
+        s["distant_model"] = None
+    if not sky:
+        s["sky_model"] = None
+    g = torch.Generator().manual_seed(9)
+    s["w"] = dict(rgb_volume=dv(torch.randn(N, 3, generator=g)), depth_volume=dv(torch.randn(N, generator=g) * 0.1),
+                  mask_volume=dv(torch.randn(N, generator=g)))
+    s["common"] = dict(with_rgb=True, with_normal=True, near=0.01, depth_use_normalized_vw=False, perturb=False)
+    return s
+
+
+def test_frozen_reference_renderer_replay(backend):
+    """The renderer mirror on the model with the distant model and the sky behind it, against the images the REFERENCE's
+    SingleVolumeRenderer produced for the same scene (tests/golden/nerf_renderer_fixture.npz, frozen by
+    tests/test_nerf_reference.py on the f32 emulator); bounds of test_reference_glue.py's fixture replay."""
+    import numpy as np
+    from pathlib import Path
+    from renderer_scenario import run_mirror
+    fx = np.load(str(Path(__file__).resolve().parent / "golden" / "nerf_renderer_fixture.npz"))
+    sc = scene(backend)
+    got = run_mirror(sc, backward=True)
+    assert torch.equal(got["samples_cnt"], torch.from_numpy(fx["samples_cnt"]))
+    for k in ("rgb_volume", "depth_volume", "mask_volume"):
+        e = float((got["rendered"][k] - torch.from_numpy(fx[k])).abs().max())
+        assert e <= (2e-2 if k == "depth_volume" else 5e-4), (k, e)
+    assert "nablas" not in got["volume_buffer"] and float(got["grads"]["main.encoding.flattened_params"].abs().sum()) > 0
+
+
+@pytest.mark.parametrize("levels", [6, 16])
+@pytest.mark.parametrize("n_appear", [0, 4])
+@pytest.mark.parametrize("precision", ["f32", "fp16"])
+def test_decoder_parity(backend, precision, n_appear, levels):
+    """sigma / alpha / rgb and every gradient at the model's own samples.  Value bounds and the f32 backward bound are those
+    of tests/test_distant.py (2e-5 | 5e-3, alpha ten times that, 3e-4).  The fp16 backward does not hold that file's 3e-2
+    here: the restatement itself, evaluated with fp16-rounded weights and layer inputs against itself in f32 on these
+    samples, differs by up to 3.12e-2 rel-L2 (rad_w at 6 levels with 4 appearance channels; 2.94e-2 den_b, 2.70e-2 table --
+    a ReLU unit whose pre-activation the rounding carries across zero changes that unit's whole gradient, and the batch
+    has ~150 samples), and the kernels reproduce those figures to three digits (3.12e-2, 2.94e-2, 2.70e-2).  The fp16
+    backward bound is twice that measurement: 6.24e-2."""
+    m, p, _ = build(backend, levels, n_appear, precision)
+    p.requires_grad_(True)
+    r = rays()
+    ha_d = leaf(r["ha"], backend) if n_appear else None
+    tested, ret = run_query(m, backend, ha_d, with_rgb=True)
+    vb = ret["volume_buffer"]
+    assert vb["type"] == "packed" and "nablas" not in vb
+    t, ridx = vb["t"].detach().cpu(), ret["details"]["ridx"].cpu()
+    assert torch.equal(ret["details"]["march_counts"].cpu(), r["counts"]) and torch.allclose(t, r["t"], atol=1e-6)
+    assert torch.equal(vb["rays_inds_hit"].cpu(), r["hit"].nonzero()[:, 0][r["counts"] > 0])
+    ha_o = leaf(r["ha"]) if n_appear else None
+    ref = nr.query_at(p, r["o"][r["hit"]], r["d"][r["hit"]], t, ridx, STEP, ha_o[r["hit"]] if n_appear else None)
+    tol = dict(f32=2e-5, fp16=5e-3)[precision]
+    es = float((vb["sigma"].detach().cpu() - ref["sigma"].detach()).abs().max()) / (1 + float(ref["sigma"].max()))
+    er = float((vb["rgb"].detach().cpu() - ref["rgb"].detach()).abs().max())
+    ea = float((vb["opacity_alpha"].detach().cpu() - ref["opacity_alpha"].detach()).abs().max())
+    print(f"[nerf parity {precision} na={n_appear} L={levels}] sigma {es:.3e} rgb {er:.3e} alpha {ea:.3e}")
+    assert es < tol and er < tol and ea < 10 * tol
+    ((ref["opacity_alpha"] * r["wa"]).sum() + (ref["rgb"] * r["wr"]).sum()).backward()
+    ((vb["opacity_alpha"] * r["wa"].to(backend)).sum() + (vb["rgb"] * r["wr"].to(backend)).sum()).backward()
+    gtol = dict(f32=3e-4, fp16=2 * 3.12e-2)[precision]
+    refg = flat_grads(p)
+    got = dict(grid=m.encoding.flattened_params.grad, den_w=m.den_w.grad, den_b=m.den_b.grad, rad_w=m.rad_w.grad, rad_b=m.rad_b.grad)
+    errs = {k: rel_l2(got[k].cpu(), refg[k]) for k in refg}
+    if n_appear:
+        errs["h_appear"] = rel_l2(ha_d.grad.cpu(), ha_o.grad)
+    print(f"[nerf parity {precision} na={n_appear} L={levels}] grads", {k: f"{v:.2e}" for k, v in errs.items()})
+    for k, e in errs.items():
+        assert e < gtol, (k, e)
+
+
+def test_weight_gradient_replicas(backend, monkeypatch):
+    """The weight gradients through the replicas of the registered scratch equal the direct flush."""
+    from neuralsim_amd import _lib
+    grads = []
+    for min_wg in ("1000000", "1"):
+        monkeypatch.setenv("NSIM_GRAD_REPLICAS_MIN_WG", min_wg)
+        m, _, _ = build(backend, 6, 0, "f32")
+        _lib.ensure_grad_scratch(backend)
+        _, ret = run_query(m, backend, with_rgb=True)
+        vb = ret["volume_buffer"]
+        (vb["opacity_alpha"].sum() + vb["rgb"].sum()).backward()
+        grads.append([q.grad.cpu().clone() for q in (m.den_w, m.den_b, m.rad_w, m.rad_b)])
+    for a, b in zip(*grads):
+        assert float(b.abs().sum()) > 0 and rel_l2(a, b) < 1e-5
+    assert float(_lib.ensure_grad_scratch(backend).abs().sum()) == 0.0
+
+
+def test_density_only_path(backend):
+    m, _, _ = build(backend, 6, 4, "f32")
+    r = rays()
+    _, full = run_query(m, backend, r["ha"].to(backend), with_rgb=True)
+    _, dens = run_query(m, backend, r["ha"].to(backend), with_rgb=False)
+    a, b = full["volume_buffer"], dens["volume_buffer"]
+    assert "rgb" not in b and "nablas" not in b
+    assert torch.equal(a["sigma"].detach(), b["sigma"].detach()) and torch.equal(a["opacity_alpha"].detach(), b["opacity_alpha"].detach())
+    b["opacity_alpha"].sum().backward()
+    assert m.rad_w.grad is None or float(m.rad_w.grad.abs().sum()) == 0.0
+    assert m.rad_b.grad is None or float(m.rad_b.grad.abs().sum()) == 0.0
+    assert float(m.den_w.grad.abs().sum()) > 0 and float(m.encoding.flattened_params.grad.abs().sum()) > 0
+    with pytest.raises(NotImplementedError, match="with_feature_dim"):
+        run_query(m, backend, with_feature_dim=3)
+
+
+@pytest.mark.parametrize("sign", [1.0, -1.0])
+def test_trunc_exp(backend, sign):
+    """Raw outputs pushed to +-20 through a scaled head weight: exp(raw - 1) forward, clamped derivative backward."""
+    m, p, _ = build(backend, 6, 0, "f32")
+    g = torch.Generator().manual_seed(3)
+    x = torch.rand(40, 3, generator=g) * 1.8 - 0.9
+    with torch.no_grad():
+        raw0 = nr.density(p, x)[2]
+        k = 20.0 / float(raw0.abs().max())
+        p.den_w[1][0] *= k
+        p.den_b[1][0] = sign * 20.0 - float((raw0 * k).mean())
+        m.den_w.copy_(torch.cat([w.reshape(-1) for w in p.den_w]).to(backend))
+        m.den_b.copy_(torch.cat(p.den_b).to(backend))
+    p.requires_grad_(True)
+    sig_o, _, raw = nr.density(p, x)
+    assert float(raw.max() if sign > 0 else -raw.min()) > 17.0
+    sig = m.forward_density(x.to(backend))["sigma"]
+    assert torch.allclose(sig.detach().cpu(), torch.exp(raw.detach() - 1.0), rtol=2e-4, atol=1e-30)
+    w = torch.rand(40, generator=g)
+    (sig_o * w).sum().backward()
+    (sig * w.to(backend)).sum().backward()
+    gg = m.encoding.flattened_params.grad.cpu()
+    assert bool(torch.isfinite(gg).all()) and rel_l2(gg, p.grid.grad) < 3e-4
+
+
+def test_empty_and_tail_cases(backend):
+    m, p, _ = build(backend, 6, 0, "f32")
+    g = torch.Generator().manual_seed(5)
+    for S in (1, 33):
+        x = torch.rand(S, 3, generator=g) * 1.8 - 0.9
+        with torch.no_grad():
+            ref = nr.density(p, x)[0]
+        got = m.query_density(x.to(backend)).cpu()
+        assert got.shape == (S,) and (got - ref).abs().max() < 2e-5 * (1 + float(ref.max()))
+        out = m.sample_pts_uniform(S)
+        assert out["sigma"].shape == (S,) and out["x"].shape == (S, 3) and out["sigma"].requires_grad
+    m.accel.occ_val.zero_()
+    m.accel.pack_bits()
+    assert m.accel.frac_occupied() == 0.0
+    _, ret = run_query(m, backend, with_rgb=True)
+    assert ret["volume_buffer"]["type"] == "empty"
+
+
+@pytest.mark.parametrize("above", [True, False])
+def test_density_occupancy(backend, above):
+    """init -> one refresh (value grid against the restatement fed the same points) -> bits = val > min(occ_thre, mean), with
+    occ_thre once above and once below the mean; collect raises exactly the voxels of the step's samples."""
+    m, p, _ = build(backend, 6, 0, "f32")
+    acc = m.accel
+    acc.init()
+    assert acc.frac_occupied() == 1.0 and float(acc.occ_val.min()) == float(acc.occ_val.max()) == float(torch.tensor(1.0e-2))
+    gen = torch.Generator(device=backend).manual_seed(7)
+    pts_d = acc.draw_points(1024, gen)
+    pts = pts_d.cpu()
+    with torch.no_grad():
+        sig = nr.density(p, pts)[0]
+    val = nr.occ_update_density(torch.full([512], 1.0e-2), pts, sig, AABB, RES, 0.95)
+    occ_thre = 50.0 if above else float(val.kthvalue(128).values)       # the restatement's lower quartile: below its mean
+    acc.occ_thre = occ_thre
+    acc.update_from_samples(pts_d, m.query_density(pts_d))
+    got = acc.occ_val.cpu()
+    assert (got - val).abs().max() < 2e-5 * (1 + float(val.max()))
+    bits, thre = nr.occ_bits(got, occ_thre, True)
+    assert (occ_thre > float(got.mean())) == above and 0 < int(bits.sum()) < 512
+    assert abs(float(acc.occ_thre_dev) - thre) < 1e-6 * thre
+    assert torch.equal(acc.occ_grid.permute(2, 1, 0).reshape(-1).cpu(), bits)
+    assert abs(acc.frac_occupied() - float(bits.float().mean())) < 1e-7
+    # collect: the samples of one query, no decay
+    acc.occ_val.copy_(pattern().float().to(backend) * 1e-3)
+    acc.occ_thre = 1e-4
+    acc.pack_bits()
+    before = acc.occ_val.cpu().clone()
+    acc.collect_armed = True
+    _, ret = run_query(m, backend, with_rgb=False)
+    vb = ret["volume_buffer"]
+    r = rays()
+    x = r["o"][r["hit"]][ret["details"]["ridx"].cpu()] + vb["t"].cpu()[:, None] * r["d"][r["hit"]][ret["details"]["ridx"].cpu()]
+    want = nr.occ_update_density(before, x, vb["sigma"].detach().cpu(), AABB, RES, 1.0)
+    after = acc.occ_val.cpu()
+    assert torch.allclose(after, want, rtol=1e-6, atol=0) and bool((after >= before).all()) and bool((after > before).any())
+    assert not acc.collect_armed
+
+
+def test_level_annealing(backend):
+    """``anneal_cfg{type: hardmask}``: masked levels contribute zero features and receive exactly zero gradient."""
+    m, p, _ = build(backend, 6, 0, "f32")
+    m.set_active_levels(3)
+    _, ret = run_query(m, backend, with_rgb=True)
+    vb = ret["volume_buffer"]
+    off = p.spec.lod_offsets[3]
+    pz = copy.deepcopy(p)
+    pz.grid[off:] = 0
+    r = rays()
+    with torch.no_grad():
+        ref = nr.query_at(pz, r["o"][r["hit"]], r["d"][r["hit"]], vb["t"].cpu(), ret["details"]["ridx"].cpu(), STEP)
+    assert (vb["sigma"].detach().cpu() - ref["sigma"]).abs().max() < 2e-5 * (1 + float(ref["sigma"].max()))
+    assert (vb["rgb"].detach().cpu() - ref["rgb"]).abs().max() < 2e-5
+    (vb["opacity_alpha"].sum() + vb["rgb"].sum()).backward()
+    gg = m.encoding.flattened_params.grad.cpu()
+    assert float(gg[off:].abs().max()) == 0.0 and float(gg[:off].abs().sum()) > 0
+    # the yaml's schedule: start_level -1, all levels by stop_it
+    from neuralsim_amd.fields.nerf import LoTDNeRFModel
+    enc = dict(yaml_params()["encoding_cfg"], anneal_cfg=dict(type="hardmask", start_level=-1, stop_it=1000))
+    m2 = LoTDNeRFModel(**yaml_params(encoding_cfg=enc))
+    m2._anneal(0)
+    assert m2.meta.lotd.n_active_levels == 1
+    m2._anneal(1000)
+    assert m2.meta.lotd.n_active_levels == 0       # 0 = all levels
+
+
+def test_config_and_state_dict(backend):
+    from neuralsim_amd.fields.nerf import LoTDNeRFModel
+    from nr3d_lib.models.fields.nerf import LoTDNeRFModel as ShimModel
+    assert ShimModel is LoTDNeRFModel
+    bad = [("density_decoder_cfg", dict(type="mlp", D=1, W=128), "density_decoder_cfg.W"),
+           ("density_decoder_cfg", dict(type="mlp", D=2, W=64), "density_decoder_cfg.D"),
+           ("radiance_decoder_cfg", dict(D=3, W=64), "radiance_decoder_cfg.D"),
+           ("n_extra_feat_from_output", 15, "n_extra_feat_from_output"),
+           ("density_decoder_cfg", dict(type="mlp", D=1, W=64, output_activation="softplus"), "output_activation"),
+           ("radiance_decoder_cfg", dict(use_pos=True, D=2, W=64), "use_pos"),
+           ("radiance_decoder_cfg", dict(use_nablas=True, D=2, W=64), "use_nablas"),
+           ("radiance_decoder_cfg", dict(dir_embed_cfg=dict(type="sinusoidal", n_frequencies=4), D=2, W=64), "dir_embed_cfg"),
+           ("radiance_decoder_cfg", dict(n_appear_embedding=8, D=2, W=64), "n_appear_embedding"),
+           ("ray_query_cfg", dict(query_mode="march_occ_multi_upsample"), "query_mode"),
+           ("accel_cfg", dict(type="occ_grid", init_cfg=dict(mode="from_net")), "init_cfg.mode"),
+           ("use_tcnn_backend", True, "use_tcnn_backend")]
+    for key, val, word in bad:
+        with pytest.raises(NotImplementedError, match=word):
+            LoTDNeRFModel(**yaml_params(**{key: val}))
+    m, _, _ = build(backend, 6, 4, "f32")
+    fresh = LoTDNeRFModel(**yaml_params(6, 4)).to(backend)
+    fresh.load_state_dict(m.state_dict())
+    fresh.accel.pack_bits()
+    r = rays()
+    ha = r["ha"].to(backend)
+    with torch.no_grad():
+        _, a = run_query(m, backend, ha, with_rgb=True)
+        _, b = run_query(fresh, backend, ha, with_rgb=True)
+    for k in ("t", "sigma", "opacity_alpha", "rgb", "pack_infos_hit", "rays_inds_hit"):
+        assert torch.equal(a["volume_buffer"][k], b["volume_buffer"][k]), k
+    o = leaf(r["o"], backend)
+    with pytest.raises(NotImplementedError, match="rays_o"):
+        m.ray_query(ray_tested=m.ray_test(o, r["d"].to(backend), near=0.01), config={})
+
+
+def test_yaml_model_params_construct():
+    """The reference's own ``assetbank_cfg.Street.model_params`` (tests/golden/ngp_withlidar_model_params.yaml: the block of
+    ngp_withlidar.230814.yaml with its interpolations resolved), loaded with nr3d_lib.config, constructs the model (sizes
+    overridden down)."""
+    from pathlib import Path
+    from nr3d_lib.config import load_config
+    cfg = load_config(str(Path(__file__).resolve().parent / "golden" / "ngp_withlidar_model_params.yaml"))
+    mp = cfg["assetbank_cfg"]["Street"]["model_params"]
+    mp = mp.to_dict() if hasattr(mp, "to_dict") else dict(mp)
+    assert mp["n_extra_feat_from_output"] == 31 and mp["encoding_cfg"]["lotd_auto_compute_cfg"]["target_num_params"] == 32 * 2 ** 20
+    from neuralsim_amd.fields.nerf import LoTDNeRFModel
+    mp = copy.deepcopy(mp)
+    mp["encoding_cfg"]["lotd_auto_compute_cfg"].update(log2_hashmap_size=9, min_res=4)
+    mp["accel_cfg"]["resolution"] = RES
+    m = LoTDNeRFModel(**mp)
+    assert m.encoding.cfg.num_levels == 16 and m.n_appear == 0 and m.meta.precision == 0
+    assert m.accel.occ_thre_consider_mean and m.ray_query_cfg["query_mode"] == "march_occ"
+    assert len(m.training_setup(dict(lr=1e-2, eps=1e-15, betas=[0.9, 0.99])).param_groups) == 3
+    assert m.get_weight_reg().shape == (2,)
+
+
+def test_nerf_training_steps(backend):
+    """30 Adam steps (the package's optimizer) on one fixed batch rendered from a restatement scene, driven through
+    ``training_before_per_step`` / ``training_after_per_step`` (annealing, the occupancy refresh on a shortened schedule, the
+    sample collection): rgb MSE + density_reg on sample_pts_uniform with a rewound point stream; the loss ends below its
+    start, parameters stay finite."""
+    from neuralsim_amd.fields.neus import volume_integration
+    scene, p_scene, _ = build(backend, 6, 0, "f32", seed=23)
+    m, _, _ = build(backend, 6, 0, "f32", seed=11)
+    r = rays()
+    dv = lambda t: t.to(backend).contiguous()      # noqa: E731
+    tested = m.ray_test(dv(r["o"]), dv(r["d"]), near=0.01)
+    with torch.no_grad():
+        ref = nr.query_at(p_scene, r["o"][r["hit"]], r["d"][r["hit"]], r["t"], r["ridx"], STEP)
+        pi = torch.stack([torch.cumsum(r["counts"], 0) - r["counts"], r["counts"]], dim=-1)
+        gt = orr.volume_integration(ref["opacity_alpha"], r["t"], ref["rgb"], None, pi, False)["rgb_volume"]
+        gt_full = torch.zeros(N, 3)
+        gt_full[r["hit"].nonzero()[:, 0]] = gt
+        gt_full = gt_full.to(backend)
+    opt = m.training_setup(dict(lr=1e-2, eps=1e-15, betas=[0.9, 0.99]))
+    m.training_initialize()
+    assert m.accel.frac_occupied() == 1.0                       # init: constant, every voxel marked
+    m.accel.n_steps_warmup, m.accel.n_steps_between_update = 8, 8      # the refresh runs at it = 8, 16, 24
+    m.refresh_generator = torch.Generator(device=backend).manual_seed(3)
+    losses, fracs = [], []
+    for it in range(30):
+        m.training_before_per_step(it)
+        assert m.accel.collect_armed
+        fracs.append(m.accel.frac_occupied())
+        gen = torch.Generator(device=backend).manual_seed(0)      # rewound point stream, jitter 0: a fixed objective
+        ret = m.ray_query(ray_tested=tested, config=dict(with_rgb=True, _jitter=torch.zeros(tested["num_rays"], device=backend)),
+                          return_details=True)
+        assert not m.accel.collect_armed                        # the step's samples were folded into the value grid
+        vb = ret["volume_buffer"]
+        rend = volume_integration(vb["opacity_alpha"], vb["t"], vb["rgb"], None, ret["details"]["pack_infos"], False,
+                                  rays_inds=tested["rays_inds"], num_rays=N)
+        loss = ((rend["rgb_volume"] - gt_full) ** 2).mean() + 1e-3 * m.sample_pts_uniform(64, generator=gen)["sigma"].mean()
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+        m.training_after_per_step(it)
+        losses.append(float(loss.detach()))
+    # the first 8 steps march the constant (all-occupied) grid; from it = 8 the refresh re-thresholds it
+    # (val = max(0.95 val, sigma) > min(occ_thre, mean)): the target image and the rays stay, the sample set follows the grid
+    assert fracs[7] == 1.0 and fracs[8] < 1.0 and float(m.accel.occ_val.max()) > 1.0e-2
+    assert losses[-1] < losses[0], losses
+    assert all(bool(torch.isfinite(q).all()) for q in m.parameters())

@@ -4,6 +4,8 @@ on this repository: its ``nr3d_lib`` imports resolve to the shim package of this
 its dataset is ``neuralsim_amd.dataio.SyntheticObjectDataset`` (``--dataset_cfg.target=...`` override: no files).
 
     python tools/run_reference_train.py [--script code_multi/tools/train.py] --config <reference yaml> [--a.b.c=value ...]
+    python tools/run_reference_train.py --config code_single/configs/waymo/ngp_withlidar.230814.yaml     (InstantNGP + UrbanNeRF:
+        ``LoTDNeRFStreet`` over neuralsim_amd/fields/nerf.py; needs the dataset the yaml names)
 
 On a machine without a HIP device (the authoring container) pass ``--emulate``: the kernels run on the test-only host
 emulator (tests/emu) and every ``cuda`` device the trainer asks for is mapped to the CPU -- the trainer hard-codes

@@ -302,6 +302,10 @@ typedef struct NsimPermutoMeta {
   uint32_t hashmap_size;               /* entries per level, a power of two */
   float scale[NSIM_MAX_LEVELS][8];
   float shift[NSIM_MAX_LEVELS][8];     /* ``apply_random_shifts_per_level`` (zeros when off) */
+  int32_t n_active_levels;             /* hardmask level annealing (encoding_cfg.anneal_cfg{type: hardmask},
+                                        * permuto_neus.bmvs.230814.yaml:118-122 and :212-216), as NsimLotdMeta: levels
+                                        * >= n_active_levels yield zero features, zero d features / d x, no gradient and
+                                        * no memory access to their tables; 0 or >= num_levels = all levels */
 } NsimPermutoMeta;
 /* PermutoEncoding.forward / forward_dydx: x [S,in_dim] -> out f32 [S, L*2]; dydx (may be NULL) f32 [S, L*2, in_dim]. */
 int nsim_permuto_fwd(const NsimPermutoMeta* meta, const void* grid_f16, const float* x, int64_t S, float* out, float* dydx,
@@ -336,6 +340,16 @@ int nsim_permuto_scatter(const NsimPermutoMeta* meta, const float* x, const floa
 int nsim_permuto_dz(const NsimPermutoMeta* meta, const void* grid_f16, const float* x, const float* rays_o,
                     const float* rays_d, const float* t, const int64_t* ridx, const float* z, int64_t S,
                     const float* dh_planes, float* dz, void* stream);
+/* Point-mode front end for decoders without normals (PermutoNeRFDistant: the NeRF++ background on a 4-D lattice):
+ * x [S,in_dim] carries every input per point (in_dim 2..8, num_levels <= 16).  Writes ONLY h_planes [16][S][2] f32,
+ * level-major with pitch S -- the layout nsim_distant_fwd_planes / nsim_distant_bwd read -- all 16 rows (zeros for masked
+ * levels and past the pyramid); no d features / d x. */
+int nsim_permuto_gather_pts(const NsimPermutoMeta* meta, const void* grid_f16, const float* x, int64_t S, float* h_planes,
+                            void* stream);
+/* ... and its backward to the table: dgrid[v][f] += w_v dh_planes[l][s][f] over the in_dim + 1 vertices per level of the
+ * points with valid[s] != 0 (the others are skipped before the simplex; their dh rows are never read). */
+int nsim_permuto_scatter_pts(const NsimPermutoMeta* meta, const float* x, const uint8_t* valid, int64_t S,
+                             const float* dh_planes, float* dgrid, void* stream);
 
 /* ------------------------------------------------------- fused NeuS field (LoTD + MLPs, MFMA) */
 /* Network description (host struct).  LoTDNeuSModel = LoTDSDF + RadianceNet
@@ -542,6 +556,10 @@ int nsim_density_alpha_bwd(const float* sigma, const float* t, const uint8_t* va
 int nsim_distant_fwd(const NsimDistantMeta* meta, const void* grid_f16, const void* wpack, const float* u4,
                      const float* rays_d, const float* h_appear, int64_t S, int K, float* sigma, float* rgb,
                      float* h_planes, void* stream);
+/* The decoders of nsim_distant_fwd on h_planes [16,S,2] the caller has ALREADY filled (nsim_permuto_gather_pts): no table
+ * is read; meta->lotd.num_levels gives F (a stub pyramid of that many levels serves as the meta). */
+int nsim_distant_fwd_planes(const NsimDistantMeta* meta, const void* wpack, const float* h_planes, const float* rays_d,
+                            const float* h_appear, int64_t S, int K, float* sigma, float* rgb, void* stream);
 /* backward of nsim_distant_fwd: accumulates dden_w/dden_b/drad_w/drad_b (layouts above), dh_appear [N,4] (may be
  * NULL) and writes dh_planes [16,S,2] for nsim_lotd4_scatter. */
 int nsim_distant_bwd(const NsimDistantMeta* meta, const void* wpack, const float* h_planes, const float* sigma_fwd,

@@ -34,7 +34,8 @@ class Lotd4Meta(C.Structure):
 
 class PermutoMeta(C.Structure):
     _fields_ = [("in_dim", C.c_int32), ("num_levels", C.c_int32), ("n_feats", C.c_int32), ("hashmap_size", C.c_uint32),
-                ("scale", (C.c_float * 8) * NSIM_MAX_LEVELS), ("shift", (C.c_float * 8) * NSIM_MAX_LEVELS)]
+                ("scale", (C.c_float * 8) * NSIM_MAX_LEVELS), ("shift", (C.c_float * 8) * NSIM_MAX_LEVELS),
+                ("n_active_levels", C.c_int32)]
 
 
 class DistantMeta(C.Structure):
@@ -140,6 +141,8 @@ SIGNATURES = {
     "nsim_permuto_gather": [C.POINTER(PermutoMeta), _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I, _P, _P],
     "nsim_permuto_scatter": [C.POINTER(PermutoMeta), _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P],
     "nsim_permuto_dz": [C.POINTER(PermutoMeta), _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P],
+    "nsim_permuto_gather_pts": [C.POINTER(PermutoMeta), _P, _P, _I64, _P],
+    "nsim_permuto_scatter_pts": [C.POINTER(PermutoMeta), _P, _P, _I64, _P, _P],
     "nsim_field_bwd_rad": [C.POINTER(FieldMeta), _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P],
     "nsim_field_bwd_sdf": [C.POINTER(FieldMeta), _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I64],
     "nsim_lotd_hess_dx": [C.POINTER(LotdMeta), _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P],
@@ -150,6 +153,7 @@ SIGNATURES = {
     "nsim_density_alpha_fwd": [_P, _P, _P, _I64, _I, _I, _P],
     "nsim_density_alpha_bwd": [_P, _P, _P, _P, _I64, _I, _I, _P],
     "nsim_distant_fwd": [C.POINTER(DistantMeta), _P, _P, _P, _P, _P, _I64, _I, _P, _P, _P],
+    "nsim_distant_fwd_planes": [C.POINTER(DistantMeta), _P, _P, _P, _P, _I64, _I, _P, _P],
     "nsim_distant_bwd": [C.POINTER(DistantMeta), _P, _P, _P, _P, _P, _P, _P, _I64, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "nsim_lotd4_scatter": [C.POINTER(Lotd4Meta), _P, _P, _I64, _P, _P],
     "nsim_ngp_pack_weights": [C.POINTER(NgpMeta), _P, _P, _P, _P, _P],

@@ -1377,6 +1377,18 @@ static unsigned nerf_grid(int64_t S, int64_t cap) {
   return (unsigned)b;
 }
 
+// forward decoders (k_nerf) of the distant model: on the gathered planes (a.h_from_planes) or with the 4-D gather fused in
+static int nerf_launch_fwd(const NsimDistantMeta* meta, const NerfArgs& a, hipStream_t stream) {
+  const size_t shmem = meta->precision == 0 ? (size_t)((a.lay.total + 15) & ~15) : 0;
+  // persistent workgroups, one per CU (decoder part of nsim_distant_fwd per 0.52 M shells: 0.125 ms at 1024, 0.113 at 256)
+  static const int fwd_grid = getenv("NSIM_NERF_FWD_GRID") ? atoi(getenv("NSIM_NERF_FWD_GRID")) : 256;
+  const dim3 grid(nerf_grid(a.S, fwd_grid)), block(64 * NERF_WAVES);
+  if (meta->precision == 0) hipLaunchKernelGGL((k_nerf<0, 0>), grid, block, shmem, stream, a);
+  else hipLaunchKernelGGL((k_nerf<1, 0>), grid, block, shmem, stream, a);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" {
 
 int64_t nsim_distant_wpack_bytes(const NsimDistantMeta* meta) {
@@ -1460,14 +1472,24 @@ int nsim_distant_fwd(const NsimDistantMeta* meta, const void* grid_f16, const vo
     NSIM_CHECK_LAUNCH();
     a.h_from_planes = 1;
   }
-  const size_t shmem = meta->precision == 0 ? (size_t)((a.lay.total + 15) & ~15) : 0;
-  // persistent workgroups, one per CU (decoder part of nsim_distant_fwd per 0.52 M shells: 0.125 ms at 1024, 0.113 at 256)
-  static const int fwd_grid = getenv("NSIM_NERF_FWD_GRID") ? atoi(getenv("NSIM_NERF_FWD_GRID")) : 256;
-  const dim3 grid(nerf_grid(S, fwd_grid)), block(64 * NERF_WAVES);
-  if (meta->precision == 0) hipLaunchKernelGGL((k_nerf<0, 0>), grid, block, shmem, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((k_nerf<1, 0>), grid, block, shmem, (hipStream_t)stream, a);
-  NSIM_CHECK_LAUNCH();
-  return 0;
+  return nerf_launch_fwd(meta, a, (hipStream_t)stream);
+}
+
+// The decoders alone, on planes another encoding has filled (nsim_permuto_gather_pts: PermutoNeRFDistant) -- the launch of
+// nsim_distant_fwd's training path without its gather.
+int nsim_distant_fwd_planes(const NsimDistantMeta* meta, const void* wpack, const float* h_planes, const float* rays_d,
+                            const float* h_appear, int64_t S, int K, float* sigma, float* rgb, void* stream) {
+  const int rc = nerf_meta_check(meta);
+  if (rc) return rc;
+  if (S <= 0) return 0;
+  if (!wpack || !h_planes || !rays_d || !sigma || !rgb || K <= 0) return 4;
+  NerfArgs a = nerf_args(meta);
+  a.wpack = (const char*)wpack;
+  a.rays_d = rays_d; a.h_appear = h_appear;
+  a.S = S; a.K = K;
+  a.sigma = sigma; a.rgb = rgb; a.h_pl = const_cast<float*>(h_planes);
+  a.h_from_planes = 1;
+  return nerf_launch_fwd(meta, a, (hipStream_t)stream);
 }
 
 int nsim_distant_bwd(const NsimDistantMeta* meta, const void* wpack, const float* h_planes, const float* sigma_fwd,

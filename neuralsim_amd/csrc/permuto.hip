@@ -8,7 +8,15 @@
 // a time.  A point touches d + 1 vertices per level (4 in 3-D, against the 8 corners of a trilinear level): d + 1 random
 // 4-byte loads forward, 2 (d + 1) f32 atomics backward.
 //
-// Two front ends share the lattice code:
+// Bounds: the forward kernels are bound by those random 4-byte loads (a 64-byte sector fetched per load, 1/16 of it used once
+// the level's table outgrows what neighbouring points share), the backward kernels by the f32 atomics (one L2 read-modify-
+// write each; same-address atomics of one instruction serialise, hence the in-wave run sums below).  The lattice arithmetic
+// (f64 elevation, (d+1)^2 / 2 rank compares) hides under either.
+//
+// Hardmask level annealing (NsimPermutoMeta.n_active_levels): a masked level is decided per block (blockIdx.y) BEFORE the
+// simplex -- its plane rows are written as zeros, its table is neither read nor given a gradient.
+//
+// Three front ends share the lattice code:
 //  * standalone encoding (nsim_permuto_fwd / _bwd): x [S,d] -> features [S, L F] (+ d features / d x over all d inputs),
 //    point-major, for callers that decode elsewhere;
 //  * the NeuS field (nsim_permuto_gather / _scatter): positions from rays (o + t d) or points, optional per-ray condition
@@ -16,14 +24,18 @@
 //    field.hip's level-major LoTD gather -- feature planes [NL][S] (f16x2 | f32x2) for the no-grad decoder, h [NL][PS][2] and
 //    dh/dx [NL][PS][2][3] (spatial derivative only) for the with-grad decoders -- so every decoder kernel of field.hip runs
 //    unchanged on a permutohedral model; the scatter takes the same dL/dh and g = dsdf/dh planes and the total dL/dnablas
-//    (second-order term: the weights are piecewise linear in x, d w_v / d x is constant inside a simplex).
+//    (second-order term: the weights are piecewise linear in x, d w_v / d x is constant inside a simplex);
+//  * point-mode planes (nsim_permuto_gather_pts / _scatter_pts) for decoders without normals -- the NeRF++ distant model on a
+//    4-D lattice (PermutoNeRFDistant): x [S,d] with every input per point -> h planes [16][S][2] f32 ONLY (pitch S, the layout
+//    k_nerf reads; no dh/dx: 3 d floats per level and point nobody would read), consecutive lanes = consecutive points, so
+//    plane reads and writes are one contiguous 512-byte run per wave; the scatter takes dh planes and a per-point valid mask.
 #include "nsim_common.h"
 
 #define PERMUTO_MAX_DIM 8
 #define PERMUTO_SDF_H_SCALE 1024.0f      // = field.hip SDF_H_SCALE (fp16 feature planes are pre-scaled)
 
 struct PermutoDev {
-  int in_dim, num_levels;
+  int in_dim, num_levels, n_active;      // levels >= n_active are masked (hardmask annealing)
   uint32_t T;
   float scale[NSIM_MAX_LEVELS][PERMUTO_MAX_DIM];
   float shift[NSIM_MAX_LEVELS][PERMUTO_MAX_DIM];
@@ -33,6 +45,7 @@ static PermutoDev permuto_dev(const NsimPermutoMeta* m) {
   PermutoDev d;
   d.in_dim = m->in_dim;
   d.num_levels = m->num_levels;
+  d.n_active = (m->n_active_levels > 0 && m->n_active_levels < m->num_levels) ? m->n_active_levels : m->num_levels;
   d.T = m->hashmap_size;
   for (int l = 0; l < NSIM_MAX_LEVELS; ++l)
     for (int i = 0; i < PERMUTO_MAX_DIM; ++i) {
@@ -185,8 +198,9 @@ __device__ __forceinline__ void permuto_load2(const f16* grid, int64_t base, uin
 struct PermutoArgs {
   PermutoDev pm;
   const f16* grid;
-  const float *x, *rays_o, *rays_d, *t, *z;      // x [S,D] (standalone) / [S,3] (field), or rays + t + ridx; z [R, D-3] or NULL
+  const float *x, *rays_o, *rays_d, *t, *z;      // x [S,D] (standalone, point planes) / [S,3] (field), or rays + t + ridx; z [R, D-3] or NULL
   const int64_t* ridx;
+  const uint8_t* valid;                            // point-plane backward: [S], 0 = skip the point
   int64_t S, PS;
   const int64_t* S_dev;
   int64_t S_add;
@@ -224,7 +238,7 @@ __device__ __forceinline__ void permuto_point(const PermutoArgs& a, int64_t s, f
   }
 }
 
-// MODE 0: standalone forward; 1: field feature planes (no-grad); 2: field h + dh/dx planes
+// MODE 0: standalone forward; 1: field feature planes (no-grad); 2: field h + dh/dx planes; 3: point-mode h planes (PS = S)
 template <int D, int MODE>
 __global__ void __launch_bounds__(256) k_permuto_fwd(PermutoArgs a) {
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -235,10 +249,21 @@ __global__ void __launch_bounds__(256) k_permuto_fwd(PermutoArgs a) {
     Sv = sd <= Sv ? sd : 0;
   }
   if (s >= Sv) return;
-  if (MODE != 0 && l >= a.pm.num_levels) {
-    // plane levels past the pyramid (pyramids of fewer than 16 levels): the 16-level decoder kernels read all 16 planes
-    // (zero weight columns) -- keep them finite, as field.hip's level-major gather does
-    if constexpr (MODE == 1) {
+  if (l >= a.pm.n_active) {      // (block-uniform; n_active <= num_levels)
+    // masked levels (hardmask annealing) and plane levels past the pyramid (pyramids of fewer than 16 levels): the 16-level
+    // decoder kernels read all 16 planes (zero weight columns past the pyramid) -- zeros, as field.hip's level-major gather
+    // writes them; the level's table is not touched
+    if constexpr (MODE == 0) {
+      const int64_t o = s * (2 * a.pm.num_levels) + 2 * l;
+      a.out[o] = a.out[o + 1] = 0.f;
+      if (a.dydx) {
+#pragma unroll
+        for (int c = 0; c < 2 * D; ++c) a.dydx[o * D + c] = 0.f;
+      }
+    } else if constexpr (MODE == 3) {
+      float* hp = a.h_pl + ((int64_t)l * a.PS + s) * 2;
+      hp[0] = hp[1] = 0.f;
+    } else if constexpr (MODE == 1) {
       const int64_t e = (int64_t)l * a.PS + s;      // feature planes [NL][P]
       if (a.feat_f32) {
         reinterpret_cast<float*>(a.feat_pl)[2 * e] = 0.f;
@@ -259,11 +284,11 @@ __global__ void __launch_bounds__(256) k_permuto_fwd(PermutoArgs a) {
   }
   constexpr int NS = MODE == 0 ? D : 3;
   float x[D];
-  permuto_point<D, MODE != 0>(a, s, x);
+  permuto_point<D, MODE == 1 || MODE == 2>(a, s, x);
   Simplex<D> sp;
   float dB[D + 1][NS];
-  const bool want_d = MODE == 2 || (MODE == 0 && a.dydx != nullptr);      // (wave-uniform)
-  if constexpr (MODE == 1) permuto_simplex<D, NS, false>(x, a.pm.scale[l], a.pm.shift[l], sp, dB);
+  const bool want_d = MODE == 2 || (MODE == 0 && a.dydx != nullptr);      // (wave-uniform; never in modes 1 and 3)
+  if constexpr (MODE == 1 || MODE == 3) permuto_simplex<D, NS, false>(x, a.pm.scale[l], a.pm.shift[l], sp, dB);
   else if constexpr (MODE == 2) permuto_simplex<D, NS, true>(x, a.pm.scale[l], a.pm.shift[l], sp, dB);
   else if (want_d) permuto_simplex<D, NS, true>(x, a.pm.scale[l], a.pm.shift[l], sp, dB);
   else permuto_simplex<D, NS, false>(x, a.pm.scale[l], a.pm.shift[l], sp, dB);
@@ -310,6 +335,10 @@ __global__ void __launch_bounds__(256) k_permuto_fwd(PermutoArgs a) {
       cv.h[1] = (f16)fminf(fmaxf(f1 * PERMUTO_SDF_H_SCALE, -65504.0f), 65504.0f);
       reinterpret_cast<uint32_t*>(a.feat_pl)[e] = cv.u;
     }
+  } else if constexpr (MODE == 3) {
+    float* hp = a.h_pl + ((int64_t)l * a.PS + s) * 2;      // 8 B per lane, contiguous in s
+    hp[0] = f0;
+    hp[1] = f1;
   } else {
     const int64_t ep = (int64_t)l * a.PS + s;
     float* hp = a.h_pl + ep * 2;
@@ -339,12 +368,21 @@ __global__ void __launch_bounds__(256) k_permuto_fwd(PermutoArgs a) {
 // "grid scatter") -- runs of equal vertex indices are summed inside the wave first (ballot run heads + segmented shuffle
 // scan, as k_lotd_scatter / k_lotd4_scatter do): 2.65 -> 0.51 ms per 0.31 M points of a 16-level pyramid on MI355X
 // (the LoTD scatter on the same points: 0.50 ms).
-template <int D, bool FIELD>
+// FRONT 0: standalone (dL/dout point-major); 1: field (dh / g planes, rays or points + condition); 2: point-mode planes with a
+// per-point valid mask (the distant model: shells the ray does not cross, or behind an opaque foreground, are skipped before
+// the simplex; a wave without a live point leaves at once)
+template <int D, int FRONT>
 __global__ void __launch_bounds__(256) k_permuto_bwd(PermutoArgs a) {
+  constexpr bool FIELD = FRONT == 1;
   const int lane = nsim_lane();
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int l = blockIdx.y;
-  const bool valid = s < a.S;            // (no early return: every lane takes part in the shuffles)
+  if (l >= a.pm.n_active) return;        // masked level (block-uniform): no gradient, no atomics
+  bool valid = s < a.S;                  // (no per-lane early return: every lane takes part in the shuffles)
+  if constexpr (FRONT == 2) {
+    valid = valid && a.valid[s] != 0;
+    if (wave_ballot(valid) == 0ull) return;      // (wave-uniform)
+  }
   float x[D];
 #pragma unroll
   for (int i = 0; i < D; ++i) x[i] = 0.f;
@@ -352,11 +390,22 @@ __global__ void __launch_bounds__(256) k_permuto_bwd(PermutoArgs a) {
   Simplex<D> sp;
   float dB[D + 1][3];
   const bool second = FIELD && a.gn != nullptr;      // (wave-uniform)
-  if (second) permuto_simplex<D, 3, true>(x, a.pm.scale[l], a.pm.shift[l], sp, dB);
+  if constexpr (FRONT == 2) {
+#pragma unroll
+    for (int i = 0; i <= D; ++i) {
+      sp.rem0[i] = sp.rank[i] = 0;
+      sp.bary[i] = 0.f;
+    }
+    if (valid) permuto_simplex<D, 3, false>(x, a.pm.scale[l], a.pm.shift[l], sp, dB);
+  } else if (second) permuto_simplex<D, 3, true>(x, a.pm.scale[l], a.pm.shift[l], sp, dB);
   else permuto_simplex<D, 3, false>(x, a.pm.scale[l], a.pm.shift[l], sp, dB);
   float d0 = 0.f, d1 = 0.f, g0 = 0.f, g1 = 0.f, gn[3] = {0.f, 0.f, 0.f};
   if (valid) {
-    if constexpr (FIELD) {
+    if constexpr (FRONT == 2) {
+      const float* dp = a.dh_pl + ((int64_t)l * a.S + s) * 2;
+      d0 = dp[0];
+      d1 = dp[1];
+    } else if constexpr (FIELD) {
       const float* dp = a.dh_pl + ((int64_t)l * a.S + s) * 2;
       d0 = dp[0];
       d1 = dp[1];
@@ -416,6 +465,7 @@ __global__ void __launch_bounds__(256) k_permuto_dz(PermutoArgs a, float* __rest
   const int lane = nsim_lane();
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int l = blockIdx.y;
+  if (l >= a.pm.n_active) return;        // masked level (block-uniform): its features do not depend on z
   const bool valid = s < a.S;
   float x[D];
 #pragma unroll
@@ -469,7 +519,7 @@ static int permuto_launch_fwd(const NsimPermutoMeta* meta, const PermutoArgs& a,
   const int rows = MODE == 0 ? meta->num_levels : (meta->num_levels < 16 ? 16 : ((meta->num_levels + 7) & ~7));
   const dim3 grid((unsigned)nsim_blocks(a.S, 256), (unsigned)rows), block(256);
   switch (meta->in_dim) {
-    case 2: hipLaunchKernelGGL((k_permuto_fwd<2, 0>), grid, block, 0, stream, a); break;      // (standalone only: the field front end needs in_dim >= 3)
+    case 2: hipLaunchKernelGGL((k_permuto_fwd<2, MODE == 3 ? 3 : 0>), grid, block, 0, stream, a); break;      // (the field front end needs in_dim >= 3: its entry points refuse 2)
     case 3: hipLaunchKernelGGL((k_permuto_fwd<3, MODE>), grid, block, 0, stream, a); break;
     case 4: hipLaunchKernelGGL((k_permuto_fwd<4, MODE>), grid, block, 0, stream, a); break;
     case 5: hipLaunchKernelGGL((k_permuto_fwd<5, MODE>), grid, block, 0, stream, a); break;
@@ -482,17 +532,17 @@ static int permuto_launch_fwd(const NsimPermutoMeta* meta, const PermutoArgs& a,
   return 0;
 }
 
-template <bool FIELD>
+template <int FRONT>
 static int permuto_launch_bwd(const NsimPermutoMeta* meta, const PermutoArgs& a, hipStream_t stream) {
   const dim3 grid((unsigned)nsim_blocks(a.S, 256), (unsigned)meta->num_levels), block(256);
   switch (meta->in_dim) {
-    case 2: hipLaunchKernelGGL((k_permuto_bwd<2, false>), grid, block, 0, stream, a); break;
-    case 3: hipLaunchKernelGGL((k_permuto_bwd<3, FIELD>), grid, block, 0, stream, a); break;
-    case 4: hipLaunchKernelGGL((k_permuto_bwd<4, FIELD>), grid, block, 0, stream, a); break;
-    case 5: hipLaunchKernelGGL((k_permuto_bwd<5, FIELD>), grid, block, 0, stream, a); break;
-    case 6: hipLaunchKernelGGL((k_permuto_bwd<6, FIELD>), grid, block, 0, stream, a); break;
-    case 7: hipLaunchKernelGGL((k_permuto_bwd<7, FIELD>), grid, block, 0, stream, a); break;
-    case 8: hipLaunchKernelGGL((k_permuto_bwd<8, FIELD>), grid, block, 0, stream, a); break;
+    case 2: hipLaunchKernelGGL((k_permuto_bwd<2, FRONT == 2 ? 2 : 0>), grid, block, 0, stream, a); break;
+    case 3: hipLaunchKernelGGL((k_permuto_bwd<3, FRONT>), grid, block, 0, stream, a); break;
+    case 4: hipLaunchKernelGGL((k_permuto_bwd<4, FRONT>), grid, block, 0, stream, a); break;
+    case 5: hipLaunchKernelGGL((k_permuto_bwd<5, FRONT>), grid, block, 0, stream, a); break;
+    case 6: hipLaunchKernelGGL((k_permuto_bwd<6, FRONT>), grid, block, 0, stream, a); break;
+    case 7: hipLaunchKernelGGL((k_permuto_bwd<7, FRONT>), grid, block, 0, stream, a); break;
+    case 8: hipLaunchKernelGGL((k_permuto_bwd<8, FRONT>), grid, block, 0, stream, a); break;
     default: return 41;
   }
   NSIM_CHECK_LAUNCH();
@@ -523,7 +573,7 @@ int nsim_permuto_bwd(const NsimPermutoMeta* meta, const float* x, int64_t S, con
   PermutoArgs a = PermutoArgs();
   a.pm = permuto_dev(meta);
   a.x = x; a.S = S; a.dL_dout = dL_dout; a.dgrid = dgrid;
-  return permuto_launch_bwd<false>(meta, a, (hipStream_t)stream);
+  return permuto_launch_bwd<0>(meta, a, (hipStream_t)stream);
 }
 
 int nsim_permuto_gather(const NsimPermutoMeta* meta, const void* grid_f16, const float* x, const float* rays_o,
@@ -567,7 +617,7 @@ int nsim_permuto_scatter(const NsimPermutoMeta* meta, const float* x, const floa
   a.x = x; a.rays_o = rays_o; a.rays_d = rays_d; a.t = t; a.ridx = ridx; a.z = z;
   a.S = S;
   a.dh_pl = dh_planes; a.g_pl = g_planes; a.gn = gn; a.dgrid = dgrid;
-  return permuto_launch_bwd<true>(meta, a, (hipStream_t)stream);
+  return permuto_launch_bwd<1>(meta, a, (hipStream_t)stream);
 }
 
 int nsim_permuto_dz(const NsimPermutoMeta* meta, const void* grid_f16, const float* x, const float* rays_o,
@@ -598,6 +648,35 @@ int nsim_permuto_dz(const NsimPermutoMeta* meta, const void* grid_f16, const flo
   }
   NSIM_CHECK_LAUNCH();
   return 0;
+}
+
+int nsim_permuto_gather_pts(const NsimPermutoMeta* meta, const void* grid_f16, const float* x, int64_t S, float* h_planes,
+                            void* stream) {
+  const int rc = permuto_meta_check(meta);
+  if (rc) return rc;
+  if (meta->num_levels > 16) return 42;      // the decoders on these planes read 16 rows
+  if (S <= 0) return 0;
+  if (!grid_f16 || !x || !h_planes) return 4;
+  PermutoArgs a = PermutoArgs();
+  a.pm = permuto_dev(meta);
+  a.grid = (const f16*)grid_f16;
+  a.x = x; a.S = S; a.PS = S;
+  a.h_pl = h_planes;
+  return permuto_launch_fwd<3>(meta, a, (hipStream_t)stream);
+}
+
+int nsim_permuto_scatter_pts(const NsimPermutoMeta* meta, const float* x, const uint8_t* valid, int64_t S,
+                             const float* dh_planes, float* dgrid, void* stream) {
+  const int rc = permuto_meta_check(meta);
+  if (rc) return rc;
+  if (meta->num_levels > 16) return 42;
+  if (S <= 0) return 0;
+  if (!x || !valid || !dh_planes || !dgrid) return 28;
+  PermutoArgs a = PermutoArgs();
+  a.pm = permuto_dev(meta);
+  a.x = x; a.valid = valid; a.S = S;
+  a.dh_pl = dh_planes; a.dgrid = dgrid;
+  return permuto_launch_bwd<2>(meta, a, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,4 +1,9 @@
-"""NeRF++ distant-view model -- host side (csrc/nerf_field.hip).
+"""NeRF++ distant-view models -- host side (csrc/nerf_field.hip; the permutohedral encoding: csrc/permuto.hip).
+
+``_DistantBase`` holds everything that is not the encoding -- shells, the two decoders, sigma -> alpha, the batched volume
+buffer, optimizer groups; ``LoTDNeRFDistantModel`` (4-D LoTD pyramid) and ``PermutoNeRFDistantModel`` (4-D permutohedral
+lattice, ``app.models.single.PermutoNeRFDistant`` of permuto_neus.bmvs.230814.yaml:196-247) add the table, its config and the
+two encoding hooks ``_enc_fwd`` / ``_enc_scatter``.
 
 Mirrors ``nr3d_lib.models.fields_distant.nerf.LoTDNeRFDistantModel`` as wrapped and driven by the reference
 (app/models/single/nerf.py:145-196 ``LoTDNeRFDistant``; call site app/renderers/single_volume_renderer.py:281-309):
@@ -76,12 +81,8 @@ class _DistantFn(torch.autograd.Function):
             rays_d = rays_d.detach()
         h_pl = torch.empty([16, S, 2], dtype=torch.float32, device=dev) if need_bwd else None
         ha = h_appear.detach().float().contiguous() if h_appear is not None else None
-        _lib.call("nsim_distant_fwd", model.meta, _lib.ptr(grid16), _lib.ptr(wpack), _lib.ptr(u4), _lib.ptr(rays_d),
-                  _lib.ptr(ha), S, K, _lib.ptr(sigma), _lib.ptr(rgb), _lib.ptr(h_pl))
-        if _lib.TIMER is not None:
-            _lib.TIMER.note_units("nsim_distant_fwd", S)
-            _lib.TIMER.note_units("nsim_distant_bwd", S)
-            _lib.TIMER.note_units("nsim_lotd4_scatter", S)
+        # the encoding's state of THIS query (the level mask): the backward uses it, whatever has been set since
+        ctx.enc_state = model._enc_fwd(grid16, wpack, u4, rays_d, ha, S, K, sigma, rgb, h_pl)
         ctx.model, ctx.S, ctx.K = model, S, K
         ctx.set_materialize_grads(False)       # an unused output arrives as None (not zeros): see backward
         ctx.holder = holder        # a plain dict of the caller's (no tensor of this node inside: no reference cycle)
@@ -116,8 +117,7 @@ class _DistantFn(torch.autograd.Function):
                   _lib.ptr(gr), _lib.ptr(dh_pl), _lib.ptr(dden_w), _lib.ptr(dden_b), _lib.ptr(drad_w), _lib.ptr(drad_b),
                   _lib.ptr(dha))
         if dgrid is not None:
-            _lib.call("nsim_lotd4_scatter", model.cfg.meta, _lib.ptr(u4), _lib.ptr(valid), ctx.S, _lib.ptr(dh_pl),
-                      _lib.ptr(dgrid))
+            model._enc_scatter(u4, valid, ctx.S, dh_pl, dgrid, ctx.enc_state)
         if gr is None:      # the colour output has no consumer (a lidar render, with_rgb=False): the radiance branch was not
             # differentiated -- no gradient rather than a zero one, as autograd reports an unused sub-network
             return (None, dgrid, dden_w, dden_b, None, None, None, None, None, None, None, None)
@@ -144,46 +144,18 @@ class _DensityAlphaFn(torch.autograd.Function):
         return dsigma, None, None, None, None, None
 
 
-class LoTDNeRFDistantModel(ModelMixin, nn.Module):
+class _DistantBase(ModelMixin, nn.Module):
+    """What the distant models share.  A subclass's ``__init__`` sets ``self.cfg`` (``out_features``, ``n_params``), calls
+    ``_init_common`` with a 4-D LoTD meta for the decoder launches (they read the level count from it) and provides
+    ``_enc_fwd`` (features -> sigma, rgb; fills ``h_pl`` when given) and ``_enc_scatter`` (dh planes -> table gradient)."""
     is_ray_query_supported = True
 
-    def __init__(self, aabb: torch.Tensor = None, precision: str = "fp16", radius_scale_min: float = 1.0,
-                 radius_scale_max: float = 1000.0, max_steps: int = 64, include_inf_distance: bool = True,
-                 use_view_dirs: bool = True, lotd_auto_compute_cfg: dict = None, param_bound: float = 1e-4,
-                 seed: int = 7, device=None, ray_query_cfg: dict = None, lotd_use_cuboid: bool = False,
-                 **reference_params):
-        """``include_inf_distance`` / ``radiance_decoder_cfg.use_view_dirs``: true / true in the object-centric configs
-        (lotd_neus.dtu.230814.yaml:221-236), false / false in the street config, which has a sky model and feeds the
-        radiance net features + appearance only (withmask_withlidar_joint.240219.yaml:281-294).  The street config's
-        ``sample_mode: fixed_cuboid_shells`` + ``interval_type: inverse_proportional`` is what the shells kernel does:
-        cuboid shells = the AABB scaled about its centre, uniform in 1/r."""
-        if reference_params:        # the reference's model_params block verbatim (fields/ref_config.py)
-            from . import ref_config
-            kw = ref_config.distant_native_kwargs(dict(
-                reference_params, include_inf_distance=include_inf_distance, radius_scale_min=radius_scale_min,
-                radius_scale_max=radius_scale_max, ray_query_cfg=ray_query_cfg))
-            kw.setdefault("max_steps", max_steps)
-            LoTDNeRFDistantModel.__init__(self, aabb=aabb, seed=seed, device=device, **kw)
-            return
-        super().__init__()
-        self._ctor = dict(precision=precision, radius_scale_min=radius_scale_min, radius_scale_max=radius_scale_max,
-                          max_steps=max_steps, include_inf_distance=include_inf_distance, use_view_dirs=use_view_dirs,
-                          lotd_auto_compute_cfg=lotd_auto_compute_cfg, param_bound=param_bound, seed=seed,
-                          ray_query_cfg=ray_query_cfg, lotd_use_cuboid=lotd_use_cuboid)
-        self.lotd_use_cuboid = bool(lotd_use_cuboid)
+    def _init_common(self, aabb, precision, radius_scale_min, radius_scale_max, max_steps, include_inf_distance,
+                     use_view_dirs, param_bound, seed, lotd4_meta):
         # ``include_inf_distance: None`` = decided at populate time from the scene (no Sky node -> the last shell reaches
         # infinity; app/models/single/nerf.py:180-182 assigns the attribute)
         self.include_inf_distance = include_inf_distance
         self.use_view_dirs = bool(use_view_dirs)
-        c = dict(lotd_auto_compute_cfg or {})
-        aspect = None
-        if self.lotd_use_cuboid and aabb is not None:
-            ext = (torch.as_tensor(aabb, dtype=torch.float32).reshape(2, 3)[1]
-                   - torch.as_tensor(aabb, dtype=torch.float32).reshape(2, 3)[0]).tolist()
-            if max(ext) / min(ext) > 1.0 + 1e-6:
-                aspect = ext
-        self.cfg = LoTD4Config(c.get("target_num_params", 8 * 2 ** 20), c.get("min_res_xyz", 8), c.get("min_res_w", 4),
-                               c.get("log2_hashmap_size", 19), c.get("per_level_scale", 1.382), aspect=aspect)
         F = self.cfg.out_features
         g = torch.Generator().manual_seed(seed)
         p = ((torch.rand(self.cfg.n_params, generator=g) * 2 - 1) * param_bound).half().float()
@@ -205,32 +177,20 @@ class LoTDNeRFDistantModel(ModelMixin, nn.Module):
         self.rad_b = nn.Parameter(torch.cat([rb1, rb2, rb3]))
         if aabb is None:
             aabb = torch.tensor([[-1.0, -1, -1], [1.0, 1, 1]])
-        self.register_buffer("aabb", aabb.float().reshape(2, 3).clone())
+        self.register_buffer("aabb", torch.as_tensor(aabb).float().reshape(2, 3).clone())
         self.r_min, self.r_max, self.K = float(radius_scale_min), float(radius_scale_max), int(max_steps)
         m = _lib.DistantMeta()
-        m.lotd = self.cfg.meta
+        m.lotd = lotd4_meta
         m.precision = {"fp16": 0, "f32": 1}[precision]
         self.meta = m
         self._wpack, self._wpack_versions = None, None
         self.ray_query_cfg = dict(query_mode="march", query_param=dict(march_cfg=dict(sample_mode="box", max_steps=self.K)))
-        if device is not None:
-            self.to(device)
 
     def populate(self, aabb: torch.Tensor = None, device=None, **unused):
         """The reference hands the close-range object's AABB over at populate time (``populate_cfg.cr_obj_classname``,
         lotd_neus.dtu.230814.yaml:239-241; app/models/single/nerf.py:145-196)."""
         if aabb is not None:
-            a = torch.as_tensor(aabb, dtype=torch.float32).reshape(2, 3).cpu()
-            ext = (a[1] - a[0]).tolist()
-            cur = (self.aabb[1] - self.aabb[0]).cpu().tolist()
-            same_shape = all(abs(e / min(ext) - c / min(cur)) < 1e-6 for e, c in zip(ext, cur))
-            if self.lotd_use_cuboid and not same_shape:
-                # per-axis pyramid: the table is sized from the AABB's aspect, which is only known now
-                dev = device if device is not None else self.den_w.device
-                LoTDNeRFDistantModel.__init__(self, aabb=a, **self._ctor)
-                device = dev
-            else:
-                self.aabb.copy_(a.to(self.aabb.device))
+            self.aabb.copy_(torch.as_tensor(aabb, dtype=torch.float32).reshape(2, 3).to(self.aabb.device))
         if device is not None:
             self.to(device)
         return self
@@ -354,3 +314,188 @@ class LoTDNeRFDistantModel(ModelMixin, nn.Module):
         if return_details:
             ret["details"] = dict(u4=u4)
         return ret
+
+
+class LoTDNeRFDistantModel(_DistantBase):
+    def __init__(self, aabb: torch.Tensor = None, precision: str = "fp16", radius_scale_min: float = 1.0,
+                 radius_scale_max: float = 1000.0, max_steps: int = 64, include_inf_distance: bool = True,
+                 use_view_dirs: bool = True, lotd_auto_compute_cfg: dict = None, param_bound: float = 1e-4,
+                 seed: int = 7, device=None, ray_query_cfg: dict = None, lotd_use_cuboid: bool = False,
+                 **reference_params):
+        """``include_inf_distance`` / ``radiance_decoder_cfg.use_view_dirs``: true / true in the object-centric configs
+        (lotd_neus.dtu.230814.yaml:221-236), false / false in the street config, which has a sky model and feeds the
+        radiance net features + appearance only (withmask_withlidar_joint.240219.yaml:281-294).  The street config's
+        ``sample_mode: fixed_cuboid_shells`` + ``interval_type: inverse_proportional`` is what the shells kernel does:
+        cuboid shells = the AABB scaled about its centre, uniform in 1/r."""
+        if reference_params:        # the reference's model_params block verbatim (fields/ref_config.py)
+            from . import ref_config
+            kw = ref_config.distant_native_kwargs(dict(
+                reference_params, include_inf_distance=include_inf_distance, radius_scale_min=radius_scale_min,
+                radius_scale_max=radius_scale_max, ray_query_cfg=ray_query_cfg))
+            kw.setdefault("max_steps", max_steps)
+            LoTDNeRFDistantModel.__init__(self, aabb=aabb, seed=seed, device=device, **kw)
+            return
+        super().__init__()
+        self._ctor = dict(precision=precision, radius_scale_min=radius_scale_min, radius_scale_max=radius_scale_max,
+                          max_steps=max_steps, include_inf_distance=include_inf_distance, use_view_dirs=use_view_dirs,
+                          lotd_auto_compute_cfg=lotd_auto_compute_cfg, param_bound=param_bound, seed=seed,
+                          ray_query_cfg=ray_query_cfg, lotd_use_cuboid=lotd_use_cuboid)
+        self.lotd_use_cuboid = bool(lotd_use_cuboid)
+        c = dict(lotd_auto_compute_cfg or {})
+        aspect = None
+        if self.lotd_use_cuboid and aabb is not None:
+            ext = (torch.as_tensor(aabb, dtype=torch.float32).reshape(2, 3)[1]
+                   - torch.as_tensor(aabb, dtype=torch.float32).reshape(2, 3)[0]).tolist()
+            if max(ext) / min(ext) > 1.0 + 1e-6:
+                aspect = ext
+        self.cfg = LoTD4Config(c.get("target_num_params", 8 * 2 ** 20), c.get("min_res_xyz", 8), c.get("min_res_w", 4),
+                               c.get("log2_hashmap_size", 19), c.get("per_level_scale", 1.382), aspect=aspect)
+        self._init_common(aabb, precision, radius_scale_min, radius_scale_max, max_steps, include_inf_distance, use_view_dirs,
+                          param_bound, seed, self.cfg.meta)
+        if device is not None:
+            self.to(device)
+
+    def populate(self, aabb: torch.Tensor = None, device=None, **unused):
+        """The reference hands the close-range object's AABB over at populate time (``populate_cfg.cr_obj_classname``,
+        lotd_neus.dtu.230814.yaml:239-241; app/models/single/nerf.py:145-196)."""
+        if aabb is not None:
+            a = torch.as_tensor(aabb, dtype=torch.float32).reshape(2, 3).cpu()
+            ext = (a[1] - a[0]).tolist()
+            cur = (self.aabb[1] - self.aabb[0]).cpu().tolist()
+            same_shape = all(abs(e / min(ext) - c / min(cur)) < 1e-6 for e, c in zip(ext, cur))
+            if self.lotd_use_cuboid and not same_shape:
+                # per-axis pyramid: the table is sized from the AABB's aspect, which is only known now
+                dev = device if device is not None else self.den_w.device
+                LoTDNeRFDistantModel.__init__(self, aabb=a, **self._ctor)
+                device = dev
+            else:
+                self.aabb.copy_(a.to(self.aabb.device))
+        if device is not None:
+            self.to(device)
+        return self
+
+    # ------------------------------------------------------------------ encoding hooks (csrc/nerf_field.hip)
+    def _enc_fwd(self, grid16, wpack, u4, rays_d, ha, S, K, sigma, rgb, h_pl):
+        _lib.call("nsim_distant_fwd", self.meta, _lib.ptr(grid16), _lib.ptr(wpack), _lib.ptr(u4), _lib.ptr(rays_d),
+                  _lib.ptr(ha), S, K, _lib.ptr(sigma), _lib.ptr(rgb), _lib.ptr(h_pl))
+        if _lib.TIMER is not None:
+            _lib.TIMER.note_units("nsim_distant_fwd", S)
+            _lib.TIMER.note_units("nsim_distant_bwd", S)
+            _lib.TIMER.note_units("nsim_lotd4_scatter", S)
+        return None
+
+    def _enc_scatter(self, u4, valid, S, dh_pl, dgrid, enc_state):
+        _lib.call("nsim_lotd4_scatter", self.cfg.meta, _lib.ptr(u4), _lib.ptr(valid), S, _lib.ptr(dh_pl), _lib.ptr(dgrid))
+
+
+class _Permuto4Cfg:
+    """The encoding config of ``PermutoNeRFDistantModel``: a 4-D ``PermutoConfig`` whose meta takes the shells kernel's
+    u4 in [0,1]^4 and sees the lattice input x = 2 u4 - 1 (the mapping is folded into the per-level scale / shift:
+    (2 u - 1 + shift) scale = (u + (shift - 1) / 2) (2 scale), no kernel work), and a stub 4-D pyramid of as many levels as
+    the meta of the decoder launches (they read the feature count from it), as ``_PermutoFieldCfg`` for the 3-D decoders."""
+
+    def __init__(self, pcfg):
+        self.permuto = pcfg
+        self.num_levels, self.out_features, self.n_params = pcfg.num_levels, pcfg.out_features, pcfg.n_params
+        self.hashmap_size = pcfg.hashmap_size
+        self.pmeta = pcfg.meta
+        for l in range(pcfg.num_levels):
+            for i in range(pcfg.in_dim):
+                self.pmeta.scale[l][i] = 2.0 * (pcfg.res[l] / math.sqrt((i + 1) * (i + 2)))
+                self.pmeta.shift[l][i] = (float(pcfg.shifts[l, i]) - 1.0) * 0.5
+        m = _lib.Lotd4Meta()
+        m.num_levels = pcfg.num_levels
+        for l in range(pcfg.num_levels):
+            m.res_xyz[l], m.res_w[l], m.type[l], m.size[l], m.offset[l] = 2, 2, 0, 16, 0
+        self.meta = m
+
+    def set_active_levels(self, n):
+        self.pmeta.n_active_levels = 0 if n is None or int(n) >= self.num_levels else max(1, int(n))
+
+
+class PermutoNeRFDistantModel(_DistantBase):
+    """``app.models.single.PermutoNeRFDistant`` (permuto_neus.bmvs.230814.yaml:196-247): the NeRF++ background on a 4-D
+    permutohedral lattice.  The lattice input is 2 u4 - 1 with u4 = (p / r on the unit cube, 1 / r) in [0,1]^4 as
+    ``nsim_distant_shells`` emits it, so ``coarsest_res`` / ``finest_res`` mean cells per unit length of a [-1,1] input, as for
+    the close-range ``PermutoNeuSModel`` (the nr3d_lib implementation is absent: this convention is fixed here, DESIGN
+    sec. 7).  ``anneal_cfg{type: hardmask, start_it, start_level, stop_it}`` (yaml :212-216) drives the level mask from
+    ``training_before_per_step``."""
+
+    def __init__(self, aabb: torch.Tensor = None, precision: str = "fp16", radius_scale_min: float = 1.0,
+                 radius_scale_max: float = 1000.0, max_steps: int = 64, include_inf_distance: bool = True,
+                 use_view_dirs: bool = True, permuto_auto_compute_cfg: dict = None, anneal_cfg: dict = None,
+                 param_bound: float = 1e-4, seed: int = 7, device=None, ray_query_cfg: dict = None, **reference_params):
+        if reference_params:        # the reference's model_params block verbatim (fields/ref_config.py)
+            from . import ref_config
+            kw = ref_config.permuto_distant_native_kwargs(dict(
+                reference_params, include_inf_distance=include_inf_distance, radius_scale_min=radius_scale_min,
+                radius_scale_max=radius_scale_max, ray_query_cfg=ray_query_cfg))
+            kw.setdefault("max_steps", max_steps)
+            PermutoNeRFDistantModel.__init__(self, aabb=aabb, seed=seed, device=device, **kw)
+            return
+        super().__init__()
+        from ..grid_encodings.permuto import PermutoConfig
+        c = dict(permuto_auto_compute_cfg or {})
+        c.setdefault("n_levels", 16)
+        c.setdefault("log2_hashmap_size", 19)
+        if int(c["n_levels"]) > 16:
+            raise ValueError("the distant decoders read at most 16 levels (32 features)")
+        self.cfg = _Permuto4Cfg(PermutoConfig(in_dim=4, **c))
+        self.anneal_cfg = dict(anneal_cfg) if anneal_cfg else None
+        self._init_common(aabb, precision, radius_scale_min, radius_scale_max, max_steps, include_inf_distance, use_view_dirs,
+                          param_bound, seed, self.cfg.meta)
+        self._anneal(0)
+        if device is not None:
+            self.to(device)
+
+    # ------------------------------------------------------------------ hardmask level annealing
+    def set_active_levels(self, n):
+        """Only the first n lattice levels are read / trained; None or >= num_levels = all."""
+        self.cfg.set_active_levels(n)
+
+    @property
+    def n_active_levels(self) -> int:
+        n = int(self.cfg.pmeta.n_active_levels)
+        return n if 0 < n < self.cfg.num_levels else self.cfg.num_levels
+
+    def _anneal(self, it: int):
+        """The rule of ``fields/neus.py anneal_levels`` / ``fields/nerf.py _anneal``: level l is active once
+        it >= start_it + (l - start_level) / (L - 1 - start_level) (stop_it - start_it); at least one level
+        (``start_level: -1``, yaml :215 ``bg_start_level``)."""
+        an = self.anneal_cfg
+        if an is None:
+            return
+        L = self.cfg.num_levels
+        r = min(max((it - an["start_it"]) / max(1, an["stop_it"] - an["start_it"]), 0.0), 1.0)
+        n = int(math.floor(an["start_level"] + r * (L - 1 - an["start_level"]) + 1e-9)) + 1
+        self.set_active_levels(max(n, 1))
+
+    def training_initialize(self, config=None, logger=None, log_prefix=None) -> bool:
+        self._anneal(0)
+        return False
+
+    def training_before_per_step(self, it: int, logger=None):
+        self._anneal(int(it))
+        if logger is not None:
+            logger.add("anneal", f"{type(self).__name__}.n_active_levels", self.n_active_levels, int(it))
+
+    # ------------------------------------------------------------------ encoding hooks (csrc/permuto.hip)
+    def _enc_fwd(self, grid16, wpack, u4, rays_d, ha, S, K, sigma, rgb, h_pl):
+        if h_pl is None:        # a no-grad query: the planes are scratch
+            h_pl = torch.empty([16, S, 2], dtype=torch.float32, device=u4.device)
+        _lib.call("nsim_permuto_gather_pts", self.cfg.pmeta, _lib.ptr(grid16), _lib.ptr(u4), S, _lib.ptr(h_pl))
+        _lib.call("nsim_distant_fwd_planes", self.meta, _lib.ptr(wpack), _lib.ptr(h_pl), _lib.ptr(rays_d), _lib.ptr(ha), S, K,
+                  _lib.ptr(sigma), _lib.ptr(rgb))
+        if _lib.TIMER is not None:
+            for k in ("nsim_permuto_gather_pts", "nsim_distant_fwd_planes", "nsim_distant_bwd", "nsim_permuto_scatter_pts"):
+                _lib.TIMER.note_units(k, S)
+        return int(self.cfg.pmeta.n_active_levels)
+
+    def _enc_scatter(self, u4, valid, S, dh_pl, dgrid, enc_state):
+        pm = self.cfg.pmeta
+        prev = int(pm.n_active_levels)      # the backward of a query uses the level mask the query was made with
+        pm.n_active_levels = int(enc_state)
+        try:
+            _lib.call("nsim_permuto_scatter_pts", pm, _lib.ptr(u4), _lib.ptr(valid), S, _lib.ptr(dh_pl), _lib.ptr(dgrid))
+        finally:
+            pm.n_active_levels = prev

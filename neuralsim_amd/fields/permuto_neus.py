@@ -49,8 +49,10 @@ class _PermutoFieldCfg:
         self.aabb = a.float()
 
     def set_active_levels(self, n):
-        if n is not None and 0 < int(n) < self.num_levels:
-            raise NotImplementedError("hardmask level annealing is a LoTD feature; the permutohedral configs do not use it")
+        """Hardmask level annealing (``anneal_cfg{type: hardmask}``, permuto_neus.bmvs.230814.yaml:118-122): the lattice
+        kernels mask levels >= n (``pmeta``); the stub pyramid's meta carries the same count for ``LoTDNeuSModel``."""
+        self._stub.set_active_levels(n)
+        self.pmeta.n_active_levels = self.meta.n_active_levels
 
 
 class _PermutoFieldEncoding(nn.Module):
@@ -259,6 +261,14 @@ class PermutoNeuSModel(LoTDNeuSModel):
             with torch.no_grad():
                 self.accel.init(self.query_sdf, logger=logger)
         return updated
+
+    def training_before_per_step(self, it: int, logger=None):
+        """``LoTDNeuSModel``'s hook (inv_s control, level annealing, occupancy refresh); the trainer's scalar log also gets the
+        number of active lattice levels."""
+        super().training_before_per_step(it, logger=logger)
+        if logger is not None:
+            n = int(self.encoding.cfg.pmeta.n_active_levels)
+            logger.add("anneal", f"{type(self).__name__}.n_active_levels", n if n > 0 else self.encoding.cfg.num_levels, int(it))
 
     def geometric_init_fn(self, *a, **k):
         raise NotImplementedError("the permutohedral model is initialised by pre-training (geometric_init_sphere)")

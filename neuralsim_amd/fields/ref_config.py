@@ -232,6 +232,12 @@ def distant_native_kwargs(params: dict) -> Dict:
                                                       "per_level_scale") if k in ac}
     kw["param_bound"] = float((enc.get("param_init_cfg") or {}).get("bound", 1e-4))
     kw["lotd_use_cuboid"] = bool(enc.get("lotd_use_cuboid", False))
+    _distant_decoder_kwargs(p, kw)
+    return kw
+
+
+def _distant_decoder_kwargs(p: dict, kw: Dict):
+    """What the distant models share below the encoding: decoders, SH, appearance, shells (checked, then added to ``kw``)."""
     if (p.get("extra_pos_embed_cfg") or {}).get("type", "identity") != "identity":
         _unsupported("extra_pos_embed_cfg.type", p["extra_pos_embed_cfg"]["type"], "identity")
     dd = dict(p.get("density_decoder_cfg") or {})
@@ -264,6 +270,41 @@ def distant_native_kwargs(params: dict) -> Dict:
         _unsupported("march_cfg.interval_type", mc.get("interval_type"), "inverse_proportional (uniform in 1/r)")
     if "max_steps" in mc:
         kw["max_steps"] = int(mc["max_steps"])
+
+
+def permuto_distant_native_kwargs(params: dict) -> Dict:
+    """Reference ``model_params`` of ``PermutoNeRFDistant`` (permuto_neus.bmvs.230814.yaml:196-247) -> native kwargs of
+    ``PermutoNeRFDistantModel``: a 4-D ``multi_res`` lattice of at most 16 levels x 2 features, hardmask annealing, and the
+    decoder / shell options of ``distant_native_kwargs``."""
+    p = dict(params)
+    if p.get("use_tcnn_backend", False):
+        _unsupported("use_tcnn_backend", True, "there is no tiny-cuda-nn here")
+    kw: Dict = dict(precision=_precision(p.get("dtype", "half")))
+    enc = dict(p.get("encoding_cfg") or {})
+    if int(enc.get("input_ch", 4)) != 4:
+        _unsupported("encoding_cfg.input_ch", enc.get("input_ch"), "the distant model encodes (x, y, z, 1/r)")
+    ac = dict(enc.get("permuto_auto_compute_cfg") or {})
+    if ac.get("type", "multi_res") != "multi_res":
+        _unsupported("encoding_cfg.permuto_auto_compute_cfg.type", ac.get("type"), "multi_res")
+    if int(ac.get("n_feats", 2)) != 2:
+        _unsupported("permuto_auto_compute_cfg.n_feats", ac.get("n_feats"), "2 features per level")
+    if not 1 <= int(ac.get("n_levels", 16)) <= 16:
+        _unsupported("permuto_auto_compute_cfg.n_levels", ac.get("n_levels"), "at most 16 levels (32 decoder input features)")
+    kw["permuto_auto_compute_cfg"] = _plain(ac)
+    pi = dict(enc.get("param_init_cfg") or {})
+    if pi.get("type", "uniform") != "uniform":
+        _unsupported("encoding_cfg.param_init_cfg.type", pi.get("type"), "uniform")
+    kw["param_bound"] = float(pi.get("bound", 1e-4))
+    an = enc.get("anneal_cfg")
+    if an is not None:
+        if an.get("type", "hardmask") != "hardmask":
+            _unsupported("encoding_cfg.anneal_cfg.type", an.get("type"), "hardmask level annealing is built")
+        kw["anneal_cfg"] = dict(start_it=int(an.get("start_it", 0)), stop_it=int(an.get("stop_it", 1000)),
+                                start_level=int(an.get("start_level", 2)))
+    unknown = set(enc) - {"input_ch", "permuto_auto_compute_cfg", "param_init_cfg", "anneal_cfg"}
+    if unknown:
+        _unsupported("encoding_cfg." + sorted(unknown)[0], enc[sorted(unknown)[0]], "not an option of the permutohedral distant model")
+    _distant_decoder_kwargs(p, kw)
     return kw
 
 

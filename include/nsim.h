@@ -766,6 +766,41 @@ int nsim_nn_grid_fill(const float* y, int64_t M, const int32_t* cell_off, const 
 int nsim_nn_grid_query(const float* x, int64_t N, const float* rec, const int32_t* cell_off, int32_t* hdr, int max_rings, float* d2,
                        int32_t* idx, int32_t* left_list, void* stream);
 
+/* ------------------------------------------------------------- error-map importance sampling of training pixels */
+/* nr3d_lib.models.importance ``ErrorMap`` / ``ImpSampler`` (built per camera by code_single/tools/train.py:105-138; config block
+ * ``training.error_map{error_map_hw, frac_uniform, min_pdf, max_pdf, n_steps_max}``, lotd_neus.dtu.230814.yaml:316-320).  The map
+ * is em f32 [n_images, h, w]; every entry point rejects n_images h w >= 2^31.
+ *
+ * ErrorMap.step_error_map(i, xy, val) (train.py:678-688; the error is the per-ray photometric term of
+ * app/loss/photometric.py:111-112, 146), first half: ray r falls into the cell cx = clamp(int(x w), 0, w - 1), cy = clamp(int(y h),
+ * 0, h - 1) of frame fidx[r * fidx_stride] (fidx_stride 0: one frame for every ray, 1: per ray); its error is added to
+ * sum [n_images h w] and 1 to cnt [n_images h w] with f32 atomics (both zero on entry) and touched [n_images] (int32, zero on
+ * entry) is set for its frame.  The error is val [N], or -- val NULL -- mean_c fn(pred - gt) of pred / gt [N,3] with fn 0 = mse,
+ * 1 = l1, computed here so that a training chain needs no launch of its own for it; err_out [N] (may be NULL) receives it.  Rays
+ * of a frame outside [0, n_images) are not accounted. */
+int nsim_errmap_accumulate(const int64_t* fidx, int64_t fidx_stride, const float* xy, const float* val, const float* pred,
+                           const float* gt, int fn, int64_t N, int64_t n_images, int h, int w, float* sum, float* cnt,
+                           int32_t* touched, float* err_out, void* stream);
+/* ... second half: cells with cnt > 0 become 0.5 em + 0.5 sum / cnt, every other cell keeps its bits; the consumed cells of sum /
+ * cnt are zeroed again, n_steps [n_images] (int64) is incremented for every touched image and the flags are cleared. */
+int nsim_errmap_blend(float* em, float* sum, float* cnt, int32_t* touched, int64_t* n_steps, int64_t n_images, int h, int w,
+                      void* stream);
+/* ErrorMap.get_pdf + get_pdf_image, as the tables ImpSampler.sample_img_pixel / sample_pixel (dataio/data_loader/
+ * pixel_loader.py:157-171, 280-302) draw from.  Per image: p = max(em, 0) + 1e-12; p /= sum p; p = max(p, min_pdf / (h w));
+ * max_pdf >= 0: p = min(p, max(max_pdf, 1)); p /= sum p -> pdf_cell [n_images, h w] (may be NULL) and its inclusive scan
+ * cdf_cell [n_images, h w], non-decreasing, last entry of every image exactly 1.  mass [n_images] = sum of em per image;
+ * pdf_img [n_images] = mass / max(sum mass, 1e-12); cdf_img [n_images] = the inclusive scan of max(mass, 0) / sum max(mass, 0)
+ * (equal shares when no image has mass), last entry exactly 1.  Any h w >= 1.  max_pdf < 0: no upper clamp. */
+int nsim_errmap_cdf(const float* em, int64_t n_images, int h, int w, float min_pdf, float max_pdf, float* cdf_cell,
+                    float* pdf_cell, float* mass, float* cdf_img, float* pdf_img, void* stream);
+/* ImpSampler.sample_img_pixel (fixed_frame < 0) / sample_pixel (fixed_frame = the frame) from uniforms u f32 [., 4]: rows row0 ..
+ * row0 + n - 1 of u, fidx_out (int64, may be NULL) and xy_out (f32 [., 2]) are served, so that several maps fill one batch.  The
+ * first n_uni of them are uniform: fidx = min(int(u0 n_images), n_images - 1), xy = (u2, u3).  The others: image = the first i with
+ * cdf_img[i] > u0, cell = the first c with cdf_cell[i][c] > u1 (both clamped to the last index), xy = ((cx + u2) / w,
+ * (cy + u3) / h), kept inside its cell: int(x w) == cx and int(y h) == cy.  All xy are clamped to [1e-6, 1 - 1e-6]. */
+int nsim_errmap_draw(const float* cdf_img, const float* cdf_cell, int64_t n_images, int h, int w, const float* u, int64_t n,
+                     int64_t n_uni, int64_t fixed_frame, int64_t row0, int64_t* fidx_out, float* xy_out, void* stream);
+
 /* MFMA layout self-test (tests only): writes D = A(32x16 f16) * B(16x32 f16) with the wrappers used by the
  * field kernels; a, b given in plain row-major. d is 32x32 f32 row-major. */
 int nsim_selftest_mfma(const float* a, const float* b, float* d, int use_f32, void* stream);

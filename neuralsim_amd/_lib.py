@@ -192,6 +192,10 @@ SIGNATURES = {
     "nsim_nn_grid_scan": [_P, _P],
     "nsim_nn_grid_fill": [_P, _I64, _P, _P, _P, _P],
     "nsim_nn_grid_query": [_P, _I64, _P, _P, _P, _I, _P, _P, _P],
+    "nsim_errmap_accumulate": [_P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I, _I, _P, _P, _P, _P],
+    "nsim_errmap_blend": [_P, _P, _P, _P, _P, _I64, _I, _I],
+    "nsim_errmap_cdf": [_P, _I64, _I, _I, _F, _F, _P, _P, _P, _P, _P],
+    "nsim_errmap_draw": [_P, _P, _I64, _I, _I, _P, _I64, _I64, _I64, _I64, _P, _P],
 }
 NOSTREAM = {
     "nsim_strerror": ([_I], C.c_char_p),

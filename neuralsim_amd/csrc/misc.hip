@@ -1183,6 +1183,7 @@ const char* nsim_strerror(int code) {
     case 53: return "sphere trace: the runtime reports no resident workgroup for the kernel (CU count / occupancy query)";
     case 38: return "the close-range NeRF decoders take 1..16 LoTD levels (<= 32 input features)";
     case 39: return "n_appear must be 0 or 4";
+    case 54: return "error map: n_images, h, w >= 1, n_images h w < 2^31 and a fixed frame below n_images";
     case 36: return "wide decoder: 0..10 embedding frequencies and at most 128 first-layer inputs (2 num_levels + 3 + 6 n_freq)";
     default: return code >= 1000 ? "HIP launch error (code - 1000 = hipError_t)" : "unknown error";
   }

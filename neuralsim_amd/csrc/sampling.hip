@@ -801,3 +801,311 @@ int nsim_compress_emit(const float* sdf, const float* t, const int64_t* pack_inf
 }
 
 }  // extern "C"
+
+// ----------------------------------------------------------------------------------- error-map importance sampling
+// The pixel sampler of the reference's trainer (``ImpSampler`` / ``ErrorMap``: code_single/tools/train.py:105-138 builds them,
+// dataio/data_loader/pixel_loader.py:157-171, 280-302 draws (frame, pixel) from them once per iteration, train.py:619-621,
+// 678-688 scatters the batch's per-ray photometric error back; config block ``training.error_map``).  Four entry points:
+//   accumulate  per ray: cell of (frame, xy), f32 atomics into the scratch planes sum / cnt, a flag per touched image
+//   blend       per cell with cnt > 0: em = 0.5 em + 0.5 sum / cnt; the consumed scratch is zeroed again, n_steps counted
+//   cdf         per image (one workgroup): the clamped, twice-normalised pdf and its inclusive scan; then the image level
+//   draw        per row: two binary searches (image, cell) + the jitter inside the cell, or the uniform formula
+// The scan runs on 48-bit fixed point (int64 sums are associative): every CDF is non-decreasing whatever the order of the
+// partial sums, and the device and the host emulator produce the same bits.  The normalising sums are f64 -- a few
+// thousand cells per image, the kernels are latency bound.
+#define EM_THREADS 256
+#define EM_PER 8
+#define EM_FIX 281474976710656.0        // 2^48
+
+__device__ __forceinline__ int em_cell_axis(float x, int n) {        // clamp(int(x n), 0, n - 1), NaN -> 0
+  const float s = x * (float)n;
+  if (!(s >= 1.0f)) return 0;
+  if (s >= (float)n) return n - 1;
+  return (int)s;
+}
+
+__global__ void __launch_bounds__(256) k_errmap_accumulate(const int64_t* __restrict__ fidx, int64_t fidx_stride,
+                                                            const float* __restrict__ xy, const float* __restrict__ val,
+                                                            const float* __restrict__ pred, const float* __restrict__ gt,
+                                                            int fn, int64_t N, int64_t V, int h, int w,
+                                                            float* __restrict__ sum, float* __restrict__ cnt,
+                                                            int32_t* __restrict__ touched, float* __restrict__ err_out) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= N) return;
+  float e;
+  if (val) {
+    e = val[r];
+  } else {       // mean_c fn(pred - gt): ``mse`` (fn 0) or ``l1`` (fn 1), app/loss/photometric.py:111-112
+    const float d0 = pred[3 * r] - gt[3 * r], d1 = pred[3 * r + 1] - gt[3 * r + 1], d2 = pred[3 * r + 2] - gt[3 * r + 2];
+    e = fn == 1 ? ((fabsf(d0) + fabsf(d1)) + fabsf(d2)) / 3.0f : ((d0 * d0 + d1 * d1) + d2 * d2) / 3.0f;
+  }
+  if (err_out) err_out[r] = e;
+  const int64_t i = fidx[r * fidx_stride];
+  if (i < 0 || i >= V) return;          // a frame outside the map: nothing to account it to
+  const int cx = em_cell_axis(xy[2 * r], w), cy = em_cell_axis(xy[2 * r + 1], h);
+  const int64_t flat = (i * h + cy) * w + cx;
+  atomicAdd(sum + flat, e);
+  atomicAdd(cnt + flat, 1.0f);
+  touched[i] = 1;                       // (every writer stores the same word)
+}
+
+__global__ void __launch_bounds__(256) k_errmap_blend(float* __restrict__ em, float* __restrict__ sum, float* __restrict__ cnt,
+                                                       int32_t* __restrict__ touched, int64_t* __restrict__ n_steps,
+                                                       int64_t V, int64_t n_cells) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_cells; c += stride) {
+    const float k = cnt[c];
+    if (k > 0.0f) {
+      em[c] = 0.5f * em[c] + 0.5f * (sum[c] / k);
+      sum[c] = 0.0f;
+      cnt[c] = 0.0f;
+    }
+  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += stride) {
+    if (touched[i]) {
+      n_steps[i] += 1;
+      touched[i] = 0;
+    }
+  }
+}
+
+// sum of v over the workgroup, returned to every thread (sh: EM_THREADS / 64 words; two barriers)
+__device__ __forceinline__ double em_block_sum(double v, double* sh) {
+  const double ws = wave_sum(v);
+  __syncthreads();                      // (the previous use of sh is over)
+  if (nsim_lane() == 0) sh[threadIdx.x >> 6] = ws;
+  __syncthreads();
+  double t = 0.0;
+#pragma unroll
+  for (int k = 0; k < EM_THREADS / 64; ++k) t += sh[k];
+  return t;
+}
+
+// the pdf of one cell before its last normalisation (ErrorMap.get_pdf): max(em, 0) + 1e-12, / S1, clamped from below to
+// min_pdf / (h w) and -- hi > 0 -- from above to hi
+__device__ __forceinline__ double em_clamped(float e, double inv_s1, double lo, double hi) {
+  double p = ((double)fmaxf(e, 0.0f) + 1e-12) * inv_s1;
+  p = p > lo ? p : lo;
+  if (hi > 0.0) p = p < hi ? p : hi;
+  return p;
+}
+
+// One workgroup per image; thread t owns EM_PER consecutive cells of every chunk of EM_THREADS * EM_PER (the arrangement of
+// k_pack_infos_from_n: one serial prefix per thread, one wave scan, the wave totals through LDS), chunks chained by a
+// carried running sum, so any h w >= 1 is covered.
+__global__ void __launch_bounds__(EM_THREADS) k_errmap_cdf(const float* __restrict__ em, int hw, float min_pdf, float max_pdf,
+                                                            float* __restrict__ cdf_cell, float* __restrict__ pdf_cell,
+                                                            float* __restrict__ mass) {
+  __shared__ double sh[EM_THREADS / 64];
+  __shared__ int64_t wtot[EM_THREADS / 64];
+  const int tid = threadIdx.x, lane = nsim_lane(), wave = tid >> 6;
+  const int64_t img = blockIdx.x;
+  const float* e = em + img * hw;
+  double s1 = 0.0, m = 0.0;
+  for (int c = tid; c < hw; c += EM_THREADS) {
+    const float v = e[c];
+    s1 += (double)fmaxf(v, 0.0f) + 1e-12;
+    m += (double)v;
+  }
+  s1 = em_block_sum(s1, sh);
+  m = em_block_sum(m, sh);
+  if (tid == 0) mass[img] = (float)m;
+  const double inv_s1 = 1.0 / s1, lo = (double)min_pdf / (double)hw;
+  const double hi = max_pdf >= 0.0f ? (double)fmaxf(max_pdf, 1.0f) : -1.0;
+  double s2 = 0.0;
+  for (int c = tid; c < hw; c += EM_THREADS) s2 += em_clamped(e[c], inv_s1, lo, hi);
+  s2 = em_block_sum(s2, sh);
+  const double inv_s2 = 1.0 / s2;
+  int64_t carry = 0;
+  for (int base = 0; base < hw; base += EM_THREADS * EM_PER) {
+    const int c0 = base + tid * EM_PER;
+    int64_t v[EM_PER];
+    int64_t mine = 0;
+#pragma unroll
+    for (int k = 0; k < EM_PER; ++k) {
+      v[k] = 0;
+      if (c0 + k < hw) {
+        const double p = em_clamped(e[c0 + k], inv_s1, lo, hi) * inv_s2;
+        if (pdf_cell) pdf_cell[img * hw + c0 + k] = (float)p;
+        v[k] = (int64_t)(p * EM_FIX + 0.5);
+      }
+      mine += v[k];
+    }
+    const int64_t incl = wave_incl_sum(mine);
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    int64_t before = 0, chunk = 0;
+#pragma unroll
+    for (int k = 0; k < EM_THREADS / 64; ++k) {
+      const int64_t x = wtot[k];
+      before += (k < wave) ? x : 0;
+      chunk += x;
+    }
+    int64_t run = carry + before + incl - mine;
+#pragma unroll
+    for (int k = 0; k < EM_PER; ++k) {
+      run += v[k];
+      if (c0 + k < hw) cdf_cell[img * hw + c0 + k] = (c0 + k == hw - 1) ? 1.0f : fminf((float)((double)run * (1.0 / EM_FIX)), 1.0f);
+    }
+    carry += chunk;
+    __syncthreads();
+  }
+}
+
+// image level: pdf_img = mass / max(sum mass, 1e-12) (ErrorMap.get_pdf_image) and its inclusive scan, last entry 1.  One
+// workgroup.  The scan takes max(mass, 0); when no image carries mass every image gets the same share.
+__global__ void __launch_bounds__(EM_THREADS) k_errmap_cdf_img(const float* __restrict__ mass, int64_t V,
+                                                                float* __restrict__ cdf_img, float* __restrict__ pdf_img) {
+  __shared__ double sh[EM_THREADS / 64];
+  __shared__ int64_t wtot[EM_THREADS / 64];
+  const int tid = threadIdx.x, lane = nsim_lane(), wave = tid >> 6;
+  double tot = 0.0, pos = 0.0;
+  for (int64_t i = tid; i < V; i += EM_THREADS) {
+    tot += (double)mass[i];
+    pos += (double)fmaxf(mass[i], 0.0f);
+  }
+  tot = em_block_sum(tot, sh);
+  pos = em_block_sum(pos, sh);
+  const double inv_tot = 1.0 / (tot > 1e-12 ? tot : 1e-12);
+  const bool flat = !(pos > 0.0);
+  const double inv_pos = flat ? 0.0 : 1.0 / pos, share = 1.0 / (double)V;
+  int64_t carry = 0;
+  for (int64_t base = 0; base < V; base += EM_THREADS) {
+    const int64_t i = base + tid;
+    int64_t mine = 0;
+    if (i < V) {
+      const float mi = mass[i];
+      pdf_img[i] = (float)((double)mi * inv_tot);
+      mine = (int64_t)((flat ? share : (double)fmaxf(mi, 0.0f) * inv_pos) * EM_FIX + 0.5);
+    }
+    const int64_t incl = wave_incl_sum(mine);
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    int64_t before = 0, chunk = 0;
+#pragma unroll
+    for (int k = 0; k < EM_THREADS / 64; ++k) {
+      const int64_t x = wtot[k];
+      before += (k < wave) ? x : 0;
+      chunk += x;
+    }
+    if (i < V) cdf_img[i] = (i == V - 1) ? 1.0f : fminf((float)((double)(carry + before + incl) * (1.0 / EM_FIX)), 1.0f);
+    carry += chunk;
+    __syncthreads();
+  }
+}
+
+// the first index in [0, n) whose entry is > u, clamped to n - 1 (cdf non-decreasing)
+__device__ __forceinline__ int64_t em_upper(const float* __restrict__ cdf, int64_t n, float u) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (cdf[mid] > u) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo < n - 1 ? lo : n - 1;
+}
+
+// (c + u) / n, moved by single ulps until int(x n) == c again (c + u may round up to c + 1, c / n may round below the border):
+// the cell a pixel was drawn from is the cell its error is accounted to
+__device__ __forceinline__ float em_in_cell(int c, float u, int n, float lo, float hi) {
+  float x = ((float)c + u) / (float)n;
+  for (int it = 0; it < 4; ++it) {
+    const int k = (int)(x * (float)n);
+    if (k == c) break;
+    x = nextafterf(x, k < c ? 2.0f : -1.0f);
+  }
+  return fminf(fmaxf(x, lo), hi);
+}
+
+__global__ void __launch_bounds__(256) k_errmap_draw(const float* __restrict__ cdf_img, const float* __restrict__ cdf_cell,
+                                                      int64_t V, int h, int w, const float* __restrict__ u, int64_t n,
+                                                      int64_t n_uni, int64_t fixed_frame, int64_t row0,
+                                                      int64_t* __restrict__ fidx_out, float* __restrict__ xy_out) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int64_t r = row0 + j;
+  const float u0 = u[4 * r], u1 = u[4 * r + 1], u2 = u[4 * r + 2], u3 = u[4 * r + 3];
+  const float lo = (float)1e-6, hi = (float)(1.0 - 1e-6);        // cameras.py:247 ``clamp_(1e-6, 1 - 1e-6)``
+  int64_t f;
+  float x, y;
+  if (j < n_uni) {
+    if (fixed_frame >= 0) {
+      f = fixed_frame;
+    } else {
+      const float s = u0 * (float)V;
+      f = s >= (float)V ? V - 1 : (s >= 0.0f ? (int64_t)s : 0);
+    }
+    x = fminf(fmaxf(u2, lo), hi);
+    y = fminf(fmaxf(u3, lo), hi);
+  } else {
+    f = fixed_frame >= 0 ? fixed_frame : em_upper(cdf_img, V, u0);
+    const int64_t hw = (int64_t)h * w;
+    const int64_t c = em_upper(cdf_cell + f * hw, hw, u1);
+    const int cy = (int)(c / w), cx = (int)(c - (int64_t)cy * w);
+    x = em_in_cell(cx, u2, w, lo, hi);
+    y = em_in_cell(cy, u3, h, lo, hi);
+  }
+  if (fidx_out) fidx_out[r] = f;
+  xy_out[2 * r] = x;
+  xy_out[2 * r + 1] = y;
+}
+
+extern "C" {
+
+static inline int em_check_sizes(int64_t V, int h, int w) {
+  if (V < 1 || h < 1 || w < 1) return 54;
+  if ((double)V * (double)h * (double)w >= 2147483648.0) return 54;
+  return 0;
+}
+
+int nsim_errmap_accumulate(const int64_t* fidx, int64_t fidx_stride, const float* xy, const float* val, const float* pred,
+                           const float* gt, int fn, int64_t N, int64_t n_images, int h, int w, float* sum, float* cnt,
+                           int32_t* touched, float* err_out, void* stream) {
+  if (N <= 0) return 0;
+  if (int rc = em_check_sizes(n_images, h, w)) return rc;
+  if (!fidx || !xy || !sum || !cnt || !touched || (!val && !(pred && gt))) return 4;
+  if ((fidx_stride != 0 && fidx_stride != 1) || (fn != 0 && fn != 1)) return 3;
+  hipLaunchKernelGGL(k_errmap_accumulate, dim3(nsim_blocks(N, 256)), dim3(256), 0, (hipStream_t)stream, fidx, fidx_stride, xy,
+                     val, pred, gt, fn, N, n_images, h, w, sum, cnt, touched, err_out);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_errmap_blend(float* em, float* sum, float* cnt, int32_t* touched, int64_t* n_steps, int64_t n_images, int h, int w,
+                      void* stream) {
+  if (int rc = em_check_sizes(n_images, h, w)) return rc;
+  if (!em || !sum || !cnt || !touched || !n_steps) return 4;
+  const int64_t n_cells = n_images * h * w;
+  hipLaunchKernelGGL(k_errmap_blend, dim3(nsim_blocks(n_cells > n_images ? n_cells : n_images, 256, 4096)), dim3(256), 0,
+                     (hipStream_t)stream, em, sum, cnt, touched, n_steps, n_images, n_cells);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_errmap_cdf(const float* em, int64_t n_images, int h, int w, float min_pdf, float max_pdf, float* cdf_cell,
+                    float* pdf_cell, float* mass, float* cdf_img, float* pdf_img, void* stream) {
+  if (int rc = em_check_sizes(n_images, h, w)) return rc;
+  if (!em || !cdf_cell || !mass || !cdf_img || !pdf_img) return 4;
+  hipLaunchKernelGGL(k_errmap_cdf, dim3((unsigned)n_images), dim3(EM_THREADS), 0, (hipStream_t)stream, em, h * w, min_pdf,
+                     max_pdf, cdf_cell, pdf_cell, mass);
+  NSIM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_errmap_cdf_img, dim3(1), dim3(EM_THREADS), 0, (hipStream_t)stream, (const float*)mass, n_images, cdf_img,
+                     pdf_img);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_errmap_draw(const float* cdf_img, const float* cdf_cell, int64_t n_images, int h, int w, const float* u, int64_t n,
+                     int64_t n_uni, int64_t fixed_frame, int64_t row0, int64_t* fidx_out, float* xy_out, void* stream) {
+  if (n <= 0) return 0;
+  if (int rc = em_check_sizes(n_images, h, w)) return rc;
+  if (n_uni < 0 || row0 < 0) return 2;
+  if (fixed_frame >= n_images) return 54;
+  if (!u || !xy_out || (n_uni < n && (!cdf_cell || (fixed_frame < 0 && !cdf_img)))) return 4;
+  hipLaunchKernelGGL(k_errmap_draw, dim3(nsim_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, cdf_img, cdf_cell, n_images, h,
+                     w, u, n, n_uni, fixed_frame, row0, fidx_out, xy_out);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // extern "C"

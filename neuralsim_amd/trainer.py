@@ -32,7 +32,7 @@ class RenderTrainer:
                  pose_refine: Optional[dict] = None, c2w_true=None, fused_step: Optional[bool] = None,
                  distortion: Optional[torch.Tensor] = None, target_images: Optional[torch.Tensor] = None,
                  mono: Optional[dict] = None, rgb_fn: str = "mse", lidar: Optional[dict] = None, w_curvature: float = 0.0,
-                 curvature_eps: float = 1.0e-4):
+                 curvature_eps: float = 1.0e-4, pixel_sample_mode: str = "uniform", error_map: Optional[dict] = None):
         """pose_refine: ``dict(lr=1e-4, start_it=500)`` -- per-frame pose corrections (an axis-angle rotation and a
         translation, ``c2w' = [R Exp(w) | T + dT]``) trained through the rays from ``start_it`` on, standing in for the
         reference's ``LearnableParams`` (withmask_withlidar_joint.240219.yaml:338-352; the parametrisation of the
@@ -56,8 +56,21 @@ class RenderTrainer:
         ``model.get_sdf_curvature_1d`` :69) on the ``num_uniform`` uniform points, ``w_curvature * mean(min(curvature, 0.5))``
         with neighbours ``curvature_eps`` away, reported as ``loss_parts['loss_curvature']``.  With ``w_curvature > 0`` the step
         takes the generic autograd path (one more with-grad query of the uniform points; the fused launch chain does not carry
-        the term); with 0 nothing changes."""
+        the term); with 0 nothing changes.
+        pixel_sample_mode: ``uniform`` | ``error_map``; error_map: the yaml's ``training.error_map`` block, ``dict(error_map_hw=(32, 32),
+        frac_uniform=0.5, min_pdf=0.01, max_pdf=None, n_steps_max=None, enable_after=0)`` (lotd_neus.dtu.230814.yaml:316-320): from
+        iteration ``enable_after`` on the batch's (frame, pixel) pairs come from an ``ImpSampler`` over one ``ErrorMap`` of all V frames
+        (``importance.py``; frac_uniform of the rows stay uniform), and after the photometric loss of every pixel step the map is
+        updated with the batch's per-ray error under ``rgb_fn``; ``last_batch_error`` keeps that update's (fidx, xy, err).  Before
+        ``enable_after`` -- and with the default mode -- the batch takes exactly the uniform path.  Every rank keeps maps of its own
+        (as every process of the reference's DDP run); the prefetched batch k + 1 is drawn from the map as of step k - 1 (see
+        ``_update_error_map``)."""
         self.model = model
+        if pixel_sample_mode not in ("uniform", "error_map"):
+            raise ValueError(f"pixel_sample_mode must be 'uniform' or 'error_map', got {pixel_sample_mode!r}")
+        self.pixel_sample_mode = "uniform"
+        self.imp_sampler, self.error_map, self.last_batch_error = None, None, None
+        self._cdf_ready, self._draw_it = None, None
         self.target_images, self.mono, self.rgb_fn = target_images, (dict(mono) if mono else None), rgb_fn
         self.lidar = dict(lidar) if lidar else None
         self._last_aux = None
@@ -128,6 +141,8 @@ class RenderTrainer:
         self.renderer = SingleVolumeRenderer(dict(with_rgb=True, with_normal=True, near=near, far=far, perturb=perturb,
                                                   depth_use_normalized_vw=False)).train()
         self.stats: Dict[str, float] = {}
+        if pixel_sample_mode == "error_map":
+            self.use_error_map_sampling(error_map)
         if world_size > 1 and getattr(model, "accel", None) is not None:
             import torch.distributed as dist
 
@@ -160,8 +175,12 @@ class RenderTrainer:
     def sample_batch(self):
         dev = self.model.device
         N = self.num_rays
-        xy = torch.rand([N, 2], device=dev, generator=self.gen).clamp_(1e-6, 1 - 1e-6)   # cameras.py:247
-        fidx = torch.randint(0, self.V, [N], device=dev, generator=self.gen)
+        if self.imp_sampler is not None and (self._it if self._draw_it is None else self._draw_it) >= self.error_map_enable_after:
+            # (frame, pixel) from the error map (pixel_loader.py:280-302): four uniforms per ray, ONE generator call
+            fidx, xy = self.imp_sampler.sample_img_pixel(N, torch.rand([N, 4], device=dev, generator=self.gen))
+        else:
+            xy = torch.rand([N, 2], device=dev, generator=self.gen).clamp_(1e-6, 1 - 1e-6)   # cameras.py:247
+            fidx = torch.randint(0, self.V, [N], device=dev, generator=self.gen)
         if self.mono is not None and self.mono.get("patch_hw"):
             # image-patch rays (code_single/tools/train.py:738-739: rays_pix [h,w,2]): rows 0 .. h*w-1 of the batch
             ph, pw = self.mono["patch_hw"]
@@ -382,6 +401,8 @@ class RenderTrainer:
                  ptr(sc[1]), None, None, ptr(d_img), None, None, ptr(dalpha), ptr(drgb), None, ptr(out_idx))
             call("nsim_neus_alpha_bwd", ptr(sdf), ptr(dalpha), ptr(pi), R, ptr(ln_inv_s), model.ln_inv_s_factor, fis, ptr(dsdf),
                  ptr(dln))
+        if self.error_map is not None:      # the image is final here; the update runs beside the backward kernels
+            self._update_error_map(batch["fidx"], batch["xy"], vec[0], gt)
         cst = getattr(self, "_fused_consts", None)
         if cst is None or cst[0] != (dev, float(self.w_eikonal)):
             cst = self._fused_consts = ((dev, float(self.w_eikonal)),
@@ -519,9 +540,52 @@ class RenderTrainer:
         return dict(xy=xy, fidx=fidx, gt=gt, rays_o=rays_o, rays_d=rays_d, tested=tested, aux=self._last_aux,
                     fidx_hit=fidx[tested["rays_inds"]], **extras)
 
+    # ------------------------------------------------------------------ error-map importance sampling
+    def use_error_map_sampling(self, error_map: Optional[dict] = None):
+        """Switch ``pixel_sample_mode`` to ``error_map`` (what the constructor argument does): a fresh all-ones map of the V frames
+        and its sampler, configured by the ``training.error_map`` block ``error_map``."""
+        from .importance import ErrorMap, ImpSampler
+        ecfg = dict(error_map or {})
+        self.error_map_enable_after = int(ecfg.pop("enable_after", 0))
+        frac_uniform = float(ecfg.pop("frac_uniform", 0.5))
+        ecfg.setdefault("error_map_hw", (32, 32))
+        self.error_map = ErrorMap(self.V, device=self.model.device, **ecfg)
+        self.imp_sampler = ImpSampler({"error_map": (self.error_map, 1.0)}, frac_uniform=frac_uniform)
+        self.pixel_sample_mode = "error_map"
+        self._prefetched = None               # (a batch drawn ahead was drawn uniformly)
+        self._publish_cdfs()
+
+    def _publish_cdfs(self):
+        """Rebuild the sampler's CDF tables from the map -- on the caller's stream, which is the one that updates the map -- and
+        record the event the prefetch stream waits for before it draws from them."""
+        self.error_map.tables()
+        if self._side is not None:
+            self._cdf_ready = torch.cuda.current_stream().record_event()
+
+    def _update_error_map(self, fidx, xy, rgb, gt):
+        """``ErrorMap.step_error_map`` with the batch's per-ray photometric error (train.py:619-621, 678-688), then the tables.
+
+        Streams.  The map and its tables are written by the training stream only; the prefetch stream only READS tables (the draw
+        of ``sample_batch``).  Batch k + 1 is produced on the prefetch stream while step k runs, so it is drawn from the tables
+        published at the end of step k - 1: one step of staleness, accepted.  The tables exist twice (``ErrorMap.tables``): the
+        rebuild at the end of step k writes the snapshot that is NOT current, i.e. not the one the draw of batch k + 1 -- queued
+        earlier in step k -- reads; its last reader was the draw of batch k, and the training stream has waited for that batch's
+        ``_ready`` event at the start of step k.  The prefetch stream in turn waits for ``_cdf_ready`` before it draws.  (A
+        prefetched batch that is dropped unconsumed -- the start of pose refinement -- is waited for first, ``_train_step_pixel``.)"""
+        err = self.error_map.step_error_map_rgb(fidx, xy, rgb, gt, self.rgb_fn)
+        self.last_batch_error = (fidx.detach(), xy.detach(), err)
+        self._publish_cdfs()
+
     def _prefetch(self):
         if self._prefetched is not None:
             return
+        self._draw_it = self._it + 1          # the batch made here is the next iteration's
+        try:
+            self._prefetch_next()
+        finally:
+            self._draw_it = None
+
+    def _prefetch_next(self):
         if self._side is None:
             self._prefetched = self._make_batch()
             return
@@ -538,6 +602,8 @@ class RenderTrainer:
         handoff = _PREFETCH_HANDOFF
         self._release_retired()
         with torch.cuda.stream(self._side):
+            if self._cdf_ready is not None:       # the tables the draw reads were written on the training stream
+                self._side.wait_event(self._cdf_ready)
             b = self._make_batch()
             b["_ready"] = self._side.record_event()
         if handoff:
@@ -676,6 +742,8 @@ class RenderTrainer:
         self._it = int(it)
         refine = self.pose_refine_active()
         if refine and self._prefetched is not None:      # a batch drawn before the refinement started: re-draw with grad
+            if self.error_map is not None and self._prefetched.get("_ready") is not None:
+                torch.cuda.current_stream().wait_event(self._prefetched["_ready"])      # (its draw read the sampler's tables)
             self._prefetched = None
         # training_before_per_step: occupancy refresh with a rank-shared seed keeps replicas consistent
         acc = model.accel
@@ -717,6 +785,8 @@ class RenderTrainer:
                 uni = dict(model.forward_sdf_nablas(x_uni), net_x=x_uni)
             loss, parts = self.loss(ret, gt, uni, aux=batch.get("aux") if batch is not None else self._last_aux)
             self.loss_parts = parts
+            if self.error_map is not None:
+                self._update_error_map(fidx, xy, ret["rendered"]["rgb_volume"].detach(), gt)
             self.optim.zero_grad()
             if refine:
                 self.pose_optim.zero_grad(set_to_none=True)

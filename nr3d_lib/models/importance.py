@@ -9,6 +9,10 @@ lotd_neus.dtu.230814.yaml:316-320).  Implementation absent (nr3d_lib): restated 
 * ``ImpSampler({name: (ErrorMap, fraction)}, frac_uniform=)``: draws pixels -- ``frac_uniform`` of them uniformly, the rest
   from the 2-D pdfs of the maps (cell by its probability, uniform inside the cell); ``sample_pixel(n, frame)`` for a given
   frame, ``sample_img_pixel(n)`` jointly over (frame, pixel); ``get_pdf_image()`` = per-image probability mass.
+
+The torch classes below are the default (the reference's trainer runs on them with their random stream).  ``NSIM_IMP_SAMPLER=hip``
+in the environment at import time re-exports ``neuralsim_amd.importance.ErrorMap`` / ``ImpSampler`` -- the same interface on the HIP
+kernels ``nsim_errmap_*`` -- under these names instead.
 """
 from typing import Dict, Tuple
 
@@ -123,3 +127,9 @@ class ImpSampler(nn.Module):
 
     def get_pdf_image(self) -> torch.Tensor:
         return torch.stack([em.get_pdf_image() * self.fracs[k] for k, em in self.error_maps.items()]).sum(0)
+
+
+TorchErrorMap, TorchImpSampler = ErrorMap, ImpSampler
+import os as _os
+if _os.environ.get("NSIM_IMP_SAMPLER", "torch") == "hip":
+    from neuralsim_amd.importance import ErrorMap, ImpSampler      # noqa: E402,F811

@@ -680,6 +680,22 @@ int nsim_curv_angle_bwd(const float* n0, const float* n1, const float* gcurv, in
 int nsim_curv_loss_fwd(const float* n0, const float* n1, int64_t n, float clamp_max, float* out, void* stream);
 int nsim_curv_loss_bwd(const float* n0, const float* n1, int64_t n, float clamp_max, const float* gout, float* dn0,
                        float* dn1, void* stream);
+/* SSIM and S3IM (Xie et al., ICCV 2023): replaces ``nr3d_lib.models.loss.ssim.ssim_module`` (absent; the pytorch-ssim form: five
+ * grouped conv2d + ~20 elementwise ops and their backward) under ``PerceptualLoss(loss_type='ssim')`` and ``S3IMLoss``,
+ * app/loss/perceptual.py:61-70, 142-157.  Window g gT with g[i] ~ exp(-(i - k/2)^2 / (2 1.5^2)) normalised to sum 1, zero
+ * padding (k - 1) / 2, stride s, per channel; C1 = 0.01^2, C2 = 0.03^2; 1 <= k <= 11; Ho = (H + 2p - k) / s + 1, Wo alike.
+ *   index == NULL  planar: x, y [BC, H, W], BC = B C single-channel images;
+ *   index != NULL  indexed: x, y [n_rows, 3]; pixel (i, j) of the ONE image [3, H, W] is row index[i W + j] (index [H W] int64,
+ *                  BC = 1; an index outside [0, n_rows) is a zero pixel without gradient) -- S3IM's virtual image
+ *                  (perceptual.py:151-156), not materialised.
+ *   ssim_fwd: out[0] += mean of the SSIM map over all windows (out zeroed by the caller); coef [3, n_windows] f32 is written for
+ *             the backward (n_windows = BC Ho Wo, times 3 in the indexed form).
+ *   ssim_bwd: dx = gout[0] d out / d x.  Planar: every element of dx [BC, H, W] is written.  Indexed: ADDED into dx [n_rows, 3],
+ *             which the caller zeroes (rows the index does not name stay zero).  No gradient to y. */
+int nsim_ssim_fwd(const float* x, const float* y, const int64_t* index, int64_t n_rows, int64_t BC, int H, int W, int k, int s,
+                  float* out, float* coef, void* stream);
+int nsim_ssim_bwd(const float* x, const float* y, const int64_t* index, int64_t n_rows, int64_t BC, int H, int W, int k, int s,
+                  const float* coef, const float* gout, float* dx, void* stream);
 /* The loss head of one training step in a single launch (the reference's total = mse + w (eikonal(render samples) +
  * eikonal(uniform points)), code_single/tools/train.py:1411-1423 with app/loss/photometric.py + eikonal.py):
  *   acc[0] += mse(pred, gt) over n_img floats; acc[1] += eikonal(nablas[:S]); acc[2] += eikonal(nablas[S:S+M]);

@@ -172,6 +172,8 @@ SIGNATURES = {
     "nsim_curv_angle_bwd": [_P, _P, _P, _I64, _P, _P],
     "nsim_curv_loss_fwd": [_P, _P, _I64, _F, _P],
     "nsim_curv_loss_bwd": [_P, _P, _I64, _F, _P, _P, _P],
+    "nsim_ssim_fwd": [_P, _P, _P, _I64, _I64, _I, _I, _I, _I, _P, _P],
+    "nsim_ssim_bwd": [_P, _P, _P, _I64, _I64, _I, _I, _I, _I, _P, _P, _P],
     "nsim_mse_loss_fwd": [_P, _P, _I64, _P],
     "nsim_train_loss_head": [_P, _P, _I64, _P, _I64, _I64, _F, _P, _P, _P],
     "nsim_mse_loss_bwd": [_P, _P, _I64, _P, _P],

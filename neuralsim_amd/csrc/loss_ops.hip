@@ -6,6 +6,8 @@
 //   * sdf curvature: acos(n0^ . n1^) / pi of the nablas at a point and at its tangentially shifted neighbour, the shift
 //     itself, and mean(min(curvature, clamp_max))     (model.get_sdf_curvature_1d + SDFCurvatureRegLoss.fn,
 //     app/loss/sdf_curvature.py:42,69,75; the regulariser of PermutoSDF, Rosu & Behnke 2023)
+//   * ssim / s3im: mean SSIM of two images, planar or gathered through an index from [N,3] rows (the virtual image of S3IM,
+//     Xie et al. 2023), gradient to the first    (nr3d_lib.models.loss.ssim.ssim_module under app/loss/perceptual.py:61-70, 142-157)
 // The reference evaluates these with a handful of torch ops each; here one launch per direction, because at 8192
 // rays per iteration the step is bounded by launch count, not by bytes.
 #include "nsim_common.h"
@@ -305,6 +307,183 @@ __global__ void __launch_bounds__(LOSS_BLOCK) k_curv_loss_bwd(const float* __res
   }
 }
 
+// ---------------------------------------------------------------------------------------------- ssim / s3im
+// SSIM of two images under a k x k Gaussian window (sigma 1.5, zero padding (k - 1) / 2, stride s, per channel) and its gradient
+// with respect to the first image, in two addressings of ONE kernel family (the template argument CH):
+//   CH = 1  planar: BC = B * C independent single-channel images [BC, H, W];
+//   CH = 3  indexed: ONE three-channel image [3, H, W] whose pixel (i, j) is row index[i * W + j] of the [n_rows, 3] arrays -- the
+//           virtual image of S3IM (app/loss/perceptual.py:151-156), never materialised.  An index outside [0, n_rows) is a zero
+//           pixel that receives no gradient.
+// Forward: one thread per window position (its CH channels in turn), two passes over the window -- the weighted means, then the
+// moments ABOUT the means -- and three coefficients per window for the backward.  Backward: one thread per pixel, a gather over
+// the windows that cover it (at most ceil(k / s)^2: one for s >= k, 121 for k = 11, s = 1), stored (planar) or added atomically
+// into the pixel's row (indexed: a row occurs once per repeat of the virtual image).
+//
+// With dm = mu2 - mu1, sdd = sum g ((x - mu1) - (y - mu2))^2 = s11 + s22 - 2 s12, B1 = mu1^2 + mu2^2 + C1, B2 = s11 + s22 + C2:
+//   ssim = (1 - dm^2 / B1) (1 - sdd / B2)                  [2 mu1 mu2 + C1 = B1 - dm^2,  2 s12 + C2 = B2 - sdd]
+//   d ssim / d x_v = g_v (alpha + beta x_v + gamma (y_v - x_v)),
+//   gamma = d ssim / d s12 = 2 (1 - dm^2 / B1) / B2,   beta = 2 d ssim / d s11 + gamma = gamma sdd / B2,
+//   alpha = d ssim / d mu1 - beta mu1 - gamma dm,      d ssim / d mu1 = (2 / B1) (1 - sdd / B2) (dm + mu1 dm^2 / B1).
+// Every difference of nearly equal numbers is taken between INPUTS (y_v - x_v, x_v - mu1), never between products of the size of
+// 1 / C2: on flat bright images the textbook form E[x^2] - mu^2 loses 2e-5 of the value and 8e-4 of the gradient in f32.
+#define SSIM_MAX_WIN 11
+#define SSIM_C1 ((float)(0.01 * 0.01))
+#define SSIM_C2 ((float)(0.03 * 0.03))
+
+struct SsimArgs {
+  const float* x;
+  const float* y;
+  const int64_t* index;      // CH = 3 only
+  int64_t n_rows;            // CH = 3 only
+  int64_t BC;
+  int H, W, Ho, Wo, k, s, p;
+  float g[SSIM_MAX_WIN];     // the 1-D window, normalised to sum 1 in double on the host
+};
+
+// offset of channel 0 of pixel (iy, ix) of image bc, -1 for an index outside the rows (CH = 3)
+template <int CH>
+__device__ __forceinline__ int64_t ssim_base(const SsimArgs& a, int64_t bc, int iy, int ix) {
+  if (CH == 1) return (bc * a.H + iy) * (int64_t)a.W + ix;
+  const int64_t r = a.index[(int64_t)iy * a.W + ix];
+  return (r >= 0 && r < a.n_rows) ? 3 * r : -1;
+}
+
+// coef [3, nW] (alpha, beta, gamma), nW = BC * CH * Ho * Wo, window id = ((bc * CH + c) * Ho + oy) * Wo + ox
+template <int CH>
+__global__ void __launch_bounds__(LOSS_BLOCK) k_ssim_fwd(SsimArgs a, float inv_nw, float* __restrict__ out,
+                                                         float* __restrict__ coef) {
+  __shared__ float g[SSIM_MAX_WIN];
+  if (threadIdx.x < SSIM_MAX_WIN) g[threadIdx.x] = threadIdx.x < a.k ? a.g[threadIdx.x] : 0.f;
+  __syncthreads();
+  const int64_t plane = (int64_t)a.Ho * a.Wo, sites = a.BC * plane, nW = sites * CH;
+  float acc = 0.f;
+  for (int64_t w = (int64_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; w < sites; w += (int64_t)gridDim.x * LOSS_BLOCK) {
+    const int64_t bc = w / plane;
+    const int oy = (int)((w - bc * plane) / a.Wo), ox = (int)((w - bc * plane) % a.Wo);
+    const int y0 = oy * a.s - a.p, x0 = ox * a.s - a.p;
+    float m1[CH], dm[CH], s11[CH], s22[CH], sdd[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) m1[c] = dm[c] = s11[c] = s22[c] = sdd[c] = 0.f;
+    // a pixel of the zero padding adds nothing to the means ...
+    for (int i = 0; i < a.k; ++i) {
+      const int iy = y0 + i;
+      if (iy < 0 || iy >= a.H) continue;
+      for (int j = 0; j < a.k; ++j) {
+        const int ix = x0 + j;
+        if (ix < 0 || ix >= a.W) continue;
+        const int64_t b = ssim_base<CH>(a, bc, iy, ix);
+        if (b < 0) continue;
+        const float wg = g[i] * g[j];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+          const float xv = a.x[b + c], yv = a.y[b + c];
+          m1[c] += wg * xv;
+          dm[c] += wg * (yv - xv);
+        }
+      }
+    }
+    // ... but its deviation from them counts
+    for (int i = 0; i < a.k; ++i) {
+      const int iy = y0 + i;
+      const bool row_in = iy >= 0 && iy < a.H;
+      for (int j = 0; j < a.k; ++j) {
+        const int ix = x0 + j;
+        const int64_t b = (row_in && ix >= 0 && ix < a.W) ? ssim_base<CH>(a, bc, iy, ix) : -1;
+        const float wg = g[i] * g[j];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+          const float xv = b >= 0 ? a.x[b + c] : 0.f, yv = b >= 0 ? a.y[b + c] : 0.f;
+          const float dx = xv - m1[c], dd = (yv - xv) - dm[c], dy = dx + dd;
+          s11[c] += wg * dx * dx;
+          s22[c] += wg * dy * dy;
+          sdd[c] += wg * dd * dd;
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const float m2 = m1[c] + dm[c];
+      const float B1 = m1[c] * m1[c] + m2 * m2 + SSIM_C1, B2 = s11[c] + s22[c] + SSIM_C2;
+      const float lum = 1.0f - dm[c] * dm[c] / B1, cs = 1.0f - sdd[c] / B2;
+      acc += lum * cs;
+      const float gamma = 2.0f * lum / B2, beta = gamma * sdd[c] / B2;
+      const float dmu1 = 2.0f / B1 * cs * (dm[c] + m1[c] * dm[c] * dm[c] / B1);
+      const int64_t wid = (bc * CH + c) * plane + (int64_t)oy * a.Wo + ox;
+      coef[wid] = dmu1 - beta * m1[c] - gamma * dm[c];
+      coef[nW + wid] = beta;
+      coef[2 * nW + wid] = gamma;
+    }
+  }
+  block_sum_atomic(acc, inv_nw, out);
+}
+
+// dx: planar [BC, H, W], every element written (zero where no window covers the pixel); indexed [n_rows, 3], zero on entry
+template <int CH>
+__global__ void __launch_bounds__(LOSS_BLOCK) k_ssim_bwd(SsimArgs a, float inv_nw, const float* __restrict__ coef,
+                                                         const float* __restrict__ gout, float* __restrict__ dx) {
+  __shared__ float g[SSIM_MAX_WIN];
+  if (threadIdx.x < SSIM_MAX_WIN) g[threadIdx.x] = threadIdx.x < a.k ? a.g[threadIdx.x] : 0.f;
+  __syncthreads();
+  const int64_t plane = (int64_t)a.Ho * a.Wo, nW = a.BC * plane * CH, img = (int64_t)a.H * a.W, npix = a.BC * img;
+  const float sc = gout[0] * inv_nw;
+  for (int64_t v = (int64_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; v < npix; v += (int64_t)gridDim.x * LOSS_BLOCK) {
+    const int64_t bc = v / img;
+    const int iy = (int)((v - bc * img) / a.W), ix = (int)((v - bc * img) % a.W);
+    const int64_t b = ssim_base<CH>(a, bc, iy, ix);
+    if (b < 0) continue;
+    // window oy holds row iy at tap iy + p - oy s in [0, k)
+    int oy_lo = iy + a.p - a.k + 1, ox_lo = ix + a.p - a.k + 1;
+    oy_lo = oy_lo > 0 ? (oy_lo + a.s - 1) / a.s : 0;
+    ox_lo = ox_lo > 0 ? (ox_lo + a.s - 1) / a.s : 0;
+    int oy_hi = (iy + a.p) / a.s, ox_hi = (ix + a.p) / a.s;
+    oy_hi = oy_hi < a.Ho - 1 ? oy_hi : a.Ho - 1;
+    ox_hi = ox_hi < a.Wo - 1 ? ox_hi : a.Wo - 1;
+    float sa[CH], sb[CH], sg[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) sa[c] = sb[c] = sg[c] = 0.f;
+    for (int oy = oy_lo; oy <= oy_hi; ++oy) {
+      const float gy = g[iy + a.p - oy * a.s];
+      for (int ox = ox_lo; ox <= ox_hi; ++ox) {
+        const float wg = gy * g[ix + a.p - ox * a.s];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+          const int64_t wid = (bc * CH + c) * plane + (int64_t)oy * a.Wo + ox;
+          sa[c] += wg * coef[wid];
+          sb[c] += wg * coef[nW + wid];
+          sg[c] += wg * coef[2 * nW + wid];
+        }
+      }
+    }
+    const bool covered = oy_lo <= oy_hi && ox_lo <= ox_hi;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const float xv = a.x[b + c], yv = a.y[b + c];
+      const float d = sc * (sa[c] + sb[c] * xv + sg[c] * (yv - xv));
+      if (CH == 1) dx[b] = covered ? d : 0.f;
+      else if (covered) atomicAdd(&dx[b + c], d);
+    }
+  }
+}
+
+// sizes of one call; 0 or the error code
+static inline int ssim_args(SsimArgs* a, const float* x, const float* y, const int64_t* index, int64_t n_rows, int64_t BC, int H,
+                            int W, int k, int s) {
+  if (BC < 1 || H < 1 || W < 1 || k < 1 || k > SSIM_MAX_WIN || s < 1 || (int64_t)H * W >= ((int64_t)1 << 31)) return 55;
+  if (index && (BC != 1 || n_rows < 0)) return 55;
+  const int p = (k - 1) / 2;
+  if (H + 2 * p - k < 0 || W + 2 * p - k < 0) return 55;        // no window fits (an even window on one row / column)
+  a->x = x, a->y = y, a->index = index, a->n_rows = n_rows, a->BC = BC;
+  a->H = H, a->W = W, a->k = k, a->s = s, a->p = p;
+  a->Ho = (H + 2 * p - k) / s + 1, a->Wo = (W + 2 * p - k) / s + 1;
+  double g[SSIM_MAX_WIN], tot = 0.0;
+  for (int i = 0; i < k; ++i) {
+    g[i] = exp(-(double)((i - k / 2) * (i - k / 2)) / (2.0 * 1.5 * 1.5));
+    tot += g[i];
+  }
+  for (int i = 0; i < SSIM_MAX_WIN; ++i) a->g[i] = i < k ? (float)(g[i] / tot) : 0.f;
+  return 0;
+}
+
 static inline dim3 loss_grid(int64_t n) {
   int64_t b = nsim_blocks(n, LOSS_BLOCK);
   return dim3((unsigned)(b > LOSS_MAX_BLOCKS ? LOSS_MAX_BLOCKS : b));
@@ -408,6 +587,45 @@ int nsim_curv_loss_bwd(const float* n0, const float* n1, int64_t n, float clamp_
   if (!n0 || !n1 || !gout) return 26;
   hipLaunchKernelGGL(k_curv_loss_bwd, curv_grid(n), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, n0, n1, n, 1.0f / (float)n,
                      clamp_max, gout, dn0, dn1);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+// out[0] must be zero on entry; out[0] += mean SSIM over the BC CH Ho Wo windows.  index NULL: planar [BC, H, W]; else the [3, H, W]
+// image gathered from rows index[i W + j] of x, y [n_rows, 3] (BC = 1).  coef [3, BC CH Ho Wo]: handed to nsim_ssim_bwd
+int nsim_ssim_fwd(const float* x, const float* y, const int64_t* index, int64_t n_rows, int64_t BC, int H, int W, int k, int s,
+                  float* out, float* coef, void* stream) {
+  SsimArgs a;
+  const int rc = ssim_args(&a, x, y, index, n_rows, BC, H, W, k, s);
+  if (rc) return rc;
+  if (!x || !y || !out || !coef) return 4;
+  const int64_t sites = BC * a.Ho * a.Wo;
+  if (index)
+    hipLaunchKernelGGL((k_ssim_fwd<3>), loss_grid(sites), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, a,
+                       1.0f / (float)(3 * sites), out, coef);
+  else
+    hipLaunchKernelGGL((k_ssim_fwd<1>), loss_grid(sites), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, a, 1.0f / (float)sites,
+                       out, coef);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+// dx = gout[0] d (mean SSIM) / d x: planar [BC, H, W], every element written; indexed [n_rows, 3], ADDED to (the caller's zero
+// fill is part of the op: rows no index names stay zero)
+int nsim_ssim_bwd(const float* x, const float* y, const int64_t* index, int64_t n_rows, int64_t BC, int H, int W, int k, int s,
+                  const float* coef, const float* gout, float* dx, void* stream) {
+  SsimArgs a;
+  const int rc = ssim_args(&a, x, y, index, n_rows, BC, H, W, k, s);
+  if (rc) return rc;
+  if (!dx || !gout) return 26;
+  if (!x || !y || !coef) return 4;
+  const int64_t sites = BC * a.Ho * a.Wo, npix = BC * H * W;
+  if (index)
+    hipLaunchKernelGGL((k_ssim_bwd<3>), curv_grid(npix), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, a,
+                       1.0f / (float)(3 * sites), coef, gout, dx);
+  else
+    hipLaunchKernelGGL((k_ssim_bwd<1>), curv_grid(npix), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, a, 1.0f / (float)sites, coef,
+                       gout, dx);
   NSIM_CHECK_LAUNCH();
   return 0;
 }

@@ -1184,6 +1184,7 @@ const char* nsim_strerror(int code) {
     case 38: return "the close-range NeRF decoders take 1..16 LoTD levels (<= 32 input features)";
     case 39: return "n_appear must be 0 or 4";
     case 54: return "error map: n_images, h, w >= 1, n_images h w < 2^31 and a fixed frame below n_images";
+    case 55: return "ssim: 1 <= window <= 11, stride >= 1, H W < 2^31, at least one window per image, the indexed form takes one image";
     case 36: return "wide decoder: 0..10 embedding frequencies and at most 128 first-layer inputs (2 num_levels + 3 + 6 n_freq)";
     default: return code >= 1000 ? "HIP launch error (code - 1000 = hipError_t)" : "unknown error";
   }

@@ -120,6 +120,107 @@ def mse_loss(pred: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:
     return _MseFn.apply(pred, gt.detach())
 
 
+SSIM_MAX_WINDOW = 11         # SSIM_MAX_WIN of csrc/loss_ops.hip
+
+
+def ssim_out_hw(H: int, W: int, window_size: int, stride: int):
+    """(Ho, Wo) of the SSIM map: zero padding (k - 1) // 2 on every side, stride s."""
+    p = (window_size - 1) // 2
+    return (H + 2 * p - window_size) // stride + 1, (W + 2 * p - window_size) // stride + 1
+
+
+def _ssim_check(k, s, H, W, second, second_name):
+    if not 1 <= int(k) <= SSIM_MAX_WINDOW:
+        raise NotImplementedError(f"neuralsim_amd: window_size={k}: the SSIM kernels take windows of 1..{SSIM_MAX_WINDOW}")
+    if int(s) < 1:
+        raise ValueError(f"neuralsim_amd: stride must be >= 1, got {s}")
+    if second.requires_grad:
+        raise NotImplementedError(f"neuralsim_amd: {second_name}.requires_grad: the SSIM kernels differentiate the first image only")
+    Ho, Wo = ssim_out_hw(H, W, int(k), int(s))
+    if H < 1 or W < 1 or Ho < 1 or Wo < 1:
+        raise ValueError(f"neuralsim_amd: no {k}x{k} window fits a {H}x{W} image")
+    return Ho, Wo
+
+
+class _SsimFn(torch.autograd.Function):
+    """index None: x, y [BC,H,W] planar; else x, y [N,3] rows, the first n_rows of them gathered through index [H*W]."""
+
+    @staticmethod
+    def forward(ctx, x, y, index, n_rows, BC, H, W, k, s):
+        Ho, Wo = ssim_out_hw(H, W, k, s)
+        n_win = BC * Ho * Wo * (1 if index is None else 3)
+        out = _lib.zeros([], device=x.device)
+        coef = torch.empty([3, n_win], dtype=torch.float32, device=x.device)
+        _lib.call("nsim_ssim_fwd", _lib.ptr(x), _lib.ptr(y), _lib.ptr(index), n_rows, BC, H, W, k, s, _lib.ptr(out), _lib.ptr(coef))
+        ctx.save_for_backward(x, y, index, coef)
+        ctx.geom = (n_rows, BC, H, W, k, s)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, index, coef = ctx.saved_tensors
+        # indexed: a row is hit once per repeat of the virtual image -- atomic adds into zeros; planar: every element is stored
+        d = torch.empty_like(x) if index is None else _lib.zeros(list(x.shape), device=x.device)
+        _lib.call("nsim_ssim_bwd", _lib.ptr(x), _lib.ptr(y), _lib.ptr(index), *ctx.geom, _lib.ptr(coef),
+                  _lib.ptr(g.float().reshape(1).contiguous()), _lib.ptr(d))
+        return d, None, None, None, None, None, None, None, None
+
+
+def ssim(img1: torch.Tensor, img2: torch.Tensor, window_size: int = 11, stride: int = 1) -> torch.Tensor:
+    """Mean SSIM of two images [B,C,H,W] in [0,1] (``ssim_module(window_size, stride)(img1, img2)`` of nr3d_lib, the pytorch-ssim
+    form; definition: DESIGN.md sec. 7): Gaussian window of sigma 1.5, zero padding (k - 1) // 2, C1 = 0.01^2, C2 = 0.03^2, mean
+    over all B C Ho Wo windows.  0-dim f32; one launch per direction, gradient to ``img1`` only."""
+    _lib.require_device(img1, "img1")
+    _lib.require_device(img2, "img2")
+    if img1.dim() != 4 or img1.shape != img2.shape:
+        raise ValueError(f"neuralsim_amd: ssim takes two [B,C,H,W] images of one shape, got {tuple(img1.shape)} and {tuple(img2.shape)}")
+    B, C, H, W = img1.shape
+    _ssim_check(window_size, stride, H, W, img2, "img2")
+    if B * C == 0:
+        raise ValueError("neuralsim_amd: ssim of an empty batch")
+    x = img1.float().contiguous()
+    out = _SsimFn.apply(x.view(B * C, H, W), img2.detach().float().contiguous().view(B * C, H, W), None, 0, B * C, H, W,
+                        int(window_size), int(stride))
+    return out
+
+
+def s3im_index(n_pixels: int, repeat_time: int, device, generator: torch.Generator = None) -> torch.Tensor:
+    """The index of S3IM's virtual image (app/loss/perceptual.py:151-152), [repeat_time * n_pixels] int64 on ``device``:
+    ``arange(n_pixels)`` followed by ``repeat_time - 1`` independent uniform permutations -- the ranks of i.i.d. float64 uniforms,
+    all repeats in ONE draw and one sort (the reference calls ``randperm`` per repeat; its random stream is not reproduced)."""
+    ident = torch.arange(n_pixels, device=device)
+    if repeat_time <= 1:
+        return ident
+    u = torch.rand([repeat_time - 1, n_pixels], dtype=torch.float64, device=device, generator=generator)
+    return torch.cat([ident, u.argsort(dim=1).reshape(-1)])
+
+
+def s3im_loss(pred: torch.Tensor, gt: torch.Tensor, index: torch.Tensor, patch_hw, kernel_size: int = 4,
+              stride: int = 4) -> torch.Tensor:
+    """``1 - SSIM`` of S3IM's virtual images (``S3IMLoss.forward``, app/loss/perceptual.py:145-159, without its weight): pred, gt
+    [N,3] rays, P = patch_h * patch_w <= N; index [R * P] with values in [0, P) (``s3im_index``); the virtual image [3, patch_h,
+    patch_w * R] holds row ``index[i * Wv + j]`` of ``pred[:P]`` / ``gt[:P]`` at (i, j) -- the flat sequence reshaped row-major.
+    The image is not materialised: the kernels gather through ``index``.  Gradient to ``pred`` only; its rows from P on get
+    exact zeros."""
+    _lib.require_device(pred, "pred")
+    _lib.require_device(gt, "gt")
+    _lib.require_device(index, "index")
+    ph, pw = int(patch_hw[0]), int(patch_hw[1])
+    P = ph * pw
+    if pred.dim() != 2 or pred.shape[1] != 3 or gt.shape != pred.shape:
+        raise ValueError(f"neuralsim_amd: s3im_loss takes pred, gt [N,3], got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    if pred.shape[0] < P:
+        raise ValueError(f"neuralsim_amd: s3im_loss needs N >= patch_h * patch_w = {P} rays, got N = {pred.shape[0]}")
+    if index.dtype != torch.long or index.dim() != 1 or P < 1 or index.shape[0] % P != 0 or index.shape[0] == 0:
+        raise ValueError(f"neuralsim_amd: index must be int64 [R * {P}], got {index.dtype} {tuple(index.shape)}")
+    Wv = index.shape[0] // ph
+    _ssim_check(kernel_size, stride, ph, Wv, gt, "gt")
+    # the kernels are told P rows (an index outside them is a zero pixel); the gradient buffer is [N,3], zero from row P on
+    val = _SsimFn.apply(pred.float().contiguous(), gt.detach().float().contiguous(), index.contiguous(), P, 1, ph, Wv,
+                        int(kernel_size), int(stride))
+    return 1.0 - val
+
+
 class _EmbedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, table, idx):

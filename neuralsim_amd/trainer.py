@@ -20,7 +20,8 @@ from .fields.neus import LoTDNeuSModel, volume_integration, append_extra_points,
 from .graphics.cameras import selected_rays
 from .optim import FusedAdam
 _PREFETCH_HANDOFF = os.environ.get("NSIM_PREFETCH_HANDOFF", "1") == "1"
-from .losses import eikonal_loss, mse_loss, embedding_lookup, mono_depth_loss, mono_normal_loss, sdf_curvature_loss
+from .losses import (eikonal_loss, mse_loss, embedding_lookup, mono_depth_loss, mono_normal_loss, sdf_curvature_loss, s3im_index,
+                     s3im_loss)
 
 
 class RenderTrainer:
@@ -32,7 +33,8 @@ class RenderTrainer:
                  pose_refine: Optional[dict] = None, c2w_true=None, fused_step: Optional[bool] = None,
                  distortion: Optional[torch.Tensor] = None, target_images: Optional[torch.Tensor] = None,
                  mono: Optional[dict] = None, rgb_fn: str = "mse", lidar: Optional[dict] = None, w_curvature: float = 0.0,
-                 curvature_eps: float = 1.0e-4, pixel_sample_mode: str = "uniform", error_map: Optional[dict] = None):
+                 curvature_eps: float = 1.0e-4, pixel_sample_mode: str = "uniform", error_map: Optional[dict] = None,
+                 w_s3im: float = 0.0, s3im: Optional[dict] = None):
         """pose_refine: ``dict(lr=1e-4, start_it=500)`` -- per-frame pose corrections (an axis-angle rotation and a
         translation, ``c2w' = [R Exp(w) | T + dT]``) trained through the rays from ``start_it`` on, standing in for the
         reference's ``LearnableParams`` (withmask_withlidar_joint.240219.yaml:338-352; the parametrisation of the
@@ -64,8 +66,18 @@ class RenderTrainer:
         updated with the batch's per-ray error under ``rgb_fn``; ``last_batch_error`` keeps that update's (fidx, xy, err).  Before
         ``enable_after`` -- and with the default mode -- the batch takes exactly the uniform path.  Every rank keeps maps of its own
         (as every process of the reference's DDP run); the prefetched batch k + 1 is drawn from the map as of step k - 1 (see
-        ``_update_error_map``)."""
+        ``_update_error_map``).
+        w_s3im, s3im: the S3IM loss (Xie et al., ICCV 2023; ``S3IMLoss``, app/loss/perceptual.py:101-159) on the pixel step's
+        ``rgb_volume``; ``s3im`` is the yaml's ``rgb_s3im`` block, ``dict(kernel_size=4, stride=4, repeat_time=10, patch_height=64,
+        patch_width=64, patch_pixels=None)`` (a ``w`` in it is ignored in favour of ``w_s3im``).  The first ``patch_height *
+        patch_width`` rays of the batch form the virtual image (``num_rays`` must cover them); its index -- the identity and
+        ``repeat_time - 1`` permutations -- is drawn from the trainer's generator every step.  The term is
+        ``w_s3im * (1 - SSIM)``, reported as ``loss_parts['rgb_s3im']`` (weighted, as the reference reports it).  With ``w_s3im > 0``
+        the step takes the generic autograd path (the fused launch chain does not carry the term); with 0 nothing is drawn and
+        nothing changes."""
         self.model = model
+        self.num_rays = num_rays             # rays per rank per iteration (weak scaling, as the reference's DDP)
+        self.use_s3im(w_s3im, s3im)
         if pixel_sample_mode not in ("uniform", "error_map"):
             raise ValueError(f"pixel_sample_mode must be 'uniform' or 'error_map', got {pixel_sample_mode!r}")
         self.pixel_sample_mode = "uniform"
@@ -117,7 +129,6 @@ class RenderTrainer:
         if self.pose_refine is not None:
             self.pose_delta = nn.Parameter(torch.zeros([self.V, 6], device=model.device))
             self.pose_optim = torch.optim.Adam([self.pose_delta], lr=float(self.pose_refine.get("lr", 1e-4)))
-        self.num_rays = num_rays             # rays per rank per iteration (weak scaling, as the reference's DDP)
         self.w_eikonal, self.num_uniform = w_eikonal, num_uniform
         self.w_curvature, self.curvature_eps = float(w_curvature), float(curvature_eps)
         self.loss_parts: Dict[str, torch.Tensor] = {}      # the terms of the last autograd-path step (detached device scalars)
@@ -260,7 +271,7 @@ class RenderTrainer:
         plain = type(m) is LoTDNeuSModel or (type(m).__name__ == "PermutoNeuSModel" and getattr(m, "z_dim", 0) == 0)
         return (self.fused_step and plain and not getattr(m, "pos_embed_E", 0) and self.distant_model is None and self.sky_model is None
                 and not self.pose_refine_active() and getattr(m, "_ctrl_mix", 0.0) == 0.0 and self.mono is None
-                and self.rgb_fn == "mse" and self.w_curvature <= 0.0)
+                and self.rgb_fn == "mse" and self.w_curvature <= 0.0 and self.w_s3im <= 0)
 
     def _train_render_fused(self, batch: dict) -> Optional[torch.Tensor]:
         """render + loss + backward of one prefetched batch WITHOUT the autograd engine: the launches the autograd path
@@ -540,6 +551,28 @@ class RenderTrainer:
         return dict(xy=xy, fidx=fidx, gt=gt, rays_o=rays_o, rays_d=rays_d, tested=tested, aux=self._last_aux,
                     fidx_hit=fidx[tested["rays_inds"]], **extras)
 
+    # ------------------------------------------------------------------ S3IM
+    def use_s3im(self, w_s3im: float, s3im: Optional[dict] = None):
+        """Set the weight and the ``rgb_s3im`` block of the S3IM term (what the constructor arguments do); 0 switches it off."""
+        self.w_s3im, self.s3im = float(w_s3im), None
+        if self.w_s3im <= 0:
+            return
+        cfg = dict(s3im or {})
+        cfg.pop("w", None)
+        cfg.pop("device", None)
+        ph, pw = int(cfg.pop("patch_height", 64)), int(cfg.pop("patch_width", 64))
+        pp = cfg.pop("patch_pixels", None)
+        if pp is not None:              # perceptual.py:131-134
+            ph = pw = int(float(pp) ** 0.5)
+            if ph * pw > pp:
+                ph = pw = pw - 1
+        self.s3im = dict(patch_hw=(ph, pw), kernel_size=int(cfg.pop("kernel_size", 4)), stride=int(cfg.pop("stride", 4)),
+                         repeat_time=int(cfg.pop("repeat_time", 10)))
+        if cfg:
+            raise NotImplementedError(f"RenderTrainer: rgb_s3im option(s) {sorted(cfg)} are not covered")
+        if self.num_rays < ph * pw:
+            raise ValueError(f"RenderTrainer: the S3IM patch {ph}x{pw} needs num_rays >= {ph * pw}, got {self.num_rays}")
+
     # ------------------------------------------------------------------ error-map importance sampling
     def use_error_map_sampling(self, error_map: Optional[dict] = None):
         """Switch ``pixel_sample_mode`` to ``error_map`` (what the constructor argument does): a fresh all-ones map of the V frames
@@ -662,6 +695,12 @@ class RenderTrainer:
         total, parts = torch.add(loss_rgb, eik, alpha=self.w_eikonal), dict(loss_rgb=loss_rgb.detach(), loss_eikonal=eik.detach())
         if curv is not None:
             total, parts["loss_curvature"] = torch.add(total, curv, alpha=self.w_curvature), curv.detach()
+        if self.w_s3im > 0:
+            c = self.s3im
+            ph, pw = c["patch_hw"]
+            index = s3im_index(ph * pw, c["repeat_time"], gt.device, generator=self.gen)
+            term = self.w_s3im * s3im_loss(ret["rendered"]["rgb_volume"], gt, index, (ph, pw), c["kernel_size"], c["stride"])
+            total, parts["rgb_s3im"] = total + term, term.detach()
         return total, parts
 
     # ------------------------------------------------------------------ lidar step (street configs)

@@ -110,11 +110,7 @@ __host__ __device__ inline SrcOff src_off(int D, int F1 = 32) {
 
 
 // ------------------------------------------------------------------------------------ weight packing
-// precision 2 ("split"): an f32 value travels through the f16 matrix cores as v = hi + lo / SPLIT_LO_SCALE with
-// hi = f16(v), lo = f16((v - hi) * SPLIT_LO_SCALE) -- 22 significant bits; a product W . x is three MFMAs (hi.hi into the
-// main accumulator, hi.lo + lo.hi into a correction accumulator that is folded in with 1 / SPLIT_LO_SCALE), the
-// dropped lo.lo term is 2^-22 relative.  The scale keeps the residuals out of the f16 subnormals.
-#define SPLIT_LO_SCALE 2048.0f
+// (SPLIT_LO_SCALE and the split form of a value: mfma_mlp.h)
 // (saturating: a feature beyond the f16 range -- a street table holds heights in metres, x SDF_H_SCALE -- becomes +-65504, a
 // point that far from every surface, instead of inf and then NaN through the products)
 __device__ __forceinline__ float f16_sat(float v) { return fminf(fmaxf(v, -65504.0f), 65504.0f); }
@@ -151,104 +147,62 @@ __device__ __forceinline__ float pack_src(int mat, int row, int col, int D, int 
   return 0.f;
 }
 
-struct PackDims {
-  int uo[M_COUNT], ui[M_COUNT];
-  int E, EB;      // embedded-position inputs of the first layer (0: none) and the input index they start at
+static_assert(M_COUNT <= PACK_MAX_MATS, "PackShape holds the field's matrices");
+static inline PackShape field_pack_shape(int nc) {
+  PackShape sh;
+  for (int m = 0; m < M_COUNT; ++m) {
+    sh.uo[m] = mat_uo(m, nc);
+    sh.ui[m] = mat_ui(m, nc);
+  }
+  return sh;
+}
+// threads of a pack launch: the matrices, the vectors, the 16-point fragments (f16)
+static inline int64_t field_pack_elems(const FieldLayout& L, const PackShape& sh) {
+  return pack_elems(sh, M_COUNT, (int64_t)V_COUNT * 64 + (L.total - L.vend) / 2);
+}
+
+// what the pack is made from: the flat masters and the first layer's split into F1 feature inputs and E embedded-position
+// inputs (0: none) that start at input EB
+struct PackSrc {
+  int D, F1, E, EB;
+  const float *sdf_w, *sdf_b, *rad_w, *rad_b;
 };
 
-__device__ __forceinline__ void field_pack_elem(const FieldLayout& L, const PackDims& dims, int D, int F1,
-                                                const float* __restrict__ sdf_w, const float* __restrict__ sdf_b,
-                                                const float* __restrict__ rad_w, const float* __restrict__ rad_b,
+__device__ __forceinline__ void field_pack_elem(const FieldLayout& L, const PackShape& sh, const PackSrc& p,
                                                 char* __restrict__ wpack, int64_t tid) {
-  // matrices: one thread per element
-  int64_t base = 0;
-  for (int m = 0; m < M_COUNT; ++m) {
-    const int Uo = dims.uo[m], Ui = dims.ui[m];
-    const int64_t cnt = (int64_t)Uo * Ui;
-    if (tid >= base && tid < base + cnt) {
-      const int64_t k = tid - base;
-      int row, col;
-      if (L.elt == 2 || L.split) {
-        const int e = (int)(k & 7), lane = (int)((k >> 3) & 63);
-        const int fs = (int)(k >> 9);
-        const int nS = Ui / 16;
-        const int mo = fs / nS, s = fs % nS;
-        row = 32 * mo + (lane & 31);
-        col = 16 * s + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        const float w = pack_src(m, row, col, D, F1, dims.E, dims.EB, sdf_w, rad_w);
-        const f16 whi = (f16)w;
-        ((f16*)(wpack + L.mat[m]))[k] = whi;
-        if (L.split) ((f16*)(wpack + L.mat[m]))[cnt + k] = (f16)((w - (float)whi) * SPLIT_LO_SCALE);
-      } else {
-        const int lane = (int)(k & 63);
-        const int fr = (int)(k >> 6);
-        const int r = fr & 15, fm = fr >> 4;
-        const int nMi = Ui / 32;
-        const int mo = fm / nMi, mi = fm % nMi;
-        row = 32 * mo + (lane & 31);
-        col = unit_of(mi, r, lane >> 5);
-        ((float*)(wpack + L.mat[m]))[k] = pack_src(m, row, col, D, F1, dims.E, dims.EB, sdf_w, rad_w);
-      }
-      return;
-    }
-    base += cnt;
-  }
-  // vectors: per-lane order [hi][m*16 + r]
-  const int64_t vtid = tid - base;
-  if (vtid >= 0 && vtid < (int64_t)V_COUNT * 64) {
-    const int v = (int)(vtid >> 6), k = (int)(vtid & 63);
-    const int hi = k >> 5, m = (k >> 4) & 1, r = k & 15;
-    const int u = unit_of(m, r, hi);
-    const SrcOff o = src_off(D, F1 + dims.E);
+  const auto src = [&](int m, int row, int col) { return pack_src(m, row, col, p.D, p.F1, p.E, p.EB, p.sdf_w, p.rad_w); };
+  if (pack_matrices(sh, M_COUNT, L.mat, pack_form(L.elt, L.split), wpack, tid, src)) return;
+  if (tid < (int64_t)V_COUNT * 64) {
+    const int v = (int)(tid >> 6), k = (int)(tid & 63), u = vec_unit(k, 64);
+    const SrcOff o = src_off(p.D, p.F1 + p.E);
     float val = 0.f;
     switch (v) {
-      case V_B1: val = sdf_b[o.b1 + u]; break;
-      case V_B2: val = D == 2 ? sdf_b[o.b2 + u] : 0.f; break;
-      case V_WH: val = sdf_w[o.wh + u]; break;
-      case V_RB1: val = rad_b[o.rb1 + u]; break;
-      case V_RB2: val = rad_b[o.rb2 + u]; break;
-      case V_RB3: val = (u < 3) ? rad_b[o.rb3 + u] : 0.f; break;
-      case V_SCAL: val = (k == 0) ? sdf_b[o.bh] : 0.f; break;
+      case V_B1: val = p.sdf_b[o.b1 + u]; break;
+      case V_B2: val = p.D == 2 ? p.sdf_b[o.b2 + u] : 0.f; break;
+      case V_WH: val = p.sdf_w[o.wh + u]; break;
+      case V_RB1: val = p.rad_b[o.rb1 + u]; break;
+      case V_RB2: val = p.rad_b[o.rb2 + u]; break;
+      case V_RB3: val = (u < 3) ? p.rad_b[o.rb3 + u] : 0.f; break;
+      case V_SCAL: val = (k == 0) ? p.sdf_b[o.bh] : 0.f; break;
     }
     ((float*)(wpack + L.vec[v]))[k] = val;
     return;
   }
-  // 16-point A fragments of M_W1 .. M_W1T (mfma_mlp.h contract16): element e of lane l of fragment (mo, c) holds
-  // W[16 mo + (l & 15)][32 c + 16 (e >> 2) + 4 (l >> 4) + (e & 3)]
-  int64_t t16 = vtid - (int64_t)V_COUNT * 64;
-  if (!field_has16(L) || t16 < 0) return;
-  for (int m = 0; m < 4; ++m) {
-    const int Uo = dims.uo[m], Ui = dims.ui[m];
-    const int64_t cnt = (int64_t)Uo * Ui;
-    if (t16 < cnt) {
-      const int e = (int)(t16 & 7), lane = (int)((t16 >> 3) & 63), fs = (int)(t16 >> 9);
-      const int nS = Ui / 32, mo = fs / nS, c = fs % nS;
-      const int row = 16 * mo + (lane & 15), col = 32 * c + 16 * (e >> 2) + 4 * (lane >> 4) + (e & 3);
-      ((f16*)(wpack + L.mat16[m]))[t16] = (f16)pack_src(m, row, col, D, F1, dims.E, dims.EB, sdf_w, rad_w);
-      return;
-    }
-    t16 -= cnt;
-  }
+  tid -= (int64_t)V_COUNT * 64;
+  if (field_has16(L)) pack_matrices(sh, 4, L.mat16, PACK_F16_16, wpack, tid, src);      // M_W1 .. M_W1T for contract16
 }
 
-__global__ void __launch_bounds__(256) k_field_pack(FieldLayout L, PackDims dims, int D, int F1, const float* __restrict__ sdf_w,
-                                                     const float* __restrict__ sdf_b, const float* __restrict__ rad_w,
-                                                     const float* __restrict__ rad_b, char* __restrict__ wpack) {
-  field_pack_elem(L, dims, D, F1, sdf_w, sdf_b, rad_w, rad_b, wpack, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+__global__ void __launch_bounds__(256) k_field_pack(FieldLayout L, PackShape sh, PackSrc p, char* __restrict__ wpack) {
+  field_pack_elem(L, sh, p, wpack, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // two packs (field precision + sampling precision) of the same weights: blockIdx.y selects the pack
 struct PackTwo {
   FieldLayout L[2];
-  PackDims dims[2];
   char* out[2];
 };
-__global__ void __launch_bounds__(256) k_field_pack2(PackTwo p, int D, int F1, const float* __restrict__ sdf_w,
-                                                      const float* __restrict__ sdf_b, const float* __restrict__ rad_w,
-                                                      const float* __restrict__ rad_b) {
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (blockIdx.y == 0) field_pack_elem(p.L[0], p.dims[0], D, F1, sdf_w, sdf_b, rad_w, rad_b, p.out[0], tid);
-  else field_pack_elem(p.L[1], p.dims[1], D, F1, sdf_w, sdf_b, rad_w, rad_b, p.out[1], tid);
+__global__ void __launch_bounds__(256) k_field_pack2(PackTwo two, PackShape sh, PackSrc p) {
+  field_pack_elem(two.L[blockIdx.y], sh, p, two.out[blockIdx.y], (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------ activations
@@ -270,42 +224,6 @@ __device__ __forceinline__ float softplus_exact(float z, float beta, float inv_b
 __device__ __forceinline__ float softplus_b(float z, float beta, float inv_beta) { return softplus_exact(z, beta, inv_beta); }
 // sigma(beta z) recovered from a = softplus(z):  1 - exp(-beta a)   (abs. error <= 6e-8)
 __device__ __forceinline__ float sig_from_softplus(float a, float beta) { return 1.0f - nsim_exp2(-a * (beta * NSIM_LOG2E)); }
-
-__device__ __forceinline__ void sh4_eval(const float d[3], float (&o)[16]) {
-  const float x = d[0], y = d[1], z = d[2];
-  const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
-  o[0] = 0.28209479177387814f;
-  o[1] = -0.48860251190291987f * y;
-  o[2] = 0.48860251190291987f * z;
-  o[3] = -0.48860251190291987f * x;
-  o[4] = 1.0925484305920792f * xy;
-  o[5] = -1.0925484305920792f * yz;
-  o[6] = 0.94617469575755997f * z2 - 0.31539156525251999f;
-  o[7] = -1.0925484305920792f * xz;
-  o[8] = 0.54627421529603959f * x2 - 0.54627421529603959f * y2;
-  o[9] = 0.59004358992664352f * y * (-3.0f * x2 + y2);
-  o[10] = 2.8906114426405538f * xy * z;
-  o[11] = 0.45704579946446572f * y * (1.0f - 5.0f * z2);
-  o[12] = 0.3731763325901154f * z * (5.0f * z2 - 3.0f);
-  o[13] = 0.45704579946446572f * x * (1.0f - 5.0f * z2);
-  o[14] = 1.4453057213202769f * z * (x2 - y2);
-  o[15] = 0.59004358992664352f * x * (-x2 + 3.0f * y2);
-}
-
-// out[c] = sum_k g[k] * d sh4_k / d d_c   (pose refinement: gradient w.r.t. the view direction)
-__device__ __forceinline__ void sh4_grad(const float d[3], const float (&g)[16], float (&out)[3]) {
-  const float x = d[0], y = d[1], z = d[2];
-  const float x2 = x * x, y2 = y * y, z2 = z * z;
-  const float a1 = 0.48860251190291987f, b = 1.0925484305920792f, c1 = 0.94617469575755997f;
-  const float e = 0.54627421529603959f, f = 0.59004358992664352f, gg = 2.8906114426405538f;
-  const float h = 0.45704579946446572f, i3 = 0.3731763325901154f, jj = 1.4453057213202769f;
-  out[0] = -a1 * g[3] + b * y * g[4] - b * z * g[7] + 2.0f * e * x * g[8] - 6.0f * f * x * y * g[9] + gg * y * z * g[10] +
-           h * (1.0f - 5.0f * z2) * g[13] + 2.0f * jj * z * x * g[14] + f * (-3.0f * x2 + 3.0f * y2) * g[15];
-  out[1] = -a1 * g[1] + b * x * g[4] - b * z * g[5] - 2.0f * e * y * g[8] + f * (-3.0f * x2 + 3.0f * y2) * g[9] +
-           gg * x * z * g[10] + h * (1.0f - 5.0f * z2) * g[11] - 2.0f * jj * z * y * g[14] + 6.0f * f * x * y * g[15];
-  out[2] = a1 * g[2] - b * y * g[5] + 2.0f * c1 * z * g[6] - b * x * g[7] + gg * x * y * g[10] - 10.0f * h * y * z * g[11] +
-           i3 * (15.0f * z2 - 3.0f) * g[12] - 10.0f * h * x * z * g[13] + jj * (x2 - y2) * g[14];
-}
 
 // Plane arrays hold 16 NC levels.  NC == 2 (17..32 levels): the gather writes the pyramid's own levels only and every
 // plane access of the decoders is guarded (a 19-level street pyramid moves 19 / 32 of the bytes).  NC == 1: the gather
@@ -2747,24 +2665,21 @@ int64_t nsim_field_wpack_bytes(const NsimFieldMeta* meta) {
   return field_layout(meta->precision, field_ni(meta)).total;
 }
 
+// the sources of a model's packs
+static inline PackSrc field_pack_src(const NsimFieldMeta* meta, const float* sdf_w, const float* sdf_b, const float* rad_w,
+                                     const float* rad_b) {
+  return PackSrc{meta->sdf_D, 2 * meta->lotd.num_levels, meta->embed_E, 32 * field_nc(meta->lotd.num_levels), sdf_w, sdf_b,
+                 rad_w, rad_b};
+}
+
 int nsim_field_pack_weights(const NsimFieldMeta* meta, const float* sdf_w, const float* sdf_b, const float* rad_w,
                             const float* rad_b, void* wpack, void* stream) {
   const int rc = field_meta_check(meta);
   if (rc) return rc;
-  const int nc = field_ni(meta);
-  const FieldLayout L = field_layout(meta->precision, nc);
-  PackDims dims;
-  dims.E = meta->embed_E;
-  dims.EB = 32 * field_nc(meta->lotd.num_levels);
-  int64_t total = 0;
-  for (int m = 0; m < M_COUNT; ++m) {
-    dims.uo[m] = mat_uo(m, nc);
-    dims.ui[m] = mat_ui(m, nc);
-    total += (int64_t)dims.uo[m] * dims.ui[m];
-  }
-  total += (int64_t)V_COUNT * 64 + (L.total - L.vend) / 2;      // (+ the 16-point fragments, f16)
-  hipLaunchKernelGGL(k_field_pack, dim3(nsim_blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, L, dims,
-                     meta->sdf_D, 2 * meta->lotd.num_levels, sdf_w, sdf_b, rad_w, rad_b, (char*)wpack);
+  const FieldLayout L = field_layout(meta->precision, field_ni(meta));
+  const PackShape sh = field_pack_shape(field_ni(meta));
+  hipLaunchKernelGGL(k_field_pack, dim3(nsim_blocks(field_pack_elems(L, sh), 256)), dim3(256), 0, (hipStream_t)stream, L, sh,
+                     field_pack_src(meta, sdf_w, sdf_b, rad_w, rad_b), (char*)wpack);
   NSIM_CHECK_LAUNCH();
   return 0;
 }
@@ -2779,27 +2694,15 @@ int nsim_field_pack_weights2(const NsimFieldMeta* meta_a, void* wpack_a, const N
   if (rc) return rc;
   if (meta_a->sdf_D != meta_b->sdf_D || meta_a->lotd.num_levels != meta_b->lotd.num_levels || meta_a->embed_E != meta_b->embed_E) return 2;
   if (!wpack_a || !wpack_b) return 4;
-  const int nc = field_ni(meta_a);
-  PackTwo p;
-  const NsimFieldMeta* ms[2] = {meta_a, meta_b};
-  int64_t most = 0;
-  for (int q = 0; q < 2; ++q) {
-    p.L[q] = field_layout(ms[q]->precision, nc);
-    int64_t total = (int64_t)V_COUNT * 64;
-    p.dims[q].E = meta_a->embed_E;
-    p.dims[q].EB = 32 * field_nc(meta_a->lotd.num_levels);
-    for (int m = 0; m < M_COUNT; ++m) {
-      p.dims[q].uo[m] = mat_uo(m, nc);
-      p.dims[q].ui[m] = mat_ui(m, nc);
-      total += (int64_t)p.dims[q].uo[m] * p.dims[q].ui[m];
-    }
-    total += (p.L[q].total - p.L[q].vend) / 2;      // (+ the 16-point fragments, f16)
-    most = total > most ? total : most;
-  }
-  p.out[0] = (char*)wpack_a;
-  p.out[1] = (char*)wpack_b;
-  hipLaunchKernelGGL(k_field_pack2, dim3(nsim_blocks(most, 256), 2), dim3(256), 0, (hipStream_t)stream, p, meta_a->sdf_D,
-                     2 * meta_a->lotd.num_levels, sdf_w, sdf_b, rad_w, rad_b);
+  const PackShape sh = field_pack_shape(field_ni(meta_a));
+  PackTwo two;
+  two.L[0] = field_layout(meta_a->precision, field_ni(meta_a));
+  two.L[1] = field_layout(meta_b->precision, field_ni(meta_a));
+  two.out[0] = (char*)wpack_a;
+  two.out[1] = (char*)wpack_b;
+  const int64_t n0 = field_pack_elems(two.L[0], sh), n1 = field_pack_elems(two.L[1], sh);
+  hipLaunchKernelGGL(k_field_pack2, dim3(nsim_blocks(n0 > n1 ? n0 : n1, 256), 2), dim3(256), 0, (hipStream_t)stream, two, sh,
+                     field_pack_src(meta_a, sdf_w, sdf_b, rad_w, rad_b));
   NSIM_CHECK_LAUNCH();
   return 0;
 }

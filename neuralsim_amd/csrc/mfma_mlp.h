@@ -1,14 +1,20 @@
-// mfma_mlp.h -- building blocks of the fused tiny-MLP kernels (field.hip: NeuS SDF + radiance; nerf_field.hip: the
-// NeRF++ distant model) on the gfx950 matrix cores.
+// mfma_mlp.h -- building blocks of the fused tiny-MLP kernels on the gfx950 matrix cores: the NeuS SDF + radiance field
+// (field.hip), the NeRF++ distant model and the close-range NGP model (nerf_field.hip), the sky MLP (sky.hip).
 //
 // Activation-register convention (one wave = 32 points): lane (j = l&31, hi = l>>5) owns point j and the units
 // U(m,r,hi) = 32m + (r&3) + 8(r>>2) + 4hi of every M-tile m -- the C/D fragment of v_mfma_f32_32x32x*.  Layers are
 // computed transposed (Out^T = W . In^T, weights = A operand), so a lane's accumulator registers are its B fragment for
 // the next layer.  Weight gradients contract over points and go through an LDS transpose ([unit][point]).
+//
+// Weight-pack format: every decoder hands its matrices to contract / contract16 as pre-packed A fragments and its biases
+// as per-lane vectors.  That format is stated HERE and nowhere else: the readers are contract / contract16, the writers
+// the frag*_ coordinate functions right below each of them (their inverses), vec_unit, and pack_matrices, the one walk
+// over a pack's matrices.  A decoder's pack kernel supplies its list of matrices (PackShape), where they go (its
+// *Layout) and where an element comes from (its source function); tests/golden/wpack_sha256.json pins the bytes.
 #pragma once
 #include "nsim_common.h"
 
-__device__ __forceinline__ int unit_of(int m, int r, int hi) { return 32 * m + (r & 3) + 8 * (r >> 2) + 4 * hi; }
+__host__ __device__ __forceinline__ int unit_of(int m, int r, int hi) { return 32 * m + (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 // ------------------------------------------------------------------------------------- MFMA helpers
 // (wave_sync_lds: nsim_prims.h)
@@ -72,6 +78,30 @@ __device__ __forceinline__ void contract(f32x16 (&acc)[MO], const char* wmat, co
       }
     }
   }
+}
+
+// The inverses of the A-fragment indexing of contract just above: element k of a packed [Uo x Ui] matrix -> (row, col).
+// f16 (also each half of the split form): k = ((mo * (Ui / 16) + s) * 64 + lane) * 8 + e
+struct FragRC {
+  int row, col;
+};
+__host__ __device__ inline FragRC frag32_f16(int64_t k, int Ui) {
+  const int e = (int)(k & 7), lane = (int)((k >> 3) & 63), fs = (int)(k >> 9), nS = Ui / 16;
+  return FragRC{32 * (fs / nS) + (lane & 31), 16 * (fs % nS) + mfma_row(e, lane >> 5)};
+}
+// f32: k = ((mo * (Ui / 32) + mi) * 16 + r) * 64 + lane.  This one and vec_unit go through unit_of, with an M-tile that is
+// not bounded at compile time, on purpose: the device link step derives value ranges for unit_of's arguments from ALL its
+// callers in a source file, and without such a caller the sin / cos kernels of sky.hip and field.hip (k_sky_fwd, k_field,
+// k_field_bwd_j) compile differently.  The pack tests cannot catch that -- the packed bytes stay the same; only a
+// comparison of those kernels' assembly shows it.
+__host__ __device__ inline FragRC frag32_f32(int64_t k, int Ui) {
+  const int lane = (int)(k & 63), fr = (int)(k >> 6), fm = fr >> 4, nMi = Ui / 32;
+  return FragRC{32 * (fm / nMi) + (lane & 31), unit_of(fm % nMi, fr & 15, lane >> 5)};
+}
+// slot k of an n-long per-lane vector (order [hi][m * 16 + r]: lane-half hi reads its n / 2 floats contiguously) -> unit
+__host__ __device__ inline int vec_unit(int k, int n) {
+  const int hi = k / (n / 2), q = k % (n / 2);
+  return unit_of(q >> 4, q & 15, hi);
 }
 
 // out[m*16+r] = (W . In^T)[unit(m,r,hi)][pt]
@@ -394,7 +424,7 @@ __device__ __forceinline__ bool halfwave_run_sum2(int64_t key, bool valid, float
 // Activation-register convention (one wave = 16 points): lane l (p = l & 15, g = l >> 4) owns point p and the units
 // 16m + 4g + r (register 4m + r) of a layer -- the C/D fragment of v_mfma_f32_16x16x32.  The B operand of K-step c is
 // registers 8c .. 8c + 7 as they stand: K index 8g + e <-> unit 16(2c + (e >> 2)) + 4g + (e & 3), and the weight pack (the A
-// operand, field.hip pack16_col) uses the same permutation, so layers chain in registers as in the 32-point convention.  Half
+// operand, frag16_f16 below) uses the same permutation, so layers chain in registers as in the 32-point convention.  Half
 // the activation registers per lane: the with-grad backward fits 256 registers and runs two waves per SIMD.
 // Weight gradients: the waves of a workgroup stage their activations side by side as [point][unit] rows (one 8-byte store
 // per m-tile and lane) and read them back column-wise with ds_read_b64_tr_b16 (J16_ROW below).
@@ -472,6 +502,12 @@ __device__ __forceinline__ void contract16(f32x4 (&acc)[MO], const char* wmat, c
   }
 }
 
+// The inverse of the A-fragment indexing of contract16 just above: k = ((mo * (Ui / 32) + c) * 64 + lane) * 8 + e
+__host__ __device__ inline FragRC frag16_f16(int64_t k, int Ui) {
+  const int e = (int)(k & 7), lane = (int)((k >> 3) & 63), fs = (int)(k >> 9), nS = Ui / 32;
+  return FragRC{16 * (fs / nS) + (lane & 15), 32 * (fs % nS) + 16 * (e >> 2) + 4 * (lane >> 4) + (e & 3)};
+}
+
 // out[4 mo + r] = (W16 . In^T)[16 mo + 4g + r][pt]   (fp16, dynamic: power-of-two re-scaling of In, as dense)
 template <int MO, int NT>
 __device__ __forceinline__ void dense16(float (&out)[MO * 4], const char* wmat, const float (&in)[NT * 4], bool dynamic) {
@@ -485,6 +521,101 @@ __device__ __forceinline__ void dense16(float (&out)[MO * 4], const char* wmat, 
   for (int mo = 0; mo < MO; ++mo)
 #pragma unroll
     for (int r = 0; r < 4; ++r) out[mo * 4 + r] = acc[mo][r] * inv;
+}
+
+// ------------------------------------------------------------------------------------- writing a weight pack
+// precision 2 ("split"): an f32 value travels through the f16 matrix cores as v = hi + lo / SPLIT_LO_SCALE with
+// hi = f16(v), lo = f16((v - hi) * SPLIT_LO_SCALE) -- 22 significant bits; a product W . x is three MFMAs (hi.hi into the
+// main accumulator, hi.lo + lo.hi into a correction accumulator that is folded in with 1 / SPLIT_LO_SCALE), the
+// dropped lo.lo term is 2^-22 relative.  The scale keeps the residuals out of the f16 subnormals.
+#define SPLIT_LO_SCALE 2048.0f
+
+// fragment form of a packed matrix: 32-point f16 | 32-point f32 | split (the f16 form twice: hi, then lo at + Uo Ui) |
+// 16-point f16
+enum { PACK_F16 = 0, PACK_F32, PACK_SPLIT, PACK_F16_16 };
+__host__ __device__ inline int pack_form(int elt, int split = 0) { return split ? PACK_SPLIT : (elt == 2 ? PACK_F16 : PACK_F32); }
+
+// the matrices of a pack, in the order of its layout
+#define PACK_MAX_MATS 10       // (every decoder asserts its matrix count against it)
+struct PackShape {
+  int uo[PACK_MAX_MATS], ui[PACK_MAX_MATS];
+};
+static inline PackShape pack_shape(int n, const int* uo, const int* ui) {
+  PackShape sh;
+  for (int m = 0; m < n; ++m) {
+    sh.uo[m] = uo[m];
+    sh.ui[m] = ui[m];
+  }
+  return sh;
+}
+// threads of a pack launch: one per element of the first n matrices + ``extra`` (vector slots, further fragment sets)
+static inline int64_t pack_elems(const PackShape& sh, int n, int64_t extra) {
+  for (int m = 0; m < n; ++m) extra += (int64_t)sh.uo[m] * sh.ui[m];
+  return extra;
+}
+
+// One thread per matrix element: thread ``tid`` finds the matrix m < n and the element k of it that are its own, and
+// stores src(m, row, col) at byte offset off[m] of ``wpack``, element k, in fragment form ``form``.  Returns false for a
+// thread past the matrices, with their element count taken off ``tid``.
+template <class Src>
+__device__ __forceinline__ bool pack_matrices(const PackShape& sh, int n, const int64_t* off, int form, char* wpack,
+                                              int64_t& tid, Src src) {
+  for (int m = 0; m < n; ++m) {
+    const int Ui = sh.ui[m];
+    const int64_t cnt = (int64_t)sh.uo[m] * Ui;
+    if (tid < cnt) {
+      const int64_t k = tid;
+      const FragRC rc = form == PACK_F32 ? frag32_f32(k, Ui) : (form == PACK_F16_16 ? frag16_f16(k, Ui) : frag32_f16(k, Ui));
+      const float w = src(m, rc.row, rc.col);
+      if (form == PACK_F32) {
+        ((float*)(wpack + off[m]))[k] = w;
+      } else {
+        const f16 whi = (f16)w;
+        ((f16*)(wpack + off[m]))[k] = whi;
+        if (form == PACK_SPLIT) ((f16*)(wpack + off[m]))[cnt + k] = (f16)((w - (float)whi) * SPLIT_LO_SCALE);
+      }
+      return true;
+    }
+    tid -= cnt;
+  }
+  return false;
+}
+
+// ------------------------------------------------------------------------------------- SH-4 of a view direction
+__device__ __forceinline__ void sh4_eval(const float d[3], float (&o)[16]) {
+  const float x = d[0], y = d[1], z = d[2];
+  const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
+  o[0] = 0.28209479177387814f;
+  o[1] = -0.48860251190291987f * y;
+  o[2] = 0.48860251190291987f * z;
+  o[3] = -0.48860251190291987f * x;
+  o[4] = 1.0925484305920792f * xy;
+  o[5] = -1.0925484305920792f * yz;
+  o[6] = 0.94617469575755997f * z2 - 0.31539156525251999f;
+  o[7] = -1.0925484305920792f * xz;
+  o[8] = 0.54627421529603959f * x2 - 0.54627421529603959f * y2;
+  o[9] = 0.59004358992664352f * y * (-3.0f * x2 + y2);
+  o[10] = 2.8906114426405538f * xy * z;
+  o[11] = 0.45704579946446572f * y * (1.0f - 5.0f * z2);
+  o[12] = 0.3731763325901154f * z * (5.0f * z2 - 3.0f);
+  o[13] = 0.45704579946446572f * x * (1.0f - 5.0f * z2);
+  o[14] = 1.4453057213202769f * z * (x2 - y2);
+  o[15] = 0.59004358992664352f * x * (-x2 + 3.0f * y2);
+}
+
+// out[c] = sum_k g[k] * d sh4_k / d d_c   (pose refinement: gradient w.r.t. the view direction)
+__device__ __forceinline__ void sh4_grad(const float d[3], const float (&g)[16], float (&out)[3]) {
+  const float x = d[0], y = d[1], z = d[2];
+  const float x2 = x * x, y2 = y * y, z2 = z * z;
+  const float a1 = 0.48860251190291987f, b = 1.0925484305920792f, c1 = 0.94617469575755997f;
+  const float e = 0.54627421529603959f, f = 0.59004358992664352f, gg = 2.8906114426405538f;
+  const float h = 0.45704579946446572f, i3 = 0.3731763325901154f, jj = 1.4453057213202769f;
+  out[0] = -a1 * g[3] + b * y * g[4] - b * z * g[7] + 2.0f * e * x * g[8] - 6.0f * f * x * y * g[9] + gg * y * z * g[10] +
+           h * (1.0f - 5.0f * z2) * g[13] + 2.0f * jj * z * x * g[14] + f * (-3.0f * x2 + 3.0f * y2) * g[15];
+  out[1] = -a1 * g[1] + b * x * g[4] - b * z * g[5] - 2.0f * e * y * g[8] + f * (-3.0f * x2 + 3.0f * y2) * g[9] +
+           gg * x * z * g[10] + h * (1.0f - 5.0f * z2) * g[11] - 2.0f * jj * z * y * g[14] + 6.0f * f * x * y * g[15];
+  out[2] = a1 * g[2] - b * y * g[5] + 2.0f * c1 * z * g[6] - b * x * g[7] + gg * x * y * g[10] - 10.0f * h * y * z * g[11] +
+           i3 * (15.0f * z2 - 3.0f) * g[12] - 10.0f * h * x * z * g[13] + jj * (x2 - y2) * g[14];
 }
 
 // ---- LDS staging [point][unit] bf16 for the workgroup-joint weight gradients: J16_PTS rows of 128 bytes (<= 64 units).

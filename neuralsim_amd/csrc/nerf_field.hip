@@ -182,6 +182,7 @@ __global__ void __launch_bounds__(256) k_density_alpha_bwd(const float* __restri
 // ----------------------------------------------------------------------------------------- weight pack
 enum { N_D1 = 0, N_D1T, N_Q1, N_Q2, N_Q3, N_Q3T, N_Q2T, N_Q1T, N_MCOUNT };
 enum { NV_DB1 = 0, NV_DWH, NV_RB1, NV_RB2, NV_RB3, NV_SCAL, NV_COUNT };
+static_assert(N_MCOUNT <= PACK_MAX_MATS, "PackShape holds the distant model's matrices");
 static const int kNUo[N_MCOUNT] = {64, 32, 64, 64, 32, 64, 64, 64};
 static const int kNUi[N_MCOUNT] = {32, 64, 64, 64, 64, 32, 64, 64};
 
@@ -229,38 +230,14 @@ __device__ __forceinline__ float nerf_src(int mat, int row, int col, int F, cons
   return 0.f;
 }
 
-struct NerfDims {
-  int uo[N_MCOUNT], ui[N_MCOUNT];
-};
-
-__global__ void __launch_bounds__(256) k_nerf_pack(NerfLayout L, NerfDims dims, int F, const float* __restrict__ den_w,
+__global__ void __launch_bounds__(256) k_nerf_pack(NerfLayout L, PackShape sh, int F, const float* __restrict__ den_w,
                                                     const float* __restrict__ den_b, const float* __restrict__ rad_w,
                                                     const float* __restrict__ rad_b, char* __restrict__ wpack) {
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t base = 0;
-  for (int m = 0; m < N_MCOUNT; ++m) {
-    const int Uo = dims.uo[m], Ui = dims.ui[m];
-    const int64_t cnt = (int64_t)Uo * Ui;
-    if (tid >= base && tid < base + cnt) {
-      const int64_t k = tid - base;
-      if (L.elt == 2) {
-        const int e = (int)(k & 7), lane = (int)((k >> 3) & 63), fs = (int)(k >> 9);
-        const int nS = Ui / 16, mo = fs / nS, s = fs % nS;
-        const int row = 32 * mo + (lane & 31), col = 16 * s + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        ((f16*)(wpack + L.mat[m]))[k] = (f16)nerf_src(m, row, col, F, den_w, rad_w);
-      } else {
-        const int lane = (int)(k & 63), fr = (int)(k >> 6), r = fr & 15, fm = fr >> 4;
-        const int nMi = Ui / 32, mo = fm / nMi, mi = fm % nMi;
-        ((float*)(wpack + L.mat[m]))[k] = nerf_src(m, 32 * mo + (lane & 31), unit_of(mi, r, lane >> 5), F, den_w, rad_w);
-      }
-      return;
-    }
-    base += cnt;
-  }
-  const int64_t vtid = tid - base;
-  if (vtid >= 0 && vtid < (int64_t)NV_COUNT * 64) {
-    const int v = (int)(vtid >> 6), k = (int)(vtid & 63);
-    const int hi = k >> 5, m = (k >> 4) & 1, r = k & 15, u = unit_of(m, r, hi);
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const auto src = [&](int m, int row, int col) { return nerf_src(m, row, col, F, den_w, rad_w); };
+  if (pack_matrices(sh, N_MCOUNT, L.mat, pack_form(L.elt), wpack, tid, src)) return;
+  if (tid < (int64_t)NV_COUNT * 64) {
+    const int v = (int)(tid >> 6), k = (int)(tid & 63), u = vec_unit(k, 64);
     float val = 0.f;
     switch (v) {
       case NV_DB1: val = den_b[u]; break;
@@ -327,26 +304,7 @@ __device__ __forceinline__ float nvec(const char* WV, const NerfLayout& L, int v
 // radiance input, second M-tile (slots 32..63): SH-4 of the view direction, appearance code, zero padding
 __device__ __forceinline__ void nerf_rin_tail(float (&rin)[32], const float vd[3], const float ha[4], int hi) {
   float sh[16];
-  {
-    const float x = vd[0], y = vd[1], z = vd[2];
-    const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
-    sh[0] = 0.28209479177387814f;
-    sh[1] = -0.48860251190291987f * y;
-    sh[2] = 0.48860251190291987f * z;
-    sh[3] = -0.48860251190291987f * x;
-    sh[4] = 1.0925484305920792f * xy;
-    sh[5] = -1.0925484305920792f * yz;
-    sh[6] = 0.94617469575755997f * z2 - 0.31539156525251999f;
-    sh[7] = -1.0925484305920792f * xz;
-    sh[8] = 0.54627421529603959f * x2 - 0.54627421529603959f * y2;
-    sh[9] = 0.59004358992664352f * y * (-3.0f * x2 + y2);
-    sh[10] = 2.8906114426405538f * xy * z;
-    sh[11] = 0.45704579946446572f * y * (1.0f - 5.0f * z2);
-    sh[12] = 0.3731763325901154f * z * (5.0f * z2 - 3.0f);
-    sh[13] = 0.45704579946446572f * x * (1.0f - 5.0f * z2);
-    sh[14] = 1.4453057213202769f * z * (x2 - y2);
-    sh[15] = 0.59004358992664352f * x * (-x2 + 3.0f * y2);
-  }
+  sh4_eval(vd, sh);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int slot = unit_of(0, r, hi);  // position inside the second M-tile
@@ -862,6 +820,7 @@ __global__ void __launch_bounds__(256) k_lotd4_scatter(Scatter4Args a) {
 
 enum { G_D1 = 0, G_D2, G_Q1, G_Q2, G_Q3, G_D1T, G_D2T, G_Q3T, G_Q2T, G_Q1T, G_MCOUNT };
 enum { GV_DB1 = 0, GV_DX0, GV_DX1, GV_DX2, GV_DB2, GV_RB1, GV_RB2, GV_RB3, GV_COUNT };
+static_assert(G_MCOUNT <= PACK_MAX_MATS, "PackShape holds the NGP model's matrices");
 static const int kGUo[G_MCOUNT] = {64, 32, 64, 64, 32, 32, 64, 64, 64, 64};
 static const int kGUi[G_MCOUNT] = {32, 64, 64, 64, 64, 64, 32, 32, 64, 64};
 
@@ -917,38 +876,14 @@ __device__ __forceinline__ float ngp_src(int mat, int row, int col, int F, int N
   return 0.f;
 }
 
-struct NgpDims {
-  int uo[G_MCOUNT], ui[G_MCOUNT];
-};
-
-__global__ void __launch_bounds__(256) k_ngp_pack(NgpLayout L, NgpDims dims, int F, int NA, const float* __restrict__ den_w,
+__global__ void __launch_bounds__(256) k_ngp_pack(NgpLayout L, PackShape sh, int F, int NA, const float* __restrict__ den_w,
                                                    const float* __restrict__ den_b, const float* __restrict__ rad_w,
                                                    const float* __restrict__ rad_b, char* __restrict__ wpack) {
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t base = 0;
-  for (int m = 0; m < G_MCOUNT; ++m) {
-    const int Uo = dims.uo[m], Ui = dims.ui[m];
-    const int64_t cnt = (int64_t)Uo * Ui;
-    if (tid >= base && tid < base + cnt) {
-      const int64_t k = tid - base;
-      if (L.elt == 2) {
-        const int e = (int)(k & 7), lane = (int)((k >> 3) & 63), fs = (int)(k >> 9);
-        const int nS = Ui / 16, mo = fs / nS, s = fs % nS;
-        const int row = 32 * mo + (lane & 31), col = 16 * s + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        ((f16*)(wpack + L.mat[m]))[k] = (f16)ngp_src(m, row, col, F, NA, den_w, rad_w);
-      } else {
-        const int lane = (int)(k & 63), fr = (int)(k >> 6), r = fr & 15, fm = fr >> 4;
-        const int nMi = Ui / 32, mo = fm / nMi, mi = fm % nMi;
-        ((float*)(wpack + L.mat[m]))[k] = ngp_src(m, 32 * mo + (lane & 31), unit_of(mi, r, lane >> 5), F, NA, den_w, rad_w);
-      }
-      return;
-    }
-    base += cnt;
-  }
-  const int64_t vtid = tid - base;
-  if (vtid >= 0 && vtid < (int64_t)GV_COUNT * 64) {
-    const int v = (int)(vtid >> 6), k = (int)(vtid & 63);
-    const int hi = k >> 5, m = (k >> 4) & 1, r = k & 15, u = unit_of(m, r, hi);
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const auto src = [&](int m, int row, int col) { return ngp_src(m, row, col, F, NA, den_w, rad_w); };
+  if (pack_matrices(sh, G_MCOUNT, L.mat, pack_form(L.elt), wpack, tid, src)) return;
+  if (tid < (int64_t)GV_COUNT * 64) {
+    const int v = (int)(tid >> 6), k = (int)(tid & 63), u = vec_unit(k, 64);
     const int FI = F + 3;
     float val = 0.f;
     switch (v) {
@@ -1401,15 +1336,9 @@ int nsim_distant_pack_weights(const NsimDistantMeta* meta, const float* den_w, c
   const int rc = nerf_meta_check(meta);
   if (rc) return rc;
   const NerfLayout L = nerf_layout(meta->precision);
-  NerfDims dims;
-  int64_t total = 0;
-  for (int m = 0; m < N_MCOUNT; ++m) {
-    dims.uo[m] = kNUo[m];
-    dims.ui[m] = kNUi[m];
-    total += (int64_t)kNUo[m] * kNUi[m];
-  }
-  total += (int64_t)NV_COUNT * 64;
-  hipLaunchKernelGGL(k_nerf_pack, dim3(nsim_blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, L, dims,
+  const PackShape sh = pack_shape(N_MCOUNT, kNUo, kNUi);
+  const int64_t total = pack_elems(sh, N_MCOUNT, (int64_t)NV_COUNT * 64);
+  hipLaunchKernelGGL(k_nerf_pack, dim3(nsim_blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, L, sh,
                      2 * meta->lotd.num_levels, den_w, den_b, rad_w, rad_b, (char*)wpack);
   NSIM_CHECK_LAUNCH();
   return 0;
@@ -1585,15 +1514,9 @@ int nsim_ngp_pack_weights(const NsimNgpMeta* meta, const float* den_w, const flo
   if (rc) return rc;
   if (!den_w || !den_b || !rad_w || !rad_b || !wpack) return 4;
   const NgpLayout L = ngp_layout(meta->precision);
-  NgpDims dims;
-  int64_t total = 0;
-  for (int m = 0; m < G_MCOUNT; ++m) {
-    dims.uo[m] = kGUo[m];
-    dims.ui[m] = kGUi[m];
-    total += (int64_t)kGUo[m] * kGUi[m];
-  }
-  total += (int64_t)GV_COUNT * 64;
-  hipLaunchKernelGGL(k_ngp_pack, dim3(nsim_blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, L, dims,
+  const PackShape sh = pack_shape(G_MCOUNT, kGUo, kGUi);
+  const int64_t total = pack_elems(sh, G_MCOUNT, (int64_t)GV_COUNT * 64);
+  hipLaunchKernelGGL(k_ngp_pack, dim3(nsim_blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, L, sh,
                      2 * meta->lotd.num_levels, meta->n_appear, den_w, den_b, rad_w, rad_b, (char*)wpack);
   NSIM_CHECK_LAUNCH();
   return 0;

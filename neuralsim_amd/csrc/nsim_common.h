@@ -93,7 +93,7 @@ __device__ __forceinline__ T wave_max(T v) {
 }
 
 // row of accumulator register r for lane-half hi within a 32-row MFMA tile
-__device__ __forceinline__ constexpr int mfma_row(int r, int hi) {
+__host__ __device__ __forceinline__ constexpr int mfma_row(int r, int hi) {
   return (r & 3) + 8 * (r >> 2) + 4 * hi;
 }
 

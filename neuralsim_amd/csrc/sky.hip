@@ -26,6 +26,7 @@
 
 enum { SM_W1 = 0, SM_W2, SM_W3, SM_W3T, SM_W2T, SM_W1T, SM_COUNT };
 enum { SV_B1 = 0, SV_B2, SV_B3, SV_COUNT };
+static_assert(SM_COUNT <= PACK_MAX_MATS, "PackShape holds the sky's matrices");
 
 struct SkyLayout {
   int elt;                   // 2: f16 A fragments, 4: f32
@@ -45,6 +46,9 @@ static inline void sky_dims(int m, int& uo, int& ui) {
   }
 }
 
+// floats of per-lane vector v: the 256-wide biases, and the 32-unit tile that holds the three outputs
+__host__ __device__ inline int sky_vlen(int v) { return v == SV_B3 ? 32 : SKY_W; }
+
 static inline SkyLayout sky_layout(int precision) {
   SkyLayout L;
   L.elt = precision == 0 ? 2 : 4;
@@ -56,19 +60,14 @@ static inline SkyLayout sky_layout(int precision) {
     off += (int64_t)uo * ui * L.elt;
     off = (off + 255) & ~(int64_t)255;
   }
-  const int vlen[SV_COUNT] = {2 * SKY_MW * 16, 2 * SKY_MW * 16, 2 * 16};
   for (int v = 0; v < SV_COUNT; ++v) {
     L.vec[v] = off;
-    off += (int64_t)vlen[v] * 4;
+    off += (int64_t)sky_vlen(v) * 4;
     off = (off + 255) & ~(int64_t)255;
   }
   L.total = off;
   return L;
 }
-
-struct SkyDims {
-  int uo[SM_COUNT], ui[SM_COUNT];
-};
 
 // flat weights in the reference's layer order: w = [W1 (256 x IN), W2 (256 x 256), W3 (3 x 256)], b = [256, 256, 3]
 __device__ __forceinline__ float sky_src(int mat, int row, int col, int IN, const float* w) {
@@ -83,51 +82,19 @@ __device__ __forceinline__ float sky_src(int mat, int row, int col, int IN, cons
   }
 }
 
-__global__ void __launch_bounds__(256) k_sky_pack(SkyLayout L, SkyDims dims, int IN, const float* __restrict__ w,
+__global__ void __launch_bounds__(256) k_sky_pack(SkyLayout L, PackShape sh, int IN, const float* __restrict__ w,
                                                    const float* __restrict__ b, char* __restrict__ wpack) {
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t base = 0;
-  for (int m = 0; m < SM_COUNT; ++m) {
-    const int Uo = dims.uo[m], Ui = dims.ui[m];
-    const int64_t cnt = (int64_t)Uo * Ui;
-    if (tid >= base && tid < base + cnt) {
-      const int64_t k = tid - base;
-      int row, col;
-      if (L.elt == 2) {   // f16x8 per lane per K-step: [(mo * nS + s) * 64 + lane][e]
-        const int e = (int)(k & 7), lane = (int)((k >> 3) & 63);
-        const int fs = (int)(k >> 9);
-        const int nS = Ui / 16;
-        const int mo = fs / nS, s = fs % nS;
-        row = 32 * mo + (lane & 31);
-        col = 16 * s + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        ((f16*)(wpack + L.mat[m]))[k] = (f16)sky_src(m, row, col, IN, w);
-      } else {            // one float per lane per (mi, r): [((mo * nMi + mi) * 16 + r) * 64 + lane]
-        const int lane = (int)(k & 63);
-        const int fr = (int)(k >> 6);
-        const int r = fr & 15, fm = fr >> 4;
-        const int nMi = Ui / 32;
-        const int mo = fm / nMi, mi = fm % nMi;
-        row = 32 * mo + (lane & 31);
-        col = unit_of(mi, r, lane >> 5);
-        ((float*)(wpack + L.mat[m]))[k] = sky_src(m, row, col, IN, w);
-      }
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const auto src = [&](int m, int row, int col) { return sky_src(m, row, col, IN, w); };
+  if (pack_matrices(sh, SM_COUNT, L.mat, pack_form(L.elt), wpack, tid, src)) return;
+  for (int v = 0; v < SV_COUNT; ++v) {
+    const int n = sky_vlen(v);
+    if (tid < n) {
+      const int u = vec_unit((int)tid, n);
+      ((float*)(wpack + L.vec[v]))[tid] = u < (v == SV_B3 ? 3 : SKY_W) ? b[v * SKY_W + u] : 0.f;
       return;
     }
-    base += cnt;
-  }
-  // biases in per-lane order [hi][m * 16 + r]
-  int64_t vt = tid - base;
-  if (vt >= 0 && vt < 2 * 2 * SKY_MW * 16) {
-    const int v = (int)(vt / (2 * SKY_MW * 16)), k = (int)(vt % (2 * SKY_MW * 16));
-    const int hi = k / (SKY_MW * 16), q = k % (SKY_MW * 16);
-    ((float*)(wpack + L.vec[v]))[k] = b[v * SKY_W + unit_of(q >> 4, q & 15, hi)];
-    return;
-  }
-  vt -= 2 * 2 * SKY_MW * 16;
-  if (vt >= 0 && vt < 32) {
-    const int hi = (int)(vt >> 4), r = (int)(vt & 15);
-    const int u = unit_of(0, r, hi);
-    ((float*)(wpack + L.vec[SV_B3]))[vt] = u < 3 ? b[2 * SKY_W + u] : 0.f;
+    tid -= n;
   }
 }
 
@@ -377,14 +344,10 @@ int nsim_sky_pack_weights(const NsimSkyMeta* meta, const float* w, const float* 
   if (int rc = sky_check(meta)) return rc;
   if (!w || !b || !wpack) return 4;
   const SkyLayout L = sky_layout(meta->precision);
-  SkyDims dims;
-  int64_t cnt = 0;
-  for (int m = 0; m < SM_COUNT; ++m) {
-    sky_dims(m, dims.uo[m], dims.ui[m]);
-    cnt += (int64_t)dims.uo[m] * dims.ui[m];
-  }
-  cnt += 2 * 2 * SKY_MW * 16 + 32;
-  hipLaunchKernelGGL(k_sky_pack, dim3(nsim_blocks(cnt, 256)), dim3(256), 0, (hipStream_t)stream, L, dims,
+  PackShape sh;
+  for (int m = 0; m < SM_COUNT; ++m) sky_dims(m, sh.uo[m], sh.ui[m]);
+  const int64_t cnt = pack_elems(sh, SM_COUNT, sky_vlen(SV_B1) + sky_vlen(SV_B2) + sky_vlen(SV_B3));
+  hipLaunchKernelGGL(k_sky_pack, dim3(nsim_blocks(cnt, 256)), dim3(256), 0, (hipStream_t)stream, L, sh,
                      3 + 6 * meta->n_frequencies + meta->n_appear, w, b, (char*)wpack);
   NSIM_CHECK_LAUNCH();
   return 0;

@@ -4,7 +4,7 @@ import pytest
 import torch
 
 from oracle import distant as od, render as orr
-from util import leaf, look_at_cameras, rel_l2
+from util import leaf, look_at_cameras, rel_l2, wpack_digest, wpack_golden
 
 AABB = torch.tensor([[-1.0, -1, -1], [1.0, 1, 1]])
 
@@ -236,3 +236,29 @@ def test_backward_skips_shells_behind_an_opaque_stretch(backend):
         assert rel_l2(a.cpu(), b.cpu()) < 2e-3
     assert float((grads[1e-4][0] != 0).float().mean()) <= float((grads[0.0][0] != 0).float().mean())
     assert float(mask.max()) > 0.99
+
+
+# target_num_params of the pyramid: 2^14 stops below 16 levels (zero-padded first-layer columns), 2^30 fills all 16
+WPACK_CASES = [f"p{prec}-{pyr}" for prec in (0, 1) for pyr in ("short", "L16")]
+
+
+def wpack_case(case, device):
+    """[byte length, sha256] of the distant model's pack of ``case`` (also called by tests/golden/make_wpack_fixture.py)."""
+    import ctypes
+    from neuralsim_amd import _lib
+    from neuralsim_amd.fields.nerf_distant import LoTDNeRFDistantModel
+    prec, pyr = case.split("-")
+    m = LoTDNeRFDistantModel(aabb=AABB, precision="f32", max_steps=16,
+                             lotd_auto_compute_cfg=dict(target_num_params=2 ** (30 if pyr == "L16" else 14), min_res_xyz=3,
+                                                        min_res_w=2, log2_hashmap_size=10, per_level_scale=1.382))
+    assert (m.cfg.num_levels == 16) == (pyr == "L16")
+    dm = _lib.DistantMeta()
+    ctypes.memmove(ctypes.byref(dm), ctypes.byref(m.meta), ctypes.sizeof(dm))
+    dm.precision = int(prec[1:])
+    return wpack_digest("distant", dm, (m.den_w, m.den_b, m.rad_w, m.rad_b), device)
+
+
+@pytest.mark.parametrize("case", WPACK_CASES)
+def test_distant_weight_pack_bytes(backend, case):
+    """The pack is the operand format of contract (csrc/mfma_mlp.h): its length and every byte are pinned."""
+    assert wpack_case(case, backend) == wpack_golden("distant")[case]

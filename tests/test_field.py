@@ -8,7 +8,7 @@ from oracle import field as ofield, lotd as olotd
 from neuralsim_amd import _lib
 from neuralsim_amd.fields.neus import _FieldFn
 from neuralsim_amd.grid_encodings.lotd import LoTDConfig, LoTDEncoding, gen_ngp_res
-from util import SMALL_RES as SMALL_RES_T, leaf, make_params, model_from_params, oracle_flat_grads, rel_l2
+from util import SMALL_RES as SMALL_RES_T, leaf, make_params, model_from_params, oracle_flat_grads, rel_l2, wpack_digest, wpack_golden
 
 
 def test_gen_ngp_matches_reference_comment():
@@ -670,3 +670,34 @@ def test_pair_pack_equals_the_two_single_packs(backend):
     ref = torch.zeros([nb], dtype=torch.uint8, device=backend)
     _lib.call("nsim_field_pack_weights", fb, *[_lib.ptr(w.detach()) for w in (m.sdf_w, m.sdf_b, m.rad_w, m.rad_b)], _lib.ptr(ref))
     assert torch.equal(wp_s.cpu(), ref.cpu())
+
+
+# pyramid -> (lod_res, frequencies of the embedded position): 16 levels (fp16: + the 16-point fragments), fewer than 16 (zero-padded
+# first-layer columns), 17..32 (two input chunks), 16 levels + embed_E = 39 (two more input chunks)
+_WPACK_PYRAMIDS = {"L16": (list(SMALL_RES_T), None), "L4": (list(SMALL_RES_T[:4]), None),
+                   "L19": ([4 + int(round(2.9 * i + 0.11 * i * i)) for i in range(19)], None), "L16E39": (list(SMALL_RES_T), 6)}
+WPACK_CASES = [f"p{prec}-D{D}-{pyr}" for prec in (0, 1, 2) for D in (1, 2) for pyr in _WPACK_PYRAMIDS]
+_WPACK_MODELS = {}
+
+
+def wpack_case(case, device):
+    """[byte length, sha256] of the field pack of ``case`` (also called by tests/golden/make_wpack_fixture.py)."""
+    import ctypes
+    from neuralsim_amd.fields.neus import LoTDNeuSModel
+    prec, D, pyr = case.split("-")
+    if (D, pyr) not in _WPACK_MODELS:
+        lod_res, n_freq = _WPACK_PYRAMIDS[pyr]
+        _WPACK_MODELS[D, pyr] = LoTDNeuSModel(lod_res=lod_res, log2_hashmap_size=12, sdf_D=int(D[1:]), precision="f32",
+                                              pos_embed_frequencies=n_freq)
+    m = _WPACK_MODELS[D, pyr]
+    fm = _lib.FieldMeta()
+    ctypes.memmove(ctypes.byref(fm), ctypes.byref(m.field_meta), ctypes.sizeof(fm))
+    fm.precision = int(prec[1:])
+    assert fm.embed_E == (39 if pyr == "L16E39" else 0) and fm.lotd.num_levels == len(_WPACK_PYRAMIDS[pyr][0])
+    return wpack_digest("field", fm, (m.sdf_w, m.sdf_b, m.rad_w, m.rad_b), device)
+
+
+@pytest.mark.parametrize("case", WPACK_CASES)
+def test_field_weight_pack_bytes(backend, case):
+    """The pack is the operand format of contract / contract16 (csrc/mfma_mlp.h): its length and every byte are pinned."""
+    assert wpack_case(case, backend) == wpack_golden("field")[case]

@@ -8,7 +8,7 @@ import torch
 
 import nerf_ref as nr
 from oracle import render as orr
-from util import leaf, look_at_cameras, rel_l2
+from util import leaf, look_at_cameras, rel_l2, wpack_digest, wpack_golden
 
 AABB = torch.tensor([[-1.0, -1, -1], [1.0, 1, 1]])
 RES = [8, 8, 8]
@@ -425,3 +425,26 @@ def test_nerf_training_steps(backend):
     assert fracs[7] == 1.0 and fracs[8] < 1.0 and float(m.accel.occ_val.max()) > 1.0e-2
     assert losses[-1] < losses[0], losses
     assert all(bool(torch.isfinite(q).all()) for q in m.parameters())
+
+
+WPACK_CASES = [f"p{prec}-A{na}" for prec in (0, 1) for na in (0, 4)]
+
+
+def wpack_case(case, device):
+    """[byte length, sha256] of the NGP model's pack of ``case`` (also called by tests/golden/make_wpack_fixture.py)."""
+    import ctypes
+    from neuralsim_amd import _lib
+    from neuralsim_amd.fields.nerf import LoTDNeRFModel
+    prec, na = case.split("-")
+    m = LoTDNeRFModel(**yaml_params(6, int(na[1:])))
+    gm = _lib.NgpMeta()
+    ctypes.memmove(ctypes.byref(gm), ctypes.byref(m.meta), ctypes.sizeof(gm))
+    gm.precision = int(prec[1:])
+    assert gm.n_appear == int(na[1:]) and gm.lotd.num_levels == 6
+    return wpack_digest("ngp", gm, (m.den_w, m.den_b, m.rad_w, m.rad_b), device)
+
+
+@pytest.mark.parametrize("case", WPACK_CASES)
+def test_ngp_weight_pack_bytes(backend, case):
+    """The pack is the operand format of contract (csrc/mfma_mlp.h): its length and every byte are pinned."""
+    assert wpack_case(case, backend) == wpack_golden("ngp")[case]

@@ -4,7 +4,7 @@ import pytest
 import torch
 
 from oracle import sky as osky
-from util import leaf
+from util import leaf, wpack_digest, wpack_golden
 
 
 def _setup(backend, precision, N, n_appear=4, F=10, seed=11):
@@ -54,3 +54,23 @@ def test_sky_no_appearance_and_shapes(backend):
     out = m(v.view(8, 12, 3).to(backend))
     assert out.shape == (8, 12, 3)
     assert float((out.detach().cpu().view(-1, 3) - ref).abs().max()) <= 2e-5
+
+
+WPACK_CASES = [f"p{prec}-F{F}-A{na}" for prec in (0, 1) for F, na in ((10, 4), (2, 0))]
+
+
+def wpack_case(case, device):
+    """[byte length, sha256] of the sky pack of ``case`` (also called by tests/golden/make_wpack_fixture.py)."""
+    from neuralsim_amd.env import SimpleSky
+    prec, F, na = case.split("-")
+    m = SimpleSky(dict(type="sinusoidal", n_frequencies=int(F[1:])), n_appear_embedding=int(na[1:]),
+                  precision={"p0": "fp16", "p1": "f32"}[prec])
+    assert m.w.numel() == 256 * (3 + 6 * int(F[1:]) + int(na[1:])) + 256 * 256 + 3 * 256
+    return wpack_digest("sky", m.meta, (m.w, m.b), device)
+
+
+@pytest.mark.parametrize("case", WPACK_CASES)
+def test_sky_weight_pack_bytes(backend, case):
+    """The pack is the operand format of contract (csrc/mfma_mlp.h): its length, every byte and its zeroed alignment gaps are
+    pinned."""
+    assert wpack_case(case, backend) == wpack_golden("sky")[case]

@@ -1,6 +1,9 @@
 """Shared helpers for the parity tests (oracle <-> product weight exchange, synthetic cameras)."""
+import hashlib
+import json
 import math
 import os
+from pathlib import Path
 
 import torch
 
@@ -162,3 +165,29 @@ def steps_on_a_fixed_objective(tr, its):
     if os.environ.get('NSIM_PRINT_LOSSES'):
         print('losses', ['%.5f' % l for l in losses])
     return losses
+
+
+# ----------------------------------------------------------------- MFMA weight packs, pinned byte for byte
+def det_weights(n, salt, device=None):
+    """``n`` f32 values from integer arithmetic alone -- no RNG, so the same on every torch build.  Exact in f32 and not
+    representable in f16 (the f16 rounding and the split residual of the packers are exercised); consecutive values are
+    distinct, so a transposed or shifted element changes the pack's hash."""
+    i = torch.arange(int(n), dtype=torch.int64)
+    return (((i * 40503 + salt) % 65521 - 32760).to(torch.float32) / 4096).to(device)
+
+
+def wpack_digest(family, meta, masters, device):
+    """[byte length, sha256] of the pack ``nsim_<family>_pack_weights`` writes into a ZEROED buffer (alignment gaps defined)
+    from masters of the shapes of ``masters`` filled by ``det_weights``."""
+    from neuralsim_amd import _lib
+    n = int(getattr(_lib.get_lib(), f"nsim_{family}_wpack_bytes")(meta))
+    buf = torch.zeros([n], dtype=torch.uint8, device=device)
+    ws = [det_weights(t.numel(), 1000 * (i + 1), device) for i, t in enumerate(masters)]
+    _lib.call(f"nsim_{family}_pack_weights", meta, *[_lib.ptr(w) for w in ws], _lib.ptr(buf))
+    return [n, hashlib.sha256(buf.cpu().numpy().tobytes()).hexdigest()]
+
+
+def wpack_golden(family):
+    """case -> [byte length, sha256] of the pack: the operand format of csrc/mfma_mlp.h, generated on the emulator backend
+    by tests/golden/make_wpack_fixture.py."""
+    return json.loads((Path(__file__).parent / "golden" / "wpack_sha256.json").read_text())[family]

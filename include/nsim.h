@@ -817,6 +817,44 @@ int nsim_errmap_cdf(const float* em, int64_t n_images, int h, int w, float min_p
 int nsim_errmap_draw(const float* cdf_img, const float* cdf_cell, int64_t n_images, int h, int w, const float* u, int64_t n,
                      int64_t n_uni, int64_t fixed_frame, int64_t row0, int64_t* fidx_out, float* xy_out, void* stream);
 
+/* ------------------------------------------------------------------------------- occupancy grids */
+/* code_single/tools/extract_occgrid.py:93-147 (sign-change detection on sub-sampled voxels), on the lattice the voxels share
+ * (neuralsim_amd/occgrid.py; conventions in csrc/misc.hip).  Voxel (ix, iy, iz) of a grid of res[3] voxels owns the (s + 1)^3
+ * lattice points of per-axis indices i s .. i s + s; the lattice is f32 [res[0] s + 1][res[1] s + 1][res[2] s + 1], z fastest,
+ * walked in slabs of nxs voxel layers in x (nxs s + 1 lattice planes).  1 <= s <= 4.
+ *   points: replaces :123-135 and :106 -- object-space coordinates x_obj f32 [n_planes][LY][LZ][3] of the lattice planes j0 ..
+ *           j0 + n_planes - 1, c = float(j / s) + float(j % s) / float(s), cn = (c / float(res)) * 2 - 1, x_world = cn * radius +
+ *           center, x_obj = (R^T (x_world - trans)) / scale with the three products of a row added left to right, every
+ *           operation rounded on its own, and state uint8 per point:
+ *           0 inside [obj_min, obj_max] (to be queried), 1 outside (the tool's invalid_sdf = +inf), 2 pruned -- only with
+ *           occ_bits (the bit-packed occupancy grid of occ, which spans the object box): the cell containing the point and its 26
+ *           neighbours, clamped at the border, are all empty;
+ *   flags:  replaces :137, :142 -- uint8 [nxs s + 1][ry][rz], the OR over the (s + 1)^2 points in y and z of: 1 = a value > 0,
+ *           2 = a value that is not, 4 = an infinite value or (state, may be NULL) a point whose state is not 0 (its value is not
+ *           read);
+ *   count:  replaces :138-145 -- a voxel is occupied iff the OR of its s + 1 flag bytes along x is exactly 3; cnt int32
+ *           [ceil(nxs ry rz / 256)] occupied voxels per block of 256 voxels (z fastest);
+ *   scan:   cnt in place -> exclusive offsets, *total = their sum, also stored as (total, seq) to the host-mapped words notify
+ *           (may be NULL) so that the host reads the size without a stream synchronisation;
+ *   emit:   replaces :145-147 -- out int32 [total][3] = (ix0 + ix, iy, iz) in ascending (ix, iy, iz). */
+typedef struct NsimOccgridFrame {
+  int32_t res[3];
+  int32_t s;
+  float center[3], radius[3]; /* of the world box: (max + min) / 2, (max - min) / 2 */
+  float rot[9];               /* object -> world rotation, row-major */
+  float trans[3];
+  float scale[3];
+  float obj_min[3], obj_max[3];
+} NsimOccgridFrame;
+int nsim_occgrid_points(const NsimOccgridFrame* frame, int64_t j0, int64_t n_planes, const int32_t* occ_bits,
+                        const NsimOccMeta* occ, float* x_obj, uint8_t* state, void* stream);
+int nsim_occgrid_flags(const float* lat, const uint8_t* state, int64_t nxs, int64_t ry, int64_t rz, int s, uint8_t* flags,
+                       void* stream);
+int nsim_occgrid_count(const uint8_t* flags, int64_t nxs, int64_t ry, int64_t rz, int s, int32_t* cnt, void* stream);
+int nsim_occgrid_scan(int32_t* cnt, int64_t n_blocks, int32_t* total, int64_t* notify, int64_t seq, void* stream);
+int nsim_occgrid_emit(const uint8_t* flags, int64_t nxs, int64_t ry, int64_t rz, int s, int64_t ix0, const int32_t* off,
+                      int32_t* out, void* stream);
+
 /* MFMA layout self-test (tests only): writes D = A(32x16 f16) * B(16x32 f16) with the wrappers used by the
  * field kernels; a, b given in plain row-major. d is 32x32 f32 row-major. */
 int nsim_selftest_mfma(const float* a, const float* b, float* d, int use_f32, void* stream);

@@ -76,6 +76,12 @@ class FieldMeta(C.Structure):
                 ("embed_E", C.c_int32)]
 
 
+class OccgridFrame(C.Structure):    # include/nsim.h NsimOccgridFrame
+    _fields_ = [("res", C.c_int32 * 3), ("s", C.c_int32), ("center", C.c_float * 3), ("radius", C.c_float * 3),
+                ("rot", C.c_float * 9), ("trans", C.c_float * 3), ("scale", C.c_float * 3), ("obj_min", C.c_float * 3),
+                ("obj_max", C.c_float * 3)]
+
+
 class ComposeSrc(C.Structure):      # include/nsim.h NsimComposeSrc
     _fields_ = [("t", C.c_void_p), ("rays_inds", C.c_void_p), ("pack_infos", C.c_void_p), ("P", C.c_int64), ("dst", C.c_void_p)]
 
@@ -194,6 +200,11 @@ SIGNATURES = {
     "nsim_nn_grid_scan": [_P, _P],
     "nsim_nn_grid_fill": [_P, _I64, _P, _P, _P, _P],
     "nsim_nn_grid_query": [_P, _I64, _P, _P, _P, _I, _P, _P, _P],
+    "nsim_occgrid_points": [C.POINTER(OccgridFrame), _I64, _I64, _P, C.POINTER(OccMeta), _P, _P],
+    "nsim_occgrid_flags": [_P, _P, _I64, _I64, _I64, _I, _P],
+    "nsim_occgrid_count": [_P, _I64, _I64, _I64, _I, _P],
+    "nsim_occgrid_scan": [_P, _I64, _P, _P, _I64],
+    "nsim_occgrid_emit": [_P, _I64, _I64, _I64, _I, _I64, _P, _P],
     "nsim_errmap_accumulate": [_P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I, _I, _P, _P, _P, _P],
     "nsim_errmap_blend": [_P, _P, _P, _P, _P, _I64, _I, _I],
     "nsim_errmap_cdf": [_P, _I64, _I, _I, _F, _F, _P, _P, _P, _P, _P],

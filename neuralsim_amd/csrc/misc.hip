@@ -1,6 +1,7 @@
 // misc.hip -- version / error strings of the C ABI, marching cubes on slabs of SDF lattices (nsim_mc_*), and exact nearest-neighbour
-// search between point clouds (nsim_nn_*).
+// search between point clouds (nsim_nn_*), and occupancy grids from lattices of SDF values (nsim_occgrid_*).
 #include "nsim_common.h"
+#include "occ_dev.h"
 
 // ------------------------------------------------------------------------------------------------ marching cubes
 // nr3d_lib.graphics.trianglemesh.extract_mesh (code_single/tools/extract_mesh.py:124), the kernels behind neuralsim_amd/mesh.py.
@@ -1137,6 +1138,257 @@ int nsim_nn_grid_query(const float* x, int64_t N, const float* rec, const int32_
 
 }  // extern "C"
 
+// ------------------------------------------------------------------------------------------------ occupancy grids
+// code_single/tools/extract_occgrid.py:93-147, the kernels behind neuralsim_amd/occgrid.py.
+//
+// A voxel grid of resolution res[3] is classified from SDF values on the lattice its voxels SHARE: voxel (ix, iy, iz) has the
+// (s + 1)^3 sample points of per-axis lattice indices i s .. i s + s, and the lattice has res[a] s + 1 points per axis.  A
+// lattice tensor is f32 [LX][LY][LZ] (z fastest: voxels then come out in ascending (ix, iy, iz), torch.nonzero's order on an
+// [X, Y, Z] array, whatever the slab cut) and is walked in slabs of nxs voxel layers in x = nxs s + 1 lattice planes.
+//   * coordinates (k_og_points): lattice index j sits at c = float(j / s) + float(j % s) / float(s), cn = (c / float(res)) * 2 - 1,
+//     x_world = cn * radius + center, x_obj[a] = ((R[0][a] d0 + R[1][a] d1) + R[2][a] d2) / scale[a] with d = x_world - t:
+//     every operation rounds on its own (no contraction, IEEE division), as the separate tensor operations of the tool do, and
+//     index i with k = s and index i + 1 with k = 0 name the same float, so both owners of a shared point see the same bits;
+//   * state of a point: 0 = inside the object box (queried), 1 = outside (the tool's +inf), 2 = pruned: inside, but the cell
+//     of the model's occupancy grid that contains it and its 26 neighbours (clamped at the border) are all empty;
+//   * classification: pos = value > 0 (0, -0 and NaN are not positive), bad = isinf(value) or state != 0; a voxel is occupied
+//     iff some sample is positive, some sample is not, and none is bad.  A pruned point has NO sign: its voxels are empty;
+//   * three predicates that are all ORs, so the reduction is separable: k_og_flags ORs them over the (s + 1)^2 points in y and z
+//     (a lattice value is read by at most 4 threads), one byte per (lattice plane, iy, iz); k_og_count / k_og_emit OR s + 1 of
+//     those bytes along x;
+//   * no atomics: counts per block of 256 voxels -> one scan (block_excl_scan_inplace) -> emission at the scanned offsets.
+#define OG_STATE_OUT 1
+#define OG_STATE_PRUNED 2
+
+__device__ __forceinline__ int og_clamp(int c, int res) { return c < 0 ? 0 : (c > res - 1 ? res - 1 : c); }
+
+__device__ __forceinline__ float og_coord(int64_t j, int s, int res) {
+#pragma clang fp contract(off)
+  const float c = (float)(j / s) + (float)(j % s) / (float)s;
+  const float u = c / (float)res;
+  const float v = u * 2.0f;
+  return v - 1.0f;
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_og_points(NsimOccgridFrame f, int64_t j0, int64_t npts, int64_t ly, int64_t lz,
+                                                        const uint32_t* __restrict__ bits, OccDev occ, float* __restrict__ x_obj,
+                                                        uint8_t* __restrict__ state) {
+#pragma clang fp contract(off)
+  const int64_t q = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+  if (q >= npts) return;
+  const int64_t jz = q % lz, jy = (q / lz) % ly, jx = j0 + q / (lz * ly);
+  const int64_t jj[3] = {jx, jy, jz};
+  float d[3], xo[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float cn = og_coord(jj[a], f.s, f.res[a]);
+    const float m = cn * f.radius[a];
+    const float xw = m + f.center[a];
+    d[a] = xw - f.trans[a];
+  }
+  bool inside = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float p0 = f.rot[0 + a] * d[0], p1 = f.rot[3 + a] * d[1], p2 = f.rot[6 + a] * d[2];
+    const float s01 = p0 + p1;
+    const float r = s01 + p2;
+    xo[a] = r / f.scale[a];
+    x_obj[3 * q + a] = xo[a];
+    inside = inside && xo[a] >= f.obj_min[a] && xo[a] <= f.obj_max[a];
+  }
+  int st = inside ? 0 : OG_STATE_OUT;
+  if (inside && bits) {
+    int g[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const float gf = floorf((xo[a] - occ.mn[a]) * occ.sc[a]);
+      g[a] = gf >= (float)(occ.res[a] - 1) ? occ.res[a] - 1 : (gf > 0.f ? (int)gf : 0);      // a point on the upper face: last cell
+    }
+    bool any = false;
+    for (int dz = -1; dz <= 1; ++dz)
+      for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+          const int cx = og_clamp(g[0] + dx, occ.res[0]), cy = og_clamp(g[1] + dy, occ.res[1]), cz = og_clamp(g[2] + dz, occ.res[2]);
+          const int64_t flat = (int64_t)cx + (int64_t)occ.res[0] * ((int64_t)cy + (int64_t)occ.res[1] * (int64_t)cz);
+          any = any || ((bits[flat >> 5] >> (flat & 31)) & 1u);
+        }
+    if (!any) st = OG_STATE_PRUNED;
+  }
+  state[q] = (uint8_t)st;
+}
+
+struct OgSlab {
+  int64_t nxs, ry, rz;   // voxel layers of the slab in x, voxels in y and z
+  int64_t ly, lz;        // lattice points in y and z
+  int s;
+};
+
+// flags [nxs s + 1][ry][rz]: bit 0 = a positive sample, bit 1 = a sample that is not positive, bit 2 = a bad sample
+__global__ void __launch_bounds__(MC_THREADS) k_og_flags(OgSlab g, const float* __restrict__ lat, const uint8_t* __restrict__ state,
+                                                       uint8_t* __restrict__ flags) {
+  const int64_t n = (g.nxs * g.s + 1) * g.ry * g.rz;
+  const int64_t p = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+  if (p >= n) return;
+  const int64_t iz = p % g.rz, iy = (p / g.rz) % g.ry, jx = p / (g.rz * g.ry);
+  int f = 0;
+  for (int dy = 0; dy <= g.s; ++dy)
+    for (int dz = 0; dz <= g.s; ++dz) {
+      const int64_t q = (jx * g.ly + (iy * g.s + dy)) * g.lz + (iz * g.s + dz);
+      if (state && state[q] != 0) {
+        f |= 4;            // its value was never written: not read
+        continue;
+      }
+      const float v = lat[q];
+      f |= (v > 0.f ? 1 : 2) | (isinf(v) ? 4 : 0);
+    }
+  flags[p] = (uint8_t)f;
+}
+
+__device__ __forceinline__ int og_occupied(const OgSlab& g, const uint8_t* __restrict__ flags, int64_t p, int64_t& ix, int64_t& iy,
+                                           int64_t& iz) {
+  const int64_t plane = g.ry * g.rz, rem = p % plane;
+  ix = p / plane;
+  iy = rem / g.rz;
+  iz = rem % g.rz;
+  int f = 0;
+  for (int dx = 0; dx <= g.s; ++dx) f |= flags[(ix * g.s + dx) * plane + rem];
+  return f == 3 ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_og_count(OgSlab g, const uint8_t* __restrict__ flags, int32_t* __restrict__ cnt) {
+  __shared__ int wsum[MC_THREADS / 64][1];
+  const int64_t p = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+  int64_t ix, iy, iz;
+  const int c[1] = {p < g.nxs * g.ry * g.rz ? og_occupied(g, flags, p, ix, iy, iz) : 0};
+  int pre[1], tot[1];
+  mc_block_scan<1>(c, pre, tot, wsum);
+  if (threadIdx.x == 0) cnt[blockIdx.x] = tot[0];
+}
+
+// exclusive scan of the block counts in place; the total to *total and, if given, (total, seq) to the host-mapped notify words
+__global__ void __launch_bounds__(MC_SCAN_THREADS) k_og_scan(int32_t* __restrict__ cnt, int64_t n, int32_t* __restrict__ total,
+                                                           int64_t* notify, int64_t seq) {
+  __shared__ int wtot[MC_SCAN_THREADS / 64];
+  const int carry = block_excl_scan_inplace(cnt, n, -1, nullptr, wtot);
+  if (threadIdx.x == 0) {
+    *total = carry;
+    if (notify) {
+      nsim_store_system(notify, (int64_t)carry, false);
+      nsim_store_system(notify + 1, seq, true);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_og_emit(OgSlab g, const uint8_t* __restrict__ flags, int64_t ix0,
+                                                      const int32_t* __restrict__ off, int32_t* __restrict__ out) {
+  __shared__ int wsum[MC_THREADS / 64][1];
+  const int64_t p = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+  int64_t ix = 0, iy = 0, iz = 0;
+  const int c[1] = {p < g.nxs * g.ry * g.rz ? og_occupied(g, flags, p, ix, iy, iz) : 0};
+  int pre[1], tot[1];
+  mc_block_scan<1>(c, pre, tot, wsum);
+  if (!c[0]) return;
+  const int64_t o = (int64_t)off[blockIdx.x] + pre[0];
+  out[3 * o + 0] = (int32_t)(ix0 + ix);
+  out[3 * o + 1] = (int32_t)iy;
+  out[3 * o + 2] = (int32_t)iz;
+}
+
+// 56 unless 1 <= s <= 4 and the slab's voxels and lattice points both stay below 2^31
+static int og_slab(int64_t nxs, int64_t ry, int64_t rz, int s, OgSlab& g) {
+  if (nxs < 1 || ry < 1 || rz < 1) return 2;
+  if (s < 1 || s > 4) return 56;
+  const int64_t lim = (int64_t)1 << 31;
+  if (nxs >= lim || ry >= lim || rz >= lim) return 56;
+  g.nxs = nxs;
+  g.ry = ry;
+  g.rz = rz;
+  g.ly = ry * s + 1;
+  g.lz = rz * s + 1;
+  g.s = s;
+  if ((double)(nxs * s + 1) * (double)g.ly * (double)g.lz >= (double)lim) return 56;
+  return 0;
+}
+
+extern "C" {
+
+int nsim_occgrid_points(const NsimOccgridFrame* frame, int64_t j0, int64_t n_planes, const int32_t* occ_bits, const NsimOccMeta* occ,
+                        float* x_obj, uint8_t* state, void* stream) {
+  if (!frame) return 5;
+  if (n_planes < 0 || j0 < 0) return 2;
+  const int s = frame->s;
+  if (s < 1 || s > 4) return 56;
+  for (int a = 0; a < 3; ++a)
+    if (frame->res[a] < 1 || (int64_t)frame->res[a] * s + 1 >= ((int64_t)1 << 24)) return 56;   // float(index) stays exact
+  const int64_t ly = (int64_t)frame->res[1] * s + 1, lz = (int64_t)frame->res[2] * s + 1;
+  if (j0 + n_planes > (int64_t)frame->res[0] * s + 1) return 56;
+  if ((double)n_planes * (double)ly * (double)lz >= 2147483648.0) return 56;
+  if (n_planes == 0) return 0;
+  if (!x_obj || !state) return 4;
+  if (occ_bits && !occ) return 5;
+  OccDev od;
+  memset(&od, 0, sizeof(od));
+  if (occ_bits) {
+    od = occ_dev(occ);
+    for (int a = 0; a < 3; ++a)
+      if (od.res[a] < 1) return 5;
+  }
+  const int64_t npts = n_planes * ly * lz;
+  hipLaunchKernelGGL(k_og_points, dim3((unsigned)((npts + MC_THREADS - 1) / MC_THREADS)), dim3(MC_THREADS), 0, (hipStream_t)stream,
+                     *frame, j0, npts, ly, lz, reinterpret_cast<const uint32_t*>(occ_bits), od, x_obj, state);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_occgrid_flags(const float* lat, const uint8_t* state, int64_t nxs, int64_t ry, int64_t rz, int s, uint8_t* flags,
+                       void* stream) {
+  OgSlab g;
+  const int rc = og_slab(nxs, ry, rz, s, g);
+  if (rc) return rc;
+  if (!lat || !flags) return 4;
+  const int64_t n = (nxs * s + 1) * ry * rz;
+  hipLaunchKernelGGL(k_og_flags, dim3((unsigned)((n + MC_THREADS - 1) / MC_THREADS)), dim3(MC_THREADS), 0, (hipStream_t)stream, g, lat,
+                     state, flags);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_occgrid_count(const uint8_t* flags, int64_t nxs, int64_t ry, int64_t rz, int s, int32_t* cnt, void* stream) {
+  OgSlab g;
+  const int rc = og_slab(nxs, ry, rz, s, g);
+  if (rc) return rc;
+  if (!flags || !cnt) return 4;
+  const int64_t n = nxs * ry * rz;
+  hipLaunchKernelGGL(k_og_count, dim3((unsigned)((n + MC_THREADS - 1) / MC_THREADS)), dim3(MC_THREADS), 0, (hipStream_t)stream, g, flags,
+                     cnt);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_occgrid_scan(int32_t* cnt, int64_t n_blocks, int32_t* total, int64_t* notify, int64_t seq, void* stream) {
+  if (n_blocks < 1) return 2;
+  if (!cnt || !total) return 4;
+  hipLaunchKernelGGL(k_og_scan, dim3(1), dim3(MC_SCAN_THREADS), 0, (hipStream_t)stream, cnt, n_blocks, total, notify, seq);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_occgrid_emit(const uint8_t* flags, int64_t nxs, int64_t ry, int64_t rz, int s, int64_t ix0, const int32_t* off, int32_t* out,
+                      void* stream) {
+  OgSlab g;
+  const int rc = og_slab(nxs, ry, rz, s, g);
+  if (rc) return rc;
+  if (ix0 < 0 || ix0 + nxs >= ((int64_t)1 << 31)) return 56;
+  if (!flags || !off || !out) return 4;
+  const int64_t n = nxs * ry * rz;
+  hipLaunchKernelGGL(k_og_emit, dim3((unsigned)((n + MC_THREADS - 1) / MC_THREADS)), dim3(MC_THREADS), 0, (hipStream_t)stream, g, flags,
+                     ix0, off, out);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // extern "C"
+
 extern "C" {
 
 int nsim_version(void) { return 100; }
@@ -1185,6 +1437,7 @@ const char* nsim_strerror(int code) {
     case 39: return "n_appear must be 0 or 4";
     case 54: return "error map: n_images, h, w >= 1, n_images h w < 2^31 and a fixed frame below n_images";
     case 55: return "ssim: 1 <= window <= 11, stride >= 1, H W < 2^31, at least one window per image, the indexed form takes one image";
+    case 56: return "occupancy grid: 1 <= subsample factor <= 4, resolutions >= 1, resolution * factor + 1 < 2^24 per axis, fewer than 2^31 voxels and lattice points per slab";
     case 36: return "wide decoder: 0..10 embedding frequencies and at most 128 first-layer inputs (2 num_levels + 3 + 6 n_freq)";
     default: return code >= 1000 ? "HIP launch error (code - 1000 = hipError_t)" : "unknown error";
   }

@@ -58,7 +58,8 @@ class SyntheticObjectDataset:
                    data=dict(hw=np.tile(np.array([[self.H, self.W]], dtype=np.float32), (V, 1)),
                              intr=self.intr.numpy().astype(np.float32), transform=self.c2w.numpy().astype(np.float32),
                              global_frame_inds=np.arange(V)))
-        return dict(scene_id=scene_id, metas=dict(n_frames=V, main_class_name="Main"), objects=objects,
+        # world_offset: what the driving scenarios' metas carry and code_single/tools/extract_occgrid.py:157 stores (none here)
+        return dict(scene_id=scene_id, metas=dict(n_frames=V, main_class_name="Main", world_offset=np.zeros([3])), objects=objects,
                     observers=dict(camera=cam))
 
     def _frame(self, fi: int):
@@ -198,7 +199,7 @@ class SyntheticStreetDataset:
             for lid in lidars:
                 observers[lid] = lidar_node(lid, self.v2w @ self.l2v[None])
         track = self.v2w[:, :3, 3]
-        metas = dict(n_frames=F_, main_class_name="Street", frame_timestamps=ts, up_vec="+z", align_orientation=align_orientation,
+        metas = dict(n_frames=F_, main_class_name="Street", world_offset=np.zeros([3]), frame_timestamps=ts, up_vec="+z", align_orientation=align_orientation,
                      average_rot_z=0.0, average_rot_mat=np.eye(3),
                      aabb=np.stack([track.min(0) - aabb_extend, track.max(0) + aabb_extend], axis=0))
         return dict(scene_id=scene_id, metas=metas, objects=objects, observers=observers)

@@ -1181,6 +1181,31 @@ class LoTDNeuSModel(ModelMixin, nn.Module):
     def forward_sdf(self, x: torch.Tensor, *, input_normalized: bool = False) -> Dict[str, torch.Tensor]:
         return dict(sdf=self.forward_sdf_nablas(self._object_coords(x, input_normalized), nablas_has_grad=False)["sdf"])
 
+    @torch.no_grad()
+    def forward_in_obj(self, x: torch.Tensor, invalid_sdf: float = math.inf, return_h: bool = False,
+                       with_normal: bool = False) -> Dict[str, torch.Tensor]:
+        """``model.implicit_surface.forward_in_obj`` (code_single/tools/extract_occgrid.py:108): the no-grad SDF at points x
+        [..., 3] in OBJECT coordinates; points outside ``space.aabb`` get ``invalid_sdf`` and are not queried.  The values come
+        from the split-precision query on the packed shadow weights (``_sdf_query``, what ``occgrid.extract_occupancy_from_model``
+        asks); ``with_normal`` adds ``nablas`` of the inside points (zeros outside) through ``forward_sdf_nablas``."""
+        if return_h:
+            raise NotImplementedError("forward_in_obj: return_h=True is not available (the kernels keep no feature vector h)")
+        shape = x.shape[:-1]
+        xf = x.detach().float().reshape(-1, 3)
+        a = self.space.aabb
+        idx = ((xf >= a[0]) & (xf <= a[1])).all(dim=-1).nonzero()[:, 0]
+        xi = xf[idx].contiguous()
+        sdf = torch.full([xf.shape[0]], float(invalid_sdf), dtype=torch.float32, device=xf.device)
+        grid16, wpack = self._shadow()
+        sdf[idx] = self._sdf_query(grid16, wpack, xi, None, None, None, None, xi.shape[0], xf.device)
+        ret = dict(sdf=sdf.reshape(shape))
+        if with_normal:
+            nablas = torch.zeros([xf.shape[0], 3], dtype=torch.float32, device=xf.device)
+            if xi.shape[0]:
+                nablas[idx] = self.forward_sdf_nablas(xi, nablas_has_grad=False)["nablas"].detach()
+            ret["nablas"] = nablas.reshape(*shape, 3)
+        return ret
+
     def forward(self, x: torch.Tensor, v: torch.Tensor, *, with_rgb: bool = True, with_normal: bool = False,
                 input_normalized: bool = False, h_appear: torch.Tensor = None) -> Dict[str, torch.Tensor]:
         """The field at free points x [..., 3] seen along directions v [..., 3] (the reference's ``model.forward(x, v,

@@ -855,6 +855,41 @@ int nsim_occgrid_scan(int32_t* cnt, int64_t n_blocks, int32_t* total, int64_t* n
 int nsim_occgrid_emit(const uint8_t* flags, int64_t nxs, int64_t ry, int64_t rz, int s, int64_t ix0, const int32_t* off,
                       int32_t* out, void* stream);
 
+/* --------------------------------------------------------------------------------- visible grids */
+/* app/visible_grid.py (VisibleGrid) and code_multi/tools/extract_visible_grid.py:205-235: the voxels the cameras saw
+ * (neuralsim_amd/visible_grid.py; conventions in csrc/misc.hip).  The grid is the cube [origin, origin + G voxel], G = 2^depth,
+ * 32 <= G <= 1024; voxel index = ix G G + iy G + iz (visible_grid.py:28-30, z fastest), int64.  hits: int32 [G^3] in that order;
+ * bit sets: uint32 [G^3 / 32] stored as int32, bit (v & 31) of word (v >> 5).
+ *   mark_samples: replaces extract_visible_grid.py:221-226 and visible_grid.py:88-89,119-121 in one pass -- for every sample s
+ *           with w[s] > thre (strict; NaN is not greater) of pack row p (pack_infos_hit int64 [n_packs][2] = (start, length),
+ *           starts non-decreasing) the point rays_o[r] + rays_d[r] * t[s], r = rays_inds_hit[p] (NULL: r = p; rows outside
+ *           [0, n_rays) are skipped), counts iff box_min <= point <= box_max; hits[voxel] += 1 with voxel coordinate
+ *           int((point - origin) / voxel) clamped to G - 1, every operation rounded on its own;
+ *   mark_points: the same for points f32 [n][3] (visible_grid.py:83-91);
+ *           stats (may be NULL): int64 [2] += (points counted, atomics issued after the in-wave run merge);
+ *   bits:   bit v = hits[v] > 0;   set_bits: bit idx[i] = 1 for 0 <= idx[i] < G^3 (visible_grid.py:149);
+ *   morph:  out = op(in) | keep (keep may be NULL or out; in != out), op 0 = 3x3x3 dilation with out-of-grid neighbours dropped,
+ *           1 = 3x3x3 erosion with out-of-grid neighbours empty (visible_grid.py:166-215 on the 26-neighbourhood of :236-245);
+ *   count:  cnt[b] = set bits of the 256 words of block b, ceil(G^3 / 8192) blocks -> nsim_occgrid_scan -> emit: out_idx int64
+ *           [total] ascending (visible_grid.py:157-164), out_hits (may be NULL) = hits at them (hits NULL: 0);
+ *   occ_val: f32 [G^3] in the occupancy grids' order (x fastest) = 1.0 where the bit is set, 0.0 elsewhere. */
+typedef struct NsimVgridFrame {
+  float origin[3], voxel[3];
+  float box_min[3], box_max[3]; /* the space's box: ``space.contains`` */
+  int32_t G;
+} NsimVgridFrame;
+int nsim_vgrid_mark_samples(const NsimVgridFrame* frame, const float* rays_o, const float* rays_d, int64_t n_rays,
+                            const int64_t* rays_inds_hit, const int64_t* pack_infos_hit, int64_t n_packs, const float* t,
+                            const float* w, int64_t S, float thre, int32_t* hits, int64_t* stats, void* stream);
+int nsim_vgrid_mark_points(const NsimVgridFrame* frame, const float* pts, int64_t n, int32_t* hits, int64_t* stats, void* stream);
+int nsim_vgrid_bits(const int32_t* hits, int64_t G, int32_t* bits, void* stream);
+int nsim_vgrid_set_bits(const int64_t* idx, int64_t n, int64_t G, int32_t* bits, void* stream);
+int nsim_vgrid_morph(const int32_t* in, const int32_t* keep, int64_t G, int op, int32_t* out, void* stream);
+int nsim_vgrid_count(const int32_t* bits, int64_t G, int32_t* cnt, void* stream);
+int nsim_vgrid_emit(const int32_t* bits, int64_t G, const int32_t* off, const int32_t* hits, int64_t* out_idx, int64_t* out_hits,
+                    void* stream);
+int nsim_vgrid_occ_val(const int32_t* bits, int64_t G, float* occ_val, void* stream);
+
 /* MFMA layout self-test (tests only): writes D = A(32x16 f16) * B(16x32 f16) with the wrappers used by the
  * field kernels; a, b given in plain row-major. d is 32x32 f32 row-major. */
 int nsim_selftest_mfma(const float* a, const float* b, float* d, int use_f32, void* stream);

@@ -82,6 +82,11 @@ class OccgridFrame(C.Structure):    # include/nsim.h NsimOccgridFrame
                 ("obj_max", C.c_float * 3)]
 
 
+class VgridFrame(C.Structure):      # include/nsim.h NsimVgridFrame
+    _fields_ = [("origin", C.c_float * 3), ("voxel", C.c_float * 3), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3),
+                ("G", C.c_int32)]
+
+
 class ComposeSrc(C.Structure):      # include/nsim.h NsimComposeSrc
     _fields_ = [("t", C.c_void_p), ("rays_inds", C.c_void_p), ("pack_infos", C.c_void_p), ("P", C.c_int64), ("dst", C.c_void_p)]
 
@@ -205,6 +210,14 @@ SIGNATURES = {
     "nsim_occgrid_count": [_P, _I64, _I64, _I64, _I, _P],
     "nsim_occgrid_scan": [_P, _I64, _P, _P, _I64],
     "nsim_occgrid_emit": [_P, _I64, _I64, _I64, _I, _I64, _P, _P],
+    "nsim_vgrid_mark_samples": [C.POINTER(VgridFrame), _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _F, _P, _P],
+    "nsim_vgrid_mark_points": [C.POINTER(VgridFrame), _P, _I64, _P, _P],
+    "nsim_vgrid_bits": [_P, _I64, _P],
+    "nsim_vgrid_set_bits": [_P, _I64, _I64, _P],
+    "nsim_vgrid_morph": [_P, _P, _I64, _I, _P],
+    "nsim_vgrid_count": [_P, _I64, _P],
+    "nsim_vgrid_emit": [_P, _I64, _P, _P, _P, _P],
+    "nsim_vgrid_occ_val": [_P, _I64, _P],
     "nsim_errmap_accumulate": [_P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I, _I, _P, _P, _P, _P],
     "nsim_errmap_blend": [_P, _P, _P, _P, _P, _I64, _I, _I],
     "nsim_errmap_cdf": [_P, _I64, _I, _I, _F, _F, _P, _P, _P, _P, _P],

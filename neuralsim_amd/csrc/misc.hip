@@ -1,5 +1,6 @@
 // misc.hip -- version / error strings of the C ABI, marching cubes on slabs of SDF lattices (nsim_mc_*), and exact nearest-neighbour
-// search between point clouds (nsim_nn_*), and occupancy grids from lattices of SDF values (nsim_occgrid_*).
+// search between point clouds (nsim_nn_*), occupancy grids from lattices of SDF values (nsim_occgrid_*), and visible grids
+// from rendered samples (nsim_vgrid_*).
 #include "nsim_common.h"
 #include "occ_dev.h"
 
@@ -1389,6 +1390,334 @@ int nsim_occgrid_emit(const uint8_t* flags, int64_t nxs, int64_t ry, int64_t rz,
 
 }  // extern "C"
 
+// ------------------------------------------------------------------------------------------------ visible grids
+// app/visible_grid.py and code_multi/tools/extract_visible_grid.py:205-235, the kernels behind neuralsim_amd/visible_grid.py.
+//
+// The grid is the cube [origin, origin + G voxel] of G^3 voxels, G = 2^octree_depth (32 .. 1024); a voxel's index is the
+// reference's ix G G + iy G + iz (z fastest) in int64 -- 2^30 voxels occur.  The working state is two dense arrays in that order:
+// hits int32 [G^3] (samples seen per voxel, summed over all calls) and bit sets uint32 [G^3 / 32] (bit v & 31 of word v >> 5).
+//   * a point counts iff box_min <= p <= box_max on every axis (``space.contains``; NaN is outside); its voxel coordinate is
+//     int((p - origin) / voxel) clamped to G - 1 (a point on the upper face of the longest axis), every operation rounded on
+//     its own and the division IEEE, as the separate tensor operations of the reference are (vg_voxel);
+//   * marking (k_vg_mark_samples: p = o + d t of the samples with w > thre -- strict, NaN is not greater -- one thread per sample,
+//     its pack found by bisection over the pack starts; k_vg_mark_points: a plain point array): consecutive samples of a ray
+//     sit in consecutive lanes and share voxels, and same-address atomics are separate requests at the memory side, so runs
+//     of equal voxels are merged in the wave (the ballot / run-head scheme of occ_max_wave, occ_dev.h) and the head lane of a
+//     run issues ONE integer atomicAdd(hits[v], run length).  Integer adds commute: the counts do not depend on the order;
+//   * k_vg_morph: out = op(in) | keep, op = 3x3x3 box dilation (out-of-grid neighbours dropped) or erosion (out-of-grid
+//     neighbours empty), one thread per 32-voxel word: z neighbours by shifts with the carry from the adjacent word of the
+//     SAME row (x, y) only, x and y neighbours from the 8 neighbouring rows;
+//   * compaction without atomics: set bits per block of 256 words (k_vg_count) -> nsim_occgrid_scan -> k_vg_emit writes the
+//     indices in storage order = ascending, and the hit counts gathered at them;
+//   * k_vg_occ_val: the accel's value grid (x fastest, sampling.hip) = 1.0 where the bit is set, else 0.0 -- the one
+//     transposition between the two voxel orders, in tiles of 32 (x) by 32 (z) through shared memory after a memset.
+#define VG_DILATE 0
+#define VG_ERODE 1
+
+__device__ __forceinline__ bool vg_voxel(const NsimVgridFrame& f, float px, float py, float pz, int64_t& flat) {
+#pragma clang fp contract(off)
+  const float p[3] = {px, py, pz};
+  bool in = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) in = in && p[a] >= f.box_min[a] && p[a] <= f.box_max[a];
+  if (!in) return false;
+  int64_t c[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float d = p[a] - f.origin[a];
+    const float q = d / f.voxel[a];
+    c[a] = q >= (float)(f.G - 1) ? f.G - 1 : (q > 0.f ? (int)q : 0);
+  }
+  flat = (c[0] * f.G + c[1]) * f.G + c[2];
+  return true;
+}
+
+// hits[flat] += 1 for the lanes with ``ok`` (all 64 lanes call): one atomicAdd of the run length per run of equal voxels
+__device__ __forceinline__ void vg_mark_wave(int32_t* __restrict__ hits, bool ok, int64_t flat_in, unsigned long long* stats) {
+  const int lane = nsim_lane();
+  const int64_t flat = ok ? flat_in : (int64_t)(-1 - lane);
+  const int64_t pk = wave_shfl(flat, lane - 1);
+  const unsigned long long heads = wave_ballot(lane == 0 || pk != flat);
+  const unsigned long long kept = wave_ballot(ok);
+  if (ok && ((heads >> lane) & 1ull)) {
+    const unsigned long long above = lane == 63 ? 0ull : (heads >> (lane + 1));
+    const int len = above ? __builtin_ctzll(above) + 1 : 64 - lane;
+    atomicAdd(hits + flat, len);
+  }
+  if (stats && lane == 0 && kept) {      // (bench only) kept samples and atomics issued
+    atomicAdd(stats, (unsigned long long)__popcll(kept));
+    atomicAdd(stats + 1, (unsigned long long)__popcll(heads & kept));
+  }
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_vg_mark_samples(NsimVgridFrame f, const float* __restrict__ rays_o,
+                                                              const float* __restrict__ rays_d, int64_t n_rays,
+                                                              const int64_t* __restrict__ rays_inds,
+                                                              const int64_t* __restrict__ pack_infos, int64_t n_packs,
+                                                              const float* __restrict__ t, const float* __restrict__ w, int64_t S,
+                                                              float thre, int32_t* __restrict__ hits, unsigned long long* stats) {
+#pragma clang fp contract(off)
+  const int64_t s = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+  bool ok = s < S;
+  int64_t flat = 0;
+  if (ok) ok = w[s] > thre;
+  if (ok) {
+    int64_t lo = 0, hi = n_packs;            // the first pack that starts after s
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (pack_infos[2 * mid] <= s) lo = mid + 1; else hi = mid;
+    }
+    const int64_t p = lo - 1;
+    ok = p >= 0 && s < pack_infos[2 * p] + pack_infos[2 * p + 1];
+    int64_t r = 0;
+    if (ok) {
+      r = rays_inds ? rays_inds[p] : p;
+      ok = r >= 0 && r < n_rays;
+    }
+    if (ok) {
+      const float tt = t[s];
+      float x[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        const float m = rays_d[3 * r + a] * tt;
+        x[a] = rays_o[3 * r + a] + m;
+      }
+      ok = vg_voxel(f, x[0], x[1], x[2], flat);
+    }
+  }
+  vg_mark_wave(hits, ok, flat, stats);
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_vg_mark_points(NsimVgridFrame f, const float* __restrict__ pts, int64_t n,
+                                                             int32_t* __restrict__ hits, unsigned long long* stats) {
+  const int64_t i = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+  bool ok = i < n;
+  int64_t flat = 0;
+  if (ok) ok = vg_voxel(f, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], flat);
+  vg_mark_wave(hits, ok, flat, stats);
+}
+
+// nvox is a multiple of 64: every wave is whole
+__global__ void __launch_bounds__(MC_THREADS) k_vg_bits(const int32_t* __restrict__ hits, int64_t nvox, uint32_t* __restrict__ bits) {
+  const int64_t v = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+  const int lane = nsim_lane();
+  const unsigned long long b = wave_ballot(v < nvox && hits[v] > 0);
+  if (v < nvox && (lane & 31) == 0) bits[v >> 5] = (uint32_t)(b >> (lane & 32));
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_vg_set_bits(const int64_t* __restrict__ idx, int64_t n, int64_t nvox,
+                                                          uint32_t* __restrict__ bits) {
+  const int64_t i = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const int64_t v = idx[i];
+  if (v < 0 || v >= nvox) return;
+  atomicOr(bits + (v >> 5), 1u << (v & 31));
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_vg_morph(const uint32_t* __restrict__ in, const uint32_t* keep, int64_t G, int op,
+                                                       uint32_t* out) {
+  const int64_t W = G >> 5, nw = G * G * W;
+  const int64_t w = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+  if (w >= nw) return;
+  const int64_t wz = w % W, y = (w / W) % G, x = w / (W * G);
+  uint32_t acc = op == VG_DILATE ? 0u : in[w];
+  if (op == VG_DILATE || acc != 0u)
+    for (int dx = -1; dx <= 1; ++dx)
+      for (int dy = -1; dy <= 1; ++dy) {
+        const int64_t xx = x + dx, yy = y + dy;
+        if (xx < 0 || xx >= G || yy < 0 || yy >= G) {
+          if (op == VG_ERODE) acc = 0u;
+          continue;
+        }
+        const int64_t base = (xx * G + yy) * W;
+        const uint32_t c = in[base + wz];
+        const uint32_t l = wz > 0 ? in[base + wz - 1] : 0u;          // the carries stay inside the row
+        const uint32_t r = wz + 1 < W ? in[base + wz + 1] : 0u;
+        const uint32_t up = (c << 1) | (l >> 31);                    // bit z = voxel z - 1
+        const uint32_t dn = (c >> 1) | (r << 31);                    // bit z = voxel z + 1
+        if (op == VG_DILATE) acc |= c | up | dn; else acc &= c & up & dn;
+      }
+  out[w] = acc | (keep ? keep[w] : 0u);
+}
+
+// exclusive prefix of c (0 .. 32 set bits of a word: mc_block_scan's ballot scan takes values below 8) among the block's threads
+// and the block total
+__device__ __forceinline__ void vg_block_scan(int c, int& pre, int& tot, int* wsum) {
+  const int lane = nsim_lane(), wave = threadIdx.x >> 6;
+  int inc = c;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int o = wave_shfl(inc, lane - d);
+    if (lane >= d) inc += o;
+  }
+  if (lane == 63) wsum[wave] = inc;
+  __syncthreads();
+  int before = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < MC_THREADS / 64; ++w) {
+    before += w < wave ? wsum[w] : 0;
+    all += wsum[w];
+  }
+  pre = inc - c + before;
+  tot = all;
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_vg_count(const uint32_t* __restrict__ bits, int64_t nw, int32_t* __restrict__ cnt) {
+  __shared__ int wsum[MC_THREADS / 64];
+  const int64_t w = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+  int pre, tot;
+  vg_block_scan(w < nw ? (int)__popc(bits[w]) : 0, pre, tot, wsum);
+  if (threadIdx.x == 0) cnt[blockIdx.x] = tot;
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_vg_emit(const uint32_t* __restrict__ bits, int64_t nw, const int32_t* __restrict__ off,
+                                                      const int32_t* __restrict__ hits, int64_t* __restrict__ out_idx,
+                                                      int64_t* __restrict__ out_hits) {
+  __shared__ int wsum[MC_THREADS / 64];
+  const int64_t w = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+  uint32_t b = w < nw ? bits[w] : 0u;
+  int pre, tot;
+  vg_block_scan((int)__popc(b), pre, tot, wsum);
+  int64_t o = (int64_t)off[blockIdx.x] + pre;
+  while (b) {
+    const int k = __builtin_ctz(b);
+    b &= b - 1u;
+    const int64_t v = (w << 5) + k;
+    out_idx[o] = v;
+    if (out_hits) out_hits[o] = hits ? (int64_t)hits[v] : 0;
+    ++o;
+  }
+}
+
+// One block per tile of 32 voxels in x by one word (32 voxels) in z at one y: the 32 words (x0 .. x0 + 31, y, wz) are read once and
+// the set bits written as rows of 32 consecutive floats in x.  The value grid was zeroed before: only set bits are written.
+__global__ void __launch_bounds__(MC_THREADS) k_vg_occ_val(const uint32_t* __restrict__ bits, int64_t G, float* __restrict__ val) {
+  __shared__ uint32_t wds[32];
+  const int64_t W = G >> 5, b = blockIdx.x;
+  const int64_t wz = b % W, y = (b / W) % G, x0 = (b / (W * G)) << 5;
+  const int tid = threadIdx.x;
+  if (tid < 32) wds[tid] = bits[((x0 + tid) * G + y) * W + wz];
+  __syncthreads();
+  const int x = tid & 31;
+  const uint32_t wd = wds[x];
+#pragma unroll
+  for (int i = 0; i < 32 / (MC_THREADS / 32); ++i) {
+    const int z = (tid >> 5) + (MC_THREADS / 32) * i;
+    if ((wd >> z) & 1u) val[(x0 + x) + G * (y + G * ((wz << 5) + z))] = 1.0f;
+  }
+}
+
+// 57 unless G is a power of two in 32 .. 1024
+static int vg_grid(int64_t G) { return (G >= 32 && G <= 1024 && (G & (G - 1)) == 0) ? 0 : 57; }
+static dim3 vg_blocks(int64_t n) { return dim3((unsigned)((n + MC_THREADS - 1) / MC_THREADS)); }
+
+extern "C" {
+
+int nsim_vgrid_mark_samples(const NsimVgridFrame* frame, const float* rays_o, const float* rays_d, int64_t n_rays,
+                            const int64_t* rays_inds_hit, const int64_t* pack_infos_hit, int64_t n_packs, const float* t,
+                            const float* w, int64_t S, float thre, int32_t* hits, int64_t* stats, void* stream) {
+  if (!frame) return 5;
+  const int rc = vg_grid(frame->G);
+  if (rc) return rc;
+  if (n_rays < 0 || n_packs < 0 || S < 0) return 2;
+  if (S >= ((int64_t)1 << 39)) return 57;
+  if (!hits) return 4;
+  if (S == 0 || n_packs == 0 || n_rays == 0) return 0;
+  if (!rays_o || !rays_d || !pack_infos_hit || !t || !w) return 24;
+  hipLaunchKernelGGL(k_vg_mark_samples, vg_blocks(S), dim3(MC_THREADS), 0, (hipStream_t)stream, *frame, rays_o, rays_d, n_rays,
+                     rays_inds_hit, pack_infos_hit, n_packs, t, w, S, thre, hits, reinterpret_cast<unsigned long long*>(stats));
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_vgrid_mark_points(const NsimVgridFrame* frame, const float* pts, int64_t n, int32_t* hits, int64_t* stats, void* stream) {
+  if (!frame) return 5;
+  const int rc = vg_grid(frame->G);
+  if (rc) return rc;
+  if (n < 0) return 2;
+  if (n >= ((int64_t)1 << 39)) return 57;
+  if (!hits) return 4;
+  if (n == 0) return 0;
+  if (!pts) return 24;
+  hipLaunchKernelGGL(k_vg_mark_points, vg_blocks(n), dim3(MC_THREADS), 0, (hipStream_t)stream, *frame, pts, n, hits,
+                     reinterpret_cast<unsigned long long*>(stats));
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_vgrid_bits(const int32_t* hits, int64_t G, int32_t* bits, void* stream) {
+  const int rc = vg_grid(G);
+  if (rc) return rc;
+  if (!hits || !bits) return 4;
+  hipLaunchKernelGGL(k_vg_bits, vg_blocks(G * G * G), dim3(MC_THREADS), 0, (hipStream_t)stream, hits, G * G * G,
+                     reinterpret_cast<uint32_t*>(bits));
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_vgrid_set_bits(const int64_t* idx, int64_t n, int64_t G, int32_t* bits, void* stream) {
+  const int rc = vg_grid(G);
+  if (rc) return rc;
+  if (n < 0) return 2;
+  if (n > G * G * G) return 57;
+  if (!bits) return 4;
+  if (n == 0) return 0;
+  if (!idx) return 24;
+  hipLaunchKernelGGL(k_vg_set_bits, vg_blocks(n), dim3(MC_THREADS), 0, (hipStream_t)stream, idx, n, G * G * G,
+                     reinterpret_cast<uint32_t*>(bits));
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_vgrid_morph(const int32_t* in, const int32_t* keep, int64_t G, int op, int32_t* out, void* stream) {
+  const int rc = vg_grid(G);
+  if (rc) return rc;
+  if (op != VG_DILATE && op != VG_ERODE) return 3;
+  if (!in || !out || in == out) return 4;
+  hipLaunchKernelGGL(k_vg_morph, vg_blocks(G * G * (G >> 5)), dim3(MC_THREADS), 0, (hipStream_t)stream,
+                     reinterpret_cast<const uint32_t*>(in), reinterpret_cast<const uint32_t*>(keep), G, op,
+                     reinterpret_cast<uint32_t*>(out));
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_vgrid_count(const int32_t* bits, int64_t G, int32_t* cnt, void* stream) {
+  const int rc = vg_grid(G);
+  if (rc) return rc;
+  if (!bits || !cnt) return 4;
+  const int64_t nw = G * G * (G >> 5);
+  hipLaunchKernelGGL(k_vg_count, vg_blocks(nw), dim3(MC_THREADS), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(bits), nw,
+                     cnt);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_vgrid_emit(const int32_t* bits, int64_t G, const int32_t* off, const int32_t* hits, int64_t* out_idx, int64_t* out_hits,
+                    void* stream) {
+  const int rc = vg_grid(G);
+  if (rc) return rc;
+  if (!bits || !off || !out_idx) return 4;
+  const int64_t nw = G * G * (G >> 5);
+  hipLaunchKernelGGL(k_vg_emit, vg_blocks(nw), dim3(MC_THREADS), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(bits), nw,
+                     off, hits, out_idx, out_hits);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_vgrid_occ_val(const int32_t* bits, int64_t G, float* occ_val, void* stream) {
+  const int rc = vg_grid(G);
+  if (rc) return rc;
+  if (!bits || !occ_val) return 4;
+  const hipError_t e = hipMemsetAsync(occ_val, 0, (size_t)(G * G * G) * sizeof(float), (hipStream_t)stream);
+  if (e != hipSuccess) return 1000 + (int)e;
+  hipLaunchKernelGGL(k_vg_occ_val, dim3((unsigned)(G * G * G / 1024)), dim3(MC_THREADS), 0, (hipStream_t)stream,
+                     reinterpret_cast<const uint32_t*>(bits), G, occ_val);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // extern "C"
+
 extern "C" {
 
 int nsim_version(void) { return 100; }
@@ -1438,6 +1767,7 @@ const char* nsim_strerror(int code) {
     case 54: return "error map: n_images, h, w >= 1, n_images h w < 2^31 and a fixed frame below n_images";
     case 55: return "ssim: 1 <= window <= 11, stride >= 1, H W < 2^31, at least one window per image, the indexed form takes one image";
     case 56: return "occupancy grid: 1 <= subsample factor <= 4, resolutions >= 1, resolution * factor + 1 < 2^24 per axis, fewer than 2^31 voxels and lattice points per slab";
+    case 57: return "visible grid: the grid edge is a power of two in 32 .. 1024 (octree depth 5 .. 10), fewer than 2^39 samples per call";
     case 36: return "wide decoder: 0..10 embedding frequencies and at most 128 first-layer inputs (2 num_levels + 3 + 6 n_freq)";
     default: return code >= 1000 ? "HIP launch error (code - 1000 = hipError_t)" : "unknown error";
   }

@@ -221,17 +221,16 @@ __global__ void __launch_bounds__(256) k_occ_update(float* __restrict__ val, con
                    inv_s);
 }
 
+// one lane per voxel (coalesced reads), a ballot packs the 64 voxels of a wave into two words; a grid of any size covers the array
 __global__ void __launch_bounds__(256) k_occ_pack_bits(const float* __restrict__ val, int64_t nvox, float thre,
                                                         uint32_t* __restrict__ bits) {
-  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t nwords = (nvox + 31) / 32;
-  if (w >= nwords) return;
-  uint32_t b = 0;
-  for (int k = 0; k < 32; ++k) {
-    const int64_t v = w * 32 + k;
-    if (v < nvox && val[v] > thre) b |= (1u << k);
+  const int lane = nsim_lane();
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t end = (nvox + 63) & ~(int64_t)63;            // whole waves take part in every ballot
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < end; v += stride) {
+    const unsigned long long b = wave_ballot(v < nvox && val[v] > thre);
+    if ((lane & 31) == 0 && v < nvox) bits[v >> 5] = (uint32_t)(b >> (lane & 32));
   }
-  bits[w] = b;
 }
 
 // ------------------------------------------------------------------------------------------ marching
@@ -706,7 +705,7 @@ int nsim_occ_collect(float* val, const float* pts, const float* sdf, int64_t n, 
 
 int nsim_occ_pack_bits(const float* val, int64_t nvox, float thre, uint32_t* bits, void* stream) {
   if (nvox <= 0) return 0;
-  hipLaunchKernelGGL(k_occ_pack_bits, dim3(nsim_blocks((nvox + 31) / 32, 256)), dim3(256), 0, (hipStream_t)stream, val,
+  hipLaunchKernelGGL(k_occ_pack_bits, dim3(nsim_blocks(nvox, 256)), dim3(256), 0, (hipStream_t)stream, val,
                      nvox, thre, bits);
   NSIM_CHECK_LAUNCH();
   return 0;

@@ -1297,7 +1297,10 @@ class LoTDNeuSModel(ModelMixin, nn.Module):
     def ray_test(self, rays_o, rays_d, near=None, far=None, **extra) -> Dict:
         """AABB slab test + compaction of the hit rays (single_volume_renderer.py:235-238); the same call as
         ``model.space.ray_test(**ray_input)`` (app/visualizer/gui_runner_single_cuboid.py:135-138)."""
-        return aabb_ray_test(self.accel.aabb, self.accel.meta, rays_o, rays_d, near=near, far=far, **extra)
+        # (a visible grid's accel spans the cube around the box: ``box_meta`` is the box itself, visible_grid.py)
+        box_meta = getattr(self.accel, "box_meta", None)
+        return aabb_ray_test(self.accel.aabb, self.accel.meta if box_meta is None else box_meta, rays_o, rays_d, near=near, far=far,
+                             **extra)
 
     def _arange_repeat(self, R: int, n: int, dev):
         """arange(R).repeat_interleave(n), cached (ray index of the batched up-sampling points)."""

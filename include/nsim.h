@@ -494,7 +494,9 @@ int nsim_wide_bwd_sdf(const NsimFieldMeta* meta, const void* wpack, const float*
                       const void* J_planes, int64_t plane_pitch, const float* dsdf, const float* gn, float* dh_planes,
                       float* g_planes, float* dsdf_w, float* dsdf_b, void* stream);
 /* (3) LoTD scatter (LoTD backward incl. the dy/dx path): dgrid[level][vertex][f] (f32, atomics) +=
- *     w_c * dh[f] + g[f] * (d w_c/d x . gn).  gn may be NULL (no second-order term).
+ *     w_c * dh[f] + g[f] * (d w_c/d x . gn).  gn may be NULL (no second-order term); g_planes is required (code 28) and
+ *     READ even then -- it must be readable [NLP,S,2] memory holding FINITE values (g * 0 is added: a NaN or Inf there
+ *     poisons the gradient); a caller without a g passes dh_planes in its place (fields/nerf.py).
  *     Levels [level_begin, level_begin + level_count) only (level_count <= 0: all) -- a data-parallel caller scatters
  *     the pyramid in two halves and starts the all-reduce of the first half's gradient while the second is computed. */
 int nsim_lotd_scatter(const NsimLotdMeta* meta, const float* x, const float* rays_o, const float* rays_d,

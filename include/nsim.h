@@ -704,6 +704,76 @@ int nsim_ssim_bwd(const float* x, const float* y, const int64_t* index, int64_t 
  *   d_pred = d total / d pred;  d_nablas [S+M,3] = d total / d nablas.   acc [3] zero on entry. */
 int nsim_train_loss_head(const float* pred, const float* gt, int64_t n_img, const float* nablas, int64_t S, int64_t M,
                          float w_eikonal, float* acc, float* d_pred, float* d_nablas, void* stream);
+/* The supervision losses of the street configs beside rgb and eikonal (withmask_withlidar_joint.240219.yaml:438-500).  Each
+ * reduction adds into an ``out`` the caller zeroes (as eikonal_loss_fwd) and carries its weight ``w``; each forward also writes
+ * the UNSCALED gradient d out / d input, so its backward is ``loss_scale_bwd``: d [n] = gout[0] g [n].
+ *   mask_bce_fwd   replaces MaskOccupancyLoss.forward, app/loss/mask.py:57-103 (F.binary_cross_entropy on the clamped
+ *                  prediction, nr3d_lib's safe_binary_cross_entropy): p = clamp(pred, lo, hi); out[0] += w / N sum of
+ *                  -(gt max(log p, -100) + (1 - gt) max(log(1 - p), -100)) over the rays of ``mode`` -- 0: all, gt as given;
+ *                  1 always_occupied: gt = 1 (gt may be NULL); 2 only_cull_non_occupied: gt < 0.5, against 0; 3
+ *                  only_preserve_occupied: gt > 0.5, against 1.  err [N] = |pred - gt| (0 outside the selection); grad [N]: the
+ *                  clamp passes the gradient where lo <= pred <= hi.
+ *   mask_entropy_* replaces MaskEntropyRegLoss.forward_code_single, app/loss/mask_entropy.py:77-160, for every mode: a mode is a
+ *                  table of up to 4 terms coef A log(max(B, eps)), A and B each one of the masks (source 0 mask_pred, 1 mask_cr,
+ *                  2 mask_dv) or its complement, a detached factor gets no gradient; out[term.out] += mean over N.  The backward
+ *                  re-evaluates the table (two sums, two upstream gradients); max(., eps) passes the gradient where B >= eps.
+ *   sparsity_fwd   replaces SparsityLoss.fn_nld / fn_normal / fn_density_reg, app/loss/sparsity.py:47-54: out[0] += w mean of
+ *                  type 0: 4 s (1 - s), s = sigmoid(param x) | 1: exp(-x^param) | 2: |1 - exp(-param x)| (sub-gradient 0 at 0).
+ *   clearance_fwd  replaces ClearanceLoss.fn_penalty_sdf, app/loss/clearance.py:51-56, without its host read: out[0] += w / M sum
+ *                  over near_sdf < thresh of exp(-beta (near_sdf - thresh)); nothing below the threshold: out stays 0, grad is 0.
+ *   kth_value_f32  out[0] = torch.sort(x).values[k], bit for bit, for finite non-negative x (their bit patterns order as the
+ *                  values): a radix select in ONE workgroup, four 8-bit passes over LDS histograms; replaces the full sort of
+ *                  app/loss/lidar.py:281-283.
+ *   lidar_valid    app/loss/lidar.py:264-266, 280: valid = (mask_pred > mask_pred_thresh) & (ranges > 0), and with discard_toofar >
+ *                  0 additionally & (ranges <= discard_toofar) -- or, toofar_replaces_mask, the reference's literal line :266,
+ *                  valid = ranges <= discard_toofar alone; err = |depth_pred - ranges| valid.
+ *   lidar_loss_fwd app/loss/lidar.py:284-292 with DepthLoss :34-53 and LineOfSightLoss :81-210 (packed buffers): keep = valid &
+ *                  !(err > median[0] * factor) (factor <= 0: keep = valid); acc[0] += w_depth mean over N of fn(pred, ranges) keep;
+ *                  per pack r of the buffer, with g = ranges[rays_inds_hit[r]]: los_fn 1 (nerf, neus_urban) acc[1] += w_los / R
+ *                  keep sum over g - bound <= t <= g + bound of (vw - Normal(t - g; 0, std))^2, acc[2] += ... sum over t < g - bound
+ *                  of vw^2; los_fn 2 (neus_unisim) acc[2] += w_los / R keep sum over |t - g| > bound of vw^2.  member [S]: 0 / 1
+ *                  neighbor / 2 empty.  g_depth [N], g_vw [S]: the unscaled gradients; the packs tile [0, S).
+ *   lidar_loss_bwd d_depth = gout_depth g_depth; d_vw = (gout_neighbor | gout_empty by member) g_vw. */
+typedef struct NsimEntropyTerm {
+  int32_t a_src, a_neg, a_detach;   /* A: source, 1 - source?, detached? */
+  int32_t b_src, b_neg, b_detach;   /* B, inside the log */
+  int32_t out;                      /* 0 or 1 */
+  float coef;
+} NsimEntropyTerm;
+typedef struct NsimEntropyTable {
+  int32_t n_terms;                  /* 0..4 */
+  NsimEntropyTerm t[4];
+} NsimEntropyTable;
+typedef struct NsimLidarLoss {
+  float factor;                     /* discard_outliers_median; <= 0: off */
+  int32_t depth_fn;                 /* -1 none, 0 l1, 1 l1_log, 2 l2, 3 l2_relative, 4 l2_normalized, 5 huber */
+  float depth_param;                /* far (4), alpha (5) */
+  float w_depth;
+  int32_t los_fn;                   /* 0 none, 1 nerf / neus_urban, 2 neus_unisim */
+  float bound;                      /* sigma (1), epsilon (2) */
+  float std;                        /* sigma / sigma_scale_factor (1) */
+  float w_los;
+} NsimLidarLoss;
+int nsim_loss_scale_bwd(const float* g, int64_t n, const float* gout, float* d, void* stream);
+int nsim_mask_bce_fwd(const float* pred, const float* gt, int64_t N, float lo, float hi, int mode, float w, float* out, float* err,
+                      float* grad, void* stream);
+int nsim_mask_entropy_fwd(const NsimEntropyTable* tab, const float* mask_pred, const float* mask_cr, const float* mask_dv,
+                          int64_t N, float eps, float* out, void* stream);
+int nsim_mask_entropy_bwd(const NsimEntropyTable* tab, const float* mask_pred, const float* mask_cr, const float* mask_dv,
+                          int64_t N, float eps, const float* gout0, const float* gout1, float* d_pred, float* d_cr, float* d_dv,
+                          void* stream);
+int nsim_sparsity_fwd(const float* x, int64_t M, int type, float param, float w, float* out, float* grad, void* stream);
+int nsim_clearance_fwd(const float* near_sdf, int64_t M, float beta, float thresh, float w, float* out, float* grad, void* stream);
+int nsim_kth_value_f32(const float* x, int64_t N, int64_t k, float* out, void* stream);
+int nsim_lidar_valid(const float* depth_pred, const float* mask_pred, const float* ranges, int64_t N, float mask_pred_thresh,
+                     float discard_toofar, int toofar_replaces_mask, uint8_t* valid, float* err, void* stream);
+int nsim_lidar_loss_fwd(const NsimLidarLoss* cfg, const float* depth_pred, const float* ranges, const uint8_t* valid,
+                        const float* err, const float* median, int64_t N, const float* t, const float* vw,
+                        const int64_t* rays_inds_hit, const int64_t* pack_infos_hit, int64_t R, int64_t S, float* acc,
+                        uint8_t* keep, float* g_depth, float* g_vw, uint8_t* member, void* stream);
+int nsim_lidar_loss_bwd(const float* g_depth, int64_t N, const float* g_vw, const uint8_t* member, int64_t S,
+                        const float* gout_depth, const float* gout_neighbor, const float* gout_empty, float* d_depth, float* d_vw,
+                        void* stream);
 /* Compaction of the AABB-tested rays, (o, d, near, far)[idx] -> [R,...] in one launch
  * (model.ray_test, app/renderers/single_volume_renderer.py:235-238). */
 int nsim_gather_rays(const float* rays_o, const float* rays_d, const float* near, const float* far, const int64_t* idx,

@@ -91,6 +91,20 @@ class ComposeSrc(C.Structure):      # include/nsim.h NsimComposeSrc
     _fields_ = [("t", C.c_void_p), ("rays_inds", C.c_void_p), ("pack_infos", C.c_void_p), ("P", C.c_int64), ("dst", C.c_void_p)]
 
 
+class EntropyTerm(C.Structure):     # include/nsim.h NsimEntropyTerm
+    _fields_ = [("a_src", C.c_int32), ("a_neg", C.c_int32), ("a_detach", C.c_int32), ("b_src", C.c_int32), ("b_neg", C.c_int32),
+                ("b_detach", C.c_int32), ("out", C.c_int32), ("coef", C.c_float)]
+
+
+class EntropyTable(C.Structure):    # include/nsim.h NsimEntropyTable
+    _fields_ = [("n_terms", C.c_int32), ("t", EntropyTerm * 4)]
+
+
+class LidarLoss(C.Structure):       # include/nsim.h NsimLidarLoss
+    _fields_ = [("factor", C.c_float), ("depth_fn", C.c_int32), ("depth_param", C.c_float), ("w_depth", C.c_float),
+                ("los_fn", C.c_int32), ("bound", C.c_float), ("std", C.c_float), ("w_los", C.c_float)]
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 _I = C.c_int
@@ -185,6 +199,16 @@ SIGNATURES = {
     "nsim_curv_loss_bwd": [_P, _P, _I64, _F, _P, _P, _P],
     "nsim_ssim_fwd": [_P, _P, _P, _I64, _I64, _I, _I, _I, _I, _P, _P],
     "nsim_ssim_bwd": [_P, _P, _P, _I64, _I64, _I, _I, _I, _I, _P, _P, _P],
+    "nsim_loss_scale_bwd": [_P, _I64, _P, _P],
+    "nsim_mask_bce_fwd": [_P, _P, _I64, _F, _F, _I, _F, _P, _P, _P],
+    "nsim_mask_entropy_fwd": [C.POINTER(EntropyTable), _P, _P, _P, _I64, _F, _P],
+    "nsim_mask_entropy_bwd": [C.POINTER(EntropyTable), _P, _P, _P, _I64, _F, _P, _P, _P, _P, _P],
+    "nsim_sparsity_fwd": [_P, _I64, _I, _F, _F, _P, _P],
+    "nsim_clearance_fwd": [_P, _I64, _F, _F, _F, _P, _P],
+    "nsim_kth_value_f32": [_P, _I64, _I64, _P],
+    "nsim_lidar_valid": [_P, _P, _P, _I64, _F, _F, _I, _P, _P],
+    "nsim_lidar_loss_fwd": [C.POINTER(LidarLoss), _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P, _P],
+    "nsim_lidar_loss_bwd": [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P],
     "nsim_mse_loss_fwd": [_P, _P, _I64, _P],
     "nsim_train_loss_head": [_P, _P, _I64, _P, _I64, _I64, _F, _P, _P, _P],
     "nsim_mse_loss_bwd": [_P, _P, _I64, _P, _P],

@@ -8,6 +8,9 @@
 //     app/loss/sdf_curvature.py:42,69,75; the regulariser of PermutoSDF, Rosu & Behnke 2023)
 //   * ssim / s3im: mean SSIM of two images, planar or gathered through an index from [N,3] rows (the virtual image of S3IM,
 //     Xie et al. 2023), gradient to the first    (nr3d_lib.models.loss.ssim.ssim_module under app/loss/perceptual.py:61-70, 142-157)
+//   * the street configs' supervision: occupancy-mask BCE, mask entropy, sparsity, clearance, the lidar depth + line-of-sight loss
+//     with its median outlier gate (an exact order statistic by radix select)   (app/loss/{mask, mask_entropy, sparsity, clearance,
+//     lidar}.py)
 // The reference evaluates these with a handful of torch ops each; here one launch per direction, because at 8192
 // rays per iteration the step is bounded by launch count, not by bytes.
 #include "nsim_common.h"
@@ -489,7 +492,518 @@ static inline dim3 loss_grid(int64_t n) {
   return dim3((unsigned)(b > LOSS_MAX_BLOCKS ? LOSS_MAX_BLOCKS : b));
 }
 
+// elementwise kernels without a reduction: 8 blocks per CU, the rest by grid stride
+static inline dim3 elem_grid(int64_t n) {
+  return dim3(nsim_blocks(n, LOSS_BLOCK, CURV_MAX_BLOCKS));
+}
+
+// ---------------------------------------------------------------------------------------------- street supervision losses
+// The loss blocks of the street configs beside rgb and eikonal (withmask_withlidar_joint.240219.yaml:438-500): occupancy-mask BCE,
+// mask entropy, sparsity, clearance and the lidar loss with its median outlier gate.  Every forward launch also writes the
+// UNSCALED gradient (as k_loss_head: none of them needs the loss value), so a backward is one scale by gout -- except the mask
+// entropy, whose two sums have upstream gradients of their own: its backward re-evaluates the term table.
+
+// several partial sums of one block into out[0..K): one atomic per non-zero sum and block
+template <int K>
+__device__ __forceinline__ void block_sums_atomic(const float (&v)[K], float* out) {
+  __shared__ float red[K][LOSS_BLOCK / 64];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const float s = wave_sum(v[k]);
+    if (nsim_lane() == 0) red[k][threadIdx.x >> 6] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < K) {
+    float tot = 0.f;
+    for (int w = 0; w < LOSS_BLOCK / 64; ++w) tot += red[threadIdx.x][w];
+    if (tot != 0.f) atomicAdd(out + threadIdx.x, tot);
+  }
+}
+
+// d[i] = gout[0] g[i]: the backward of every loss whose forward left its unscaled gradient
+__global__ void __launch_bounds__(LOSS_BLOCK) k_loss_scale(const float* __restrict__ g, int64_t n, const float* __restrict__ gout,
+                                                           float* __restrict__ d) {
+  const float s = gout[0];
+  for (int64_t i = (int64_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * LOSS_BLOCK) d[i] = s * g[i];
+}
+
+// mode 0: gt as given; 1 always_occupied: gt = 1; 2 only_cull_non_occupied: rays with gt < 0.5 against 0; 3 only_preserve_occupied:
+// rays with gt > 0.5 against 1.  The unselected rays of modes 2, 3 add nothing, get no gradient and err 0; the divisor stays N.
+__global__ void __launch_bounds__(LOSS_BLOCK) k_mask_bce(const float* __restrict__ pred, const float* __restrict__ gt, int64_t N,
+                                                         float lo, float hi, int mode, float scale, float* __restrict__ out,
+                                                         float* __restrict__ err, float* __restrict__ grad) {
+  float acc = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; i < N; i += (int64_t)gridDim.x * LOSS_BLOCK) {
+    const float x = pred[i];
+    float y = mode == 1 ? 1.0f : gt[i];
+    bool sel = true;
+    if (mode == 2) sel = y < 0.5f, y = 0.f;
+    if (mode == 3) sel = y > 0.5f, y = 1.0f;
+    float e = 0.f, g = 0.f;
+    if (sel) {
+      const float p = fminf(fmaxf(x, lo), hi);
+      // F.binary_cross_entropy: both logs floored at -100; its backward (p - y) / max(p (1 - p), 1e-12)
+      acc += -(y * fmaxf(logf(p), -100.0f) + (1.0f - y) * fmaxf(logf(1.0f - p), -100.0f));
+      if (x >= lo && x <= hi) g = scale * (p - y) / fmaxf((1.0f - p) * p, 1e-12f);
+      e = fabsf(x - y);
+    }
+    err[i] = e;
+    grad[i] = g;
+  }
+  block_sum_atomic(acc, scale, out);
+}
+
+// One term of a mask-entropy mode: coef * A * log(max(B, eps)) with A, B each one of the three masks m or its complement 1 - m,
+// summed into out[term.out]; a detached factor is a constant of the backward.
+#define ENT_MAX_TERMS 4
+struct EntropyTerm {
+  int32_t a_src, a_neg, a_detach, b_src, b_neg, b_detach, out;
+  float coef;
+};
+struct EntropyTable {
+  int32_t n_terms;
+  EntropyTerm t[ENT_MAX_TERMS];
+};
+
+__device__ __forceinline__ float ent_pick(float v0, float v1, float v2, int src, int neg) {
+  const float v = src == 0 ? v0 : (src == 1 ? v1 : v2);
+  return neg ? 1.0f - v : v;
+}
+
+__global__ void __launch_bounds__(LOSS_BLOCK) k_mask_entropy_fwd(EntropyTable tab, const float* __restrict__ m0,
+                                                                 const float* __restrict__ m1, const float* __restrict__ m2,
+                                                                 int64_t N, float eps, float inv_n, float* __restrict__ out) {
+  float acc[2] = {0.f, 0.f};
+  for (int64_t i = (int64_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; i < N; i += (int64_t)gridDim.x * LOSS_BLOCK) {
+    const float v0 = m0 ? m0[i] : 0.f, v1 = m1 ? m1[i] : 0.f, v2 = m2 ? m2[i] : 0.f;
+    for (int k = 0; k < tab.n_terms; ++k) {
+      const EntropyTerm& t = tab.t[k];
+      const float a = ent_pick(v0, v1, v2, t.a_src, t.a_neg), b = ent_pick(v0, v1, v2, t.b_src, t.b_neg);
+      const float term = t.coef * inv_n * (a * logf(fmaxf(b, eps)));
+      if (t.out) acc[1] += term;
+      else acc[0] += term;
+    }
+  }
+  block_sums_atomic<2>(acc, out);
+}
+
+// d0 / d1 / d2 [N] (NULL: not wanted) = gout_k d out[k] / d mask; clamp_min passes the gradient where its argument >= eps
+__global__ void __launch_bounds__(LOSS_BLOCK) k_mask_entropy_bwd(EntropyTable tab, const float* __restrict__ m0,
+                                                                 const float* __restrict__ m1, const float* __restrict__ m2,
+                                                                 int64_t N, float eps, float inv_n, const float* __restrict__ gout0,
+                                                                 const float* __restrict__ gout1, float* __restrict__ d0,
+                                                                 float* __restrict__ d1, float* __restrict__ d2) {
+  const float go0 = gout0 ? gout0[0] * inv_n : 0.f, go1 = gout1 ? gout1[0] * inv_n : 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; i < N; i += (int64_t)gridDim.x * LOSS_BLOCK) {
+    const float v0 = m0 ? m0[i] : 0.f, v1 = m1 ? m1[i] : 0.f, v2 = m2 ? m2[i] : 0.f;
+    float e0 = 0.f, e1 = 0.f, e2 = 0.f;
+    for (int k = 0; k < tab.n_terms; ++k) {
+      const EntropyTerm& t = tab.t[k];
+      const float a = ent_pick(v0, v1, v2, t.a_src, t.a_neg), b = ent_pick(v0, v1, v2, t.b_src, t.b_neg);
+      const float c = (t.out ? go1 : go0) * t.coef;
+      if (!t.a_detach) {
+        const float g = (t.a_neg ? -c : c) * logf(fmaxf(b, eps));
+        e0 += t.a_src == 0 ? g : 0.f, e1 += t.a_src == 1 ? g : 0.f, e2 += t.a_src == 2 ? g : 0.f;
+      }
+      if (!t.b_detach && b >= eps) {
+        const float g = (t.b_neg ? -c : c) * a / b;
+        e0 += t.b_src == 0 ? g : 0.f, e1 += t.b_src == 1 ? g : 0.f, e2 += t.b_src == 2 ? g : 0.f;
+      }
+    }
+    if (d0) d0[i] = e0;
+    if (d1) d1[i] = e1;
+    if (d2) d2[i] = e2;
+  }
+}
+
+// type 0 normalized_logistic_density 4 s(1 - s), s = sigmoid(param x); 1 normal exp(-x^param); 2 density_reg |1 - exp(-param x)|
+__global__ void __launch_bounds__(LOSS_BLOCK) k_sparsity(const float* __restrict__ x, int64_t M, int type, float param, float scale,
+                                                         float* __restrict__ out, float* __restrict__ grad) {
+  float acc = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; i < M; i += (int64_t)gridDim.x * LOSS_BLOCK) {
+    const float v = x[i];
+    float f, g;
+    if (type == 0) {
+      const float s = 1.0f / (1.0f + expf(-param * v));
+      f = 4.0f * s * (1.0f - s);
+      g = param * f * (1.0f - 2.0f * s);
+    } else if (type == 1) {
+      f = expf(-powf(v, param));
+      g = param == 0.f ? 0.f : -param * powf(v, param - 1.0f) * f;      // torch.pow's backward: 0 for a zero exponent
+    } else {
+      const float e = expf(-param * v), r = 1.0f - e;
+      f = fabsf(r);
+      g = r > 0.f ? param * e : (r < 0.f ? -param * e : 0.f);          // abs: sub-gradient 0 at 0
+    }
+    acc += f;
+    grad[i] = scale * g;
+  }
+  block_sum_atomic(acc, scale, out);
+}
+
+// sum over near_sdf < thresh of exp(-beta (near_sdf - thresh)) / M: no point below the threshold adds nothing to the caller's zero
+__global__ void __launch_bounds__(LOSS_BLOCK) k_clearance(const float* __restrict__ x, int64_t M, float beta, float thresh,
+                                                          float scale, float* __restrict__ out, float* __restrict__ grad) {
+  float acc = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; i < M; i += (int64_t)gridDim.x * LOSS_BLOCK) {
+    const float v = x[i];
+    float g = 0.f;
+    if (v < thresh) {
+      const float e = expf(-beta * (v - thresh));
+      acc += e;
+      g = -beta * scale * e;
+    }
+    grad[i] = g;
+  }
+  block_sum_atomic(acc, scale, out);
+}
+
+// The k-th smallest of x [N] (0-based), exactly: a radix select over the bit pattern, which orders non-negative floats as their
+// values.  ONE workgroup, four passes of eight bits from the top: an LDS histogram of the digit among the elements that share the
+// digits fixed so far, then thread 0 walks its 256 bins to the one that holds rank k.  Every loop is bounded by N or 256.
+__global__ void __launch_bounds__(LOSS_BLOCK) k_kth_value(const float* __restrict__ x, int64_t N, int64_t k, float* __restrict__ out) {
+  __shared__ unsigned hist[256];
+  __shared__ unsigned s_prefix, s_k;
+  if (threadIdx.x == 0) s_prefix = 0u, s_k = (unsigned)k;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    hist[threadIdx.x] = 0u;                       // LOSS_BLOCK == 256 bins
+    __syncthreads();
+    const unsigned prefix = s_prefix;
+    const unsigned fixed = shift == 24 ? 0u : (0xffffffffu << (shift + 8));
+    for (int64_t i = threadIdx.x; i < N; i += LOSS_BLOCK) {
+      unsigned b;
+      const float v = x[i];
+      __builtin_memcpy(&b, &v, 4);
+      if ((b & fixed) == prefix) atomicAdd(&hist[(b >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned left = s_k, bin = 255u;
+      for (unsigned j = 0; j < 256u; ++j) {
+        if (left < hist[j]) {
+          bin = j;
+          break;
+        }
+        left -= hist[j];
+      }
+      s_k = left;
+      s_prefix = prefix | (bin << shift);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const unsigned b = s_prefix;
+    float v;
+    __builtin_memcpy(&v, &b, 4);
+    out[0] = v;
+  }
+}
+
+// per beam: is it a return the rendering saw, and its absolute depth error (0 for the others) -- the input of the median
+__global__ void __launch_bounds__(LOSS_BLOCK) k_lidar_valid(const float* __restrict__ depth, const float* __restrict__ mask,
+                                                            const float* __restrict__ ranges, int64_t N, float mask_thresh,
+                                                            float toofar, int replaces, uint8_t* __restrict__ valid,
+                                                            float* __restrict__ err) {
+  for (int64_t i = (int64_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; i < N; i += (int64_t)gridDim.x * LOSS_BLOCK) {
+    const float r = ranges[i];
+    bool v = mask[i] > mask_thresh && r > 0.f;
+    if (toofar > 0.f) v = replaces ? r <= toofar : (v && r <= toofar);
+    valid[i] = v ? 1 : 0;
+    err[i] = fabsf(depth[i] - r) * (v ? 1.0f : 0.f);
+  }
+}
+
+struct LidarArgs {
+  const float* depth;          // [N]
+  const float* ranges;         // [N]
+  const uint8_t* valid;        // [N]
+  const float* err;            // [N]
+  const float* median;         // [1], read when factor > 0
+  int64_t N;
+  float factor;                // discard_outliers_median
+  int depth_fn;                // -1 none, 0 l1, 1 l1_log, 2 l2, 3 l2_relative, 4 l2_normalized, 5 huber
+  float depth_param;           // far (4), alpha (5)
+  float w_depth;
+  int los_fn;                  // 0 none, 1 nerf / neus_urban, 2 neus_unisim
+  float bound;                 // sigma (1), epsilon (2)
+  float std;                   // sigma / sigma_scale_factor (1)
+  float w_los;
+  const float* t;              // [S]
+  const float* vw;             // [S]
+  const int64_t* rays_inds;    // [R]
+  const int64_t* pack_infos;   // [R, 2]
+  int64_t R, S;
+  float* acc;                  // [3]: depth, los.neighbor, los.empty (weighted)
+  uint8_t* keep;               // [N]: the final mask
+  float* g_depth;              // [N]
+  float* g_vw;                 // [S]
+  uint8_t* member;             // [S]: 0 no term, 1 neighbor, 2 empty
+};
+
+__device__ __forceinline__ bool lidar_keep(const LidarArgs& a, int64_t i, float thr) {
+  return a.valid[i] && !(a.factor > 0.f && a.err[i] > thr);
+}
+
+// Blocks [0, depth_blocks) walk the beams, the others the packs of the line-of-sight buffer, one wave per pack.  Both halves form
+// the final mask of a beam from (valid, err, median) themselves, so neither waits for the other.
+__global__ void __launch_bounds__(LOSS_BLOCK) k_lidar_loss(LidarArgs a, int depth_blocks) {
+  const float thr = a.factor > 0.f ? a.median[0] * a.factor : 0.f;        // the product in f32, as the reference forms it
+  float acc[3] = {0.f, 0.f, 0.f};
+  if ((int)blockIdx.x < depth_blocks) {
+    const float sc = a.w_depth / (float)a.N;
+    for (int64_t i = (int64_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; i < a.N; i += (int64_t)depth_blocks * LOSS_BLOCK) {
+      const bool m = lidar_keep(a, i, thr);
+      a.keep[i] = m ? 1 : 0;
+      if (a.depth_fn < 0) continue;
+      const float mf = m ? 1.0f : 0.f, p = a.depth[i], g = a.ranges[i];
+      float f, df;
+      switch (a.depth_fn) {
+        case 0: {
+          const float d = p - g;
+          f = fabsf(d), df = d > 0.f ? 1.0f : (d < 0.f ? -1.0f : 0.f);
+        } break;
+        case 1: {
+          // log(p + 1) - log(g + 1) as log1p((p - g) / (g + 1)): the difference is taken between the INPUTS -- two logs of ~3
+          // that differ by ~1e-2 lose 1e-5 of the term in f32 (p, g >= 0: the same real number)
+          const float d = log1pf((p - g) / (g + 1.0f));
+          f = fabsf(d), df = (d > 0.f ? 1.0f : (d < 0.f ? -1.0f : 0.f)) / (p + 1.0f);
+        } break;
+        case 2: {
+          const float d = p - g;
+          f = d * d, df = 2.0f * d;
+        } break;
+        case 3: {
+          const float d = p - g, q = g * g + 1e-2f;
+          f = d * d / q, df = 2.0f * d / q;
+        } break;
+        case 4: {
+          const float d = (p - g) / a.depth_param;        // p / far - g / far, the difference taken between the inputs
+          f = d * d, df = 2.0f * d / a.depth_param;
+        } break;
+        default: {
+          const float d = p - g, ad = fabsf(d), al = a.depth_param;
+          f = ad < al ? 0.5f * d * d : al * (ad - 0.5f * al);
+          df = ad < al ? d : (d > 0.f ? al : -al);
+        } break;
+      }
+      acc[0] += f * mf;
+      a.g_depth[i] = sc * df * mf;
+    }
+    acc[0] *= sc;
+  } else if (a.los_fn != 0) {
+    const float sc = a.w_los / (float)a.R;
+    const int lane = nsim_lane();
+    const int64_t wave = (int64_t)((int)blockIdx.x - depth_blocks) * (LOSS_BLOCK / 64) + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)((int)gridDim.x - depth_blocks) * (LOSS_BLOCK / 64);
+    const float inv_norm = 1.0f / (a.std * 2.5066282746310002f);           // 1 / (std sqrt(2 pi))
+    for (int64_t r = wave; r < a.R; r += n_waves) {
+      const int64_t ray = a.rays_inds[r], begin = a.pack_infos[2 * r], cnt = a.pack_infos[2 * r + 1];
+      const bool in = ray >= 0 && ray < a.N;
+      const float g = in ? a.ranges[ray] : 0.f;
+      const float mf = (in && lidar_keep(a, ray, thr)) ? 1.0f : 0.f;
+      for (int64_t j = begin + lane; j < begin + cnt; j += 64) {
+        if (j < 0 || j >= a.S) continue;
+        const float t = a.t[j], w = a.vw[j];
+        uint8_t mem = 0;
+        float gv = 0.f;
+        if (a.los_fn == 1) {
+          if (t <= g + a.bound && t >= g - a.bound) {
+            const float z = (t - g) / a.std, d = w - inv_norm * expf(-0.5f * z * z);
+            mem = 1, acc[1] += d * d * mf, gv = 2.0f * d;
+          } else if (t < g - a.bound) {
+            mem = 2, acc[2] += w * w * mf, gv = 2.0f * w;
+          }
+        } else if (fabsf(t - g) > a.bound) {
+          mem = 2, acc[2] += w * w * mf, gv = 2.0f * w;
+        }
+        a.member[j] = mem;
+        a.g_vw[j] = sc * gv * mf;
+      }
+    }
+    acc[1] *= sc;
+    acc[2] *= sc;
+  }
+  block_sums_atomic<3>(acc, a.acc);
+}
+
+// d_depth = gout[0] g_depth; d_vw = gout[member] g_vw (a NULL gout: that term is not part of the graph)
+__global__ void __launch_bounds__(LOSS_BLOCK) k_lidar_loss_bwd(const float* __restrict__ g_depth, int64_t N,
+                                                               const float* __restrict__ g_vw, const uint8_t* __restrict__ member,
+                                                               int64_t S, const float* __restrict__ go_depth,
+                                                               const float* __restrict__ go_nb, const float* __restrict__ go_em,
+                                                               float* __restrict__ d_depth, float* __restrict__ d_vw) {
+  const float s0 = go_depth ? go_depth[0] : 0.f, s1 = go_nb ? go_nb[0] : 0.f, s2 = go_em ? go_em[0] : 0.f;
+  const int64_t top = N > S ? N : S;
+  for (int64_t i = (int64_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; i < top; i += (int64_t)gridDim.x * LOSS_BLOCK) {
+    if (d_depth && i < N) d_depth[i] = s0 * g_depth[i];
+    if (d_vw && i < S) {
+      const uint8_t m = member[i];
+      d_vw[i] = m == 1 ? s1 * g_vw[i] : (m == 2 ? s2 * g_vw[i] : 0.f);
+    }
+  }
+}
+
 extern "C" {
+
+// d [n] = gout[0] g [n]
+int nsim_loss_scale_bwd(const float* g, int64_t n, const float* gout, float* d, void* stream) {
+  if (n < 0) return 2;
+  if (n == 0) return 0;
+  if (!g || !gout || !d) return 26;
+  hipLaunchKernelGGL(k_loss_scale, elem_grid(n), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, g, n, gout, d);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+// out[0] must be zero on entry; out[0] += w / N sum of the selected rays' BCE; err [N], grad [N] = w d mean / d pred are written
+int nsim_mask_bce_fwd(const float* pred, const float* gt, int64_t N, float lo, float hi, int mode, float w, float* out, float* err,
+                      float* grad, void* stream) {
+  if (N < 0) return 2;
+  if (mode < 0 || mode > 3 || !(lo <= hi)) return 58;
+  if (!out) return 4;
+  if (N == 0) return 0;
+  if (!pred || (!gt && mode != 1) || !err || !grad) return 4;
+  hipLaunchKernelGGL(k_mask_bce, loss_grid(N), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, pred, gt, N, lo, hi, mode, w / (float)N,
+                     out, err, grad);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+static inline int entropy_table(EntropyTable* t, const NsimEntropyTable* tab, const float* const* m) {
+  if (!tab || tab->n_terms < 0 || tab->n_terms > ENT_MAX_TERMS) return 58;
+  t->n_terms = tab->n_terms;
+  for (int k = 0; k < tab->n_terms; ++k) {
+    const NsimEntropyTerm& s = tab->t[k];
+    if (s.a_src < 0 || s.a_src > 2 || s.b_src < 0 || s.b_src > 2 || s.out < 0 || s.out > 1) return 58;
+    if (!m[s.a_src] || !m[s.b_src]) return 4;
+    EntropyTerm& d = t->t[k];
+    d.a_src = s.a_src, d.a_neg = s.a_neg, d.a_detach = s.a_detach, d.b_src = s.b_src, d.b_neg = s.b_neg, d.b_detach = s.b_detach;
+    d.out = s.out, d.coef = s.coef;
+  }
+  return 0;
+}
+
+// out [2] must be zero on entry; masks a table term does not name may be NULL
+int nsim_mask_entropy_fwd(const NsimEntropyTable* tab, const float* mask_pred, const float* mask_cr, const float* mask_dv,
+                          int64_t N, float eps, float* out, void* stream) {
+  if (N < 0) return 2;
+  const float* m[3] = {mask_pred, mask_cr, mask_dv};
+  EntropyTable t;
+  const int rc = entropy_table(&t, tab, m);
+  if (rc) return rc;
+  if (!out) return 4;
+  if (N == 0 || t.n_terms == 0) return 0;
+  hipLaunchKernelGGL(k_mask_entropy_fwd, loss_grid(N), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, t, m[0], m[1], m[2], N, eps,
+                     1.0f / (float)N, out);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+// gout0 / gout1 [1]: the upstream gradients of out[0] / out[1] (NULL: zero); d_pred / d_cr / d_dv [N]: any may be NULL
+int nsim_mask_entropy_bwd(const NsimEntropyTable* tab, const float* mask_pred, const float* mask_cr, const float* mask_dv,
+                          int64_t N, float eps, const float* gout0, const float* gout1, float* d_pred, float* d_cr, float* d_dv,
+                          void* stream) {
+  if (N < 0) return 2;
+  const float* m[3] = {mask_pred, mask_cr, mask_dv};
+  EntropyTable t;
+  const int rc = entropy_table(&t, tab, m);
+  if (rc) return rc;
+  if (N == 0 || (!d_pred && !d_cr && !d_dv)) return 0;
+  hipLaunchKernelGGL(k_mask_entropy_bwd, elem_grid(N), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, t, m[0], m[1], m[2], N, eps,
+                     1.0f / (float)N, gout0, gout1, d_pred, d_cr, d_dv);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+// out[0] must be zero on entry; out[0] += w mean(f(x)); grad [M] = w d mean / d x
+int nsim_sparsity_fwd(const float* x, int64_t M, int type, float param, float w, float* out, float* grad, void* stream) {
+  if (M < 0) return 2;
+  if (type < 0 || type > 2) return 58;
+  if (!out) return 4;
+  if (M == 0) return 0;
+  if (!x || !grad) return 4;
+  hipLaunchKernelGGL(k_sparsity, loss_grid(M), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, x, M, type, param, w / (float)M, out,
+                     grad);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+// out[0] must be zero on entry; out[0] += w / M sum over near_sdf < thresh of exp(-beta (near_sdf - thresh)); grad [M] written
+int nsim_clearance_fwd(const float* near_sdf, int64_t M, float beta, float thresh, float w, float* out, float* grad, void* stream) {
+  if (M < 0) return 2;
+  if (!out) return 4;
+  if (M == 0) return 0;
+  if (!near_sdf || !grad) return 4;
+  hipLaunchKernelGGL(k_clearance, loss_grid(M), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, near_sdf, M, beta, thresh,
+                     w / (float)M, out, grad);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+// out[0] = sort(x)[k] for finite non-negative x [N], 0 <= k < N < 2^32; one workgroup, the value stays on the device
+int nsim_kth_value_f32(const float* x, int64_t N, int64_t k, float* out, void* stream) {
+  if (N < 0) return 2;
+  if (N == 0 || k < 0 || k >= N || N >= ((int64_t)1 << 32)) return 58;
+  if (!x || !out) return 4;
+  hipLaunchKernelGGL(k_kth_value, dim3(1), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, x, N, k, out);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+// valid [N] uint8, err [N] = |depth_pred - ranges| valid.  discard_toofar <= 0: no range gate
+int nsim_lidar_valid(const float* depth_pred, const float* mask_pred, const float* ranges, int64_t N, float mask_pred_thresh,
+                     float discard_toofar, int toofar_replaces_mask, uint8_t* valid, float* err, void* stream) {
+  if (N < 0) return 2;
+  if (N == 0) return 0;
+  if (!depth_pred || !mask_pred || !ranges || !valid || !err) return 4;
+  hipLaunchKernelGGL(k_lidar_valid, loss_grid(N), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, depth_pred, mask_pred, ranges, N,
+                     mask_pred_thresh, discard_toofar, toofar_replaces_mask, valid, err);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+// acc [3] must be zero on entry.  The packs of pack_infos_hit tile [0, S): every element of g_vw / member is written.
+int nsim_lidar_loss_fwd(const NsimLidarLoss* cfg, const float* depth_pred, const float* ranges, const uint8_t* valid,
+                        const float* err, const float* median, int64_t N, const float* t, const float* vw,
+                        const int64_t* rays_inds_hit, const int64_t* pack_infos_hit, int64_t R, int64_t S, float* acc,
+                        uint8_t* keep, float* g_depth, float* g_vw, uint8_t* member, void* stream) {
+  if (N < 0 || R < 0 || S < 0) return 2;
+  if (!cfg || cfg->depth_fn < -1 || cfg->depth_fn > 5 || cfg->los_fn < 0 || cfg->los_fn > 2) return 58;
+  if (cfg->depth_fn == 4 && !(cfg->depth_param > 0.f)) return 58;
+  if (cfg->los_fn == 1 && !(cfg->std > 0.f)) return 58;
+  if (!acc) return 4;
+  if (N == 0) return 0;
+  if (!depth_pred || !ranges || !valid || !err || !keep || (cfg->factor > 0.f && !median)) return 4;
+  if (cfg->depth_fn >= 0 && !g_depth) return 4;
+  const bool los = cfg->los_fn != 0 && R > 0 && S > 0;
+  if (los && (!t || !vw || !rays_inds_hit || !pack_infos_hit || !g_vw || !member)) return 4;
+  LidarArgs a;
+  a.depth = depth_pred, a.ranges = ranges, a.valid = valid, a.err = err, a.median = median, a.N = N;
+  a.factor = cfg->factor, a.depth_fn = cfg->depth_fn, a.depth_param = cfg->depth_param, a.w_depth = cfg->w_depth;
+  a.los_fn = los ? cfg->los_fn : 0, a.bound = cfg->bound, a.std = cfg->std, a.w_los = cfg->w_los;
+  a.t = t, a.vw = vw, a.rays_inds = rays_inds_hit, a.pack_infos = pack_infos_hit, a.R = R, a.S = S;
+  a.acc = acc, a.keep = keep, a.g_depth = g_depth, a.g_vw = g_vw, a.member = member;
+  const int db = (int)loss_grid(N).x;
+  const int lb = los ? (int)loss_grid(R * 64).x : 0;
+  hipLaunchKernelGGL(k_lidar_loss, dim3((unsigned)(db + lb)), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, a, db);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+// d_depth [N] / d_vw [S] (either may be NULL) from the forward's g_depth, g_vw, member and the three upstream gradients (NULL: 0)
+int nsim_lidar_loss_bwd(const float* g_depth, int64_t N, const float* g_vw, const uint8_t* member, int64_t S,
+                        const float* gout_depth, const float* gout_neighbor, const float* gout_empty, float* d_depth, float* d_vw,
+                        void* stream) {
+  if (N < 0 || S < 0) return 2;
+  if (d_depth && !g_depth) return 26;
+  if (d_vw && (!g_vw || !member)) return 26;
+  const int64_t top = (d_depth ? N : 0) > (d_vw ? S : 0) ? N : (d_vw ? S : 0);
+  if (top == 0) return 0;
+  hipLaunchKernelGGL(k_lidar_loss_bwd, elem_grid(top), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, g_depth, d_depth ? N : 0, g_vw,
+                     member, d_vw ? S : 0, gout_depth, gout_neighbor, gout_empty, d_depth, d_vw);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
 
 // out[0] must be zero on entry (the caller's memset is part of the op); out[0] += mean((|nab_i| - 1)^2)
 int nsim_eikonal_loss_fwd(const float* nablas, int64_t S, float* out, void* stream) {

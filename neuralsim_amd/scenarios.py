@@ -150,6 +150,22 @@ def render_dataset(world: AnalyticWorld, intr, c2w, WH, with_mono: bool = False,
     return (img, dep, nrm) if with_mono else img
 
 
+def render_occupancy_masks(world: AnalyticWorld, intr, c2w, WH, chunk: int = 2 ** 18):
+    """The dataset's ``image_occupancy_mask`` [V,H,W] f32 (1 = the pixel sees the scene, 0 = sky): ``world.trace(...)['hit']`` from
+    every camera, resident on the cameras' device (what the "withmask" street configs supervise ``mask_volume`` with)."""
+    from .eval import all_pixel_xy
+    V, dev = intr.shape[0], intr.device
+    W, H = int(WH[0, 0]), int(WH[0, 1])
+    xy = all_pixel_xy(W, H, dev)
+    out = torch.empty([V, H, W], dtype=torch.float32, device=dev)
+    for f in range(V):
+        for s in range(0, xy.shape[0], chunk):
+            q = xy[s:s + chunk]
+            o, d = selected_rays(q, torch.full([q.shape[0]], f, dtype=torch.long, device=dev), intr, c2w, WH)
+            out[f].view(-1)[s:s + chunk] = world.trace(o, d)["hit"].float()
+    return out
+
+
 def _pose(eye, fwd, world_up=(0.0, 0.0, 1.0)):
     """OpenCV camera-to-world (+x right, +y down, +z forward) at ``eye`` looking along ``fwd``."""
     fwd = F.normalize(torch.as_tensor(fwd, dtype=torch.float32), dim=0)
@@ -286,7 +302,9 @@ def street_lidar(world: AnalyticWorld, n_ego: int = 10, beams: int = 16384, x_ra
 
 def build_street_trainer(device, rank: int = 0, world_size: int = 1, precision: str = "fp16", rays_per_gpu: int = 16384,
                          seed: int = 42, small: bool = False, num_uniform: Optional[int] = None, n_ego: int = None,
-                         lidar_rays: int = 0):
+                         lidar_rays: int = 0, loss_cfg: Optional[dict] = None):
+    """``loss_cfg``: the yaml's remaining loss blocks (``RenderTrainer(loss_cfg=)``; ``STREET_LOSS_CFG`` is the config's own);
+    with one the dataset also carries the occupancy masks.  None: the trainer as it always was."""
     from . import distributed as ndist
     from .trainer import RenderTrainer
     world = street_world()
@@ -306,7 +324,26 @@ def build_street_trainer(device, rank: int = 0, world_size: int = 1, precision: 
                      discard_toofar=80.0, near=0.1, far=200.0)
     return RenderTrainer(m, intr, c2w, WH, num_rays=rays_per_gpu, lr=1e-3, w_eikonal=0.01, num_uniform=num_uniform,
                          near=0.1, far=200.0, rank=rank, world_size=world_size, seed=seed, learn_inv_s=False,
-                         distant_model=dm, sky_model=sm, target_images=images, rgb_fn="l1", lidar=lidar)
+                         distant_model=dm, sky_model=sm, target_images=images, rgb_fn="l1", lidar=lidar,
+                         loss_cfg=loss_cfg, target_masks=render_occupancy_masks(world, intr, c2w, WH) if loss_cfg else None)
+
+
+# the loss blocks of withmask_withlidar_joint.240219.yaml:438-508 beside rgb and eikonal, its interpolations resolved with the
+# config's own values (w_mask 0.3, w_lidar 0.02, lidar_fn l1, w_los 0.1, sparsity_enable_after 0 + anneal over 1000, w_sparsity
+# 0.002, clw 0.2, clbeta 10, clearance_sdf 0.02: yaml:27-53)
+STREET_LOSS_CFG = dict(
+    occupancy_mask=dict(w=0.3, safe_bce=True, pred_clip=0),
+    mask_entropy=dict(w=0.005, mode="crisp_cr", enable_after=2000,
+                      anneal=dict(type="linear", start_it=2000, stop_it=5000, start_val=0, stop_val=0.005, update_every=100)),
+    lidar=dict(discard_outliers=0, discard_outliers_median=100.0, discard_toofar=80.0, depth=dict(w=0.02, fn_type="l1", fn_param={}),
+               line_of_sight=dict(w=0.1, fn_type="neus_unisim",
+                                  fn_param=dict(epsilon_anneal=dict(type="milestones", milestones=[5000, 10000], vals=[1.5, 0.75, 0.5])))),
+    sparsity=dict(enable_after=0, class_name_cfgs=dict(Street=dict(
+        key="sdf", type="normalized_logistic_density", inv_scale=16.0, w=2.0e-3,
+        anneal=dict(type="linear", start_it=0, start_val=0, stop_it=1000, stop_val=2.0e-3, update_every=100)))),
+    clearance=dict(class_name_cfgs=dict(Street=dict(w=0.2, beta=10.0, thresh=0.02))),
+    weight_reg=dict(class_name_cfgs=dict(Street=dict(norm_type=2.0, w=1.0e-6), Distant=dict(norm_type=2.0, w=1.0e-6))),
+)
 
 
 # ------------------------------------------------------------------------------------------------ indoor (configs[2])

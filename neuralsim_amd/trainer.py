@@ -8,6 +8,7 @@ Follows ``Trainer.train_step_pixel`` and the main loop of the reference
 embeddings (app/models/scene/image_embeddings.py:23-80).  Data is synthetic (posed pinhole cameras of
 SURVEY.md sec. 8d; targets = the analytic image of the synthetic sphere, or random colours).
 """
+from collections.abc import Mapping
 from typing import Dict, Optional
 
 import torch
@@ -34,7 +35,8 @@ class RenderTrainer:
                  distortion: Optional[torch.Tensor] = None, target_images: Optional[torch.Tensor] = None,
                  mono: Optional[dict] = None, rgb_fn: str = "mse", lidar: Optional[dict] = None, w_curvature: float = 0.0,
                  curvature_eps: float = 1.0e-4, pixel_sample_mode: str = "uniform", error_map: Optional[dict] = None,
-                 w_s3im: float = 0.0, s3im: Optional[dict] = None):
+                 w_s3im: float = 0.0, s3im: Optional[dict] = None, target_masks: Optional[torch.Tensor] = None,
+                 loss_cfg: Optional[dict] = None, main_class_name: str = "Street"):
         """pose_refine: ``dict(lr=1e-4, start_it=500)`` -- per-frame pose corrections (an axis-angle rotation and a
         translation, ``c2w' = [R Exp(w) | T + dT]``) trained through the rays from ``start_it`` on, standing in for the
         reference's ``LearnableParams`` (withmask_withlidar_joint.240219.yaml:338-352; the parametrisation of the
@@ -74,8 +76,21 @@ class RenderTrainer:
         ``repeat_time - 1`` permutations -- is drawn from the trainer's generator every step.  The term is
         ``w_s3im * (1 - SSIM)``, reported as ``loss_parts['rgb_s3im']`` (weighted, as the reference reports it).  With ``w_s3im > 0``
         the step takes the generic autograd path (the fused launch chain does not carry the term); with 0 nothing is drawn and
-        nothing changes."""
+        nothing changes.
+        loss_cfg: the street yaml's remaining loss blocks (withmask_withlidar_joint.240219.yaml:438-508), any of ``occupancy_mask``,
+        ``mask_entropy``, ``sparsity``, ``clearance``, ``weight_reg``, ``lidar`` in the yaml's own form (``class_name_cfgs: {Street:
+        {...}, Distant: {...}}``, ``enable_after``, ``anneal``), evaluated by the fused ops of ``losses.py``.  Pixel
+        step: mask BCE of ``mask_volume`` against ``target_masks`` [V,H,W] (gathered per batch like ``target_images``), the entropy of
+        the masks of the main / the distant model, sparsity on the uniform points' ``sdf``, clearance on ``details['near_sdf']``
+        (``with_near_sdf`` is switched on in the render call only when the block is there), weight regularisation through
+        ``get_weight_reg``.  Lidar step: ``loss_cfg['lidar']`` replaces ``lidar_losses`` by ``losses.lidar_loss`` and adds sparsity,
+        clearance and weight regularisation (train.py:929-954; the weight term there covers the tensors of the lidar graph only, so
+        the radiance side keeps its optimizer state).  The terms are reported in ``loss_parts`` / ``_lidar_parts`` under the
+        reference's keys as detached device scalars.  ``main_class_name``: the class the main model's blocks are looked up under;
+        the distant model's is ``Distant``.  With a ``loss_cfg`` the step takes the autograd path; None changes nothing."""
         self.model = model
+        self.target_masks, self.main_class_name = target_masks, str(main_class_name)
+        self.loss_cfg = self._check_loss_cfg(loss_cfg, distant_model, num_uniform, target_masks)
         self.num_rays = num_rays             # rays per rank per iteration (weak scaling, as the reference's DDP)
         self.use_s3im(w_s3im, s3im)
         if pixel_sample_mode not in ("uniform", "error_map"):
@@ -211,6 +226,8 @@ class RenderTrainer:
             self._last_aux = None
             if self.mono is not None:
                 self._last_aux = dict(depth=self.mono["depth"][fidx, iy, ix], normals=self.mono["normals"][fidx, iy, ix])
+            if self.target_masks is not None and self.loss_cfg is not None:
+                self._last_aux = dict(self._last_aux or {}, mask=self.target_masks[fidx, iy, ix], mask_of=xy)
             return xy, fidx, self.target_images[fidx, iy, ix]
         if self.target_sphere_radius is None:
             gt = torch.rand([N, 3], device=dev, generator=self.gen)
@@ -238,6 +255,8 @@ class RenderTrainer:
         ``batch``: a prefetched batch (``_make_batch``): rays and AABB test are already there, and the prefetch of
         the NEXT batch is queued right before this render's blocking sample-count read."""
         bypass = dict(_extra_pts=extra_pts) if extra_pts is not None else {}
+        if self.loss_cfg is not None and "clearance" in self.loss_cfg:
+            bypass["with_near_sdf"] = True          # ``renderer._config_train.with_near_sdf`` (train.py:244-245)
         tested = None
         if batch is not None:
             rays_o, rays_d, tested = batch["rays_o"], batch["rays_d"], dict(batch["tested"])
@@ -271,7 +290,7 @@ class RenderTrainer:
         plain = type(m) is LoTDNeuSModel or (type(m).__name__ == "PermutoNeuSModel" and getattr(m, "z_dim", 0) == 0)
         return (self.fused_step and plain and not getattr(m, "pos_embed_E", 0) and self.distant_model is None and self.sky_model is None
                 and not self.pose_refine_active() and getattr(m, "_ctrl_mix", 0.0) == 0.0 and self.mono is None
-                and self.rgb_fn == "mse" and self.w_curvature <= 0.0 and self.w_s3im <= 0)
+                and self.rgb_fn == "mse" and self.w_curvature <= 0.0 and self.w_s3im <= 0 and self.loss_cfg is None)
 
     def _train_render_fused(self, batch: dict) -> Optional[torch.Tensor]:
         """render + loss + backward of one prefetched batch WITHOUT the autograd engine: the launches the autograd path
@@ -701,7 +720,128 @@ class RenderTrainer:
             index = s3im_index(ph * pw, c["repeat_time"], gt.device, generator=self.gen)
             term = self.w_s3im * s3im_loss(ret["rendered"]["rgb_volume"], gt, index, (ph, pw), c["kernel_size"], c["stride"])
             total, parts["rgb_s3im"] = total + term, term.detach()
+        if self.loss_cfg is not None:
+            terms = self._street_terms(ret, self._it, "pixel", uni=uni, mask_gt=None if aux is None else aux.get("mask"))
+            for k, v in terms.items():
+                total, parts[k] = total + v, v.detach()
         return total, parts
+
+    # ------------------------------------------------------------------ the street configs' supervision blocks (loss_cfg)
+    _LOSS_BLOCKS = ("occupancy_mask", "mask_entropy", "sparsity", "clearance", "weight_reg", "lidar")
+
+    def _check_loss_cfg(self, loss_cfg, distant_model, num_uniform, target_masks):
+        """-> a plain-dict copy of the blocks (None for no blocks), refused at construction for what the step cannot do"""
+        if not loss_cfg:
+            return None
+        import copy
+        from numbers import Number
+        from .losses import MASK_ENTROPY_MODES
+        cfg = {k: copy.deepcopy(dict(v)) if isinstance(v, Mapping) else v for k, v in dict(loss_cfg).items()}
+        for k in cfg:
+            if k not in self._LOSS_BLOCKS:
+                raise NotImplementedError(f"RenderTrainer: loss_cfg block {k!r} is not covered (takes {', '.join(self._LOSS_BLOCKS)})")
+        classes = [self.main_class_name] + (["Distant"] if distant_model is not None else [])
+        for k in ("sparsity", "clearance", "weight_reg"):
+            if k not in cfg:
+                continue
+            blk = cfg[k] if isinstance(cfg[k], Mapping) else dict(class_name_cfgs=cfg[k])
+            blk.pop("drawable_class_names", None)
+            cc = blk.get("class_name_cfgs", {})
+            if isinstance(cc, Number):           # one weight for every class that has the quantity (clearance.py:43-44, weight_reg.py:38-39)
+                cc = {c: dict(w=cc) for c in (classes if k == "weight_reg" else classes[:1])}
+            blk["class_name_cfgs"] = {c: (dict(w=v) if isinstance(v, Number) else dict(v)) for c, v in dict(cc).items()}
+            cfg[k] = blk
+            if k != "weight_reg" and any(c != self.main_class_name for c in blk["class_name_cfgs"]):
+                other = next(c for c in blk["class_name_cfgs"] if c != self.main_class_name)
+                raise NotImplementedError(f"RenderTrainer: loss_cfg {k}.class_name_cfgs.{other}: only the main model "
+                                          f"({self.main_class_name!r}) has uniform samples / a near sdf")
+        if "sparsity" in cfg:
+            if num_uniform <= 0:
+                raise ValueError("RenderTrainer: loss_cfg['sparsity'] needs num_uniform > 0 (the uniform points it is evaluated on)")
+            for c, v in cfg["sparsity"]["class_name_cfgs"].items():
+                if v.get("key", "sdf") != "sdf":
+                    raise NotImplementedError(f"RenderTrainer: loss_cfg sparsity.class_name_cfgs.{c}.key={v['key']!r}")
+        if "occupancy_mask" in cfg and target_masks is None and cfg["occupancy_mask"].get("special_mask_mode") != "always_occupied":
+            raise ValueError("RenderTrainer: loss_cfg['occupancy_mask'] needs target_masks [V,H,W]")
+        if "mask_entropy" in cfg:
+            mode = cfg["mask_entropy"].get("mode", "crisp_cr")
+            if mode not in MASK_ENTROPY_MODES:
+                raise NotImplementedError(f"RenderTrainer: loss_cfg mask_entropy.mode={mode!r}")
+            if mode not in ("crisp", "nop") and distant_model is None:
+                raise ValueError(f"RenderTrainer: mask_entropy mode={mode!r} only functions in cr-dv joint training (no distant model)")
+        return cfg
+
+    def _gather_mask(self, xy, fidx):
+        H_, W_ = self.target_masks.shape[1], self.target_masks.shape[2]
+        return self.target_masks[fidx, (xy[:, 1] * H_).long().clamp_(0, H_ - 1), (xy[:, 0] * W_).long().clamp_(0, W_ - 1)]
+
+    @staticmethod
+    def _block_w(cfg: dict, it: int):
+        from nr3d_lib.models.annealers import get_anneal_val
+        return cfg.get("w") if cfg.get("anneal") is None else get_anneal_val(it=it, **cfg["anneal"])
+
+    def _street_terms(self, ret, it: int, mode: str, uni=None, mask_gt=None) -> Dict[str, torch.Tensor]:
+        """The blocks of ``loss_cfg`` on one render (``mode`` 'pixel' | 'lidar'; code_single/tools/train.py:629-674, 937-954) -> the
+        weighted terms under the reference's keys.  A model whose buffer is empty is skipped, as every one of the reference's
+        per-class loops does; weights and annealed values are resolved on the host, nothing is read back from the device."""
+        from . import losses as L_
+        cfg, out = self.loss_cfg, {}
+        raw = ret["raw_per_obj_model"]
+        objs = [(self.main_class_name, self.model, raw["main"])]
+        if "distant" in raw:
+            objs.append(("Distant", self.distant_model, raw["distant"]))
+        live = [(c, m, r) for c, m, r in objs if r["volume_buffer"]["type"] != "empty"]
+        N, dev = ret["rendered"]["mask_volume"].shape[0], ret["rendered"]["mask_volume"].device
+        if mode == "pixel" and "occupancy_mask" in cfg:
+            c = dict(cfg["occupancy_mask"])
+            w = self._block_w(c, it)
+            c.pop("anneal", None)
+            c.pop("w", None)
+            out["loss_mask"], self._last_mask_err = L_.mask_occupancy_loss(ret["rendered"]["mask_volume"], mask_gt, w=1.0 if w is None else w, **c)
+        if mode == "pixel" and "mask_entropy" in cfg:
+            c = dict(cfg["mask_entropy"])
+            emode = c.get("mode", "crisp_cr")
+            if emode != "nop" and it >= int(c.get("enable_after", 0)):
+                bad = sorted(set(c) - {"w", "anneal", "mode", "eps", "enable_after", "drawable_class_names"})
+                if bad:
+                    raise TypeError(f"RenderTrainer: loss_cfg mask_entropy got an unexpected key {bad[0]!r}")
+                masks = dict(mask_pred=ret["rendered"]["mask_volume"]) if emode == "crisp" else {}
+                if emode != "crisp" and "cr" in emode:
+                    masks["mask_cr"] = L_.object_mask_in_total(raw["main"]["volume_buffer"], N, device=dev)
+                if emode != "crisp" and "dv" in emode:
+                    masks["mask_dv"] = L_.object_mask_in_total(raw["distant"]["volume_buffer"], N, device=dev)
+                out.update(L_.mask_entropy_loss(emode, eps=c.get("eps", 1.0e-5), w=self._block_w(c, it), **masks))
+        for cname, model, r in live:
+            if "sparsity" in cfg and cname in cfg["sparsity"]["class_name_cfgs"] and it >= int(cfg["sparsity"].get("enable_after", 0)):
+                c = dict(cfg["sparsity"]["class_name_cfgs"][cname])
+                w = self._block_w(c, it)
+                assert w is not None, f"Can not get w for SparsityLoss.{cname}"
+                for k in ("w", "anneal", "key"):
+                    c.pop(k, None)
+                assert uni is not None, f"uniform_samples should contain {cname}"
+                out[f"loss_sparsity.{cname}"] = L_.sparsity_loss(uni["sdf"], c.pop("type", "normalized_logistic_density"), w=w, **c)
+            if "clearance" in cfg and cname in cfg["clearance"]["class_name_cfgs"]:
+                c = dict(cfg["clearance"]["class_name_cfgs"][cname])
+                w = self._block_w(c, it)
+                assert w is not None, f"Can not get w for ClearanceLoss.{cname}"
+                c.pop("w", None)
+                c.pop("anneal", None)
+                if "near_sdf" not in r.get("details", {}):
+                    raise RuntimeError(f"Can not find 'near_sdf' in details for {cname}")
+                out[f"loss_clearance.{cname}"] = L_.clearance_loss(r["details"]["near_sdf"], w=w, **c)
+            if "weight_reg" in cfg and cname in cfg["weight_reg"]["class_name_cfgs"]:
+                c = dict(cfg["weight_reg"]["class_name_cfgs"][cname])
+                w = self._block_w(c, it)
+                assert w is not None, f"Can not get w for WeightRegLoss.{cname}"
+                c.pop("w", None)
+                c.pop("anneal", None)
+                if mode == "lidar":      # the tensors of the lidar graph: the radiance decoders are outside it (with_rgb=False)
+                    rad = getattr(model, "rad_w", None)
+                    norms = torch.stack([p.float().norm(p=c.get("norm_type", 2.0)) for p in model._weight_reg_tensors() if p is not rad])
+                else:
+                    norms = model.get_weight_reg(**c)
+                out[f"loss_weight_reg.{cname}"] = w * norms.sum()
+        return out
 
     # ------------------------------------------------------------------ lidar step (street configs)
     def sample_lidar_batch(self):
@@ -743,11 +883,19 @@ class RenderTrainer:
         o, d, ranges = self.sample_lidar_batch()
         w_eik = float(L.get("w_eikonal", self.w_eikonal))
         with_normal = w_eik > 0.0
+        street = self.loss_cfg is not None and "lidar" in self.loss_cfg      # the yaml's lidar block on the fused ops
+        far = float(L.get("far", self.far)) if (L.get("far", self.far) is not None) else None
         ret = self.renderer.render(self.model, rays=[o, d], rays_h_appear=None, with_rgb=False, with_normal=with_normal,
-                                   return_buffer=True, return_details=with_normal, distant_model=self.distant_model,
-                                   sky_model=None, near=float(L.get("near", self.near or 0.0)),
-                                   far=float(L.get("far", self.far)) if (L.get("far", self.far) is not None) else None)
-        loss, parts = self.lidar_losses(ret, ranges)
+                                   return_buffer=True, return_details=with_normal or street, distant_model=self.distant_model,
+                                   sky_model=None, near=float(L.get("near", self.near or 0.0)), far=far,
+                                   bypass_ray_query_cfg=dict(with_near_sdf=True) if (street and "clearance" in self.loss_cfg) else None)
+        if street:
+            from .losses import lidar_loss
+            parts = lidar_loss(ret["rendered"], ret["volume_buffer"], ranges, far=far, it=it, **self.loss_cfg["lidar"])
+            loss = sum(parts.values()) if parts else torch.zeros([], device=ranges.device)
+        else:
+            loss, parts = self.lidar_losses(ret, ranges)
+        uni = None
         if with_normal:
             cr_vb = ret["raw_per_obj_model"]["main"]["volume_buffer"]
             r_ratio = float(L.get("on_render_ratio", 1.0))
@@ -759,6 +907,15 @@ class RenderTrainer:
                 uni = self.model.sample_pts_uniform(n_uni, generator=self.gen)
                 parts["eikonal_uniform"] = w_eik * eikonal_loss(uni["nablas"])
                 loss = loss + parts["eikonal_uniform"]
+        if street:
+            sp = self.loss_cfg.get("sparsity")
+            if uni is None and sp is not None and it >= int(sp.get("enable_after", 0)) and \
+                    ret["raw_per_obj_model"]["main"]["volume_buffer"]["type"] != "empty":
+                # ``uniform_samples[class_name] = model.sample_pts_uniform(num)`` of the lidar step (train.py:912-923)
+                uni = self.model.sample_pts_uniform(int(L.get("num_uniform", 0)) or self.num_uniform, generator=self.gen)
+            for k, v in self._street_terms(ret, it, "lidar", uni=uni).items():
+                parts[k] = v
+                loss = loss + v
         self.optim.zero_grad()
         if loss.requires_grad:          # no beam hit anything and no distant model: nothing to differentiate on this rank
             with backward_on_calling_thread():
@@ -767,7 +924,8 @@ class RenderTrainer:
             ndist.allreduce_grads(self.optim.params(), average=False, skip_absent=True)
         self.optim.step(grad_scale=1.0 if self.skip_allreduce else 1.0 / self.world_size)
         self.stats["lidar_samples"] = int(ret["volume_buffer"]["t"].shape[0]) if ret["volume_buffer"]["type"] != "empty" else 0
-        self._lidar_parts = {k: float(v.detach()) for k, v in parts.items()}
+        # (the street blocks' terms stay on the device: no host read per step)
+        self._lidar_parts = {k: v.detach() for k, v in parts.items()} if street else {k: float(v.detach()) for k, v in parts.items()}
         return loss.detach()
 
     def train_step(self, it: int) -> torch.Tensor:
@@ -822,7 +980,10 @@ class RenderTrainer:
             uni = None
             if x_uni is not None and "extra_pts" not in ret["raw_per_obj_model"]["main"]:     # no ray hit anything
                 uni = dict(model.forward_sdf_nablas(x_uni), net_x=x_uni)
-            loss, parts = self.loss(ret, gt, uni, aux=batch.get("aux") if batch is not None else self._last_aux)
+            aux = batch.get("aux") if batch is not None else self._last_aux
+            if self.loss_cfg is not None and "occupancy_mask" in self.loss_cfg and (aux is None or aux.get("mask_of") is not xy):
+                aux = dict(aux or {}, mask=self._gather_mask(xy, fidx))      # (a batch that did not come from sample_batch)
+            loss, parts = self.loss(ret, gt, uni, aux=aux)
             self.loss_parts = parts
             if self.error_map is not None:
                 self._update_error_map(fidx, xy, ret["rendered"]["rgb_volume"].detach(), gt)

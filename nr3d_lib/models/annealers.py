@@ -7,8 +7,12 @@ import math
 
 
 def get_anneal_val(type: str = "linear", it: int = 0, start_it: int = 0, stop_it: int = 1, start_val: float = 0.0,
-                   stop_val: float = 1.0, update_every: int = 1, **unused) -> float:
+                   stop_val: float = 1.0, update_every: int = 1, milestones=None, vals=None, **unused) -> float:
     it = int(it)
+    if milestones is not None and vals is not None:
+        # ``{type: milestones, milestones: [5000, 10000], vals: [1.5, 0.75, 0.5]}`` (the line-of-sight epsilon_anneal,
+        # withmask_withlidar_joint.240219.yaml:466-469): piecewise constant, one value per interval
+        return float(get_anneal_val_milestones(it, milestones, vals))
     if update_every and update_every > 1:
         it = (it // int(update_every)) * int(update_every)
     p = min(max((it - start_it) / max(stop_it - start_it, 1), 0.0), 1.0)

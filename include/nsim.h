@@ -774,6 +774,73 @@ int nsim_lidar_loss_fwd(const NsimLidarLoss* cfg, const float* depth_pred, const
 int nsim_lidar_loss_bwd(const float* g_depth, int64_t N, const float* g_vw, const uint8_t* member, int64_t S,
                         const float* gout_depth, const float* gout_neighbor, const float* gout_empty, float* d_depth, float* d_vw,
                         void* stream);
+/* The monocular depth / normal cue losses (app/loss/mono.py; the ``mono_depth`` / ``mono_normals`` blocks of
+ * lotd_neus.replica.230814.yaml:272-288 and withmask_nolidar.240219.yaml:463-483).  Masks are uint8 (0 / non-zero).  Every sum is
+ * taken in f64 into a workspace ``ws`` the caller zeroes; the workgroup that finishes last writes the f32 losses ``out``, so no
+ * value is converted or read back by a further launch.  Weights are folded in.
+ *   mono_remain_mask  replaces the ignore list and erosion of MonoDepthLoss.forward / MonoNormalLoss.forward (mono.py:358-397,
+ *                     510-528): out [H,W] = 1 where no selected rule ignores the pixel.  flags: bit 0 toofar (depth_pred0 > far),
+ *                     1 pred_not_occupied (!(mask_pred > mask_pred_thresh)), 2 not_occupied (!occupancy_gt), 3 dynamic, 4 human,
+ *                     5 pred_distant (depth_pred > far08), 6 mono_distant (depth_gt > f32(depth_gt_sum / (H W)) - 1e-5; the sum by
+ *                     mono_sum_f64); a map no set bit needs may be NULL.  keep_all: every pixel remains (the depth loss with an
+ *                     empty list, :396-397).  erode e in 0..32: kornia.morphology.erosion with a flat 2e x 2e kernel of ones --
+ *                     out[y,x] = min over rows y-e .. y+e-1, columns x-e .. x+e-1, pixels outside the image not eroding.
+ *   mono_sum_f64      out[0] += sum of x [n] (the mean of depth_gt for mono_distant)
+ *   mono_ssi_*        replace MonoSDFDepthLoss.forward (mono.py:136-158) on pred, gt, mask [H,W].  ws [12]:
+ *                     moments: ws[0..5) += a00 a01 a11 b0 b1 of compute_scale_and_shift (:88-113), target = gt_pre_scale gt + gt_pre_shift;
+ *                     fwd:     the solve (det == 0: scale = shift = 0), out[0] = w mean over H W of mask f, out[1] = w alpha_grad_reg
+ *                              image-gradient regulariser (:115-134; alpha 0: 0), g_depth / g_reg [H,W] = the direct gradients
+ *                              of the two to pred, ws[7..11) = d out / d (scale, shift);
+ *                     bwd:     d_pred = gout_depth (g_depth + chain) + gout_reg (g_reg + chain), the chain through the solve in
+ *                              closed form from the moments (none with detach_scale_shift or det == 0); a NULL gout is 0.
+ *   mono_pearson_*    replace PearsonCorrDepthLoss.forward (mono.py:222-240, reverse_gt False): out[0] = w (1 - r) over the masked
+ *                     pixels, out[1] = w alpha sum over scales of (1 - r_x) + (1 - r_y) of the finite differences over the pairs
+ *                     with both mask pixels set (a set without a sample adds 0), r = C / max(sqrt(A) sqrt(B), 1e-12) of the
+ *                     centred moments.  ws [103]: six raw sums per set, the ticket.  One launch per direction.
+ *   mono_normal_fwd   replaces MonoNormalLoss.fn (mono.py:479-484) behind the rotation of :507: n' = rot n (rot_mode 0 none,
+ *                     1 one [3,3], 2 per row [N,3,3]), both sides v / max(|v|, 1e-12); out[0] = w_l1 mean over N of mask sum_c |.|,
+ *                     out[1] = w_cos mean of mask (1 - dot); mask NULL: all rows.  g_l1 / g_cos [N,3] = d out / d normals_pred; ws [3].
+ *   mono_scale2_bwd   d [n] = gout0[0] g0 [n] + gout1[0] g1 [n]: the backward of mono_normal_fwd (a NULL gout is 0). */
+typedef struct NsimMonoSsi {
+  int32_t fn;                       /* 0 mse | l2, 1 l1, 2 log_l1, 3 smooth_l1, 4 relative_l1 | mape, 5 smape, 6 relative_l2, 7 huber */
+  int32_t scale_gt_to_pred, detach_scale_shift, grad_reg_scales;
+  double fn_param;                  /* beta (3), eps (4, 5, 6), alpha (7) */
+  double gt_pre_scale, gt_pre_shift, alpha_grad_reg, w;
+} NsimMonoSsi;
+int nsim_mono_remain_mask(const float* mask_pred, const float* depth_pred0, const float* depth_pred, const float* depth_gt,
+                          const uint8_t* occupancy_gt, const uint8_t* dynamic_gt, const uint8_t* human_gt, const double* depth_gt_sum,
+                          int64_t H, int64_t W, float mask_pred_thresh, float far, float far08, int flags, int keep_all, int erode,
+                          uint8_t* out, void* stream);
+int nsim_mono_sum_f64(const float* x, int64_t n, double* out, void* stream);
+int nsim_mono_ssi_moments(const NsimMonoSsi* cfg, const float* pred, const float* gt, const uint8_t* mask, int64_t H, int64_t W,
+                          double* ws, void* stream);
+int nsim_mono_ssi_fwd(const NsimMonoSsi* cfg, const float* pred, const float* gt, const uint8_t* mask, int64_t H, int64_t W,
+                      double* ws, float* out, float* g_depth, float* g_reg, void* stream);
+int nsim_mono_ssi_bwd(const NsimMonoSsi* cfg, const float* pred, const float* gt, const uint8_t* mask, int64_t H, int64_t W,
+                      double* ws, const float* g_depth, const float* g_reg, const float* gout_depth, const float* gout_reg,
+                      float* d_pred, void* stream);
+int nsim_mono_pearson_fwd(const float* pred, const float* gt, const uint8_t* mask, int64_t H, int64_t W, double alpha_grad_reg,
+                          int grad_reg_scales, double w, double* ws, float* out, void* stream);
+int nsim_mono_pearson_bwd(const float* pred, const float* gt, const uint8_t* mask, int64_t H, int64_t W, double alpha_grad_reg,
+                          int grad_reg_scales, double w, const double* ws, const float* gout_depth, const float* gout_reg,
+                          float* d_pred, void* stream);
+int nsim_mono_normal_fwd(const float* normals_pred, const float* normals_gt, const uint8_t* mask, const float* rot, int rot_mode,
+                         int64_t N, double w_l1, double w_cos, double* ws, float* out, float* g_l1, float* g_cos, void* stream);
+int nsim_mono_scale2_bwd(const float* g0, const float* g1, int64_t n, const float* gout0, const float* gout1, float* d, void* stream);
+/* One object's share of the joint rendering: replaces SingleVolumeRenderer._volume_integration_in_total
+ * (app/renderers/single_volume_renderer.py:104-120; the ``cr_only`` depth of the mono losses reads it).  Per pack r of the object's
+ * buffer (pack_infos [P,2] = begin, count; rays_inds [P]; samples vw_in_total, t [S], rgb / nablas [S,3] or NULL):
+ *   mask[ray] = sum vw, depth[ray] = sum vw t / (mask + 1e-10) (normalized_depth) or sum vw t, rgb / normals[ray] = sum vw x;
+ *   normalize_nablas: the integrated normal is normalize(clamp(nabla, -1, 1)) (the reference outside training).
+ * The outputs [N(,3)] are zeroed by the caller (rays the object does not hit keep the zeros).  bwd: mask / depth are the forward's
+ * outputs; every g_* [N(,3)] and every d_* [S(,3)] may be NULL; no gradient to t. */
+int nsim_packed_share_fwd(const float* vw_in_total, const float* t, const float* rgb, const float* nablas, const int64_t* pack_infos,
+                          const int64_t* rays_inds, int64_t P, int64_t N, int normalized_depth, int normalize_nablas, float* mask,
+                          float* depth, float* rgb_out, float* normals_out, void* stream);
+int nsim_packed_share_bwd(const float* vw_in_total, const float* t, const float* rgb, const float* nablas, const int64_t* pack_infos,
+                          const int64_t* rays_inds, int64_t P, int64_t N, int normalized_depth, int normalize_nablas, const float* mask,
+                          const float* depth, const float* g_mask, const float* g_depth, const float* g_rgb, const float* g_normals,
+                          float* d_vw, float* d_rgb, float* d_nablas, void* stream);
 /* Compaction of the AABB-tested rays, (o, d, near, far)[idx] -> [R,...] in one launch
  * (model.ray_test, app/renderers/single_volume_renderer.py:235-238). */
 int nsim_gather_rays(const float* rays_o, const float* rays_d, const float* near, const float* far, const int64_t* idx,

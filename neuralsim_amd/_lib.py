@@ -105,10 +105,17 @@ class LidarLoss(C.Structure):       # include/nsim.h NsimLidarLoss
                 ("los_fn", C.c_int32), ("bound", C.c_float), ("std", C.c_float), ("w_los", C.c_float)]
 
 
+class MonoSsi(C.Structure):         # include/nsim.h NsimMonoSsi
+    _fields_ = [("fn", C.c_int32), ("scale_gt_to_pred", C.c_int32), ("detach_scale_shift", C.c_int32), ("grad_reg_scales", C.c_int32),
+                ("fn_param", C.c_double), ("gt_pre_scale", C.c_double), ("gt_pre_shift", C.c_double), ("alpha_grad_reg", C.c_double),
+                ("w", C.c_double)]
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 _I = C.c_int
 _F = C.c_float
+_D = C.c_double
 
 # name -> argtypes (every function additionally takes the trailing ``void* stream`` unless listed in _NOSTREAM)
 SIGNATURES = {
@@ -209,6 +216,17 @@ SIGNATURES = {
     "nsim_lidar_valid": [_P, _P, _P, _I64, _F, _F, _I, _P, _P],
     "nsim_lidar_loss_fwd": [C.POINTER(LidarLoss), _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P, _P],
     "nsim_lidar_loss_bwd": [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P],
+    "nsim_mono_remain_mask": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _F, _F, _F, _I, _I, _I, _P],
+    "nsim_mono_sum_f64": [_P, _I64, _P],
+    "nsim_mono_ssi_moments": [C.POINTER(MonoSsi), _P, _P, _P, _I64, _I64, _P],
+    "nsim_mono_ssi_fwd": [C.POINTER(MonoSsi), _P, _P, _P, _I64, _I64, _P, _P, _P, _P],
+    "nsim_mono_ssi_bwd": [C.POINTER(MonoSsi), _P, _P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P],
+    "nsim_mono_pearson_fwd": [_P, _P, _P, _I64, _I64, _D, _I, _D, _P, _P],
+    "nsim_mono_pearson_bwd": [_P, _P, _P, _I64, _I64, _D, _I, _D, _P, _P, _P, _P],
+    "nsim_mono_normal_fwd": [_P, _P, _P, _P, _I, _I64, _D, _D, _P, _P, _P, _P],
+    "nsim_mono_scale2_bwd": [_P, _P, _I64, _P, _P, _P],
+    "nsim_packed_share_fwd": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I, _I, _P, _P, _P, _P],
+    "nsim_packed_share_bwd": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "nsim_mse_loss_fwd": [_P, _P, _I64, _P],
     "nsim_train_loss_head": [_P, _P, _I64, _P, _I64, _I64, _F, _P, _P, _P],
     "nsim_mse_loss_bwd": [_P, _P, _I64, _P, _P],

@@ -11,6 +11,8 @@
 //   * the street configs' supervision: occupancy-mask BCE, mask entropy, sparsity, clearance, the lidar depth + line-of-sight loss
 //     with its median outlier gate (an exact order statistic by radix select)   (app/loss/{mask, mask_entropy, sparsity, clearance,
 //     lidar}.py)
+//   * the monocular depth / normal cue losses with their remain mask, and an object's share of the joint rendering (app/loss/mono.py,
+//     app/renderers/single_volume_renderer.py:104-120): the last section of this file
 // The reference evaluates these with a handful of torch ops each; here one launch per direction, because at 8192
 // rays per iteration the step is bounded by launch count, not by bytes.
 #include "nsim_common.h"
@@ -1214,6 +1216,784 @@ int nsim_gather_rays(const float* rays_o, const float* rays_d, const float* near
   if (!o_out || !d_out || !near_out || !far_out) return 4;
   hipLaunchKernelGGL(k_gather_rays, dim3(nsim_blocks(R, LOSS_BLOCK)), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, rays_o,
                      rays_d, near, far, idx, R, o_out, d_out, near_out, far_out);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- monocular depth / normal cues
+// The monocular depth / normal cue losses (app/loss/mono.py) and an object's share of the joint rendering:
+//   * remain mask: the ignore list of MonoDepthLoss / MonoNormalLoss (mono.py:358-391, 510-524) evaluated into an LDS tile with
+//     halo and eroded by a flat 2e x 2e window of ones (kornia.morphology.erosion, geodesic border: mono.py:393-395) -- one launch
+//   * scale-and-shift-invariant depth (MonoSDFDepthLoss.forward, mono.py:136-158): five masked moments, the 2x2 solve, one of nine
+//     regressions and the multi-scale depth-gradient regulariser, with the gradient THROUGH the solve
+//   * Pearson depth (PearsonCorrDepthLoss.forward, mono.py:222-246, reverse_gt False) with its gradient-correlation regulariser
+//   * normal cue (MonoNormalLoss.fn, mono.py:479-484) with the world -> camera rotation of mono.py:507
+// The reference composes each of these from tens of torch ops on a 64x64 / 80x120 patch; here at most two launches forward and
+// one backward.  Every sum is taken in f64 (per thread, per workgroup, one f64 atomic per workgroup and quantity): the determinant
+// a00 a11 - a01^2 of the solve and the centred moments of the correlation cancel badly in f32.  The LAST workgroup to finish (a
+// ticket counter in the zeroed workspace) turns the f64 totals into the f32 losses, so nothing is converted by a further launch.
+
+#define MONO_BLOCK 256
+#define MONO_MAX_BLOCKS 256
+#define MONO_TILE 32
+#define MONO_MAX_ERODE 32
+#define MONO_REGION (MONO_TILE + 2 * MONO_MAX_ERODE - 1)
+#define MONO_MAX_SCALES 8
+#define MONO_MAX_SETS (1 + 2 * MONO_MAX_SCALES)
+
+static inline dim3 mono_grid(int64_t n) {
+  return dim3(nsim_blocks(n, MONO_BLOCK, MONO_MAX_BLOCKS));
+}
+
+// K partial sums of one block added into acc[0..K) (f64 atomics, one per non-zero sum)
+template <int K>
+__device__ __forceinline__ void mono_block_sums(const double (&v)[K], double* acc) {
+  __shared__ double red[K][MONO_BLOCK / 64];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const double s = wave_sum(v[k]);
+    if (nsim_lane() == 0) red[k][threadIdx.x >> 6] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < K) {
+    double tot = 0.0;
+    for (int w = 0; w < MONO_BLOCK / 64; ++w) tot += red[threadIdx.x][w];
+    if (tot != 0.0) atomicAdd(acc + threadIdx.x, tot);
+  }
+  __syncthreads();
+}
+
+// Outside a HIP compile (the host emulator of the tests) workgroups run one after another: nothing to order.
+#if defined(__HIP__)
+__device__ __forceinline__ void mono_release() { nsim_release_agent(); }
+#else
+inline void mono_release() {}
+#endif
+
+// true in thread 0 of the block that finishes last (its view of every other block's atomics is complete)
+__device__ __forceinline__ bool mono_last_block(unsigned* ticket) {
+  if (threadIdx.x != 0) return false;
+  mono_release();                // the sums above left through atomics of THIS wave (threads 0..K-1): complete before the ticket
+  return atomicAdd(ticket, 1u) == gridDim.x - 1;
+}
+
+__device__ __forceinline__ double mono_read(double* p) { return atomicAdd(p, 0.0); }
+
+// ---------------------------------------------------------------------------------------------- remain mask
+struct MonoMaskArgs {
+  const float *mask_pred, *depth_pred0, *depth_pred, *depth_gt;
+  const uint8_t *occ, *dyn, *human;
+  const double* gt_sum;     // sum of depth_gt (mono_distant)
+  float thresh, far, far08;
+  int flags;                // bit 0 toofar, 1 pred_not_occupied, 2 not_occupied, 3 dynamic, 4 human, 5 pred_distant, 6 mono_distant
+  int keep_all;             // the depth loss with an empty list: every pixel remains (mono.py:396-397)
+  int H, W, e;
+  int64_t n;
+};
+
+__device__ __forceinline__ uint8_t mono_remain(const MonoMaskArgs& a, int64_t i, float gt_gate) {
+  if (a.keep_all) return 1;
+  bool ign = false;
+  if (a.flags & 1) ign |= a.depth_pred0[i] > a.far;
+  if (a.flags & 2) ign |= !(a.mask_pred[i] > a.thresh);
+  if (a.flags & 4) ign |= !a.occ[i];
+  if (a.flags & 8) ign |= a.dyn[i] != 0;
+  if (a.flags & 16) ign |= a.human[i] != 0;
+  if (a.flags & 32) ign |= a.depth_pred[i] > a.far08;
+  if (a.flags & 64) ign |= a.depth_gt[i] > gt_gate;
+  return ign ? 0 : 1;
+}
+
+__device__ __forceinline__ float mono_gt_gate(const MonoMaskArgs& a) {
+  // depth_gt.mean() - 1e-5 in f32 (mono.py:388); the mean itself from the f64 sum
+  return (a.flags & 64) ? (float)(a.gt_sum[0] / (double)a.n) - 1e-5f : 0.f;
+}
+
+__global__ void __launch_bounds__(MONO_BLOCK) k_mono_mask_flat(MonoMaskArgs a, uint8_t* __restrict__ out) {
+  const float gate = mono_gt_gate(a);
+  for (int64_t i = (int64_t)blockIdx.x * MONO_BLOCK + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * MONO_BLOCK)
+    out[i] = mono_remain(a, i, gate);
+}
+
+// one 32 x 32 tile of the output per block: the predicates of the tile and its halo (e before, e - 1 after; a pixel outside the
+// image is 1: it does not erode) into LDS, the row minimum over 2e columns, then the column minimum over 2e rows
+__global__ void __launch_bounds__(MONO_BLOCK) k_mono_mask_erode(MonoMaskArgs a, uint8_t* __restrict__ out) {
+  __shared__ uint8_t P[MONO_REGION * MONO_REGION];
+  __shared__ uint8_t R[MONO_REGION * MONO_TILE];
+  const float gate = mono_gt_gate(a);
+  const int e = a.e, k = 2 * e, reg = MONO_TILE + k - 1;
+  const int y0 = (int)blockIdx.y * MONO_TILE - e, x0 = (int)blockIdx.x * MONO_TILE - e;
+  for (int j = threadIdx.x; j < reg * reg; j += MONO_BLOCK) {
+    const int y = y0 + j / reg, x = x0 + j % reg;
+    P[j] = (y >= 0 && y < a.H && x >= 0 && x < a.W) ? mono_remain(a, (int64_t)y * a.W + x, gate) : 1;
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < reg * MONO_TILE; j += MONO_BLOCK) {
+    const int r = j / MONO_TILE, c = j % MONO_TILE;
+    uint8_t m = 1;
+    for (int d = 0; d < k; ++d) m &= P[r * reg + c + d];
+    R[j] = m;
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < MONO_TILE * MONO_TILE; j += MONO_BLOCK) {
+    const int r = j / MONO_TILE, c = j % MONO_TILE;
+    const int y = (int)blockIdx.y * MONO_TILE + r, x = (int)blockIdx.x * MONO_TILE + c;
+    if (y >= a.H || x >= a.W) continue;
+    uint8_t m = 1;
+    for (int d = 0; d < k; ++d) m &= R[(r + d) * MONO_TILE + c];
+    out[(int64_t)y * a.W + x] = m;
+  }
+}
+
+__global__ void __launch_bounds__(MONO_BLOCK) k_mono_sum_f64(const float* __restrict__ x, int64_t n, double* __restrict__ out) {
+  double acc[1] = {0.0};
+  for (int64_t i = (int64_t)blockIdx.x * MONO_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * MONO_BLOCK) acc[0] += (double)x[i];
+  mono_block_sums<1>(acc, out);
+}
+
+// ---------------------------------------------------------------------------------------------- scale-and-shift-invariant depth
+// workspace (f64, zero on entry): [0..5) a00 a01 a11 b0 b1, [5] sum m f, [6] sum of the regulariser's |differences|,
+// [7..11) d depth / d scale, d depth / d shift, d reg / d scale, d reg / d shift, [11] the ticket (its first 4 bytes)
+#define SSI_WS 12
+struct SsiArgs {
+  const float *pred, *gt;
+  const uint8_t* mask;
+  int H, W;
+  int fn;                   // 0 mse, 1 l1, 2 log_l1, 3 smooth_l1 (beta), 4 relative_l1 / mape (eps), 5 smape (eps), 6 relative_l2 (eps),
+  double param;             // 7 huber (alpha)
+  double pre_scale, pre_shift;
+  int gt_to_pred, detach, n_scales;
+  double w_depth, w_reg;    // w / (H W), w alpha_grad_reg
+};
+
+__device__ __forceinline__ double ssi_target(const SsiArgs& a, int64_t i) {
+  return a.pre_scale * (double)a.gt[i] + a.pre_shift;
+}
+
+struct SsiSolve {
+  double scale, shift, det;
+};
+
+// (the moments are a previous launch's: plain reads)
+__device__ __forceinline__ SsiSolve ssi_solve(const double* ws) {
+  const double a00 = ws[0], a01 = ws[1], a11 = ws[2], b0 = ws[3], b1 = ws[4];
+  SsiSolve s;
+  s.det = a00 * a11 - a01 * a01;
+  s.scale = s.det != 0.0 ? (a11 * b0 - a01 * b1) / s.det : 0.0;
+  s.shift = s.det != 0.0 ? (-a01 * b0 + a00 * b1) / s.det : 0.0;
+  return s;
+}
+
+__device__ __forceinline__ double mono_sign(double x) { return x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : 0.0); }
+
+// f(a, b) of nr3d_lib/models/loss/recon.py (log_l1: mono.py:64) and its derivatives to both arguments
+__device__ __forceinline__ double ssi_fn(int fn, double prm, double a, double b, double& fa, double& fb) {
+  const double d = a - b, sd = mono_sign(d), ad = fabs(d);
+  switch (fn) {
+    case 0:
+      fa = 2.0 * d, fb = -fa;
+      return d * d;
+    case 1:
+      fa = sd, fb = -sd;
+      return ad;
+    case 2: {
+      const double ac = a + 1.0 > 1e-3 ? a + 1.0 : 1e-3;
+      const double u = log(ac) - log(b + 1.0), su = mono_sign(u);
+      fa = a + 1.0 >= 1e-3 ? su / ac : 0.0;
+      fb = -su / (b + 1.0);
+      return fabs(u);
+    }
+    case 3:
+      if (ad < prm) {
+        fa = d / prm, fb = -fa;
+        return 0.5 * d * d / prm;
+      }
+      fa = sd, fb = -sd;
+      return ad - 0.5 * prm;
+    case 4: {
+      const double q = fabs(b) + prm;
+      fa = sd / q;
+      fb = -sd / q - ad * mono_sign(b) / (q * q);
+      return ad / q;
+    }
+    case 5: {
+      const double q = 0.5 * (fabs(a) + fabs(b)) + prm;
+      fa = sd / q - ad * 0.5 * mono_sign(a) / (q * q);
+      fb = -sd / q - ad * 0.5 * mono_sign(b) / (q * q);
+      return ad / q;
+    }
+    case 6: {
+      const double q = b * b + prm;
+      fa = 2.0 * d / q;
+      fb = -fa - d * d * 2.0 * b / (q * q);
+      return d * d / q;
+    }
+    default:
+      if (ad < prm) {
+        fa = d, fb = -d;
+        return 0.5 * d * d;
+      }
+      fa = prm * sd, fb = -fa;
+      return prm * (ad - 0.5 * prm);
+  }
+}
+
+__global__ void __launch_bounds__(MONO_BLOCK) k_ssi_moments(SsiArgs a, double* __restrict__ ws) {
+  double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  const int64_t n = (int64_t)a.H * a.W;
+  for (int64_t i = (int64_t)blockIdx.x * MONO_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * MONO_BLOCK) {
+    if (!a.mask[i]) continue;
+    const double p = (double)a.pred[i], t = ssi_target(a, i);
+    acc[0] += p * p, acc[1] += p, acc[2] += 1.0, acc[3] += p * t, acc[4] += t;
+  }
+  mono_block_sums<5>(acc, ws);
+}
+
+// the two compared images at pixel i: (scale pred + shift, target) or (pred, (target - shift) / scale)
+__device__ __forceinline__ void ssi_pair(const SsiArgs& a, const SsiSolve& s, int64_t i, double& pa, double& pb) {
+  const double p = (double)a.pred[i], t = ssi_target(a, i);
+  if (a.gt_to_pred) pa = p, pb = (t - s.shift) / s.scale;
+  else pa = s.scale * p + s.shift, pb = t;
+}
+
+__global__ void __launch_bounds__(MONO_BLOCK) k_ssi_main(SsiArgs a, double* __restrict__ ws, float* __restrict__ out,
+                                                         float* __restrict__ g_depth, float* __restrict__ g_reg) {
+  __shared__ SsiSolve sol;
+  if (threadIdx.x == 0) sol = ssi_solve(ws);
+  __syncthreads();
+  const SsiSolve s = sol;
+  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  const int64_t n = (int64_t)a.H * a.W;
+  for (int64_t i = (int64_t)blockIdx.x * MONO_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * MONO_BLOCK) {
+    float gd = 0.f, gr = 0.f;
+    if (a.mask[i]) {      // a masked-out pixel is not evaluated (the reference multiplies its value by 0)
+      const int y = (int)(i / a.W), x = (int)(i % a.W);
+      const double p = (double)a.pred[i];
+      double pa, pb, fa, fb;
+      ssi_pair(a, s, i, pa, pb);
+      acc[0] += ssi_fn(a.fn, a.param, pa, pb, fa, fb);
+      // the regulariser: L1 of the x- and y-differences of (pa - pb) on the ::2^k sub-images, pairs with both mask pixels set
+      // (mono.py:115-134).  G = d (sum) / d (pa - pb) at this pixel; the pair's value is counted by its left / upper pixel.
+      double G = 0.0;
+      if (a.w_reg != 0.0) {
+        const double D = pa - pb;
+        for (int k = 0; k < a.n_scales; ++k) {
+          const int step = 1 << k;
+          if ((y & (step - 1)) || (x & (step - 1))) break;
+          const int64_t nb[4] = {x + step < a.W ? i + step : -1, y + step < a.H ? i + (int64_t)step * a.W : -1,
+                                 x - step >= 0 ? i - step : -1, y - step >= 0 ? i - (int64_t)step * a.W : -1};
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            if (nb[q] < 0 || !a.mask[nb[q]]) continue;
+            double qa, qb;
+            ssi_pair(a, s, nb[q], qa, qb);
+            const double df = q < 2 ? (qa - qb) - D : D - (qa - qb);
+            if (q < 2) acc[1] += fabs(df), G -= mono_sign(df);
+            else G += mono_sign(df);
+          }
+        }
+      }
+      // direct gradients to pred, and the chain sums d L / d scale, d L / d shift (the backward multiplies them by d scale /
+      // d pred, d shift / d pred: closed-form from the moments)
+      const double wd = a.w_depth, wr = a.w_reg;
+      if (a.gt_to_pred) {
+        gd = (float)(wd * fa), gr = (float)(wr * G);
+        const double b_s = -pb / s.scale, b_h = -1.0 / s.scale;
+        acc[2] += fb * b_s, acc[3] += fb * b_h, acc[4] += -G * b_s, acc[5] += -G * b_h;
+      } else {
+        gd = (float)(wd * fa * s.scale), gr = (float)(wr * G * s.scale);
+        acc[2] += fa * p, acc[3] += fa, acc[4] += G * p, acc[5] += G;
+      }
+    }
+    g_depth[i] = gd;
+    g_reg[i] = gr;
+  }
+  acc[0] *= a.w_depth, acc[2] *= a.w_depth, acc[3] *= a.w_depth;
+  acc[1] *= a.w_reg, acc[4] *= a.w_reg, acc[5] *= a.w_reg;
+  mono_block_sums<6>(acc, ws + 5);
+  if (mono_last_block(reinterpret_cast<unsigned*>(ws + 11))) {
+    out[0] = (float)mono_read(ws + 5);
+    out[1] = (float)mono_read(ws + 6);
+  }
+}
+
+__global__ void __launch_bounds__(MONO_BLOCK) k_ssi_bwd(SsiArgs a, double* __restrict__ ws, const float* __restrict__ g_depth,
+                                                        const float* __restrict__ g_reg, const float* __restrict__ gout0,
+                                                        const float* __restrict__ gout1, float* __restrict__ d_pred) {
+  const double a01 = ws[1], a11 = ws[2], b0 = ws[3], b1 = ws[4];
+  const SsiSolve s = ssi_solve(ws);
+  const double det = s.det, scale = s.scale, shift = s.shift;
+  const bool chain = det != 0.0 && !a.detach;
+  const double g0 = gout0 ? (double)gout0[0] : 0.0, g1 = gout1 ? (double)gout1[0] : 0.0;
+  const double c_s = g0 * ws[7] + g1 * ws[9], c_h = g0 * ws[8] + g1 * ws[10];
+  const int64_t n = (int64_t)a.H * a.W;
+  for (int64_t i = (int64_t)blockIdx.x * MONO_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * MONO_BLOCK) {
+    double d = g0 * (double)g_depth[i] + g1 * (double)g_reg[i];
+    if (chain && a.mask[i]) {
+      const double p = (double)a.pred[i], t = ssi_target(a, i);
+      const double ddet = 2.0 * (p * a11 - a01);
+      d += (c_s * ((a11 * t - b1) - scale * ddet) + c_h * ((2.0 * p * b1 - b0 - a01 * t) - shift * ddet)) / det;
+    }
+    d_pred[i] = (float)d;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- Pearson depth
+// set 0: (pred, gt) over the masked pixels; set 1 + 2k / 2 + 2k: their x- / y-differences on the ::2^k sub-image over the pairs
+// with both mask pixels set.  workspace (f64, zero on entry): per set n, Sx, Sy, Sxx, Syy, Sxy; then the ticket.
+#define PEARSON_WS (6 * MONO_MAX_SETS + 1)
+struct PearsonArgs {
+  const float *pred, *gt;
+  const uint8_t* mask;
+  int H, W, n_scales;       // n_scales 0: no regulariser
+  double w_depth, w_reg;    // w, w alpha_grad_reg
+};
+
+// the pair (x, y) pixel i adds to ``set``, false when it adds none
+__device__ __forceinline__ bool pearson_sample(const PearsonArgs& a, int set, int64_t i, double& x, double& y) {
+  if (!a.mask[i]) return false;
+  if (set == 0) {
+    x = (double)a.pred[i], y = (double)a.gt[i];
+    return true;
+  }
+  const int k = (set - 1) >> 1, step = 1 << k, py = (int)(i / a.W), px = (int)(i % a.W);
+  if ((py & (step - 1)) || (px & (step - 1))) return false;
+  int64_t j;
+  if ((set - 1) & 1) {
+    if (py + step >= a.H) return false;
+    j = i + (int64_t)step * a.W;
+  } else {
+    if (px + step >= a.W) return false;
+    j = i + step;
+  }
+  if (!a.mask[j]) return false;
+  x = (double)a.pred[j] - (double)a.pred[i], y = (double)a.gt[j] - (double)a.gt[i];
+  return true;
+}
+
+struct PearsonSet {
+  double mx, my, inv_d, c_over_a, r;
+  int valid;
+};
+
+// centred moments from the raw f64 sums; r = C / max(sqrt(A) sqrt(B), 1e-12)
+__device__ __forceinline__ PearsonSet pearson_set(const double* s) {
+  PearsonSet o;
+  o.valid = s[0] > 0.0;
+  o.mx = o.my = o.inv_d = o.c_over_a = o.r = 0.0;
+  if (!o.valid) return o;
+  o.mx = s[1] / s[0], o.my = s[2] / s[0];
+  const double A = fmax(s[3] - s[1] * o.mx, 0.0), B = fmax(s[4] - s[2] * o.my, 0.0), C = s[5] - s[1] * o.my;
+  const double den = sqrt(A) * sqrt(B);
+  if (den >= 1e-12) o.inv_d = 1.0 / den, o.c_over_a = C / A;
+  else o.inv_d = 1e12;
+  o.r = C * o.inv_d;
+  return o;
+}
+
+__global__ void __launch_bounds__(MONO_BLOCK) k_pearson_fwd(PearsonArgs a, double* __restrict__ ws, float* __restrict__ out) {
+  const int64_t n = (int64_t)a.H * a.W;
+  const int n_sets = 1 + 2 * a.n_scales;
+  for (int set = 0; set < n_sets; ++set) {
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int64_t i = (int64_t)blockIdx.x * MONO_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * MONO_BLOCK) {
+      double x, y;
+      if (!pearson_sample(a, set, i, x, y)) continue;
+      acc[0] += 1.0, acc[1] += x, acc[2] += y, acc[3] += x * x, acc[4] += y * y, acc[5] += x * y;
+    }
+    mono_block_sums<6>(acc, ws + 6 * set);
+  }
+  if (mono_last_block(reinterpret_cast<unsigned*>(ws + 6 * MONO_MAX_SETS))) {
+    double reg = 0.0, dep = 0.0;
+    for (int set = 0; set < n_sets; ++set) {
+      double s[6];
+      for (int q = 0; q < 6; ++q) s[q] = mono_read(ws + 6 * set + q);
+      const PearsonSet ps = pearson_set(s);
+      if (!ps.valid) continue;       // no pixel / no valid pair: the term is 0 (mono.py:181-194), decided here
+      if (set == 0) dep = 1.0 - ps.r;
+      else reg += 1.0 - ps.r;
+    }
+    out[0] = (float)(a.w_depth * dep);
+    out[1] = (float)(a.w_reg * reg);
+  }
+}
+
+__global__ void __launch_bounds__(MONO_BLOCK) k_pearson_bwd(PearsonArgs a, const double* __restrict__ ws, const float* __restrict__ gout0,
+                                                            const float* __restrict__ gout1, float* __restrict__ d_pred) {
+  __shared__ PearsonSet sets[MONO_MAX_SETS];
+  const int n_sets = 1 + 2 * a.n_scales;
+  if ((int)threadIdx.x < n_sets) sets[threadIdx.x] = pearson_set(ws + 6 * threadIdx.x);
+  __syncthreads();
+  const double g0 = (gout0 ? (double)gout0[0] : 0.0) * a.w_depth, g1 = (gout1 ? (double)gout1[0] : 0.0) * a.w_reg;
+  const int64_t n = (int64_t)a.H * a.W;
+  for (int64_t i = (int64_t)blockIdx.x * MONO_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * MONO_BLOCK) {
+    double d = 0.0;
+    if (a.mask[i]) {
+      // d (1 - r) / d x_j = -((y_j - my) - (C / A) (x_j - mx)) / den; a difference x = pred[j] - pred[i] hands it to j and, negated, to i
+      const int py = (int)(i / a.W), px = (int)(i % a.W);
+      for (int set = 0; set < n_sets; ++set) {
+        const PearsonSet& ps = sets[set];
+        if (!ps.valid) continue;
+        double x, y;
+        const double g = set == 0 ? g0 : g1;
+        if (pearson_sample(a, set, i, x, y)) {
+          const double t = -((y - ps.my) - ps.c_over_a * (x - ps.mx)) * ps.inv_d;
+          d += set == 0 ? g * t : -g * t;
+        }
+        if (set > 0) {           // the pair this pixel closes (its left / upper neighbour opens it)
+          const int step = 1 << ((set - 1) >> 1);
+          const bool vert = (set - 1) & 1;
+          if ((py & (step - 1)) || (px & (step - 1))) continue;
+          if (vert ? py - step < 0 : px - step < 0) continue;
+          const int64_t j = vert ? i - (int64_t)step * a.W : i - step;
+          if (pearson_sample(a, set, j, x, y)) d += g * -((y - ps.my) - ps.c_over_a * (x - ps.mx)) * ps.inv_d;
+        }
+      }
+    }
+    d_pred[i] = (float)d;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- normal cue
+// rot_mode 0: none; 1: one [3,3]; 2: per row [N,3,3] -- n' = rot n (world -> camera), a constant of the backward.
+// workspace (f64, zero on entry): the two sums, the ticket.
+#define NORMAL_WS 3
+__device__ __forceinline__ void mono_normalize(const double v[3], double y[3], double& len) {
+  len = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+  const double dnm = len > 1e-12 ? len : 1e-12;      // F.normalize: v / max(|v|, eps)
+  y[0] = v[0] / dnm, y[1] = v[1] / dnm, y[2] = v[2] / dnm;
+}
+
+__global__ void __launch_bounds__(MONO_BLOCK) k_normal_cue_fwd(const float* __restrict__ np, const float* __restrict__ ng,
+                                                               const uint8_t* __restrict__ mask, const float* __restrict__ rot,
+                                                               int rot_mode, int64_t N, double w_l1, double w_cos, double* __restrict__ ws,
+                                                               float* __restrict__ out, float* __restrict__ g_l1,
+                                                               float* __restrict__ g_cos) {
+  double acc[2] = {0.0, 0.0};
+  const double s1 = w_l1 / (double)N, s2 = w_cos / (double)N;
+  for (int64_t i = (int64_t)blockIdx.x * MONO_BLOCK + threadIdx.x; i < N; i += (int64_t)gridDim.x * MONO_BLOCK) {
+    double d1[3] = {0.0, 0.0, 0.0}, d2[3] = {0.0, 0.0, 0.0};
+    if (!mask || mask[i]) {
+      double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+      if (rot_mode) {
+        const float* r = rot + (rot_mode == 2 ? 9 * i : 0);
+        for (int q = 0; q < 9; ++q) R[q] = (double)r[q];
+      }
+      const double v[3] = {(double)np[3 * i], (double)np[3 * i + 1], (double)np[3 * i + 2]};
+      const double u[3] = {R[0] * v[0] + R[1] * v[1] + R[2] * v[2], R[3] * v[0] + R[4] * v[1] + R[5] * v[2],
+                           R[6] * v[0] + R[7] * v[1] + R[8] * v[2]};
+      const double gt[3] = {(double)ng[3 * i], (double)ng[3 * i + 1], (double)ng[3 * i + 2]};
+      double yp[3], yg[3], lp, lg;
+      mono_normalize(u, yp, lp);
+      mono_normalize(gt, yg, lg);
+      double a1[3], a2[3];       // d l1 / d yp, d cos-term / d yp
+      for (int c = 0; c < 3; ++c) {
+        const double df = yp[c] - yg[c];
+        acc[0] += fabs(df);
+        a1[c] = mono_sign(df), a2[c] = -yg[c];
+      }
+      acc[1] += 1.0 - (yp[0] * yg[0] + yp[1] * yg[1] + yp[2] * yg[2]);
+      // through the normalisation: (a - y (y . a)) / |u|, or a / eps where the clamp holds; then through the rotation: R^T
+      double b1[3], b2[3];
+      if (lp > 1e-12) {
+        const double p1 = yp[0] * a1[0] + yp[1] * a1[1] + yp[2] * a1[2], p2 = yp[0] * a2[0] + yp[1] * a2[1] + yp[2] * a2[2];
+        for (int c = 0; c < 3; ++c) b1[c] = (a1[c] - yp[c] * p1) / lp, b2[c] = (a2[c] - yp[c] * p2) / lp;
+      } else {
+        for (int c = 0; c < 3; ++c) b1[c] = a1[c] * 1e12, b2[c] = a2[c] * 1e12;
+      }
+      for (int c = 0; c < 3; ++c) {
+        d1[c] = s1 * (R[c] * b1[0] + R[3 + c] * b1[1] + R[6 + c] * b1[2]);
+        d2[c] = s2 * (R[c] * b2[0] + R[3 + c] * b2[1] + R[6 + c] * b2[2]);
+      }
+    }
+    for (int c = 0; c < 3; ++c) g_l1[3 * i + c] = (float)d1[c], g_cos[3 * i + c] = (float)d2[c];
+  }
+  acc[0] *= s1, acc[1] *= s2;
+  mono_block_sums<2>(acc, ws);
+  if (mono_last_block(reinterpret_cast<unsigned*>(ws + 2))) {
+    out[0] = (float)mono_read(ws);
+    out[1] = (float)mono_read(ws + 1);
+  }
+}
+
+// d [n] = gout0[0] g0 [n] + gout1[0] g1 [n] (a NULL upstream gradient is 0)
+__global__ void __launch_bounds__(MONO_BLOCK) k_mono_scale2(const float* __restrict__ g0, const float* __restrict__ g1, int64_t n,
+                                                            const float* __restrict__ gout0, const float* __restrict__ gout1,
+                                                            float* __restrict__ d) {
+  const float s0 = gout0 ? gout0[0] : 0.f, s1 = gout1 ? gout1[0] : 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * MONO_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * MONO_BLOCK)
+    d[i] = s0 * g0[i] + s1 * g1[i];
+}
+
+// ---------------------------------------------------------------------------------------------- an object's share of the joint rendering
+// _volume_integration_in_total (app/renderers/single_volume_renderer.py:104-120): per pack of one object's buffer the sums of its
+// samples weighted by vw_in_total, placed at the pack's ray.  One wave per pack, f64 partial sums.
+struct ShareArgs {
+  const float *vw, *t, *rgb, *nab;
+  const int64_t *pack_infos, *rays_inds;
+  int64_t P, N;
+  int norm_depth, norm_nablas;
+};
+
+// the integrated normal of a sample: the nabla itself (training) or normalize(clamp(nabla, -1, 1)) (mono.py's eval branch, :118)
+__device__ __forceinline__ void share_normal(const ShareArgs& a, int64_t j, double y[3], double c[3], double& len) {
+  for (int q = 0; q < 3; ++q) y[q] = c[q] = (double)a.nab[3 * j + q];
+  len = 1.0;
+  if (!a.norm_nablas) return;
+  for (int q = 0; q < 3; ++q) c[q] = fmin(fmax(c[q], -1.0), 1.0);
+  mono_normalize(c, y, len);
+}
+
+__global__ void __launch_bounds__(MONO_BLOCK) k_packed_share_fwd(ShareArgs a, float* __restrict__ mask, float* __restrict__ depth,
+                                                                 float* __restrict__ rgb, float* __restrict__ nrm) {
+  const int lane = nsim_lane();
+  for (int64_t r = (int64_t)blockIdx.x * (MONO_BLOCK / 64) + (threadIdx.x >> 6); r < a.P; r += (int64_t)gridDim.x * (MONO_BLOCK / 64)) {
+    const int64_t b = a.pack_infos[2 * r], n = a.pack_infos[2 * r + 1], ray = a.rays_inds[r];
+    double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int64_t j = b + lane; j < b + n; j += 64) {
+      const double w = (double)a.vw[j];
+      acc[0] += w, acc[1] += w * (double)a.t[j];
+      if (a.rgb)
+        for (int q = 0; q < 3; ++q) acc[2 + q] += w * (double)a.rgb[3 * j + q];
+      if (a.nab) {
+        double y[3], c[3], len;
+        share_normal(a, j, y, c, len);
+        for (int q = 0; q < 3; ++q) acc[5 + q] += w * y[q];
+      }
+    }
+    for (int q = 0; q < 8; ++q) acc[q] = wave_sum(acc[q]);
+    if (lane == 0 && ray >= 0 && ray < a.N) {
+      mask[ray] = (float)acc[0];
+      depth[ray] = (float)(a.norm_depth ? acc[1] / (acc[0] + 1e-10) : acc[1]);
+      if (a.rgb)
+        for (int q = 0; q < 3; ++q) rgb[3 * ray + q] = (float)acc[2 + q];
+      if (a.nab)
+        for (int q = 0; q < 3; ++q) nrm[3 * ray + q] = (float)acc[5 + q];
+    }
+  }
+}
+
+// mask / depth: the forward's outputs (the normalised depth's derivative is (t - depth) / (mask + 1e-10)); a NULL g_* is 0
+__global__ void __launch_bounds__(MONO_BLOCK) k_packed_share_bwd(ShareArgs a, const float* __restrict__ mask,
+                                                                 const float* __restrict__ depth, const float* __restrict__ g_mask,
+                                                                 const float* __restrict__ g_depth, const float* __restrict__ g_rgb,
+                                                                 const float* __restrict__ g_nrm, float* __restrict__ d_vw,
+                                                                 float* __restrict__ d_rgb, float* __restrict__ d_nab) {
+  const int lane = nsim_lane();
+  for (int64_t r = (int64_t)blockIdx.x * (MONO_BLOCK / 64) + (threadIdx.x >> 6); r < a.P; r += (int64_t)gridDim.x * (MONO_BLOCK / 64)) {
+    const int64_t b = a.pack_infos[2 * r], n = a.pack_infos[2 * r + 1], ray = a.rays_inds[r];
+    const bool ok = ray >= 0 && ray < a.N;
+    const double gm = ok && g_mask ? (double)g_mask[ray] : 0.0, gd = ok && g_depth ? (double)g_depth[ray] : 0.0;
+    const double m = ok ? (double)mask[ray] : 0.0, dep = ok ? (double)depth[ray] : 0.0;
+    double gc[3] = {0.0, 0.0, 0.0}, gn[3] = {0.0, 0.0, 0.0};
+    for (int q = 0; q < 3; ++q) {
+      if (ok && g_rgb) gc[q] = (double)g_rgb[3 * ray + q];
+      if (ok && g_nrm) gn[q] = (double)g_nrm[3 * ray + q];
+    }
+    for (int64_t j = b + lane; j < b + n; j += 64) {
+      const double w = (double)a.vw[j], t = (double)a.t[j];
+      double d = gm + gd * (a.norm_depth ? (t - dep) / (m + 1e-10) : t);
+      if (a.rgb) {
+        for (int q = 0; q < 3; ++q) d += gc[q] * (double)a.rgb[3 * j + q];
+        if (d_rgb)
+          for (int q = 0; q < 3; ++q) d_rgb[3 * j + q] = (float)(w * gc[q]);
+      }
+      if (a.nab) {
+        double y[3], c[3], len;
+        share_normal(a, j, y, c, len);
+        for (int q = 0; q < 3; ++q) d += gn[q] * y[q];
+        if (d_nab) {
+          double o[3] = {w * gn[0], w * gn[1], w * gn[2]};
+          if (a.norm_nablas) {       // through normalize (v / max(|v|, 1e-12)) and the clamp (passes inside [-1, 1])
+            const double dot = y[0] * o[0] + y[1] * o[1] + y[2] * o[2];
+            for (int q = 0; q < 3; ++q) {
+              o[q] = len > 1e-12 ? (o[q] - y[q] * dot) / len : o[q] * 1e12;
+              const double v = (double)a.nab[3 * j + q];
+              if (v < -1.0 || v > 1.0) o[q] = 0.0;
+            }
+          }
+          for (int q = 0; q < 3; ++q) d_nab[3 * j + q] = (float)o[q];
+        }
+      }
+      if (d_vw) d_vw[j] = (float)d;
+    }
+  }
+}
+
+extern "C" {
+
+int nsim_mono_sum_f64(const float* x, int64_t n, double* out, void* stream) {
+  if (n < 0) return 2;
+  if (!out) return 4;
+  if (n == 0) return 0;
+  if (!x) return 4;
+  hipLaunchKernelGGL(k_mono_sum_f64, mono_grid(n), dim3(MONO_BLOCK), 0, (hipStream_t)stream, x, n, out);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_mono_remain_mask(const float* mask_pred, const float* depth_pred0, const float* depth_pred, const float* depth_gt,
+                          const uint8_t* occupancy_gt, const uint8_t* dynamic_gt, const uint8_t* human_gt, const double* depth_gt_sum,
+                          int64_t H, int64_t W, float mask_pred_thresh, float far, float far08, int flags, int keep_all, int erode,
+                          uint8_t* out, void* stream) {
+  if (H < 0 || W < 0 || H * W > ((int64_t)1 << 30)) return 2;
+  if (erode < 0 || erode > MONO_MAX_ERODE || (flags & ~127)) return 58;
+  if (H * W == 0) return 0;
+  if (!out) return 4;
+  if (!keep_all) {
+    if (((flags & 1) && !depth_pred0) || ((flags & 2) && !mask_pred) || ((flags & 4) && !occupancy_gt) || ((flags & 8) && !dynamic_gt) ||
+        ((flags & 16) && !human_gt) || ((flags & 32) && !depth_pred) || ((flags & 64) && (!depth_gt || !depth_gt_sum)))
+      return 4;
+  }
+  MonoMaskArgs a;
+  a.mask_pred = mask_pred, a.depth_pred0 = depth_pred0, a.depth_pred = depth_pred, a.depth_gt = depth_gt;
+  a.occ = occupancy_gt, a.dyn = dynamic_gt, a.human = human_gt, a.gt_sum = depth_gt_sum;
+  a.thresh = mask_pred_thresh, a.far = far, a.far08 = far08, a.flags = keep_all ? 0 : flags, a.keep_all = keep_all;
+  a.H = (int)H, a.W = (int)W, a.e = erode, a.n = H * W;
+  if (erode == 0) {
+    hipLaunchKernelGGL(k_mono_mask_flat, mono_grid(a.n), dim3(MONO_BLOCK), 0, (hipStream_t)stream, a, out);
+  } else {
+    const dim3 grid((unsigned)((W + MONO_TILE - 1) / MONO_TILE), (unsigned)((H + MONO_TILE - 1) / MONO_TILE));
+    if (grid.y > 65535u) return 2;
+    hipLaunchKernelGGL(k_mono_mask_erode, grid, dim3(MONO_BLOCK), 0, (hipStream_t)stream, a, out);
+  }
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+static inline int ssi_args(SsiArgs* a, const NsimMonoSsi* cfg, const float* pred, const float* gt, const uint8_t* mask, int64_t H,
+                           int64_t W) {
+  if (!cfg) return 4;
+  if (H < 1 || W < 1 || H * W > ((int64_t)1 << 30)) return 2;
+  if (cfg->fn < 0 || cfg->fn > 7 || cfg->grad_reg_scales < 0 || cfg->grad_reg_scales > MONO_MAX_SCALES) return 58;
+  if (!pred || !gt || !mask) return 4;
+  a->pred = pred, a->gt = gt, a->mask = mask, a->H = (int)H, a->W = (int)W;
+  a->fn = cfg->fn, a->param = cfg->fn_param, a->pre_scale = cfg->gt_pre_scale, a->pre_shift = cfg->gt_pre_shift;
+  a->gt_to_pred = cfg->scale_gt_to_pred != 0, a->detach = cfg->detach_scale_shift != 0;
+  a->n_scales = cfg->alpha_grad_reg != 0.0 ? cfg->grad_reg_scales : 0;
+  a->w_depth = cfg->w / (double)(H * W);
+  a->w_reg = a->n_scales ? cfg->w * cfg->alpha_grad_reg : 0.0;
+  return 0;
+}
+
+int nsim_mono_ssi_moments(const NsimMonoSsi* cfg, const float* pred, const float* gt, const uint8_t* mask, int64_t H, int64_t W,
+                          double* ws, void* stream) {
+  SsiArgs a;
+  if (int rc = ssi_args(&a, cfg, pred, gt, mask, H, W)) return rc;
+  if (!ws) return 4;
+  hipLaunchKernelGGL(k_ssi_moments, mono_grid(H * W), dim3(MONO_BLOCK), 0, (hipStream_t)stream, a, ws);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_mono_ssi_fwd(const NsimMonoSsi* cfg, const float* pred, const float* gt, const uint8_t* mask, int64_t H, int64_t W,
+                      double* ws, float* out, float* g_depth, float* g_reg, void* stream) {
+  SsiArgs a;
+  if (int rc = ssi_args(&a, cfg, pred, gt, mask, H, W)) return rc;
+  if (!ws || !out || !g_depth || !g_reg) return 4;
+  hipLaunchKernelGGL(k_ssi_main, mono_grid(H * W), dim3(MONO_BLOCK), 0, (hipStream_t)stream, a, ws, out, g_depth, g_reg);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_mono_ssi_bwd(const NsimMonoSsi* cfg, const float* pred, const float* gt, const uint8_t* mask, int64_t H, int64_t W,
+                      double* ws, const float* g_depth, const float* g_reg, const float* gout_depth, const float* gout_reg,
+                      float* d_pred, void* stream) {
+  SsiArgs a;
+  if (int rc = ssi_args(&a, cfg, pred, gt, mask, H, W)) return rc;
+  if (!ws || !g_depth || !g_reg || !d_pred) return 4;
+  hipLaunchKernelGGL(k_ssi_bwd, mono_grid(H * W), dim3(MONO_BLOCK), 0, (hipStream_t)stream, a, ws, g_depth, g_reg, gout_depth,
+                     gout_reg, d_pred);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+static inline int pearson_args(PearsonArgs* a, const float* pred, const float* gt, const uint8_t* mask, int64_t H, int64_t W,
+                               double alpha_grad_reg, int grad_reg_scales, double w) {
+  if (H < 1 || W < 1 || H * W > ((int64_t)1 << 30)) return 2;
+  if (grad_reg_scales < 0 || grad_reg_scales > MONO_MAX_SCALES) return 58;
+  if (!pred || !gt || !mask) return 4;
+  a->pred = pred, a->gt = gt, a->mask = mask, a->H = (int)H, a->W = (int)W;
+  a->n_scales = alpha_grad_reg != 0.0 ? grad_reg_scales : 0;
+  a->w_depth = w, a->w_reg = w * alpha_grad_reg;
+  return 0;
+}
+
+int nsim_mono_pearson_fwd(const float* pred, const float* gt, const uint8_t* mask, int64_t H, int64_t W, double alpha_grad_reg,
+                          int grad_reg_scales, double w, double* ws, float* out, void* stream) {
+  PearsonArgs a;
+  if (int rc = pearson_args(&a, pred, gt, mask, H, W, alpha_grad_reg, grad_reg_scales, w)) return rc;
+  if (!ws || !out) return 4;
+  hipLaunchKernelGGL(k_pearson_fwd, mono_grid(H * W), dim3(MONO_BLOCK), 0, (hipStream_t)stream, a, ws, out);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_mono_pearson_bwd(const float* pred, const float* gt, const uint8_t* mask, int64_t H, int64_t W, double alpha_grad_reg,
+                          int grad_reg_scales, double w, const double* ws, const float* gout_depth, const float* gout_reg,
+                          float* d_pred, void* stream) {
+  PearsonArgs a;
+  if (int rc = pearson_args(&a, pred, gt, mask, H, W, alpha_grad_reg, grad_reg_scales, w)) return rc;
+  if (!ws || !d_pred) return 4;
+  hipLaunchKernelGGL(k_pearson_bwd, mono_grid(H * W), dim3(MONO_BLOCK), 0, (hipStream_t)stream, a, ws, gout_depth, gout_reg, d_pred);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_mono_normal_fwd(const float* normals_pred, const float* normals_gt, const uint8_t* mask, const float* rot, int rot_mode,
+                         int64_t N, double w_l1, double w_cos, double* ws, float* out, float* g_l1, float* g_cos, void* stream) {
+  if (N < 1) return 2;
+  if (rot_mode < 0 || rot_mode > 2) return 58;
+  if (!normals_pred || !normals_gt || (rot_mode && !rot) || !ws || !out || !g_l1 || !g_cos) return 4;
+  hipLaunchKernelGGL(k_normal_cue_fwd, mono_grid(N), dim3(MONO_BLOCK), 0, (hipStream_t)stream, normals_pred, normals_gt, mask, rot,
+                     rot_mode, N, w_l1, w_cos, ws, out, g_l1, g_cos);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_mono_scale2_bwd(const float* g0, const float* g1, int64_t n, const float* gout0, const float* gout1, float* d, void* stream) {
+  if (n < 0) return 2;
+  if (n == 0) return 0;
+  if (!g0 || !g1 || !d) return 4;
+  hipLaunchKernelGGL(k_mono_scale2, mono_grid(n), dim3(MONO_BLOCK), 0, (hipStream_t)stream, g0, g1, n, gout0, gout1, d);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+static inline int share_args(ShareArgs* a, const float* vw, const float* t, const float* rgb, const float* nablas,
+                             const int64_t* pack_infos, const int64_t* rays_inds, int64_t P, int64_t N, int norm_depth, int norm_nablas) {
+  if (P < 0 || N < 0) return 2;
+  if (P && (!vw || !t || !pack_infos || !rays_inds)) return 4;
+  a->vw = vw, a->t = t, a->rgb = rgb, a->nab = nablas, a->pack_infos = pack_infos, a->rays_inds = rays_inds;
+  a->P = P, a->N = N, a->norm_depth = norm_depth != 0, a->norm_nablas = norm_nablas != 0;
+  return 0;
+}
+
+int nsim_packed_share_fwd(const float* vw_in_total, const float* t, const float* rgb, const float* nablas, const int64_t* pack_infos,
+                          const int64_t* rays_inds, int64_t P, int64_t N, int normalized_depth, int normalize_nablas, float* mask,
+                          float* depth, float* rgb_out, float* normals_out, void* stream) {
+  ShareArgs a;
+  if (int rc = share_args(&a, vw_in_total, t, rgb, nablas, pack_infos, rays_inds, P, N, normalized_depth, normalize_nablas)) return rc;
+  if (P == 0) return 0;
+  if (!mask || !depth || (rgb && !rgb_out) || (nablas && !normals_out)) return 4;
+  hipLaunchKernelGGL(k_packed_share_fwd, dim3(nsim_blocks(P, MONO_BLOCK / 64, 2048)), dim3(MONO_BLOCK), 0, (hipStream_t)stream, a, mask,
+                     depth, rgb_out, normals_out);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_packed_share_bwd(const float* vw_in_total, const float* t, const float* rgb, const float* nablas, const int64_t* pack_infos,
+                          const int64_t* rays_inds, int64_t P, int64_t N, int normalized_depth, int normalize_nablas, const float* mask,
+                          const float* depth, const float* g_mask, const float* g_depth, const float* g_rgb, const float* g_normals,
+                          float* d_vw, float* d_rgb, float* d_nablas, void* stream) {
+  ShareArgs a;
+  if (int rc = share_args(&a, vw_in_total, t, rgb, nablas, pack_infos, rays_inds, P, N, normalized_depth, normalize_nablas)) return rc;
+  if (P == 0) return 0;
+  if (!mask || !depth) return 4;
+  hipLaunchKernelGGL(k_packed_share_bwd, dim3(nsim_blocks(P, MONO_BLOCK / 64, 2048)), dim3(MONO_BLOCK), 0, (hipStream_t)stream, a, mask,
+                     depth, g_mask, g_depth, g_rgb, g_normals, d_vw, d_rgb, d_nablas);
   NSIM_CHECK_LAUNCH();
   return 0;
 }

@@ -124,6 +124,12 @@ __device__ __forceinline__ void wave_sync_lds() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+// every memory operation this WAVE has issued -- the atomics of a last-block-done reduction -- is complete at agent scope before
+// what follows (the ticket add).  The explicit wait stays: the fence's own one is not relied on.
+__device__ __forceinline__ void nsim_release_agent() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
 // the same for values handed over through memory (LDS or global) by plain stores
 __device__ __forceinline__ void nsim_wave_fence() { __threadfence_block(); }
 // a zero the compiler cannot see through (keeps loop-invariant address arithmetic from being hoisted into registers)

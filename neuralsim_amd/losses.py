@@ -683,3 +683,414 @@ def mono_normal_loss(normals_pred: torch.Tensor, normals_gt: torch.Tensor, mask:
         m = mask.reshape(-1).to(l1.dtype)
         l1, cos = l1 * m, cos * m
     return w_l1 * l1.mean() + w_cos * cos.mean()
+
+
+# ------------------------------------------------------------------------------------------------ monocular depth / normal cues
+# The full ``mono_depth`` / ``mono_normals`` blocks (app/loss/mono.py; lotd_neus.replica.230814.yaml:272-288, withmask_nolidar.240219.yaml:
+# 463-483) on the kernels of csrc/loss_ops.hip: the remain mask with its erosion in one launch, the depth losses in
+# at most two launches forward and one backward, the normal cue in one per direction.  ``mono_depth_loss`` / ``mono_normal_loss``
+# above stay the plain-torch core they were.
+MONO_IGNORE = {"toofar": 1, "pred_not_occupied": 2, "not_occupied": 4, "dynamic": 8, "human": 16, "pred_distant": 32, "mono_distant": 64}
+_MONO_NORMAL_IGNORE = ("pred_not_occupied", "not_occupied", "dynamic", "human")     # the entries MonoNormalLoss.forward looks at
+MONO_MAX_ERODE = 32          # MONO_MAX_ERODE of csrc/loss_ops.hip
+MONO_MAX_SCALES = 8          # MONO_MAX_SCALES
+
+
+def _u8(t: torch.Tensor, name: str) -> torch.Tensor:
+    _lib.require_device(t, name)
+    t = t.detach()
+    if t.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"neuralsim_amd: {name} must be a bool or uint8 map, got {t.dtype}")
+    return t.reshape(-1).contiguous().view(torch.uint8)
+
+
+def mono_remain_mask(mask_pred: torch.Tensor = None, *, depth_pred0: torch.Tensor = None, depth_pred: torch.Tensor = None,
+                     depth_gt: torch.Tensor = None, occupancy_gt: torch.Tensor = None, dynamic_gt: torch.Tensor = None,
+                     human_gt: torch.Tensor = None, far: float = None, ignore_mask_list=(), mask_pred_thresh: float = 0.95,
+                     mask_erode: int = 0, for_normals: bool = False, shape=None) -> torch.Tensor:
+    """The pixels the monocular losses keep, bool [H,W] or [N] (no gradient): ``MonoDepthLoss.forward`` (app/loss/mono.py:358-397)
+    or, ``for_normals=True``, ``MonoNormalLoss.forward`` (:503-528).  A pixel is ignored by any listed rule: ``toofar`` depth_pred0 >
+    far | ``pred_not_occupied`` not (mask_pred > mask_pred_thresh) | ``not_occupied`` ~occupancy_gt | ``dynamic`` | ``human`` |
+    ``pred_distant`` depth_pred > 0.8 far | ``mono_distant`` depth_gt > mean(depth_gt) - 1e-5 (the mean on the device, one extra
+    launch).  A map a listed rule needs and that is missing is a ``ValueError``.  Two quirks of the reference are kept: the DEPTH loss
+    with an empty list keeps every pixel, erosion or not (:396-397); the NORMAL loss always builds the mask, erodes it, and looks at
+    four entries only (pred_not_occupied, not_occupied, dynamic, human -- another known entry is accepted and has no effect).
+    ``mask_erode`` e > 0 (at most 32; needs a 2-D shape): ``kornia.morphology.erosion`` with a flat 2e x 2e kernel of ones, read as
+    out[y,x] = min over rows y-e .. y+e-1 and columns x-e .. x+e-1, pixels outside the image not eroding (unpinned).
+    One launch.  ``shape``: of the result when no map is handed in (empty list)."""
+    names = list(ignore_mask_list)
+    for n in names:
+        if n not in MONO_IGNORE:
+            raise ValueError(f"neuralsim_amd: unknown ignore_mask_list entry {n!r}")
+    if for_normals:
+        names = [n for n in names if n in _MONO_NORMAL_IGNORE]
+    keep_all = (not for_normals) and len(names) == 0
+    flags = 0
+    for n in names:
+        flags |= MONO_IGNORE[n]
+    maps = dict(mask_pred=mask_pred, depth_pred0=depth_pred0, depth_pred=depth_pred, depth_gt=depth_gt, occupancy_gt=occupancy_gt,
+                dynamic_gt=dynamic_gt, human_gt=human_gt)
+    needs = {1: ("depth_pred0",), 2: ("mask_pred",), 4: ("occupancy_gt",), 8: ("dynamic_gt",), 16: ("human_gt",), 32: ("depth_pred",),
+             64: ("depth_gt",)}
+    for bit, ms in needs.items():
+        for m in ms:
+            if (flags & bit) and maps[m] is None:
+                raise ValueError(f"neuralsim_amd: ignore_mask_list entry {[k for k, v in MONO_IGNORE.items() if v == bit][0]!r} needs {m}")
+    if (flags & (1 | 32)) and far is None:
+        raise ValueError("neuralsim_amd: ignore_mask_list entries 'toofar' / 'pred_distant' need far")
+    given = [m for m in maps.values() if m is not None]
+    if shape is None:
+        if not given:
+            raise ValueError("neuralsim_amd: mono_remain_mask needs a map or a shape")
+        shape = tuple(given[0].shape)
+    shape = tuple(int(s) for s in shape)
+    n = 1
+    for s_ in shape:
+        n *= s_
+    for k, m in maps.items():
+        if m is not None and m.numel() != n:
+            raise ValueError(f"neuralsim_amd: {k} {tuple(m.shape)} does not have the {n} pixels of {shape}")
+    e = int(mask_erode)
+    if e < 0 or e > MONO_MAX_ERODE:
+        raise NotImplementedError(f"neuralsim_amd: mask_erode={mask_erode}: the erosion kernel takes 0..{MONO_MAX_ERODE}")
+    if e > 0 and len(shape) != 2:
+        raise ValueError(f"neuralsim_amd: mask_erode > 0 needs a 2-D [H,W] shape, got {shape}")
+    H, W = (shape if len(shape) == 2 else (1, n))
+    fl = {k: (None if maps[k] is None else _flat(maps[k], k)) for k in ("mask_pred", "depth_pred0", "depth_pred", "depth_gt")}
+    u8 ={k: (None if maps[k] is None else _u8(maps[k], k)) for k in ("occupancy_gt", "dynamic_gt", "human_gt")}
+    dev = next((t.device for t in given), None)
+    if dev is None:
+        raise ValueError("neuralsim_amd: mono_remain_mask without a map needs one to name the device")
+    gsum = None
+    if flags & 64:
+        gsum = torch.zeros([1], dtype=torch.float64, device=dev)
+        _lib.call("nsim_mono_sum_f64", _lib.ptr(fl["depth_gt"]), n, _lib.ptr(gsum))
+    out = torch.empty([n], dtype=torch.uint8, device=dev)
+    farv = 0.0 if far is None else float(far)
+    _lib.call("nsim_mono_remain_mask", _lib.ptr(fl["mask_pred"]), _lib.ptr(fl["depth_pred0"]), _lib.ptr(fl["depth_pred"]),
+              _lib.ptr(fl["depth_gt"]), _lib.ptr(u8["occupancy_gt"]), _lib.ptr(u8["dynamic_gt"]), _lib.ptr(u8["human_gt"]), _lib.ptr(gsum),
+              H, W, _f32(mask_pred_thresh), _f32(farv), _f32(farv * 0.8), flags, int(keep_all), 0 if keep_all else e, _lib.ptr(out))
+    return out.view(torch.bool).reshape(shape)
+
+
+_SSI_FNS = {"mse": (0, None, 0.0), "l2": (0, None, 0.0), "l1": (1, None, 0.0), "log_l1": (2, None, 0.0), "smooth_l1": (3, "beta", 1.0),
+            "relative_l1": (4, "eps", 1e-2), "mape": (4, "eps", 1e-2), "smape": (5, "eps", 1e-2), "relative_l2": (6, "eps", 1e-2),
+            "huber": (7, "alpha", 1.0)}
+
+
+def _depth_images(pred, gt, mask, what):
+    _lib.require_device(pred, "pred")
+    _lib.require_device(gt, "gt")
+    if pred.dim() != 2 or gt.shape != pred.shape or mask.shape != pred.shape:
+        raise ValueError(f"neuralsim_amd: {what} takes pred, gt, mask of one [H,W] shape, got {tuple(pred.shape)}, {tuple(gt.shape)}, "
+                         f"{tuple(mask.shape)}")
+    if pred.numel() == 0:
+        raise ValueError(f"neuralsim_amd: {what} of an empty image")
+    if gt.requires_grad:
+        raise NotImplementedError(f"neuralsim_amd: gt.requires_grad: {what} differentiates the prediction only")
+    return pred.detach().float().contiguous(), gt.detach().float().contiguous(), _u8(mask, "mask")
+
+
+class _MonoSsiFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, gt, mask, cfg):
+        import ctypes
+        p, g, m = _depth_images(pred, gt, mask, "mono_depth_ssi_loss")
+        H, W = p.shape
+        ws = torch.zeros([12], dtype=torch.float64, device=p.device)
+        out = torch.empty([2], dtype=torch.float32, device=p.device)
+        gd, gr = torch.empty_like(p), torch.empty_like(p)
+        _lib.call("nsim_mono_ssi_moments", ctypes.byref(cfg), _lib.ptr(p), _lib.ptr(g), _lib.ptr(m), H, W, _lib.ptr(ws))
+        _lib.call("nsim_mono_ssi_fwd", ctypes.byref(cfg), _lib.ptr(p), _lib.ptr(g), _lib.ptr(m), H, W, _lib.ptr(ws), _lib.ptr(out),
+                  _lib.ptr(gd), _lib.ptr(gr))
+        ctx.saved = (p, g, m, ws, gd, gr)
+        ctx.cfg = cfg
+        ctx.set_materialize_grads(False)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g0, g1):
+        import ctypes
+        p, g, m, ws, gd, gr = ctx.saved
+        go = [None if x is None else x.float().reshape(1).contiguous() for x in (g0, g1)]
+        d = torch.empty_like(p)
+        _lib.call("nsim_mono_ssi_bwd", ctypes.byref(ctx.cfg), _lib.ptr(p), _lib.ptr(g), _lib.ptr(m), p.shape[0], p.shape[1], _lib.ptr(ws),
+                  _lib.ptr(gd), _lib.ptr(gr), _lib.ptr(go[0]), _lib.ptr(go[1]), _lib.ptr(d))
+        return d, None, None, None
+
+
+def mono_depth_ssi_loss(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, *, fn_type: str = "mse", fn_param: dict = None,
+                        gt_pre_scale: float = 1.0, gt_pre_shift: float = 0.0, scale_gt_to_pred: bool = False,
+                        detach_scale_shift: bool = False, alpha_grad_reg: float = 0.01, grad_reg_scales: int = 4, w: float = 1.0):
+    """``MonoSDFDepthLoss.forward`` (app/loss/mono.py:136-158) on one patch, pred / gt [H,W], mask bool [H,W]: -> (loss_depth,
+    loss_reg | None), both times ``w``.  target = gt_pre_scale gt + gt_pre_shift; (scale, shift) = the masked least-squares fit of the
+    prediction to it (det == 0: both 0); loss_depth = mean over ALL H W of mask f(scale pred + shift, target) -- or f(pred, (target -
+    shift) / scale) with ``scale_gt_to_pred`` --, f = mse | l2 | l1 | log_l1 | smooth_l1 (beta) | relative_l1 | mape | smape |
+    relative_l2 (eps) | huber (alpha) as nr3d_lib/models/loss/recon.py; loss_reg = alpha_grad_reg x the summed L1 of the x- and y-
+    differences of mask (a - b) on the ::2^k sub-images, k < grad_reg_scales, over the pairs with both mask pixels set
+    (``alpha_grad_reg == 0``: None).  The gradient goes to ``pred``, THROUGH the solve unless ``detach_scale_shift`` (DESIGN.md
+    sec. 7).  Masked-out pixels are not evaluated (the reference multiplies whatever they give by 0).  An empty mask gives zeros
+    with zero gradients, without a read-back (the reference returns no terms after ``.any()``).  Two launches forward, one backward."""
+    if fn_type not in _SSI_FNS:
+        raise NotImplementedError(f"neuralsim_amd: mono depth fn_type={fn_type!r}")
+    code, key, default = _SSI_FNS[fn_type]
+    fp = dict(fn_param or {})
+    _only_keys(fp, (key,) if key else (), f"mono_depth_ssi_loss(fn_param) of fn_type={fn_type!r}")
+    if not 0 <= int(grad_reg_scales) <= MONO_MAX_SCALES:
+        raise NotImplementedError(f"neuralsim_amd: grad_reg_scales={grad_reg_scales}: the kernels take 0..{MONO_MAX_SCALES}")
+    cfg = _lib.MonoSsi()
+    cfg.fn, cfg.fn_param = code, float(fp.get(key, default)) if key else 0.0
+    cfg.scale_gt_to_pred, cfg.detach_scale_shift = int(bool(scale_gt_to_pred)), int(bool(detach_scale_shift))
+    cfg.grad_reg_scales = int(grad_reg_scales)
+    cfg.gt_pre_scale, cfg.gt_pre_shift, cfg.alpha_grad_reg, cfg.w = float(gt_pre_scale), float(gt_pre_shift), float(alpha_grad_reg), float(w)
+    depth, reg = _MonoSsiFn.apply(pred, gt, mask, cfg)
+    return depth, (reg if alpha_grad_reg > 0 else None)
+
+
+class _MonoPearsonFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, gt, mask, alpha, scales, w):
+        p, g, m = _depth_images(pred, gt, mask, "mono_depth_pearson_loss")
+        ws = torch.zeros([6 * (1 + 2 * MONO_MAX_SCALES) + 1], dtype=torch.float64, device=p.device)
+        out = torch.empty([2], dtype=torch.float32, device=p.device)
+        _lib.call("nsim_mono_pearson_fwd", _lib.ptr(p), _lib.ptr(g), _lib.ptr(m), p.shape[0], p.shape[1], alpha, scales, w, _lib.ptr(ws),
+                  _lib.ptr(out))
+        ctx.saved, ctx.args = (p, g, m, ws), (alpha, scales, w)
+        ctx.set_materialize_grads(False)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g0, g1):
+        p, g, m, ws = ctx.saved
+        go = [None if x is None else x.float().reshape(1).contiguous() for x in (g0, g1)]
+        d = torch.empty_like(p)
+        _lib.call("nsim_mono_pearson_bwd", _lib.ptr(p), _lib.ptr(g), _lib.ptr(m), p.shape[0], p.shape[1], *ctx.args, _lib.ptr(ws),
+                  _lib.ptr(go[0]), _lib.ptr(go[1]), _lib.ptr(d))
+        return d, None, None, None, None, None
+
+
+def mono_depth_pearson_loss(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, alpha_grad_reg: float = 0.01,
+                            grad_reg_scales: int = 4, w: float = 1.0):
+    """``PearsonCorrDepthLoss.forward`` with ``reverse_gt=False`` (app/loss/mono.py:222-240; the class default ``loss_type`` of
+    ``MonoDepthLoss``): -> (w (1 - r), w alpha_grad_reg sum over the ::2^k sub-images of (1 - r_x) + (1 - r_y) | None).  r is the
+    Pearson correlation of pred and gt over the masked pixels, r_x / r_y that of their x- / y-differences over the pairs with both
+    mask pixels set; a set without a sample adds 0, decided on the device.  r = sum(xc yc) / max(|xc| |yc|, 1e-12) on the centred
+    values (the form of the tests' stand-in for ``torchmetrics.functional.pearson_corrcoef``: unpinned), the
+    moments centred from f64 raw sums.  Gradient to ``pred``.  One launch per direction; an empty mask gives zeros."""
+    if not 0 <= int(grad_reg_scales) <= MONO_MAX_SCALES:
+        raise NotImplementedError(f"neuralsim_amd: grad_reg_scales={grad_reg_scales}: the kernels take 0..{MONO_MAX_SCALES}")
+    depth, reg = _MonoPearsonFn.apply(pred, gt, mask, float(alpha_grad_reg), int(grad_reg_scales), float(w))
+    return depth, (reg if alpha_grad_reg > 0 else None)
+
+
+class _MonoNormalFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, gt, mask, rot, rot_mode, w_l1, w_cos):
+        a, b = _rows3(pred, "normals_pred"), _rows3(gt, "normals_gt")
+        N = a.shape[0]
+        ws = torch.zeros([3], dtype=torch.float64, device=a.device)
+        out = torch.empty([2], dtype=torch.float32, device=a.device)
+        g1, g2 = torch.empty_like(a), torch.empty_like(a)
+        _lib.call("nsim_mono_normal_fwd", _lib.ptr(a), _lib.ptr(b), _lib.ptr(mask), _lib.ptr(rot), rot_mode, N, w_l1, w_cos, _lib.ptr(ws),
+                  _lib.ptr(out), _lib.ptr(g1), _lib.ptr(g2))
+        ctx.save_for_backward(g1, g2)
+        ctx.shape = pred.shape
+        ctx.set_materialize_grads(False)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g0, g1):
+        a, b = ctx.saved_tensors
+        go = [None if x is None else x.float().reshape(1).contiguous() for x in (g0, g1)]
+        d = torch.empty_like(a)
+        _lib.call("nsim_mono_scale2_bwd", _lib.ptr(a), _lib.ptr(b), a.numel(), _lib.ptr(go[0]), _lib.ptr(go[1]), _lib.ptr(d))
+        return d.reshape(ctx.shape), None, None, None, None, None, None
+
+
+def mono_normal_cue_loss(normals_pred: torch.Tensor, normals_gt: torch.Tensor, mask: torch.Tensor = None, rot: torch.Tensor = None,
+                         w_l1: float = 1.0, w_cos: float = 1.0):
+    """``MonoNormalLoss.fn`` behind the camera-frame rotation (app/loss/mono.py:479-484, 507): -> (w_l1 l1, w_cos cos).
+    normals_pred, normals_gt [..., 3] (N rows), mask bool [N] or None; ``rot`` the world -> camera rotation, None | [3,3] | per
+    row [N,3,3], applied as n' = rot n and constant (the reference detaches the camera transform).  Both sides are normalised as
+    ``F.normalize`` (v / max(|v|, 1e-12)); l1 = mean over ALL N of mask sum_c |n'_c - g_c|, cos = mean of mask (1 - n' . g).  Rows the
+    mask clears are not evaluated: a zero normal there gets a zero gradient.  Gradient to ``normals_pred``; one launch per direction."""
+    if normals_pred.shape != normals_gt.shape or normals_pred.shape[-1] != 3 or normals_pred.numel() == 0:
+        raise ValueError(f"neuralsim_amd: mono_normal_cue_loss takes two [..., 3] tensors of one shape, got {tuple(normals_pred.shape)} "
+                         f"and {tuple(normals_gt.shape)}")
+    if normals_gt.requires_grad:
+        raise NotImplementedError("neuralsim_amd: normals_gt.requires_grad: the normal cue differentiates the prediction only")
+    N = normals_pred.numel() // 3
+    m = None
+    if mask is not None:
+        if mask.numel() != N:
+            raise ValueError(f"neuralsim_amd: mask {tuple(mask.shape)} does not have the {N} rows of the normals")
+        m = _u8(mask, "mask")
+    r, mode = None, 0
+    if rot is not None:
+        _lib.require_device(rot, "rot")
+        if tuple(rot.shape) == (3, 3):
+            mode = 1
+        elif tuple(rot.shape) == (N, 3, 3):
+            mode = 2
+        else:
+            raise ValueError(f"neuralsim_amd: rot must be [3,3] or [{N},3,3], got {tuple(rot.shape)}")
+        r = rot.detach().float().contiguous()
+    return _MonoNormalFn.apply(normals_pred, normals_gt, m, r, mode, float(w_l1), float(w_cos))
+
+
+class _PackedShareFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, vw, rgb, nablas, t, pack_infos, rays_inds, N, normalized_depth, normalize_nablas):
+        w, tt = _flat(vw, "vw_in_total"), _flat(t, "t")
+        c = None if rgb is None else _rows3(rgb, "rgb")
+        nb = None if nablas is None else _rows3(nablas, "nablas")
+        pi, ri = pack_infos.long().contiguous(), rays_inds.long().contiguous()
+        dev = w.device
+        sc = _lib.zeros([2, N], device=dev)
+        nv = int(c is not None) + int(nb is not None)
+        vec = _lib.zeros([nv, N, 3], device=dev) if nv else None
+        o_rgb = vec[0] if c is not None else None
+        o_nrm = vec[nv - 1] if nb is not None else None
+        args = (_lib.ptr(w), _lib.ptr(tt), _lib.ptr(c), _lib.ptr(nb), _lib.ptr(pi), _lib.ptr(ri), pi.shape[0], N, int(normalized_depth),
+                int(normalize_nablas))
+        if w.numel():                          # (packs without a sample: the zeros stand)
+            _lib.call("nsim_packed_share_fwd", *args, _lib.ptr(sc[0]), _lib.ptr(sc[1]), _lib.ptr(o_rgb), _lib.ptr(o_nrm))
+        ctx.args, ctx.outs = args, (sc[0], sc[1])
+        ctx.shapes = (vw.shape, None if rgb is None else rgb.shape, None if nablas is None else nablas.shape)
+        ctx.set_materialize_grads(False)
+        # (None outputs are not allowed between tensors: absent channels come back as empty tensors and are dropped by the caller)
+        e = torch.zeros([0], device=dev)
+        return sc[0], sc[1], (o_rgb if o_rgb is not None else e), (o_nrm if o_nrm is not None else e)
+
+    @staticmethod
+    def backward(ctx, g_mask, g_depth, g_rgb, g_nrm):
+        w, tt, c, nb = ctx.args[:4]
+        gs = [None if g is None else g.float().contiguous() for g in (g_mask, g_depth, g_rgb, g_nrm)]
+        if c is None:
+            gs[2] = None
+        if nb is None:
+            gs[3] = None
+        d_vw = torch.empty_like(w) if ctx.needs_input_grad[0] else None
+        d_rgb = torch.empty_like(c) if (c is not None and ctx.needs_input_grad[1]) else None
+        d_nb = torch.empty_like(nb) if (nb is not None and ctx.needs_input_grad[2]) else None
+        if w.numel():
+            _lib.call("nsim_packed_share_bwd", *ctx.args, _lib.ptr(ctx.outs[0]), _lib.ptr(ctx.outs[1]), *[_lib.ptr(g) for g in gs],
+                      _lib.ptr(d_vw), _lib.ptr(d_rgb), _lib.ptr(d_nb))
+        s = ctx.shapes
+        return (None if d_vw is None else d_vw.reshape(s[0]), None if d_rgb is None else d_rgb.reshape(s[1]),
+                None if d_nb is None else d_nb.reshape(s[2]), None, None, None, None, None, None)
+
+
+def packed_share(vw_in_total: torch.Tensor, t: torch.Tensor, rgb: torch.Tensor, nablas: torch.Tensor, pack_infos: torch.Tensor,
+                 rays_inds: torch.Tensor, N: int, normalized_depth: bool = True, normalize_nablas: bool = False):
+    """One object's share of the joint rendering, ``SingleVolumeRenderer._volume_integration_in_total``
+    (app/renderers/single_volume_renderer.py:104-120): -> (mask [N], depth [N], rgb [N,3] | None, normals [N,3] | None).  Per pack
+    (``pack_infos`` [P,2], its ray ``rays_inds`` [P], the packs must cover samples that exist): mask = sum vw_in_total, depth = sum vw t
+    / (mask + 1e-10) -- or sum vw t with ``normalized_depth=False`` --, rgb / normals = sum vw x; ``normalize_nablas``: the
+    integrated normal is ``normalize(clamp(nablas, -1, 1))``, as the reference integrates outside training.  Rays the object does
+    not hit get zeros.  Gradients to ``vw_in_total``, ``rgb`` and ``nablas``, not to ``t``.  One launch per direction."""
+    N = int(N)
+    if pack_infos.dim() != 2 or pack_infos.shape[1] != 2 or rays_inds.shape[0] != pack_infos.shape[0]:
+        raise ValueError(f"neuralsim_amd: packed_share takes pack_infos [P,2] and rays_inds [P], got {tuple(pack_infos.shape)} and "
+                         f"{tuple(rays_inds.shape)}")
+    S = vw_in_total.numel()
+    if t.numel() != S or (rgb is not None and rgb.numel() != 3 * S) or (nablas is not None and nablas.numel() != 3 * S):
+        raise ValueError("neuralsim_amd: packed_share: t, rgb, nablas must have the samples of vw_in_total")
+    if t.requires_grad:
+        raise NotImplementedError("neuralsim_amd: t.requires_grad: packed_share has no gradient to the depths")
+    m, d, c, nr = _PackedShareFn.apply(vw_in_total, rgb, nablas, t, pack_infos, rays_inds, N, bool(normalized_depth),
+                                       bool(normalize_nablas))
+    return m, d, (c if rgb is not None else None), (nr if nablas is not None else None)
+
+
+def rendered_share(volume_buffer: dict, n_rays: int, device=None, with_rgb: bool = True, with_normal: bool = False,
+                   normalized_depth: bool = True, training: bool = True) -> dict:
+    """``packed_share`` of an object's volume buffer as a ``rendered`` dict (mask_volume, depth_volume, rgb_volume, normals_volume);
+    the empty rendered dict (zeros) for an ``empty`` buffer, which names no device (pass ``device``)."""
+    from .renderers.single_volume_renderer import prepare_empty_rendered
+    vb = volume_buffer
+    if vb["type"] == "empty" or "vw_in_total" not in vb:
+        if device is None:
+            raise ValueError("neuralsim_amd: rendered_share of an empty buffer needs the device")
+        return prepare_empty_rendered([int(n_rays)], torch.device(device), with_rgb=with_rgb, with_normal=with_normal)
+    rgb = vb["rgb"].flatten(0, -2) if (with_rgb and "rgb" in vb) else None
+    nab = vb["nablas_in_world"].flatten(0, -2) if (with_normal and "nablas_in_world" in vb) else None
+    m, d, c, nr = packed_share(vb["vw_in_total"].reshape(-1), vb["t"].detach().reshape(-1), rgb, nab, vb["pack_infos_collect"],
+                               vb["rays_inds_collect"], n_rays, normalized_depth, normalize_nablas=not training)
+    out = dict(mask_volume=m, depth_volume=d)
+    dev = m.device
+    if with_rgb:
+        out["rgb_volume"] = c if c is not None else torch.zeros([int(n_rays), 3], dtype=torch.float32, device=dev)
+    if with_normal:
+        out["normals_volume"] = nr if nr is not None else torch.zeros([int(n_rays), 3], dtype=torch.float32, device=dev)
+    return out
+
+
+_MONO_DEPTH_KEYS = ("w", "anneal", "loss_type", "loss_param", "far", "distant_mode", "ignore_mask_list", "mask_pred_thresh", "mask_erode",
+                    "debug_val_every", "enable_after")
+_MONO_DEPTH_FLAT = ("fn_type", "fn_param", "gt_pre_scale", "gt_pre_shift", "detach_scale_shift", "scale_gt_to_pred", "grad_reg_scales")
+_MONO_LOSS_PARAMS = {"monosdf": _MONO_DEPTH_FLAT + ("alpha_grad_reg",), "pearson": ("alpha_grad_reg", "grad_reg_scales")}
+_MONO_NORMAL_KEYS = ("w_l1", "w_cos", "loss_per", "distant_mode", "ignore_mask_list", "mask_pred_thresh", "mask_erode",
+                     "apply_in_pixel_train_step", "enable_after", "debug_val_every")
+
+
+def mono_depth_cfg(block: dict) -> dict:
+    """A ``mono_depth`` yaml block as the constructor arguments of ``MonoDepthLoss`` (app/loss/mono.py:253-269), every key present.
+    Takes those keys, and the flat spelling of the shipped yamls (lotd_neus.replica.230814.yaml:272-283,
+    withmask_nolidar.240219.yaml:471-483), which predates the class: ``fn_type, fn_param, gt_pre_scale, gt_pre_shift,
+    detach_scale_shift, scale_gt_to_pred, grad_reg_scales`` go into the ``loss_param`` of ``loss_type: monosdf``, and ``w_grad_reg``
+    is read as the weight of the ``.reg`` term itself, alpha_grad_reg = w_grad_reg / w (unpinned).  Anything
+    else is refused by name."""
+    blk = dict(block)
+    _only_keys(blk, _MONO_DEPTH_KEYS + _MONO_DEPTH_FLAT + ("w_grad_reg",), "loss_cfg mono_depth")
+    flat = {k: blk.pop(k) for k in _MONO_DEPTH_FLAT + ("w_grad_reg",) if k in blk}
+    out = dict(w=1.0, anneal=None, loss_type="monosdf" if flat else "pearson", loss_param={}, far=None, distant_mode=None,
+               ignore_mask_list=[], mask_pred_thresh=0.95, mask_erode=0, enable_after=0)
+    out.update({k: v for k, v in blk.items() if k != "debug_val_every"})
+    if out["loss_type"] not in _MONO_LOSS_PARAMS:
+        raise NotImplementedError(f"neuralsim_amd: mono_depth loss_type={out['loss_type']!r}")
+    lp = dict(out["loss_param"] or {})
+    if flat:
+        if out["loss_type"] != "monosdf":
+            raise TypeError(f"neuralsim_amd: loss_cfg mono_depth: {sorted(flat)[0]!r} belongs to loss_type 'monosdf', got {out['loss_type']!r}")
+        if "w_grad_reg" in flat:
+            w_reg = flat.pop("w_grad_reg")
+            if "alpha_grad_reg" in lp:
+                raise TypeError("neuralsim_amd: loss_cfg mono_depth got both w_grad_reg and loss_param.alpha_grad_reg")
+            if not out["w"]:
+                raise ValueError("neuralsim_amd: loss_cfg mono_depth: w_grad_reg is relative to a non-zero w")
+            lp["alpha_grad_reg"] = float(w_reg) / float(out["w"])
+        dup = sorted(set(flat) & set(lp))
+        if dup:
+            raise TypeError(f"neuralsim_amd: loss_cfg mono_depth got {dup[0]!r} twice")
+        lp.update(flat)
+    _only_keys(lp, _MONO_LOSS_PARAMS[out["loss_type"]], f"loss_cfg mono_depth.loss_param of loss_type={out['loss_type']!r}")
+    out["loss_param"] = lp
+    if out["distant_mode"] not in (None, "clamp_far", "cr_only"):
+        raise RuntimeError(f"Invalid distant_mode={out['distant_mode']}")
+    out["ignore_mask_list"] = list(out["ignore_mask_list"])
+    for n in out["ignore_mask_list"]:
+        if n not in MONO_IGNORE:
+            raise ValueError(f"neuralsim_amd: unknown ignore_mask_list entry {n!r}")
+    return out
+
+
+def mono_normals_cfg(block: dict) -> dict:
+    """A ``mono_normals`` yaml block as the constructor arguments of ``MonoNormalLoss`` (app/loss/mono.py:426-436), every key present;
+    ``loss_per: points`` is refused as the reference raises (:538-539)."""
+    blk = dict(block)
+    _only_keys(blk, _MONO_NORMAL_KEYS, "loss_cfg mono_normals")
+    out = dict(w_l1=1.0, w_cos=1.0, loss_per="pixels", distant_mode="crdv", ignore_mask_list=["pred_not_occupied", "not_occupied", "human"],
+               mask_pred_thresh=0.5, mask_erode=0, apply_in_pixel_train_step=False, enable_after=0)
+    out.update({k: v for k, v in blk.items() if k != "debug_val_every"})
+    if out["loss_per"] == "points":
+        raise NotImplementedError("neuralsim_amd: mono_normals loss_per='points' (the reference raises NotImplementedError, mono.py:539)")
+    if out["loss_per"] != "pixels":
+        raise RuntimeError(f"Invalid loss_per={out['loss_per']}")
+    if out["distant_mode"] not in ("crdv", "cr_only"):
+        raise RuntimeError(f"Invalid distant_mode={out['distant_mode']}")
+    out["ignore_mask_list"] = list(out["ignore_mask_list"])
+    for n in out["ignore_mask_list"]:
+        if n not in MONO_IGNORE:
+            raise ValueError(f"neuralsim_amd: unknown ignore_mask_list entry {n!r}")
+    return out

@@ -77,8 +77,14 @@ class SingleVolumeRenderer(nn.Module):
                   near=None, far=None, with_rgb: bool = None, with_normal: bool = None, return_buffer=False,
                   return_details=False, render_per_obj_individual=False, bypass_ray_query_cfg: dict = None,
                   distant_model=None, sky_model=None, with_env: bool = None, cr_ray_tested: dict = None,
-                  world_transform=None) -> Dict:
-        """``cr_ray_tested``: a ``model.ray_test`` result computed ahead of time for exactly these rays (the trainer
+                  world_transform=None, render_per_obj_in_scene=False, render_per_class_in_scene=False) -> Dict:
+        """``render_per_obj_in_scene`` / ``render_per_class_in_scene`` (reference :194-213, 417-442): every object's share of the
+        JOINT rendering -- its samples weighted by ``vw_in_total`` (``_volume_integration_in_total``, :104-120; one launch per
+        object, ``losses.packed_share``) -- as ``ret["rendered_per_obj_in_scene"]`` under the ids "main" / "distant" and
+        ``ret["rendered_per_class_in_scene"]`` under the class names (plus "Sky": the blended sky and the residual
+        transmittance, as ``BufferComposeRenderer``).  The reference writes its per-class results into the per-obj dict
+        (:426-442) -- read as a slip, DESIGN.md sec. 7.
+        ``cr_ray_tested``: a ``model.ray_test`` result computed ahead of time for exactly these rays (the trainer
         prefetches the next batch's AABB test while it waits on the current batch's sample count).
         ``world_transform`` = (rotation [3,3] or per-ray [N,3,3], translation [3] / [N,3], scale): the object -> world
         pose of the main object's scene node; rays are brought into the object frame before the queries
@@ -232,6 +238,25 @@ class SingleVolumeRenderer(nn.Module):
                     (1.0 - total_rendered["mask_volume"][..., None]) * env_rgb
                 total_rendered["rgb_volume"] = total_rendered["rgb_volume"] + env_blend
         ret = dict(ray_intersections=dict(samples_cnt=total_num_samples_per_ray), rendered=total_rendered)
+        if render_per_obj_in_scene or render_per_class_in_scene:
+            from .. import losses
+            norm_depth = config.get("depth_use_normalized_vw", True)
+            shares = {"main": (config.get("main_class_name", "Main"), vb)}
+            if dv_vb is not None:
+                shares["distant"] = ("Distant", dv_vb)
+            shares = {oid: (cls, losses.rendered_share(b, N, device=device, with_rgb=with_rgb, with_normal=with_normal,
+                                                       normalized_depth=norm_depth, training=self.training))
+                      for oid, (cls, b) in shares.items()}
+            if render_per_obj_in_scene:
+                ret["rendered_per_obj_in_scene"] = {oid: dict(r) for oid, (_, r) in shares.items()}
+            if render_per_class_in_scene:
+                per_class = {cls: dict(r) for _, (cls, r) in shares.items()}
+                if sky_model is not None:
+                    per_class["Sky"] = prepare_empty_rendered([N], device, with_rgb=with_rgb, with_normal=with_normal)
+                    if "rgb_volume_non_occupied" in total_rendered:
+                        per_class["Sky"]["rgb_volume"] = total_rendered["rgb_volume_non_occupied"]
+                        per_class["Sky"]["mask_volume"] = 1 - total_rendered["mask_volume"]
+                ret["rendered_per_class_in_scene"] = per_class
         if return_buffer:
             ret["volume_buffer"] = total_volume_buffer
         if return_details:
@@ -244,7 +269,7 @@ class SingleVolumeRenderer(nn.Module):
                far=None, rayschunk: int = None, with_rgb=None, with_normal=None, return_buffer=False,
                return_details=False, render_per_obj_individual=False, bypass_ray_query_cfg: dict = None,
                distant_model=None, sky_model=None, with_env: bool = None, cr_ray_tested: dict = None,
-               world_transform=None) -> Dict:
+               world_transform=None, render_per_obj_in_scene=False, render_per_class_in_scene=False) -> Dict:
         """rays = [rays_o, rays_d(, rays_ts, rays_pix)] with arbitrary prefix shape (reference :495-581)."""
         if rayschunk is None:
             rayschunk = self.config.get("rayschunk", 0)
@@ -256,7 +281,8 @@ class SingleVolumeRenderer(nn.Module):
                           return_buffer=return_buffer, return_details=return_details,
                           render_per_obj_individual=render_per_obj_individual, bypass_ray_query_cfg=bypass_ray_query_cfg,
                           distant_model=distant_model, sky_model=sky_model, with_env=with_env,
-                          cr_ray_tested=cr_ray_tested, world_transform=world_transform)
+                          cr_ray_tested=cr_ray_tested, world_transform=world_transform,
+                          render_per_obj_in_scene=render_per_obj_in_scene, render_per_class_in_scene=render_per_class_in_scene)
             if self.training or (not rayschunk) or flat[0].shape[0] <= rayschunk:
                 ret = self(*flat[:2], rays_h_appear=ha, **kwargs)
             else:
@@ -270,7 +296,10 @@ class SingleVolumeRenderer(nn.Module):
                     ret = batchify_query(fn, flat[0], flat[1], ha, chunk=rayschunk)
             ret.update(rays_o=flat[0], rays_d=flat[1])
             if len(prefix_shape) > 1:
-                for k in self.image_keys:
-                    if k in ret["rendered"]:
-                        ret["rendered"][k] = ret["rendered"][k].unflatten(0, prefix_shape)
+                groups = [ret["rendered"]] + [r for key in ("rendered_per_obj_in_scene", "rendered_per_class_in_scene")
+                                              for r in ret.get(key, {}).values()]
+                for rendered in groups:
+                    for k in self.image_keys:
+                        if k in rendered:
+                            rendered[k] = rendered[k].unflatten(0, prefix_shape)
         return ret

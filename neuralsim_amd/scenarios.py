@@ -372,7 +372,9 @@ def indoor_model(device, precision: str = "fp16", seed: int = 42, small: bool = 
 
 
 def build_indoor_trainer(device, rank: int = 0, world_size: int = 1, precision: str = "fp16", rays_per_gpu: int = 16384,
-                         seed: int = 42, small: bool = False, num_uniform: Optional[int] = None):
+                         seed: int = 42, small: bool = False, num_uniform: Optional[int] = None, loss_cfg: Optional[dict] = None):
+    """``loss_cfg``: ``RenderTrainer(loss_cfg=)``, e.g. ``INDOOR_MONO_LOSS_CFG`` -- the config's own monocular blocks, which then replace
+    the plain-torch ``w_depth`` / ``w_normal`` terms.  None: the trainer as it always was."""
     from . import distributed as ndist
     from .trainer import RenderTrainer
     world = indoor_world()
@@ -386,9 +388,19 @@ def build_indoor_trainer(device, rank: int = 0, world_size: int = 1, precision: 
     tr = RenderTrainer(m, intr, c2w, WH, num_rays=rays_per_gpu, lr=1e-3, w_eikonal=0.1,
                        num_uniform=(256 if small else 4096) if num_uniform is None else num_uniform, near=0.01, rank=rank,
                        world_size=world_size, seed=seed, learn_inv_s=False, target_images=img,
-                       mono=dict(depth=dep, normals=nrm, patch_hw=patch, w_depth=0.1, w_normal=0.05))
+                       mono=dict(depth=dep, normals=nrm, patch_hw=patch, w_depth=0.1, w_normal=0.05), loss_cfg=loss_cfg)
     tr.renderer.config.update(depth_use_normalized_vw=False)
     return tr
+
+
+# the two monocular blocks of lotd_neus.replica.230814.yaml:271-288 in the yaml's own (flat) spelling, its interpolations resolved
+# with the config's values (mono_fn mse, mono_w 1e-3, mono_w_reg 1e-5, mono_erode 8, mono_after 1500, w_mono_normal_l1 / _cos 0.01:
+# yaml:24-31)
+INDOOR_MONO_LOSS_CFG = dict(
+    mono_depth=dict(fn_type="mse", w=1.0e-3, w_grad_reg=1.0e-5, gt_pre_scale=50.0, gt_pre_shift=1.0, ignore_mask_list=[],
+                    mask_pred_thresh=0.5, mask_erode=8, enable_after=1500, detach_scale_shift=False, scale_gt_to_pred=False),
+    mono_normals=dict(w_l1=0.01, w_cos=0.01, ignore_mask_list=[], apply_in_pixel_train_step=True),
+)
 
 
 # ------------------------------------------------------------------------------------------------ multi (configs[4])

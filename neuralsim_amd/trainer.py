@@ -87,7 +87,15 @@ class RenderTrainer:
         clearance and weight regularisation (train.py:929-954; the weight term there covers the tensors of the lidar graph only, so
         the radiance side keeps its optimizer state).  The terms are reported in ``loss_parts`` / ``_lidar_parts`` under the
         reference's keys as detached device scalars.  ``main_class_name``: the class the main model's blocks are looked up under;
-        the distant model's is ``Distant``.  With a ``loss_cfg`` the step takes the autograd path; None changes nothing."""
+        the distant model's is ``Distant``.  ``mono_depth`` / ``mono_normals``: the monocular cue blocks (lotd_neus.replica.230814.yaml:
+        272-288, withmask_nolidar.240219.yaml:463-483) with the constructor keys of ``MonoDepthLoss`` / ``MonoNormalLoss`` or the yamls'
+        flat spelling (``losses.mono_depth_cfg``), on the fused ops of csrc/loss_ops.hip; the data is ``mono=`` (new optional entries
+        ``human_mask``, ``dynamic_mask`` [V,H,W] bool and ``normals_in_camera_frame``: False = the priors are world-space; True = the
+        rendered normals are rotated by the transposed camera rotation of every ray's frame), the occupancy mask ``target_masks``.  The
+        depth term covers the patch rows, the normal term every row with ``apply_in_pixel_train_step`` (else the patch rows);
+        ``distant_mode: cr_only`` renders with ``render_per_obj_in_scene``.  A block replaces the plain-torch ``w_depth`` / ``w_normal``
+        term; the terms are ``loss_mono_depth.depth``, ``.reg``, ``loss_mono_normal.l1``, ``.cos``.
+        With a ``loss_cfg`` the step takes the autograd path; None changes nothing."""
         self.model = model
         self.target_masks, self.main_class_name = target_masks, str(main_class_name)
         self.loss_cfg = self._check_loss_cfg(loss_cfg, distant_model, num_uniform, target_masks)
@@ -101,6 +109,7 @@ class RenderTrainer:
         self.target_images, self.mono, self.rgb_fn = target_images, (dict(mono) if mono else None), rgb_fn
         self.lidar = dict(lidar) if lidar else None
         self._last_aux = None
+        self._mono_per_obj = False
         self.distortion = distortion
         # fused_step (default on, env NSIM_FUSED_STEP=0 turns it off): the differentiable part of the iteration -- field
         # forward, sdf->alpha, compositing, losses and their whole backward -- is issued as one straight chain of
@@ -148,6 +157,7 @@ class RenderTrainer:
         self.w_curvature, self.curvature_eps = float(w_curvature), float(curvature_eps)
         self.loss_parts: Dict[str, torch.Tensor] = {}      # the terms of the last autograd-path step (detached device scalars)
         self.near, self.far, self.perturb = near, far, perturb
+        self._check_mono_blocks()
         self.rank, self.world_size = rank, world_size
         dev = model.device
         self.gen = torch.Generator(device=dev).manual_seed(seed + 1000 * rank)
@@ -226,6 +236,11 @@ class RenderTrainer:
             self._last_aux = None
             if self.mono is not None:
                 self._last_aux = dict(depth=self.mono["depth"][fidx, iy, ix], normals=self.mono["normals"][fidx, iy, ix])
+                if self.loss_cfg is not None and ("mono_depth" in self.loss_cfg or "mono_normals" in self.loss_cfg):
+                    self._last_aux["fidx"] = fidx
+                    for k in ("human_mask", "dynamic_mask"):
+                        if self.mono.get(k) is not None:
+                            self._last_aux[k] = self.mono[k][fidx, iy, ix]
             if self.target_masks is not None and self.loss_cfg is not None:
                 self._last_aux = dict(self._last_aux or {}, mask=self.target_masks[fidx, iy, ix], mask_of=xy)
             return xy, fidx, self.target_images[fidx, iy, ix]
@@ -281,7 +296,8 @@ class RenderTrainer:
                 else embedding_lookup(h_appear, tested["rays_inds"])
         ret = self.renderer.render(self.model, rays=[rays_o, rays_d], rays_h_appear=h_appear, with_normal=with_normal,
                                    return_buffer=True, return_details=True, distant_model=self.distant_model,
-                                   sky_model=self.sky_model, bypass_ray_query_cfg=bypass or None, cr_ray_tested=tested)
+                                   sky_model=self.sky_model, bypass_ray_query_cfg=bypass or None, cr_ray_tested=tested,
+                                   **(dict(render_per_obj_in_scene=True) if self._mono_per_obj else {}))
         return ret
 
     # ------------------------------------------------------------------ the differentiable part as one launch chain
@@ -689,8 +705,10 @@ class RenderTrainer:
             r_ = ret["rendered"]
             occupied = (r_["mask_volume"].detach() > 0.5).float()          # ``pred_not_occupied`` of the ignore list
             w_n, w_d = float(self.mono.get("w_normal", 0.05)), float(self.mono.get("w_depth", 0.1))
-            loss_rgb = loss_rgb + w_n * mono_normal_loss(r_["normals_volume"], aux["normals"], occupied)
-            if self.mono.get("patch_hw"):
+            blocks = self.loss_cfg or {}          # a ``mono_normals`` / ``mono_depth`` block replaces the plain-torch term
+            if "mono_normals" not in blocks:
+                loss_rgb = loss_rgb + w_n * mono_normal_loss(r_["normals_volume"], aux["normals"], occupied)
+            if self.mono.get("patch_hw") and "mono_depth" not in blocks:
                 n_p = self.mono["patch_hw"][0] * self.mono["patch_hw"][1]
                 loss_rgb = loss_rgb + w_d * mono_depth_loss(r_["depth_volume"][:n_p], aux["depth"][:n_p], occupied[:n_p])
         eik, curv = None, None
@@ -722,12 +740,14 @@ class RenderTrainer:
             total, parts["rgb_s3im"] = total + term, term.detach()
         if self.loss_cfg is not None:
             terms = self._street_terms(ret, self._it, "pixel", uni=uni, mask_gt=None if aux is None else aux.get("mask"))
+            if aux is not None and self.mono is not None:
+                terms.update(self._mono_terms(ret, self._it, aux))
             for k, v in terms.items():
                 total, parts[k] = total + v, v.detach()
         return total, parts
 
     # ------------------------------------------------------------------ the street configs' supervision blocks (loss_cfg)
-    _LOSS_BLOCKS = ("occupancy_mask", "mask_entropy", "sparsity", "clearance", "weight_reg", "lidar")
+    _LOSS_BLOCKS = ("occupancy_mask", "mask_entropy", "sparsity", "clearance", "weight_reg", "lidar", "mono_depth", "mono_normals")
 
     def _check_loss_cfg(self, loss_cfg, distant_model, num_uniform, target_masks):
         """-> a plain-dict copy of the blocks (None for no blocks), refused at construction for what the step cannot do"""
@@ -769,7 +789,42 @@ class RenderTrainer:
                 raise NotImplementedError(f"RenderTrainer: loss_cfg mask_entropy.mode={mode!r}")
             if mode not in ("crisp", "nop") and distant_model is None:
                 raise ValueError(f"RenderTrainer: mask_entropy mode={mode!r} only functions in cr-dv joint training (no distant model)")
+        from .losses import mono_depth_cfg, mono_normals_cfg
+        if "mono_depth" in cfg:
+            cfg["mono_depth"] = mono_depth_cfg(cfg["mono_depth"])
+        if "mono_normals" in cfg:
+            cfg["mono_normals"] = mono_normals_cfg(cfg["mono_normals"])
         return cfg
+
+    def _check_mono_blocks(self):
+        """the ``mono_depth`` / ``mono_normals`` blocks against the data the trainer has (``mono=``, ``target_masks``, ``far``)"""
+        cfg = self.loss_cfg or {}
+        blocks = [(k, cfg[k]) for k in ("mono_depth", "mono_normals") if k in cfg]
+        if not blocks:
+            return
+        if self.mono is None:
+            raise ValueError("RenderTrainer: loss_cfg mono_depth / mono_normals need mono=dict(depth, normals, patch_hw)")
+        patch = self.mono.get("patch_hw")
+        if "mono_depth" in cfg and not patch:
+            raise ValueError("RenderTrainer: loss_cfg['mono_depth'] needs mono['patch_hw'] (the depth term is taken on an image patch)")
+        for name, c in blocks:
+            on_patch = name == "mono_depth" or not c["apply_in_pixel_train_step"]
+            if not on_patch and int(c["mask_erode"]) > 0:
+                raise ValueError(f"RenderTrainer: loss_cfg {name}.mask_erode > 0 needs an image patch: with apply_in_pixel_train_step the "
+                                 "term covers every ray of the batch")
+            if on_patch and not patch:
+                raise ValueError(f"RenderTrainer: loss_cfg[{name!r}] needs mono['patch_hw'] unless apply_in_pixel_train_step")
+            names = c["ignore_mask_list"] if name == "mono_depth" else [n for n in c["ignore_mask_list"]
+                                                                       if n in ("pred_not_occupied", "not_occupied", "dynamic", "human")]
+            for entry, key in (("human", "human_mask"), ("dynamic", "dynamic_mask")):
+                if entry in names and self.mono.get(key) is None:
+                    raise ValueError(f"RenderTrainer: loss_cfg {name}.ignore_mask_list entry {entry!r} needs mono[{key!r}] [V,H,W]")
+            if "not_occupied" in names and self.target_masks is None:
+                raise ValueError(f"RenderTrainer: loss_cfg {name}.ignore_mask_list entry 'not_occupied' needs target_masks [V,H,W]")
+            if name == "mono_depth" and ({"toofar", "pred_distant"} & set(names) or c["distant_mode"] == "clamp_far") \
+                    and c["far"] is None and self.far is None:
+                raise ValueError("RenderTrainer: loss_cfg mono_depth needs far (toofar / pred_distant / clamp_far)")
+        self._mono_per_obj = any(c["distant_mode"] == "cr_only" for _, c in blocks)
 
     def _gather_mask(self, xy, fidx):
         H_, W_ = self.target_masks.shape[1], self.target_masks.shape[2]
@@ -841,6 +896,62 @@ class RenderTrainer:
                 else:
                     norms = model.get_weight_reg(**c)
                 out[f"loss_weight_reg.{cname}"] = w * norms.sum()
+        return out
+
+    def _mono_terms(self, ret, it: int, aux: dict) -> Dict[str, torch.Tensor]:
+        """The ``mono_depth`` / ``mono_normals`` blocks on the pixel step's render (``MonoDepthLoss.forward`` / ``MonoNormalLoss.forward``,
+        app/loss/mono.py:324-423, 486-572) -> the weighted terms under the reference's keys.  The depth term sees the patch rows
+        as an [h,w] image; the normal term every row with ``apply_in_pixel_train_step``, else the patch rows.  ``enable_after`` and
+        ``anneal`` are resolved on the host; a mask that leaves no pixel gives zero terms (the reference returns none after a
+        read-back)."""
+        from . import losses as L_
+        cfg, out, r = self.loss_cfg, {}, ret["rendered"]
+        ph, pw = self.mono["patch_hw"] if self.mono.get("patch_hw") else (0, 0)
+        P, N = ph * pw, r["mask_volume"].shape[0]
+
+        def gt_maps(sl, shape):
+            occ = aux.get("mask")
+            if occ is not None:                # ``target_masks`` may hold the BCE target as floats
+                occ = occ[sl].reshape(shape)
+                occ = occ > 0.5 if occ.dtype.is_floating_point else occ
+            maps = dict(occupancy_gt=occ)
+            for k, src in (("human_gt", "human_mask"), ("dynamic_gt", "dynamic_mask")):
+                maps[k] = None if aux.get(src) is None else aux[src][sl].reshape(shape)
+            return maps
+        c = cfg.get("mono_depth")
+        if c is not None and it >= int(c["enable_after"]):
+            w = self._block_w(c, it)
+            far = c["far"] if c["far"] is not None else self.far
+            sl, shape = slice(0, P), (ph, pw)
+            depth0 = r["depth_volume"][sl]
+            if c["distant_mode"] == "cr_only":          # the close-range model's share of the joint rendering (mono.py:351-354)
+                rend = ret["rendered_per_obj_in_scene"]["main"]
+                depth = rend["depth_volume"][sl]
+            else:
+                rend = r
+                depth = depth0.clamp_max(far) if c["distant_mode"] == "clamp_far" else depth0
+            gt = aux["depth"][sl].reshape(shape)
+            remain = L_.mono_remain_mask(rend["mask_volume"][sl].reshape(shape), depth_pred0=depth0.reshape(shape),
+                                         depth_pred=depth.reshape(shape), depth_gt=gt, far=far, ignore_mask_list=c["ignore_mask_list"],
+                                         mask_pred_thresh=c["mask_pred_thresh"], mask_erode=c["mask_erode"], **gt_maps(sl, shape))
+            fn = L_.mono_depth_ssi_loss if c["loss_type"] == "monosdf" else L_.mono_depth_pearson_loss
+            dep, reg = fn(depth.reshape(shape), gt, remain, w=1.0 if w is None else w, **c["loss_param"])
+            out["loss_mono_depth.depth"] = dep
+            if reg is not None:
+                out["loss_mono_depth.reg"] = reg
+        c = cfg.get("mono_normals")
+        if c is not None and it >= int(c["enable_after"]):
+            rows = N if c["apply_in_pixel_train_step"] else P
+            sl, shape = slice(0, rows), ((ph, pw) if rows == P and int(c["mask_erode"]) > 0 else (rows,))
+            remain = L_.mono_remain_mask(r["mask_volume"][sl].reshape(shape), ignore_mask_list=c["ignore_mask_list"],
+                                         mask_pred_thresh=c["mask_pred_thresh"], mask_erode=c["mask_erode"], for_normals=True,
+                                         **gt_maps(sl, shape))
+            rot = None
+            if self.mono.get("normals_in_camera_frame", False):      # world -> camera: the transposed rotation of the ray's frame
+                rot = self.current_c2w().detach()[aux["fidx"][sl], :3, :3].transpose(-1, -2).contiguous()
+            l1, cos = L_.mono_normal_cue_loss(r["normals_volume"][sl], aux["normals"][sl], remain.reshape(-1), rot=rot,
+                                              w_l1=c["w_l1"], w_cos=c["w_cos"])
+            out["loss_mono_normal.l1"], out["loss_mono_normal.cos"] = l1, cos
         return out
 
     # ------------------------------------------------------------------ lidar step (street configs)

@@ -115,6 +115,32 @@ typedef struct NsimComposeSrc {
 } NsimComposeSrc;
 int nsim_compose_collect_sort(const NsimComposeSrc* src, int32_t K, const int64_t* total_pack_infos, int64_t N,
                               float* t_sorted, void* stream);
+/* The instance / class segmentation z-buffer of BufferComposeRenderer.ray_query(render_per_obj_individual=True)
+ * (code_multi/app/renderers/buffer_compose_renderer.py:186-188 the three buffers, :268-311 a batched group, :427-450 and :549-572
+ * a single model) for ALL drawable groups of a render in one call.  K <= 64 sources in the renderer's processing order; source
+ * k: M candidates on the rays ``rays_inds`` [M] (the group's tested rays) with the object's INDIVIDUAL mask / depth -- pair form
+ * (B == 0): ``mask`` / ``depth`` [M]; image form (B >= 1): ``mask`` / ``depth`` are [B, N] images read at (bidx[j], rays_inds[j]),
+ * row 0 when bidx is NULL (a single model's [N] image) --,
+ * the instance index per candidate (``ins`` [M]) or one for all (ins NULL: ins_scalar), and the class index.  Per ray: the
+ * candidates are the entries with mask > threshold (strict) and depth < +inf (a NaN never wins; -0.0 counts as 0.0); the one of
+ * smallest depth wins, among equal depths the earliest in processing order (source order, then position; the reference's strict
+ * ``depth < z_buffer`` across groups -- inside a batched group its scatter_min leaves ties unspecified).  Outputs, written for every
+ * ray: ins_seg / class_seg [N] (-1: no candidate) and z_buffer [N] (+inf: no candidate).  ``keys`` [N]: workspace of the caller,
+ * initialised here when ordinal_base == 0.  More than 64 sources: further calls with the SAME keys and outputs and ordinal_base =
+ * the candidates of the calls before (all ordinals < 2^32 - 1).  No host read, no synchronisation. */
+typedef struct NsimSegSrc {
+  const int64_t* rays_inds;
+  int64_t M;
+  const float* mask;
+  const float* depth;
+  const int64_t* bidx;
+  int64_t B;
+  const int64_t* ins;
+  int64_t ins_scalar;
+  int64_t class_ind;
+} NsimSegSrc;
+int nsim_seg_zbuffer(const NsimSegSrc* src, int32_t K, int64_t N, float threshold, int64_t ordinal_base, uint64_t* keys,
+                     int64_t* ins_seg, int64_t* class_seg, float* z_buffer, void* stream);
 /* interleave_linstep(start [P], n [P], step): pack_infos = get_pack_infos_from_n(n)  (buffer_compose_renderer.py:1036) */
 int nsim_interleave_linstep(const int64_t* start, const int64_t* pack_infos, int64_t P, int64_t step,
                             int64_t* out, void* stream);

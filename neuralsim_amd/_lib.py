@@ -91,6 +91,11 @@ class ComposeSrc(C.Structure):      # include/nsim.h NsimComposeSrc
     _fields_ = [("t", C.c_void_p), ("rays_inds", C.c_void_p), ("pack_infos", C.c_void_p), ("P", C.c_int64), ("dst", C.c_void_p)]
 
 
+class SegSrc(C.Structure):          # include/nsim.h NsimSegSrc
+    _fields_ = [("rays_inds", C.c_void_p), ("M", C.c_int64), ("mask", C.c_void_p), ("depth", C.c_void_p), ("bidx", C.c_void_p),
+                ("B", C.c_int64), ("ins", C.c_void_p), ("ins_scalar", C.c_int64), ("class_ind", C.c_int64)]
+
+
 class EntropyTerm(C.Structure):     # include/nsim.h NsimEntropyTerm
     _fields_ = [("a_src", C.c_int32), ("a_neg", C.c_int32), ("a_detach", C.c_int32), ("b_src", C.c_int32), ("b_neg", C.c_int32),
                 ("b_detach", C.c_int32), ("out", C.c_int32), ("coef", C.c_float)]
@@ -165,7 +170,8 @@ SIGNATURES = {
     "nsim_lotd_gather_lm": [C.POINTER(FieldMeta), _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P],
     "nsim_field_fwd": [C.POINTER(FieldMeta), _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64],
     "nsim_compose_collect_sort": [_P, _I, _P, _I64, _P],
-    "nsim_wide_sdf": [C.POINTER(FieldMeta), _I, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P],
+    "nsim_seg_zbuffer": [_P, _I, _I64, _F, _I64, _P, _P, _P, _P],
+    "nsim_wide_sdf": [C.POINTER(FieldMeta), _I,_P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P],
     "nsim_wide_bwd_sdf": [C.POINTER(FieldMeta), _P, _P, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _P],
     "nsim_set_grad_scratch": [_P, _I64],
     "nsim_permuto_fwd": [C.POINTER(PermutoMeta), _P, _P, _I64, _P, _P],

@@ -1769,6 +1769,7 @@ const char* nsim_strerror(int code) {
     case 56: return "occupancy grid: 1 <= subsample factor <= 4, resolutions >= 1, resolution * factor + 1 < 2^24 per axis, fewer than 2^31 voxels and lattice points per slab";
     case 57: return "visible grid: the grid edge is a power of two in 32 .. 1024 (octree depth 5 .. 10), fewer than 2^39 samples per call";
     case 58: return "street losses: unknown mode / type / function, lo > hi, more than 4 entropy terms or a source outside 0..2, 0 <= k < N < 2^32 for the order statistic, far / std > 0 where the function divides by it";
+    case 59: return "segmentation z-buffer: at most 64 sources per call, candidate ordinals (ordinal_base + the call's candidates) below 2^32 - 1";
     case 36: return "wide decoder: 0..10 embedding frequencies and at most 128 first-layer inputs (2 num_levels + 3 + 6 n_freq)";
     default: return code >= 1000 ? "HIP launch error (code - 1000 = hipError_t)" : "unknown error";
   }

@@ -476,6 +476,126 @@ __global__ void __launch_bounds__(PACK_BLOCK) k_compose_collect_sort(ComposeArgs
   }
 }
 
+// ------------------------------------------------------------------------------------ compose: segmentation z-buffer
+// BufferComposeRenderer's instance / class segmentation (code_multi/app/renderers/buffer_compose_renderer.py:268-311, 427-450,
+// 549-572).  The reference walks the drawable groups one after the other: the group's tested rays whose INDIVIDUAL mask
+// exceeds the threshold are its candidates (nonzero + .any()), a batched group keeps each ray's nearest candidate (unique +
+// scatter_min), and a candidate takes the ray when its depth is below the z-buffer (three indexed stores) -- per group a chain
+// of torch ops with host reads.  Here the groups of one render are the sources of ONE call:
+//   pass 1, a thread per candidate of the concatenation of all sources: 64-bit atomicMin on keys[ray] with
+//           key = (order-preserving 32-bit image of the depth) << 32 | ordinal of the candidate in processing order;
+//   pass 2, a thread per ray: the winning ordinal -> its source (search over the <= 64 prefix sums) -> instance index, class
+//           index, and z decoded from the key.
+// The smallest key is the nearest candidate and, among equal depths, the earliest in processing order -- across groups the
+// reference's strict ``depth < z_buffer``, inside a batched group (where its scatter_min leaves ties open) the lower position.
+// The minimum of a set does not depend on the order the atomics arrive in: the result is reproducible.
+#define SEG_MAX_SRC 64
+#define SEG_BLOCK 256
+#define SEG_KEY_NONE 0xffffffffffffffffull      // (no candidate reaches it: the image of +inf, the largest depth taken, is 0xff800000)
+struct SegCandSrc {
+  const int64_t* ri;
+  const float *mask, *depth;
+  const int64_t* bidx;
+  int32_t B;      // 0: mask / depth are [M]; else the base of [B, N] images read at (bidx[j] or row 0, ri[j])
+};
+struct SegCandArgs {
+  int K;
+  SegCandSrc src[SEG_MAX_SRC];
+  uint32_t start[SEG_MAX_SRC + 1];      // prefix sums of the sources' candidate counts (this call's)
+  int64_t N;
+  float thr;
+  uint64_t base;      // ordinal of this call's first candidate
+  unsigned long long* keys;
+};
+struct SegRaySrc {
+  const int64_t* ins;      // per candidate, or NULL: ins_scalar
+  int64_t ins_scalar, cls;
+};
+struct SegRayArgs {
+  int K;
+  SegRaySrc src[SEG_MAX_SRC];
+  uint32_t start[SEG_MAX_SRC + 1];
+  int64_t N;
+  uint64_t base;
+  const unsigned long long* keys;
+  int64_t *ins_seg, *cls_seg;
+  float* z;
+};
+
+// the last k in [0, K) with start[k] <= j  (sources without candidates are empty ranges: never returned for a valid j)
+__device__ __forceinline__ int seg_source_of(const uint32_t* start, int K, uint32_t j) {
+  int lo = 0, hi = K - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (start[mid] <= j) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// float -> uint32 with the same order (-inf .. -0 = +0 .. +inf), and back
+__device__ __forceinline__ uint32_t seg_depth_image(float d) {
+  if (d == 0.0f) d = 0.0f;      // -0.0 counts as 0.0
+  uint32_t u;
+  memcpy(&u, &d, 4);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float seg_depth_of(uint32_t im) {
+  const uint32_t u = (im & 0x80000000u) ? (im & 0x7fffffffu) : ~im;
+  float d;
+  memcpy(&d, &u, 4);
+  return d;
+}
+
+__global__ void __launch_bounds__(SEG_BLOCK) k_seg_fill_keys(unsigned long long* keys, int64_t N) {
+  const int64_t stride = (int64_t)gridDim.x * SEG_BLOCK;
+  for (int64_t r = (int64_t)blockIdx.x * SEG_BLOCK + threadIdx.x; r < N; r += stride) keys[r] = SEG_KEY_NONE;
+}
+
+__global__ void __launch_bounds__(SEG_BLOCK) k_seg_candidates(SegCandArgs a) {
+  const int64_t total = a.start[a.K], stride = (int64_t)gridDim.x * SEG_BLOCK;
+  for (int64_t c = (int64_t)blockIdx.x * SEG_BLOCK + threadIdx.x; c < total; c += stride) {
+    const int k = seg_source_of(a.start, a.K, (uint32_t)c);
+    const SegCandSrc& s = a.src[k];
+    const int64_t j = c - a.start[k];
+    const int64_t r = s.ri[j];
+    if (r < 0 || r >= a.N) continue;
+    int64_t at = j;
+    if (s.B > 0) {
+      const int64_t b = s.bidx ? s.bidx[j] : 0;
+      if (b < 0 || b >= s.B) continue;
+      at = b * a.N + r;
+    }
+    const float m = s.mask[at], d = s.depth[at];
+    // strict comparisons, as the reference's ``mask > threshold`` and ``depth < z_buffer`` on a buffer that starts at +inf: a
+    // mask of exactly the threshold, a NaN of either and a depth of +inf are no candidates
+    if (!(m > a.thr) || !(d < INFINITY)) continue;
+    const unsigned long long key = ((unsigned long long)seg_depth_image(d) << 32) | (unsigned long long)(a.base + (uint64_t)c);
+    atomicMin(a.keys + r, key);
+  }
+}
+
+__global__ void __launch_bounds__(SEG_BLOCK) k_seg_resolve(SegRayArgs a) {
+  const int64_t stride = (int64_t)gridDim.x * SEG_BLOCK;
+  const uint64_t total = a.start[a.K];
+  for (int64_t r = (int64_t)blockIdx.x * SEG_BLOCK + threadIdx.x; r < a.N; r += stride) {
+    const unsigned long long key = a.keys[r];
+    if (key == SEG_KEY_NONE) {
+      a.ins_seg[r] = -1;
+      a.cls_seg[r] = -1;
+      a.z[r] = INFINITY;
+      continue;
+    }
+    const uint64_t ord = key & 0xffffffffull;
+    if (ord < a.base || ord - a.base >= total) continue;      // the winner so far belongs to an earlier call: its outputs stand
+    const uint32_t c = (uint32_t)(ord - a.base);
+    const int k = seg_source_of(a.start, a.K, c);
+    const SegRaySrc& s = a.src[k];
+    a.ins_seg[r] = s.ins ? s.ins[c - a.start[k]] : s.ins_scalar;
+    a.cls_seg[r] = s.cls;
+    a.z[r] = seg_depth_of((uint32_t)(key >> 32));
+  }
+}
+
 // lower_bound / upper_bound on a sorted global array segment
 __device__ __forceinline__ int64_t seg_lower_bound(const float* a, int64_t n, float v) {  // #elements < v
   int64_t lo = 0, hi = n;
@@ -1108,6 +1228,57 @@ int nsim_compose_collect_sort(const NsimComposeSrc* src, int32_t K, const int64_
   a.N = N;
   a.t_sorted = t_sorted;
   hipLaunchKernelGGL(k_compose_collect_sort, pack_grid(N), dim3(PACK_BLOCK), 0, (hipStream_t)stream, a);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_seg_zbuffer(const NsimSegSrc* src, int32_t K, int64_t N, float threshold, int64_t ordinal_base, uint64_t* keys,
+                     int64_t* ins_seg, int64_t* class_seg, float* z_buffer, void* stream) {
+  if (K < 0 || K > SEG_MAX_SRC || ordinal_base < 0) return 59;
+  if (N <= 0) return 0;
+  if (!keys || !ins_seg || !class_seg || !z_buffer || (K > 0 && !src)) return 2;
+  SegCandArgs ca;
+  SegRayArgs ra;
+  memset(&ca, 0, sizeof(ca));
+  memset(&ra, 0, sizeof(ra));
+  uint64_t total = 0;
+  for (int k = 0; k < K; ++k) {
+    const NsimSegSrc& s = src[k];
+    if (s.M < 0 || s.B < 0 || (s.bidx && s.B == 0) || s.B > 0x7fffffff) return 2;
+    if (s.M > 0 && !(s.rays_inds && s.mask && s.depth)) return 2;
+    ca.src[k].ri = s.rays_inds;
+    ca.src[k].mask = s.mask;
+    ca.src[k].depth = s.depth;
+    ca.src[k].bidx = s.bidx;
+    ca.src[k].B = (int32_t)s.B;
+    ra.src[k].ins = s.ins;
+    ra.src[k].ins_scalar = s.ins_scalar;
+    ra.src[k].cls = s.class_ind;
+    ca.start[k] = ra.start[k] = (uint32_t)total;
+    total += (uint64_t)s.M;
+    if ((uint64_t)ordinal_base + total >= 0xffffffffull) return 59;
+  }
+  for (int k = K; k <= SEG_MAX_SRC; ++k) ca.start[k] = ra.start[k] = (uint32_t)total;
+  ca.K = ra.K = K;
+  ca.N = ra.N = N;
+  ca.thr = threshold;
+  ca.base = ra.base = (uint64_t)ordinal_base;
+  ca.keys = (unsigned long long*)keys;
+  ra.keys = (const unsigned long long*)keys;
+  ra.ins_seg = ins_seg;
+  ra.cls_seg = class_seg;
+  ra.z = z_buffer;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 ray_grid(nsim_blocks(N, SEG_BLOCK, 1 << 16));
+  if (ordinal_base == 0) {      // the first call of a render: every ray starts without a winner
+    hipLaunchKernelGGL(k_seg_fill_keys, ray_grid, dim3(SEG_BLOCK), 0, st, (unsigned long long*)keys, N);
+    NSIM_CHECK_LAUNCH();
+  }
+  if (total > 0) {
+    hipLaunchKernelGGL(k_seg_candidates, dim3(nsim_blocks((int64_t)total, SEG_BLOCK, 1 << 16)), dim3(SEG_BLOCK), 0, st, ca);
+    NSIM_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(k_seg_resolve, ray_grid, dim3(SEG_BLOCK), 0, st, ra);
   NSIM_CHECK_LAUNCH();
   return 0;
 }

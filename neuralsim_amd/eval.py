@@ -37,6 +37,54 @@ def render_image(renderer, model, intr, c2w, WH, frame: int, rays_h_appear=None,
     return {k: v.reshape(H, W, *v.shape[1:]) for k, v in ret["rendered"].items()}
 
 
+@torch.no_grad()
+def render_scene_image(renderer, drawables, intr, c2w, WH, frame: int, *, sky_model=None, distant_model=None,
+                       rays_h_appear=None, rayschunk: int = 65536, with_segmentation: bool = False,
+                       render_per_obj_individual: bool = False, distortion=None, **ray_query_kwargs):
+    """``render_image`` for a multi-object scene: the full view of camera ``frame`` through a ``BufferComposeRenderer`` in
+    ``rayschunk`` pieces (the reference's ``BufferComposeRenderer.render``, app/renderers/buffer_compose_renderer.py:876-940, in
+    eval mode), with the validation settings of ``render_image``.
+    -> dict of [H, W(,3)] images (``rgb_volume``, ``depth_volume``, ``mask_volume``, ``normals_volume`` ...); with
+    ``with_segmentation`` also ``ins_seg_mask_buffer`` / ``class_seg_mask_buffer`` [H, W] (long, -1: no object) and the two index
+    maps; with ``render_per_obj_individual`` also ``rendered_per_obj``: id -> dict of [H, W(,3)] images of that object alone.
+    Every output is per ray, so the chunk size changes none of them."""
+    W, H = int(WH[frame, 0]), int(WH[frame, 1])
+    xy = all_pixel_xy(W, H, intr.device)
+    n = xy.shape[0]
+    fidx = torch.full([n], frame, dtype=torch.long, device=intr.device)
+    rays_o, rays_d = selected_rays(xy, fidx, intr, c2w, WH, distortion=distortion)
+    ha = rays_h_appear.expand(n, -1).contiguous() if rays_h_appear is not None else None
+    individual = bool(with_segmentation or render_per_obj_individual)
+    step = int(rayschunk) if rayschunk and int(rayschunk) > 0 else n
+    was_training, cfg_saved = renderer.training, dict(renderer.config)
+    renderer.eval()
+    renderer.config.update(perturb=False, depth_use_normalized_vw=True)
+    pieces = []
+    try:
+        for s in range(0, n, step):
+            pieces.append(renderer.ray_query(rays_o[s:s + step].contiguous(), rays_d[s:s + step].contiguous(), drawables=drawables,
+                                             rays_h_appear=ha[s:s + step].contiguous() if ha is not None else None, sky_model=sky_model,
+                                             distant_model=distant_model, render_per_obj_individual=individual,
+                                             **ray_query_kwargs))
+    finally:
+        renderer.train(was_training)
+        renderer.config.clear()
+        renderer.config.update(cfg_saved)
+
+    def image(vs):
+        v = torch.cat(vs)
+        return v.reshape(H, W, *v.shape[1:])
+    out = {k: image([p["rendered"][k] for p in pieces]) for k in pieces[0]["rendered"]}
+    if with_segmentation:
+        for k in ("ins_seg_mask_buffer", "class_seg_mask_buffer"):
+            out[k] = image([p[k] for p in pieces])
+        out["instance_ind_map"], out["class_ind_map"] = pieces[0]["instance_ind_map"], pieces[0]["class_ind_map"]
+    if render_per_obj_individual:
+        out["rendered_per_obj"] = {oid: {k: image([p["rendered_per_obj"][oid][k] for p in pieces]) for k in imgs}
+                                   for oid, imgs in pieces[0]["rendered_per_obj"].items()}
+    return out
+
+
 def psnr(pred: torch.Tensor, target: torch.Tensor, mask: torch.Tensor = None, only_in_mask: bool = False) -> float:
     """``nr3d_lib.graphics.utils.PSNR`` as the eval tool calls it (code_single/tools/eval.py:269, 285-286):
     -10 log10(mse) for images in [0,1]; with ``mask`` [H,W,1] the squared error is masked, and averaged over the

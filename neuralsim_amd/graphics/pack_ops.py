@@ -291,6 +291,66 @@ def compose_collect_sort(sources, total_pack_infos: torch.Tensor, S: int):
     return t_sorted, dsts
 
 
+SEG_MAX_SOURCES = 64      # sources per nsim_seg_zbuffer call (include/nsim.h)
+
+
+def seg_zbuffer(sources, N: int, threshold: float = 0.6, device=None):
+    """The instance / class segmentation z-buffer of ``BufferComposeRenderer.ray_query(render_per_obj_individual=True)``
+    (buffer_compose_renderer.py:186-188, 268-311, 427-450, 549-572) over all drawable groups at once (``nsim_seg_zbuffer``).
+    ``sources``: list, in processing order, of dicts ``rays_inds`` [M] (the group's candidates), ``mask`` / ``depth`` (the
+    INDIVIDUAL renders: [M] per candidate; or -- with ``bidx`` [M] -- [B', N] images read at (bidx, rays_inds); or -- with
+    ``image=True`` -- [N] images read at rays_inds), ``ins`` (an int, or a LongTensor [M]) and ``class_ind`` (int).
+    -> (ins_seg [N] long, class_seg [N] long, z_buffer [N] f32): per ray the candidate (mask > threshold, strictly) of smallest
+    depth, ties to the earliest in processing order; -1 / -1 / +inf where there is none.  No host read."""
+    N = int(N)
+    if device is None:
+        device = next((s["rays_inds"].device for s in sources), None)
+        assert device is not None, "seg_zbuffer: no source to take the device from -- pass device="
+    ins_seg = torch.empty([N], dtype=torch.long, device=device)
+    cls_seg = torch.empty([N], dtype=torch.long, device=device)
+    z = torch.empty([N], dtype=torch.float32, device=device)
+    keys = torch.empty([N], dtype=torch.long, device=device)       # workspace: (depth image << 32 | ordinal) per ray
+    base, keep = 0, []
+    chunks = [sources[i:i + SEG_MAX_SOURCES] for i in range(0, len(sources), SEG_MAX_SOURCES)] or [[]]
+    for chunk in chunks:
+        arr = (_lib.SegSrc * max(len(chunk), 1))()
+        total = 0
+        for k, s in enumerate(chunk):
+            ri = s["rays_inds"].long().contiguous()
+            mask, depth = _f32c(s["mask"].detach()), _f32c(s["depth"].detach())
+            M = int(ri.shape[0])
+            bidx = s.get("bidx")
+            if bidx is not None:
+                assert mask.dim() == 2 and mask.shape == depth.shape and mask.shape[1] == N, "image form: mask / depth are [B', N]"
+                bidx = bidx.long().contiguous()
+                assert bidx.shape[0] == M
+                B = int(mask.shape[0])
+            elif s.get("image", False):        # a single model's [N] images, read at rays_inds
+                assert mask.shape == depth.shape == (N,), "image form without bidx: mask / depth are [N]"
+                B = 1
+            else:
+                assert mask.numel() == M and depth.numel() == M, "pair form: one mask / depth per candidate"
+                B = 0
+            ins = s["ins"]
+            if torch.is_tensor(ins):
+                ins = ins.long().contiguous()
+                assert ins.numel() == M
+                ins_scalar = 0
+            else:
+                ins, ins_scalar = None, int(ins)
+            tensors = (ri, mask, depth, bidx, ins)
+            a = arr[k]
+            a.rays_inds, a.mask, a.depth, a.bidx, a.ins = _lib._marshal(tensors)
+            a.M, a.B, a.ins_scalar, a.class_ind = M, B, ins_scalar, int(s["class_ind"])
+            keep.append(tensors)
+            total += M
+        assert base + total < 2 ** 32 - 1, "seg_zbuffer: candidate ordinals are 32-bit"
+        _lib.call("nsim_seg_zbuffer", C.cast(arr, C.c_void_p), len(chunk), N, float(threshold), base, _lib.ptr(keys),
+                  _lib.ptr(ins_seg), _lib.ptr(cls_seg), _lib.ptr(z))
+        base += total
+    return ins_seg, cls_seg, z
+
+
 def interleave_linstep(start: torch.Tensor, n: torch.Tensor, step=1, return_idx: bool = False):
     """concat_p(start[p] + step*arange(n[p]))  (buffer_compose_renderer.py:668,1036)."""
     assert not torch.is_floating_point(start), "interleave_linstep: integer start expected"

@@ -13,8 +13,12 @@ path:
 
 There is no Scene graph in this repository (harness, out of scope): drawables are passed explicitly as
 ``Drawable(id, class_name, model, rotation [3,3], translation [3], scale)`` -- the object-to-world transform of the
-frame being rendered.  ``render_per_class_in_scene`` / ``render_per_obj_in_scene`` (:729-806) are mirrored; not
-mirrored: ``render_per_obj_individual`` and its segmentation z-buffer (:276-311), which are evaluation outputs.
+frame being rendered.  ``render_per_class_in_scene`` / ``render_per_obj_in_scene`` (:729-806) are mirrored, and so is
+``render_per_obj_individual`` (:182-188, :268-311, :427-450, :549-572): every object's own all-rays images and the instance /
+class segmentation built from them.  The reference updates its z-buffer group by group with a chain of torch ops and host reads
+(``nonzero``, ``.any()``, ``unique``, ``scatter_min``, three indexed stores); here the groups are the sources of ONE
+``nsim_seg_zbuffer`` call per render (csrc/pack_ops.hip) that reads no size back.  The index maps of the reference's Scene
+(app/resources/scenes.py:597-603) are arguments, by default the drawables / class names in the order given.
 """
 from dataclasses import dataclass
 import os
@@ -94,8 +98,13 @@ class BufferComposeRenderer(nn.Module):
                   with_normal: bool = None, sky_model=None, distant_model=None, distant_cr_id: str = None,
                   return_buffer=False, return_details=False,
                   bypass_ray_query_cfg: Dict[str, dict] = None, render_per_obj_in_scene: bool = False,
-                  render_per_class_in_scene: bool = False) -> Dict:
-        """``render_per_class_in_scene`` / ``render_per_obj_in_scene``: every class's / object's share of the JOINT
+                  render_per_class_in_scene: bool = False, render_per_obj_individual: bool = False,
+                  instance_ind_map: Dict[str, int] = None, class_ind_map: Dict[str, int] = None) -> Dict:
+        """``render_per_obj_individual``: every object ALONE -- ``rendered_per_obj[id]`` = its model's all-rays ``rendered`` dict
+        (+ ``normals_volume_in_world``) -- and ``ins_seg_mask_buffer`` / ``class_seg_mask_buffer`` [N]: per ray the index
+        (``instance_ind_map`` / ``class_ind_map``) of the nearest object among those whose individual mask exceeds
+        ``segmentation_threshold`` (config, 0.6) on their tested rays, -1 where there is none.
+        ``render_per_class_in_scene`` / ``render_per_obj_in_scene``: every class's / object's share of the JOINT
         rendering -- its samples weighted by ``vw_in_total`` (reference :729-806; the per-class masks feed the
         importance sampler of code_multi/tools/train.py:589-592, the per-object images the mono / manhattan losses).
         ``distant_model``: the 'Distant' class, queried LAST (reference :162-164) on ALL rays in the frame of its
@@ -113,6 +122,24 @@ class BufferComposeRenderer(nn.Module):
         total_rendered = prepare_empty_rendered([N], dev, with_rgb=with_rgb, with_normal=with_normal)
         ray_visible_samples = torch.zeros([N], dtype=torch.long, device=dev)
         raw_per_obj_model: Dict[str, Dict] = {}
+        individual = bool(render_per_obj_individual)
+        rendered_individual: Dict[str, Dict] = {}
+        seg_sources = []          # one per queried object / batched group, in processing order (the reference's z-buffer order)
+        if individual:
+            if instance_ind_map is None:      # Scene.get_drawable_instance_ind_map (scenes.py:601-603)
+                ids = [dr.id for dr in drawables] + (["distant"] if distant_model is not None else [])
+                instance_ind_map = {oid: i for i, oid in enumerate(ids)}
+            if class_ind_map is None:         # Scene.get_drawable_class_ind_map (scenes.py:597-600)
+                names = [dr.class_name for dr in drawables] + (["Distant"] if distant_model is not None else [])
+                class_ind_map = {cn: i for i, cn in enumerate(dict.fromkeys(names))}
+
+        def take_individual(r_, oid, rotation):
+            """reference :272-275, :428-431, :550-553: the object's own images; its normals rotated to world"""
+            rendered_individual[oid] = r_
+            if "normals_volume" in r_:
+                nv = r_["normals_volume"]
+                r_["normals_volume_in_world"] = nv if rotation is None else (rotation.to(nv) * nv.unsqueeze(-2)).sum(-1)
+            return r_
 
         # ---- group drawables by model: one query per single model, ONE batched query per shared model
         groups: Dict[int, List[Drawable]] = {}
@@ -129,9 +156,18 @@ class BufferComposeRenderer(nn.Module):
                     extra["rays_h_appear"] = rays_h_appear.unsqueeze(0).expand(len(grp), *rays_h_appear.shape)
                 bt = model.batched_ray_test(oo, dd, near=near, far=far, compact_batch=True, **extra)
                 model.set_condition({"ins_id": [dr.id for dr in grp]})
+                ind_kw = dict(batched_ray_input=dict(rays_o=oo, rays_d=dd), render_per_obj_individual=True) if individual else {}
                 raw = model.batched_ray_query(batched_ray_tested=bt, config=qcfg, return_buffer=True,
-                                              return_details=return_details)
+                                              return_details=return_details, **ind_kw)
                 model.clean_condition()
+                if individual:      # reference :268-311: [B', N] images, one row per item; candidates = the tested (item, ray) pairs
+                    imgs = raw.pop("rendered")
+                    for i, dr in enumerate(grp):
+                        take_individual({k: v[i] for k, v in imgs.items()}, dr.id, dr.rotation)
+                    ins_items = torch.tensor([instance_ind_map[dr.id] for dr in grp], dtype=torch.long, device=dev)
+                    seg_sources.append(dict(rays_inds=bt["rays_inds"], bidx=bt["rays_full_bidx"], mask=imgs["mask_volume"],
+                                            depth=imgs["depth_volume"], ins=ins_items[bt["rays_full_bidx"]],
+                                            class_ind=class_ind_map[cls]))
                 vb = raw["volume_buffer"]
                 if vb["type"] != "empty" and "nablas" in vb:
                     rot = torch.stack([dr.rotation if dr.rotation is not None else torch.eye(3) for dr in grp]).to(dev)
@@ -143,8 +179,14 @@ class BufferComposeRenderer(nn.Module):
                 for dr in grp:
                     o_o, d_o = dr.rays_in_object(rays_o, rays_d)
                     tested = model.ray_test(o_o, d_o, near=near, far=far, rays_h_appear=rays_h_appear)
+                    ind_kw = dict(ray_input=dict(rays_o=o_o, rays_d=d_o), render_per_obj_individual=True) if individual else {}
                     raw = model.ray_query(ray_tested=tested, config=qcfg, return_buffer=True,
-                                          return_details=return_details)
+                                          return_details=return_details, **ind_kw)
+                    if individual:      # reference :427-450, :549-572: candidates = the tested rays
+                        r_ = take_individual(raw.pop("rendered"), dr.id, dr.rotation)
+                        seg_sources.append(dict(rays_inds=tested["rays_inds"], image=True, mask=r_["mask_volume"],
+                                                depth=r_["depth_volume"], ins=instance_ind_map[dr.id],
+                                                class_ind=class_ind_map[dr.class_name]))
                     vb = raw["volume_buffer"]
                     if vb["type"] != "empty" and "nablas" in vb:
                         if dr.rotation is None:
@@ -168,7 +210,13 @@ class BufferComposeRenderer(nn.Module):
                              num_rays=N, rays_inds=torch.arange(N, device=dev))
             raw = distant_model.ray_query(ray_tested=dv_tested, config=self._query_cfg(distant_model, with_rgb, with_normal,
                                                                                          bypass.get("Distant")),
-                                          return_buffer=True, return_details=return_details)
+                                          return_buffer=True, return_details=return_details,
+                                          **(dict(ray_input=dv_tested, render_per_obj_individual=True) if individual else {}))
+            if individual:          # every ray is tested (reference :532)
+                r_ = take_individual(raw.pop("rendered"), "distant", None)
+                seg_sources.append(dict(rays_inds=dv_tested["rays_inds"], image=True, mask=r_["mask_volume"],
+                                        depth=r_["depth_volume"], ins=instance_ind_map["distant"],
+                                        class_ind=class_ind_map["Distant"]))
             vb = raw["volume_buffer"]
             vb["pack_infos_hit"] = po.get_pack_infos_from_n(torch.full([N], int(vb["num_per_hit"]), dtype=torch.long, device=dev))
             raw.update(class_name="Distant", obj_id="distant", num_rays=N)
@@ -328,6 +376,11 @@ class BufferComposeRenderer(nn.Module):
             ret["rendered_per_class_in_scene"] = rendered_per_class
         if render_per_obj_in_scene:
             ret["rendered_per_obj_in_scene"] = rendered_per_obj
+        if individual:
+            # the z-buffer of the reference (:186-188 and the per-group updates), all groups in one call and without a host read
+            ins_seg, cls_seg, _ = po.seg_zbuffer(seg_sources, N, float(cfgd.get("segmentation_threshold", 0.6)), device=dev)
+            ret.update(rendered_per_obj=rendered_individual, ins_seg_mask_buffer=ins_seg, class_seg_mask_buffer=cls_seg,
+                       instance_ind_map=instance_ind_map, class_ind_map=class_ind_map)
         if return_buffer:
             ret["volume_buffer"] = total_volume_buffer
         if return_details:

@@ -1055,6 +1055,34 @@ int nsim_vgrid_emit(const int32_t* bits, int64_t G, const int32_t* off, const in
                     void* stream);
 int nsim_vgrid_occ_val(const int32_t* bits, int64_t G, float* occ_val, void* stream);
 
+/* --------------------------------------------------------------------------------- simulated LiDAR sensors */
+/* The ``Lidar`` observer node and the tools that render its sweeps (neuralsim_amd/lidar_sim.py).
+ *   raygen: replaces Lidar.get_all_rays, app/resources/observers/lidars.py:208-232 (meshgrid, four sin / cos tensors, three
+ *           broadcast products, normalize, tile).  mode 0 (grid): N = n_beams n_az rays, ray r = i n_beams + j takes phis[i]
+ *           and thetas[j] -- the flatten order of meshgrid(thetas, phis, indexing='xy'), lidars.py:218, 432, beam fastest;
+ *           mode 1 (paired, n_beams == n_az == N): ray r takes (thetas[r], phis[r]), lidars.py:494-504, 566-588.
+ *           l2w f32 [3][4] row-major ON THE DEVICE = the caller's world_transform x carla_to_opencv (lidars.py:188-192, 211),
+ *           columns X, Y, Z, T; it may carry a scale.  rays_d[r] = normalize((a X + b Y) + c Z), every product and sum rounded on
+ *           its own, normalize = d / max(|d|, 1e-12); (a, b, c) = (sinT cosP, sinT sinP, cosT) for axis 0 (lidars.py:226-227),
+ *           (cosT, sinT sinP, -(sinT cosP)) for axis 1 (lidars.py:221-224); rays_o[r] = T; theta_phi (may be NULL) f32 [N][2] =
+ *           the two angles of ray r.  N = 0 launches nothing.  60: see nsim_strerror.
+ *   returns_count / nsim_occgrid_scan / returns_emit: replace the mask and the masked gathers of code_multi/tools/render.py:
+ *           331-346 (and :298-313) by a stable compaction.  Ray r is a return iff acc[r] > thresh (strict, f32; NaN is not).
+ *           count: cnt[b] = returns among the 256 rays of block b, ceil(N / 256) blocks; the scan turns cnt into offsets (and
+ *           stores the total M to its host-mapped notify words); emit writes, for the M returns in ray order: ray_inds int64,
+ *           ranges = depth[r], mask = acc[r], pts_world [M][3] = rays_o[r] + rays_d[r] * depth[r] (one multiply, then one add),
+ *           pts_local [M][3] (may be NULL) with w2l f32 [3][4] row-major on the device, component k summed in the FIXED order
+ *           ((w2l[k][0] x + w2l[k][1] y) + w2l[k][2] z) + w2l[k][3], (x, y, z) = pts_world; out_rgb [M][3] = rgb[r] and out_ids
+ *           int64 [M] = ids[r] (``ins_seg_mask_buffer``) when non-NULL; range_image (may be NULL) f32 [N] = depth[r] on a
+ *           return, 0 elsewhere.  Nothing past row M is written.  61: see nsim_strerror. */
+int nsim_lidar_raygen(const float* thetas, const float* phis, int64_t n_beams, int64_t n_az, int mode, int axis, const float* l2w,
+                      float* rays_o, float* rays_d, float* theta_phi, void* stream);
+int nsim_lidar_returns_count(const float* acc, int64_t N, float thresh, int32_t* cnt, void* stream);
+int nsim_lidar_returns_emit(const float* acc, const float* depth, const float* rays_o, const float* rays_d, int64_t N, float thresh,
+                            const int32_t* off, const float* w2l, const float* rgb, const int64_t* ids, int64_t* ray_inds,
+                            float* ranges, float* mask, float* pts_world, float* pts_local, float* out_rgb, int64_t* out_ids,
+                            float* range_image, void* stream);
+
 /* MFMA layout self-test (tests only): writes D = A(32x16 f16) * B(16x32 f16) with the wrappers used by the
  * field kernels; a, b given in plain row-major. d is 32x32 f32 row-major. */
 int nsim_selftest_mfma(const float* a, const float* b, float* d, int use_f32, void* stream);

@@ -266,6 +266,9 @@ SIGNATURES = {
     "nsim_vgrid_count": [_P, _I64, _P],
     "nsim_vgrid_emit": [_P, _I64, _P, _P, _P, _P],
     "nsim_vgrid_occ_val": [_P, _I64, _P],
+    "nsim_lidar_raygen": [_P, _P, _I64, _I64, _I, _I, _P, _P, _P, _P],
+    "nsim_lidar_returns_count": [_P, _I64, _F, _P],
+    "nsim_lidar_returns_emit": [_P, _P, _P, _P, _I64, _F] + [_P] * 12,
     "nsim_errmap_accumulate": [_P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I, _I, _P, _P, _P, _P],
     "nsim_errmap_blend": [_P, _P, _P, _P, _P, _I64, _I, _I],
     "nsim_errmap_cdf": [_P, _I64, _I, _I, _F, _F, _P, _P, _P, _P, _P],

@@ -1718,6 +1718,120 @@ int nsim_vgrid_occ_val(const int32_t* bits, int64_t G, float* occ_val, void* str
 
 }  // extern "C"
 
+// ------------------------------------------------------------------------------------------------ simulated LiDAR returns
+// The point cloud of a rendered sweep (code_multi/tools/render.py:331-346 and :298-313: a boolean mask and five to seven masked
+// gathers), the kernels behind neuralsim_amd/lidar_sim.py.  A ray is a return iff acc[r] > thresh (strict, f32; NaN is not
+// greater).  Compaction without atomics, in ray order: returns per block of 256 rays (k_lr_count) -> nsim_occgrid_scan ->
+// k_lr_emit; the rank inside a wave is the popcount of the ballot below the lane.  Per return at output row o:
+//   ray_inds[o] = r, ranges[o] = depth[r], mask[o] = acc[r], rgb / ids rows copied,
+//   pts_world[o] = o_r + d_r * range          one multiply then one add per component (never fused),
+//   pts_local[o][k] = ((m[k][0] x + m[k][1] y) + m[k][2] z) + m[k][3]    with (x, y, z) = pts_world[o], m = w2l [3,4].
+// range_image [N] (optional, dense): depth[r] on a return, 0 elsewhere.
+__device__ __forceinline__ int lr_block_rank(int c, int& tot, int* wsum) {
+  const int lane = nsim_lane(), wave = threadIdx.x >> 6;
+  const unsigned long long b = wave_ballot(c);
+  if (lane == 0) wsum[wave] = __popcll(b);
+  __syncthreads();
+  int before = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < MC_THREADS / 64; ++w) {
+    before += w < wave ? wsum[w] : 0;
+    all += wsum[w];
+  }
+  tot = all;
+  return before + __popcll(b & ((1ull << lane) - 1ull));
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_lr_count(const float* __restrict__ acc, int64_t N, float thresh,
+                                                       int32_t* __restrict__ cnt) {
+  __shared__ int wsum[MC_THREADS / 64];
+  const int64_t r = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+  int tot;
+  lr_block_rank(r < N && acc[r] > thresh ? 1 : 0, tot, wsum);
+  if (threadIdx.x == 0) cnt[blockIdx.x] = tot;
+}
+
+struct LrOut {
+  int64_t* ray_inds;
+  float *ranges, *mask, *pts_world, *pts_local, *rgb;
+  int64_t* ids;
+  float* range_image;
+};
+
+__global__ void __launch_bounds__(MC_THREADS) k_lr_emit(const float* __restrict__ acc, const float* __restrict__ depth,
+                                                      const float* __restrict__ rays_o, const float* __restrict__ rays_d, int64_t N,
+                                                      float thresh, const int32_t* __restrict__ off, const float* __restrict__ w2l,
+                                                      const float* __restrict__ rgb, const int64_t* __restrict__ ids, LrOut out) {
+  __shared__ int wsum[MC_THREADS / 64];
+  const int64_t r = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+  const float a = r < N ? acc[r] : 0.f;
+  const int c = r < N && a > thresh ? 1 : 0;
+  int tot;
+  const int rank = lr_block_rank(c, tot, wsum);
+  if (r >= N) return;
+  const float rg = depth[r];
+  if (out.range_image) out.range_image[r] = c ? rg : 0.f;
+  if (!c) return;
+  const int64_t o = (int64_t)off[blockIdx.x] + rank;
+  out.ray_inds[o] = r;
+  out.ranges[o] = rg;
+  out.mask[o] = a;
+  float p[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float t = rays_d[3 * r + k] * rg;
+    p[k] = rays_o[3 * r + k] + t;
+    out.pts_world[3 * o + k] = p[k];
+  }
+  if (out.pts_local)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out.pts_local[3 * o + k] = ((w2l[4 * k] * p[0] + w2l[4 * k + 1] * p[1]) + w2l[4 * k + 2] * p[2]) + w2l[4 * k + 3];
+  if (out.rgb)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out.rgb[3 * o + k] = rgb[3 * r + k];
+  if (out.ids) out.ids[o] = ids[r];
+}
+
+extern "C" {
+
+int nsim_lidar_returns_count(const float* acc, int64_t N, float thresh, int32_t* cnt, void* stream) {
+  if (N < 0) return 2;
+  if (N >= ((int64_t)1 << 31)) return 61;
+  if (N == 0) return 0;
+  if (!cnt) return 4;
+  if (!acc) return 61;
+  hipLaunchKernelGGL(k_lr_count, vg_blocks(N), dim3(MC_THREADS), 0, (hipStream_t)stream, acc, N, thresh, cnt);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_lidar_returns_emit(const float* acc, const float* depth, const float* rays_o, const float* rays_d, int64_t N, float thresh,
+                            const int32_t* off, const float* w2l, const float* rgb, const int64_t* ids, int64_t* ray_inds,
+                            float* ranges, float* mask, float* pts_world, float* pts_local, float* out_rgb, int64_t* out_ids,
+                            float* range_image, void* stream) {
+  if (N < 0) return 2;
+  if (N >= ((int64_t)1 << 31)) return 61;
+  if (N == 0) return 0;
+  if (!ray_inds || !ranges || !mask || !pts_world) return 4;
+  if (!acc || !depth || !rays_o || !rays_d || !off) return 61;
+  if ((pts_local && !w2l) || (out_rgb && !rgb) || (out_ids && !ids)) return 61;
+  LrOut out;
+  out.ray_inds = ray_inds;
+  out.ranges = ranges;
+  out.mask = mask;
+  out.pts_world = pts_world;
+  out.pts_local = pts_local;
+  out.rgb = out_rgb;
+  out.ids = out_ids;
+  out.range_image = range_image;
+  hipLaunchKernelGGL(k_lr_emit, vg_blocks(N), dim3(MC_THREADS), 0, (hipStream_t)stream, acc, depth, rays_o, rays_d, N, thresh, off,
+                     w2l, rgb, ids, out);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // extern "C"
+
 extern "C" {
 
 int nsim_version(void) { return 100; }
@@ -1770,6 +1884,8 @@ const char* nsim_strerror(int code) {
     case 57: return "visible grid: the grid edge is a power of two in 32 .. 1024 (octree depth 5 .. 10), fewer than 2^39 samples per call";
     case 58: return "street losses: unknown mode / type / function, lo > hi, more than 4 entropy terms or a source outside 0..2, 0 <= k < N < 2^32 for the order statistic, far / std > 0 where the function divides by it";
     case 59: return "segmentation z-buffer: at most 64 sources per call, candidate ordinals (ordinal_base + the call's candidates) below 2^32 - 1";
+    case 60: return "lidar ray generation: thetas, phis and l2w are required, paired mode takes as many thetas as phis, fewer than 2^31 beams and azimuths and 2^39 rays";
+    case 61: return "lidar returns: fewer than 2^31 rays per sweep; acc, depth, rays and offsets are required, and w2l / rgb / ids wherever their output is requested";
     case 36: return "wide decoder: 0..10 embedding frequencies and at most 128 first-layer inputs (2 num_levels + 3 + 6 n_freq)";
     default: return code >= 1000 ? "HIP launch error (code - 1000 = hipError_t)" : "unknown error";
   }

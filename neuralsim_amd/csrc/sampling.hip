@@ -801,6 +801,129 @@ int nsim_compress_emit(const float* sdf, const float* t, const int64_t* pack_inf
 
 }  // extern "C"
 
+// ----------------------------------------------------------------------------------- simulated LiDAR: beam-pattern rays
+// Lidar.get_all_rays (app/resources/observers/lidars.py:208-232): the reference builds meshgrid tensors of both angles, four
+// sin / cos tensors, three broadcast products, a normalize and a tile; here it is one pass over the outputs.
+//   grid   ray r = i n_beams + j takes phis[i], thetas[j] (the flatten order of meshgrid(thetas, phis, indexing='xy'): beam
+//          fastest); a workgroup owns LG_TILE consecutive rays, i.e. at most LG_TILE / n_beams + 2 azimuths and min(n_beams,
+//          LG_TILE) beams: their sines and cosines are staged in LDS once, the per-ray work is multiplies, adds and the normalise
+//          (sensors with more than LG_TILE beams -- none known -- take the sines of their thetas per ray);
+//   paired ray r takes (thetas[r], phis[r]) (solid-state / Risley scan patterns, lidars.py:494-504, 566-588).
+// d = normalize((a X + b Y) + c Z), X, Y, Z the columns of l2w [3,4] (products and sums rounded on their own, as the separate
+// tensor operations are), (a, b, c) = (sinT cosP, sinT sinP, cosT), for axis 1 (lidars.py:221-224) (cosT, sinT sinP, -(sinT
+// cosP)); normalize = d / max(|d|, 1e-12) with IEEE sqrt and division (torch.nn.functional.normalize).  sinf / cosf are the
+// precise library functions: the hardware sine of nsim_sin is outside the accuracy bound of tests/test_lidar_sim.py.
+#define LG_THREADS 256
+#define LG_PER 4
+#define LG_TILE (LG_THREADS * LG_PER)
+
+__device__ __forceinline__ void lg_store_ray(const float* __restrict__ M, int axis, float sT, float cT, float sP, float cP, int64_t r,
+                                             float* __restrict__ rays_o, float* __restrict__ rays_d) {
+  const float sc = sT * cP, ss = sT * sP;
+  const float a = axis ? cT : sc, b = ss, c = axis ? -sc : cT;
+  const float d0 = (a * M[0] + b * M[1]) + c * M[2];
+  const float d1 = (a * M[4] + b * M[5]) + c * M[6];
+  const float d2 = (a * M[8] + b * M[9]) + c * M[10];
+  const float nrm = fmaxf(sqrtf((d0 * d0 + d1 * d1) + d2 * d2), 1e-12f);
+  rays_d[3 * r + 0] = d0 / nrm;
+  rays_d[3 * r + 1] = d1 / nrm;
+  rays_d[3 * r + 2] = d2 / nrm;
+  rays_o[3 * r + 0] = M[3];
+  rays_o[3 * r + 1] = M[7];
+  rays_o[3 * r + 2] = M[11];
+}
+
+__global__ void __launch_bounds__(LG_THREADS) k_lidar_raygen_grid(const float* __restrict__ thetas, const float* __restrict__ phis,
+                                                                  int64_t n_beams, int64_t N, int axis,
+                                                                  const float* __restrict__ l2w, float* __restrict__ rays_o,
+                                                                  float* __restrict__ rays_d, float* __restrict__ theta_phi) {
+  __shared__ float s_sT[LG_TILE], s_cT[LG_TILE], s_sP[LG_TILE + 2], s_cP[LG_TILE + 2];
+  const int tid = threadIdx.x;
+  const int64_t r0 = (int64_t)blockIdx.x * LG_TILE;
+  const int64_t r_last = (r0 + LG_TILE < N ? r0 + LG_TILE : N) - 1;
+  const int64_t i0 = r0 / n_beams;
+  const int n_i = (int)(r_last / n_beams - i0) + 1;                     // <= LG_TILE / n_beams + 2 <= LG_TILE + 2
+  const bool staged = n_beams <= LG_TILE;
+  if (staged)
+    for (int j = tid; j < (int)n_beams; j += LG_THREADS) {
+      const float t = thetas[j];
+      s_sT[j] = sinf(t);
+      s_cT[j] = cosf(t);
+    }
+  for (int k = tid; k < n_i; k += LG_THREADS) {
+    const float p = phis[i0 + k];
+    s_sP[k] = sinf(p);
+    s_cP[k] = cosf(p);
+  }
+  __syncthreads();
+  float M[12];
+#pragma unroll
+  for (int q = 0; q < 12; ++q) M[q] = l2w[q];
+#pragma unroll
+  for (int q = 0; q < LG_PER; ++q) {
+    const int64_t r = r0 + q * LG_THREADS + tid;
+    if (r >= N) break;
+    const int64_t i = r / n_beams, j = r - i * n_beams;
+    float sT, cT;
+    if (staged) {
+      sT = s_sT[j];
+      cT = s_cT[j];
+    } else {
+      const float t = thetas[j];
+      sT = sinf(t);
+      cT = cosf(t);
+    }
+    lg_store_ray(M, axis, sT, cT, s_sP[i - i0], s_cP[i - i0], r, rays_o, rays_d);
+    if (theta_phi) {
+      theta_phi[2 * r + 0] = thetas[j];
+      theta_phi[2 * r + 1] = phis[i];
+    }
+  }
+}
+
+__global__ void __launch_bounds__(LG_THREADS) k_lidar_raygen_paired(const float* __restrict__ thetas, const float* __restrict__ phis,
+                                                                    int64_t N, int axis, const float* __restrict__ l2w,
+                                                                    float* __restrict__ rays_o, float* __restrict__ rays_d,
+                                                                    float* __restrict__ theta_phi) {
+  const int64_t r = (int64_t)blockIdx.x * LG_THREADS + threadIdx.x;
+  if (r >= N) return;
+  float M[12];
+#pragma unroll
+  for (int q = 0; q < 12; ++q) M[q] = l2w[q];
+  const float t = thetas[r], p = phis[r];
+  lg_store_ray(M, axis, sinf(t), cosf(t), sinf(p), cosf(p), r, rays_o, rays_d);
+  if (theta_phi) {
+    theta_phi[2 * r + 0] = t;
+    theta_phi[2 * r + 1] = p;
+  }
+}
+
+extern "C" {
+
+int nsim_lidar_raygen(const float* thetas, const float* phis, int64_t n_beams, int64_t n_az, int mode, int axis, const float* l2w,
+                      float* rays_o, float* rays_d, float* theta_phi, void* stream) {
+  if (n_beams < 0 || n_az < 0) return 2;
+  if (mode != 0 && mode != 1) return 3;
+  if (axis != 0 && axis != 1) return 3;
+  if (mode == 1 && n_beams != n_az) return 60;
+  if (n_beams >= ((int64_t)1 << 31) || n_az >= ((int64_t)1 << 31)) return 60;
+  const int64_t N = mode == 0 ? n_beams * n_az : n_beams;
+  if (N == 0) return 0;
+  if (N >= ((int64_t)1 << 39)) return 60;
+  if (!rays_o || !rays_d) return 4;
+  if (!thetas || !phis || !l2w) return 60;
+  if (mode == 0)
+    hipLaunchKernelGGL(k_lidar_raygen_grid, dim3((unsigned)((N + LG_TILE - 1) / LG_TILE)), dim3(LG_THREADS), 0, (hipStream_t)stream,
+                       thetas, phis, n_beams, N, axis, l2w, rays_o, rays_d, theta_phi);
+  else
+    hipLaunchKernelGGL(k_lidar_raygen_paired, dim3((unsigned)((N + LG_THREADS - 1) / LG_THREADS)), dim3(LG_THREADS), 0,
+                       (hipStream_t)stream, thetas, phis, N, axis, l2w, rays_o, rays_d, theta_phi);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // extern "C"
+
 // ----------------------------------------------------------------------------------- error-map importance sampling
 // The pixel sampler of the reference's trainer (``ImpSampler`` / ``ErrorMap``: code_single/tools/train.py:105-138 builds them,
 // dataio/data_loader/pixel_loader.py:157-171, 280-302 draws (frame, pixel) from them once per iteration, train.py:619-621,

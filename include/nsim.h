@@ -1083,6 +1083,45 @@ int nsim_lidar_returns_emit(const float* acc, const float* depth, const float* r
                             float* ranges, float* mask, float* pts_world, float* pts_local, float* out_rgb, int64_t* out_ids,
                             float* range_image, void* stream);
 
+/* --------------------------------------------------------------------------------- LiDAR ground-truth filter */
+/* SceneDataLoader.filter_lidar_gts / _filter_lidar_gts (dataio/data_loader/base_loader.py:649-844) and Camera / MultiCamBundle
+ * .project_pts_in_image (app/resources/observers/cameras.py:397-446, 537-538), behind neuralsim_amd/lidar_filter.py.  The
+ * reference's four sequential filters (each a mask, a nonzero and a gather of every column) are one conjunction per point.
+ * Every product is rounded before its sum and every 3-term sum runs left to right.
+ *   world point   p_local = rays_o + rays_d * range (one multiply, one add: torch.addcmul, base_loader.py:700, 709);
+ *                 p[k] = ((R[k][0] x + R[k][1] y) + R[k][2] z) + t[k] with (R, t) = l2w[fi[r]][li[r]], l2w f32 [F][L][3][4];
+ *                 li, fi int64 [N] (NULL: 0).  A point whose index is outside [0, L) / [0, F) is not kept and reads no table.
+ *   filter_valid  (non-zero) keep iff range > 0 (base_loader.py:748-751; NaN and -0.0 are not kept).
+ *   cameras       (C > 0; base_loader.py:753-787) cams f32 [F][C][24] on the device, a record = c2w [3][4], fx, skew, cx, fy,
+ *                 cy, W, H (as floats, after any downscale), five distortion coefficients; cam_models int32 [C] ON THE HOST, one
+ *                 id per camera of the rig (0 pinhole, 1 OpenCV k1 k2 p1 p2 k3, 2 fisheye k1..k4), C <= 32.  q = p - t_c,
+ *                 cam[k] = (R_c[0][k] q0 + R_c[1][k] q1) + R_c[2][k] q2; (u, v, d) operation for operation as the ``proj`` of
+ *                 nr3d_lib/models/attributes (pinhole :511-520, OpenCV :565-579, fisheye :619-632: the |z| < 1e-9 -> 1e-9 guard
+ *                 and the skew term included); in view iff d > near_clip and 0 <= u < W and 0 <= v < H; with ignore u8
+ *                 [F][C][Hm][Wm] (non-zero: ignored; padded bottom / right with 0) additionally ignore[(int)v][(int)u] == 0,
+ *                 read only after the view test passed (a pixel outside [Hm][Wm] counts as padding).  Keep iff any camera of
+ *                 the point's frame has it in view.
+ *   aabb          (non-NULL; base_loader.py:789-800) f32 [2][3] on the device: keep iff min[k] <= p[k] <= max[k] for all k.
+ *   boxes         (B > 0; base_loader.py:802-842) f32 [B][15] = a [3][4] transform and 3 sizes; the boxes of frame f are rows
+ *                 box_offsets[f] .. box_offsets[f + 1] (int32 [F + 1] on the device); b = R_b^T (p - t_b) as above; inside iff
+ *                 -s[k] / 2 <= b[k] <= s[k] / 2 for all k; keep iff inside no box.
+ *   count: keep u8 [N] and cnt[b] = kept among the 256 points of block b, ceil(N / 256) blocks; nsim_occgrid_scan turns cnt
+ *   into offsets; emit compacts, in point order, rays_o, rays_d, ranges and (where the output is non-NULL) li, fi, keep_inds
+ *   int64 (the kept points' indices) and pts_world [M][3] (the world point above).  project: the dense projection of N world
+ *   points into C cameras of ONE frame through the same device function as the filter: mask u8, u, v, d f32, all [C][N]
+ *   (ignore u8 [C][Hm][Wm] or NULL).  N = 0 (and C = 0 for project) launch nothing.  62: see nsim_strerror. */
+int nsim_lidar_filter_count(const float* rays_o, const float* rays_d, const float* ranges, const int64_t* li, const int64_t* fi,
+                            int64_t N, const float* l2w, int64_t L, int64_t F, int filter_valid, const float* cams,
+                            const int32_t* cam_models, int64_t C, float near_clip, const uint8_t* ignore, int64_t Hm, int64_t Wm,
+                            const float* aabb, const float* boxes, const int32_t* box_offsets, int64_t B, uint8_t* keep,
+                            int32_t* cnt, void* stream);
+int nsim_lidar_filter_emit(const uint8_t* keep, const int32_t* off, const float* rays_o, const float* rays_d, const float* ranges,
+                           const int64_t* li, const int64_t* fi, int64_t N, const float* l2w, int64_t L, int64_t F,
+                           float* out_rays_o, float* out_rays_d, float* out_ranges, int64_t* out_li, int64_t* out_fi,
+                           int64_t* keep_inds, float* pts_world, void* stream);
+int nsim_cam_project(const float* pts, int64_t N, const float* cams, const int32_t* cam_models, int64_t C, float near_clip,
+                     const uint8_t* ignore, int64_t Hm, int64_t Wm, uint8_t* mask, float* u, float* v, float* d, void* stream);
+
 /* MFMA layout self-test (tests only): writes D = A(32x16 f16) * B(16x32 f16) with the wrappers used by the
  * field kernels; a, b given in plain row-major. d is 32x32 f32 row-major. */
 int nsim_selftest_mfma(const float* a, const float* b, float* d, int use_f32, void* stream);

@@ -269,6 +269,9 @@ SIGNATURES = {
     "nsim_lidar_raygen": [_P, _P, _I64, _I64, _I, _I, _P, _P, _P, _P],
     "nsim_lidar_returns_count": [_P, _I64, _F, _P],
     "nsim_lidar_returns_emit": [_P, _P, _P, _P, _I64, _F] + [_P] * 12,
+    "nsim_lidar_filter_count": [_P] * 5 + [_I64, _P, _I64, _I64, _I, _P, _P, _I64, _F, _P, _I64, _I64, _P, _P, _P, _I64, _P, _P],
+    "nsim_lidar_filter_emit": [_P] * 7 + [_I64, _P, _I64, _I64] + [_P] * 7,
+    "nsim_cam_project": [_P, _I64, _P, _P, _I64, _F, _P, _I64, _I64, _P, _P, _P, _P],
     "nsim_errmap_accumulate": [_P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I, _I, _P, _P, _P, _P],
     "nsim_errmap_blend": [_P, _P, _P, _P, _P, _I64, _I, _I],
     "nsim_errmap_cdf": [_P, _I64, _I, _I, _F, _F, _P, _P, _P, _P, _P],

@@ -1832,6 +1832,340 @@ int nsim_lidar_returns_emit(const float* acc, const float* depth, const float* r
 
 }  // extern "C"
 
+// ------------------------------------------------------------------------------------------------ LiDAR ground-truth filter
+// SceneDataLoader._filter_lidar_gts (dataio/data_loader/base_loader.py:732-844) on top of Camera.project_pts_in_image
+// (app/resources/observers/cameras.py:397-446), the kernels behind neuralsim_amd/lidar_filter.py.  The reference applies four
+// filters one after another, each a mask, a nonzero and a gather of every column; the rule is per point, so they are ONE
+// conjunction here: k_lf_count writes keep u8 [N] and the kept points per block of 256 -> nsim_occgrid_scan -> k_lf_emit
+// compacts the columns in point order (ranks from the ballot popcount, lr_block_rank).  Every product is rounded before its sum
+// (-ffp-contract=off), every 3-term sum runs left to right:
+//   p_local = o + d * range (one multiply, one add);  p[k] = ((R[k][0] x + R[k][1] y) + R[k][2] z) + t[k], (R, t) = l2w[fi][li];
+//   a camera / box frame: q = p - t, b[k] = (R[0][k] q0 + R[1][k] q1) + R[2][k] q2 (the transposed rotation, no inverse);
+//   (u, v, d) by lf_uvd, operation for operation the ``proj`` of the three camera models; in view iff d > near_clip and
+//   0 <= u < W and 0 <= v < H; an ignore mask is read at [(int)v][(int)u] only after that test passed (outside the mask's
+//   own extent a pixel counts as padding, 0).
+// A camera record is LF_CAM floats: c2w [3][4], fx, skew, cx, fy, cy, W, H, five distortion coefficients; the model ids (one
+// per camera of the rig, the same in every frame) travel as a launch argument, 2 bits each.  A block whose points share a
+// frame (a frame-sorted bank: all but the blocks on a frame boundary) stages that frame's cameras and its boxes, LF_BOX_CHUNK
+// at a time, in LDS; any other block reads the records of each point's own frame from global memory.  A point whose frame or
+// lidar index is outside the tables is not kept (and reads nothing).
+#define LF_CAM 24
+#define LF_MAX_CAMS 32
+#define LF_BOX 15
+#define LF_BOX_CHUNK 64
+
+struct LfPoses {
+  const float* l2w;        // [F L][3][4]
+  const int64_t *li, *fi;  // per point, may be NULL (0)
+  int64_t L, F;
+};
+
+// -> false when the point's frame / lidar index is outside the tables
+__device__ __forceinline__ bool lf_world_point(const LfPoses& ps, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                               float range, int64_t r, int64_t& f, float p[3]) {
+  f = ps.fi ? ps.fi[r] : 0;
+  const int64_t l = ps.li ? ps.li[r] : 0;
+  if (f < 0 || f >= ps.F || l < 0 || l >= ps.L) return false;
+  float q[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float t = rays_d[3 * r + k] * range;
+    q[k] = rays_o[3 * r + k] + t;
+  }
+  const float* m = ps.l2w + 12 * (f * ps.L + l);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) p[k] = ((m[4 * k] * q[0] + m[4 * k + 1] * q[1]) + m[4 * k + 2] * q[2]) + m[4 * k + 3];
+  return true;
+}
+
+// b = R^T (p - t) of a row-major [3][4] transform m
+__device__ __forceinline__ void lf_to_frame(const float* m, const float p[3], float b[3]) {
+  const float q0 = p[0] - m[3], q1 = p[1] - m[7], q2 = p[2] - m[11];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) b[k] = (m[k] * q0 + m[4 + k] * q1) + m[8 + k] * q2;
+}
+
+// camera-frame point -> (u, v, depth): nr3d_lib attributes ``proj`` of the pinhole (0), OpenCV (1) and fisheye (2) intrinsics
+__device__ __forceinline__ void lf_uvd(const float* cam, int model, const float c[3], float& u, float& v, float& d) {
+  const float fx = cam[12], sk = cam[13], cx = cam[14], fy = cam[15], cy = cam[16];
+  const float* k = cam + 19;
+  const float x = c[0], y = c[1], z = c[2];
+  d = z;
+  if (model == 2) {
+    const float r = sqrtf(x * x + y * y);
+    const float th = atan2f(r, z);
+    const float t2 = th * th;
+    const float thd = th * (1.0f + (((k[3] * t2 + k[2]) * t2 + k[1]) * t2 + k[0]) * t2);
+    const float sc = r > 1e-12f ? thd / fmaxf(r, 1e-12f) : 1.0f;
+    u = fx * (x * sc) + cx;
+    v = fy * (y * sc) + cy;
+    return;
+  }
+  const float zs = fabsf(z) < 1e-9f ? 1e-9f : z;
+  if (model == 0) {
+    u = ((fx * x) / zs + (sk * y) / zs) + cx;
+    v = (fy * y) / zs + cy;
+    return;
+  }
+  const float xn = x / zs, yn = y / zs;
+  const float r2 = xn * xn + yn * yn;
+  const float cd = 1.0f + ((k[4] * r2 + k[1]) * r2 + k[0]) * r2;
+  const float xd = (xn * cd + ((2.0f * k[2]) * xn) * yn) + k[3] * (r2 + (2.0f * xn) * xn);
+  const float yd = (yn * cd + k[2] * (r2 + (2.0f * yn) * yn)) + ((2.0f * k[3]) * xn) * yn;
+  u = (fx * xd + sk * yd) + cx;
+  v = fy * yd + cy;
+}
+
+// THE view test, of the filter and of the dense projection alike.  ign: this camera's ignore plane [Hm][Wm] or NULL.
+__device__ __forceinline__ bool lf_in_view(const float* cam, int model, const float p[3], float near_clip,
+                                           const uint8_t* __restrict__ ign, int64_t Hm, int64_t Wm, float& u, float& v, float& d) {
+  float c[3];
+  lf_to_frame(cam, p, c);
+  lf_uvd(cam, model, c, u, v, d);
+  if (!(d > near_clip && u < cam[17] && u >= 0.f && v < cam[18] && v >= 0.f)) return false;
+  if (ign) {
+    const int64_t iu = (int64_t)u, iv = (int64_t)v;
+    if (iu < Wm && iv < Hm && ign[iv * Wm + iu]) return false;
+  }
+  return true;
+}
+
+__device__ __forceinline__ bool lf_in_box(const float* box, const float p[3]) {
+  float b[3];
+  lf_to_frame(box, p, b);
+  bool in = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float h = box[12 + k] / 2.0f;
+    in = in && b[k] >= -h && b[k] <= h;
+  }
+  return in;
+}
+
+struct LfRule {
+  int filter_valid;
+  const float* cams;       // [F C][LF_CAM] or NULL
+  uint64_t models;         // 2 bits per camera
+  int64_t C;
+  float near_clip;
+  const uint8_t* ignore;   // [F C][Hm][Wm] or NULL
+  int64_t Hm, Wm;
+  const float* aabb;       // [2][3] or NULL
+  const float* boxes;      // [B][LF_BOX] or NULL
+  const int32_t* box_off;  // [F + 1]
+  int64_t B;
+};
+
+__global__ void __launch_bounds__(MC_THREADS) k_lf_count(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                       const float* __restrict__ ranges, int64_t N, LfPoses ps, LfRule rl,
+                                                       uint8_t* __restrict__ keep, int32_t* __restrict__ cnt) {
+  __shared__ int wsum[MC_THREADS / 64];
+  __shared__ int mixed;
+  __shared__ float s_cam[LF_MAX_CAMS * LF_CAM];
+  __shared__ float s_box[LF_BOX_CHUNK * LF_BOX];
+  const int tid = threadIdx.x;
+  const int64_t r = (int64_t)blockIdx.x * MC_THREADS + tid;
+  const int64_t r0 = (int64_t)blockIdx.x * MC_THREADS;
+  const int64_t f0 = ps.fi ? ps.fi[r0] : 0;        // the block's frame, if it has one (r0 < N for every launched block)
+  if (tid == 0) mixed = 0;
+  __syncthreads();
+  float p[3] = {0.f, 0.f, 0.f};
+  int64_t f = 0;
+  bool live = false;
+  if (r < N) {
+    const float rg = ranges[r];
+    live = lf_world_point(ps, rays_o, rays_d, rg, r, f, p);
+    if (ps.fi && ps.fi[r] != f0) mixed = 1;         // (an index outside the table as well: f0 may be such a one)
+    if (rl.filter_valid && !(rg > 0.f)) live = false;
+    if (live && rl.aabb) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) live = live && p[k] >= rl.aabb[k] && p[k] <= rl.aabb[3 + k];
+    }
+  }
+  __syncthreads();
+  const bool staged = !mixed && f0 >= 0 && f0 < ps.F;      // block-uniform
+  // cameras: kept iff any camera of the point's frame has it in view
+  if (rl.cams) {
+    if (staged) {
+      for (int i = tid; i < (int)rl.C * LF_CAM; i += MC_THREADS) s_cam[i] = rl.cams[f0 * rl.C * LF_CAM + i];
+      __syncthreads();
+    }
+    if (live) {
+      bool seen = false;
+      for (int64_t c = 0; c < rl.C && !seen; ++c) {
+        const float* cam = staged ? s_cam + c * LF_CAM : rl.cams + (f * rl.C + c) * LF_CAM;
+        const uint8_t* ign = rl.ignore ? rl.ignore + (f * rl.C + c) * rl.Hm * rl.Wm : nullptr;
+        float u, v, d;
+        seen = lf_in_view(cam, (int)((rl.models >> (2 * c)) & 3ull), p, rl.near_clip, ign, rl.Hm, rl.Wm, u, v, d);
+      }
+      live = seen;
+    }
+  }
+  // boxes: kept iff inside no box of the point's frame
+  if (rl.boxes) {
+    if (staged) {
+      int64_t lo = rl.box_off[f0], hi = rl.box_off[f0 + 1];
+      lo = lo < 0 ? 0 : lo;
+      hi = hi > rl.B ? rl.B : hi;
+      for (int64_t b0 = lo; b0 < hi; b0 += LF_BOX_CHUNK) {
+        const int nb = (int)(hi - b0 < LF_BOX_CHUNK ? hi - b0 : LF_BOX_CHUNK);
+        __syncthreads();                            // the previous chunk (or the cameras) has been read
+        for (int i = tid; i < nb * LF_BOX; i += MC_THREADS) s_box[i] = rl.boxes[b0 * LF_BOX + i];
+        __syncthreads();
+        for (int b = 0; b < nb && live; ++b) live = !lf_in_box(s_box + b * LF_BOX, p);
+      }
+    } else if (live) {
+      int64_t lo = rl.box_off[f], hi = rl.box_off[f + 1];
+      lo = lo < 0 ? 0 : lo;
+      hi = hi > rl.B ? rl.B : hi;
+      for (int64_t b = lo; b < hi && live; ++b) live = !lf_in_box(rl.boxes + b * LF_BOX, p);
+    }
+  }
+  if (r < N) keep[r] = live ? 1 : 0;
+  int tot;
+  lr_block_rank(live ? 1 : 0, tot, wsum);
+  if (tid == 0) cnt[blockIdx.x] = tot;
+}
+
+struct LfOut {
+  float *rays_o, *rays_d, *ranges;
+  int64_t *li, *fi, *keep_inds;
+  float* pts_world;
+};
+
+__global__ void __launch_bounds__(MC_THREADS) k_lf_emit(const uint8_t* __restrict__ keep, const int32_t* __restrict__ off,
+                                                      const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                      const float* __restrict__ ranges, int64_t N, LfPoses ps, LfOut out) {
+  __shared__ int wsum[MC_THREADS / 64];
+  const int64_t r = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+  const int c = r < N && keep[r] ? 1 : 0;
+  int tot;
+  const int rank = lr_block_rank(c, tot, wsum);
+  if (!c) return;
+  const int64_t o = (int64_t)off[blockIdx.x] + rank;
+  const float rg = ranges[r];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    out.rays_o[3 * o + k] = rays_o[3 * r + k];
+    out.rays_d[3 * o + k] = rays_d[3 * r + k];
+  }
+  out.ranges[o] = rg;
+  if (out.li) out.li[o] = ps.li[r];
+  if (out.fi) out.fi[o] = ps.fi[r];
+  if (out.keep_inds) out.keep_inds[o] = r;
+  if (out.pts_world) {
+    float p[3];
+    int64_t f;
+    lf_world_point(ps, rays_o, rays_d, rg, r, f, p);       // a kept point's indices are inside the tables
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out.pts_world[3 * o + k] = p[k];
+  }
+}
+
+// the dense projection of world points into C cameras: mask u8, u, v, d f32, all [C][N]
+__global__ void __launch_bounds__(MC_THREADS) k_cam_project(const float* __restrict__ pts, int64_t N, const float* __restrict__ cams,
+                                                          uint64_t models, int64_t C, float near_clip,
+                                                          const uint8_t* __restrict__ ignore, int64_t Hm, int64_t Wm,
+                                                          uint8_t* __restrict__ mask, float* __restrict__ u, float* __restrict__ v,
+                                                          float* __restrict__ d) {
+  __shared__ float s_cam[LF_MAX_CAMS * LF_CAM];
+  for (int i = threadIdx.x; i < (int)C * LF_CAM; i += MC_THREADS) s_cam[i] = cams[i];
+  __syncthreads();
+  const int64_t r = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+  if (r >= N) return;
+  const float p[3] = {pts[3 * r], pts[3 * r + 1], pts[3 * r + 2]};
+  for (int64_t c = 0; c < C; ++c) {
+    float uu, vv, dd;
+    const bool in = lf_in_view(s_cam + c * LF_CAM, (int)((models >> (2 * c)) & 3ull), p, near_clip,
+                               ignore ? ignore + c * Hm * Wm : nullptr, Hm, Wm, uu, vv, dd);
+    mask[c * N + r] = in ? 1 : 0;
+    u[c * N + r] = uu;
+    v[c * N + r] = vv;
+    d[c * N + r] = dd;
+  }
+}
+
+// cam_models: HOST int32 [C], 0 pinhole / 1 opencv / 2 fisheye -> 2 bits each
+static int lf_pack_models(const int32_t* cam_models, int64_t C, uint64_t& packed) {
+  packed = 0;
+  if (C < 0) return 2;
+  if (C > LF_MAX_CAMS) return 62;
+  if (C > 0 && !cam_models) return 62;
+  for (int64_t c = 0; c < C; ++c) {
+    if (cam_models[c] < 0 || cam_models[c] > 2) return 62;
+    packed |= (uint64_t)cam_models[c] << (2 * c);
+  }
+  return 0;
+}
+
+extern "C" {
+
+int nsim_lidar_filter_count(const float* rays_o, const float* rays_d, const float* ranges, const int64_t* li, const int64_t* fi,
+                            int64_t N, const float* l2w, int64_t L, int64_t F, int filter_valid, const float* cams,
+                            const int32_t* cam_models, int64_t C, float near_clip, const uint8_t* ignore, int64_t Hm, int64_t Wm,
+                            const float* aabb, const float* boxes, const int32_t* box_offsets, int64_t B, uint8_t* keep,
+                            int32_t* cnt, void* stream) {
+  if (N < 0 || L < 0 || F < 0 || B < 0 || Hm < 0 || Wm < 0) return 2;
+  if (N >= ((int64_t)1 << 31)) return 62;
+  LfRule rl;
+  const int rc = lf_pack_models(cam_models, C, rl.models);
+  if (rc) return rc;
+  if (N == 0) return 0;
+  if (!keep || !cnt) return 4;
+  if (!rays_o || !rays_d || !ranges || !l2w || L < 1 || F < 1) return 62;
+  if ((C > 0 && !cams) || (ignore && (C == 0 || Hm < 1 || Wm < 1)) || (B > 0 && (!boxes || !box_offsets))) return 62;
+  LfPoses ps = {l2w, li, fi, L, F};
+  rl.filter_valid = filter_valid;
+  rl.cams = C > 0 ? cams : nullptr;        // C = 0: no camera filter
+  rl.C = C;
+  rl.near_clip = near_clip;
+  rl.ignore = ignore;
+  rl.Hm = Hm;
+  rl.Wm = Wm;
+  rl.aabb = aabb;
+  rl.boxes = B > 0 ? boxes : nullptr;      // B = 0: no box removes a point
+  rl.box_off = box_offsets;
+  rl.B = B;
+  hipLaunchKernelGGL(k_lf_count, vg_blocks(N), dim3(MC_THREADS), 0, (hipStream_t)stream, rays_o, rays_d, ranges, N, ps, rl, keep, cnt);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_lidar_filter_emit(const uint8_t* keep, const int32_t* off, const float* rays_o, const float* rays_d, const float* ranges,
+                           const int64_t* li, const int64_t* fi, int64_t N, const float* l2w, int64_t L, int64_t F,
+                           float* out_rays_o, float* out_rays_d, float* out_ranges, int64_t* out_li, int64_t* out_fi,
+                           int64_t* keep_inds, float* pts_world, void* stream) {
+  if (N < 0 || L < 0 || F < 0) return 2;
+  if (N >= ((int64_t)1 << 31)) return 62;
+  if (N == 0) return 0;
+  if (!out_rays_o || !out_rays_d || !out_ranges) return 4;
+  if (!keep || !off || !rays_o || !rays_d || !ranges) return 62;
+  if ((out_li && !li) || (out_fi && !fi) || (pts_world && (!l2w || L < 1 || F < 1))) return 62;
+  LfPoses ps = {l2w, li, fi, L, F};
+  LfOut out = {out_rays_o, out_rays_d, out_ranges, out_li, out_fi, keep_inds, pts_world};
+  hipLaunchKernelGGL(k_lf_emit, vg_blocks(N), dim3(MC_THREADS), 0, (hipStream_t)stream, keep, off, rays_o, rays_d, ranges, N, ps, out);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_cam_project(const float* pts, int64_t N, const float* cams, const int32_t* cam_models, int64_t C, float near_clip,
+                     const uint8_t* ignore, int64_t Hm, int64_t Wm, uint8_t* mask, float* u, float* v, float* d, void* stream) {
+  if (N < 0 || Hm < 0 || Wm < 0) return 2;
+  if (N >= ((int64_t)1 << 31)) return 62;
+  uint64_t models;
+  const int rc = lf_pack_models(cam_models, C, models);
+  if (rc) return rc;
+  if (N == 0 || C == 0) return 0;
+  if (!mask || !u || !v || !d) return 4;
+  if (!pts || !cams || (ignore && (Hm < 1 || Wm < 1))) return 62;
+  hipLaunchKernelGGL(k_cam_project, vg_blocks(N), dim3(MC_THREADS), 0, (hipStream_t)stream, pts, N, cams, models, C, near_clip, ignore,
+                     Hm, Wm, mask, u, v, d);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // extern "C"
+
 extern "C" {
 
 int nsim_version(void) { return 100; }
@@ -1886,6 +2220,7 @@ const char* nsim_strerror(int code) {
     case 59: return "segmentation z-buffer: at most 64 sources per call, candidate ordinals (ordinal_base + the call's candidates) below 2^32 - 1";
     case 60: return "lidar ray generation: thetas, phis and l2w are required, paired mode takes as many thetas as phis, fewer than 2^31 beams and azimuths and 2^39 rays";
     case 61: return "lidar returns: fewer than 2^31 rays per sweep; acc, depth, rays and offsets are required, and w2l / rgb / ids wherever their output is requested";
+    case 62: return "lidar filter / camera projection: fewer than 2^31 points, at most 32 cameras per frame with model ids 0..2 (a host array), at least one frame and one lidar pose; rays, ranges and poses are required, and the camera / box / offset / source tables wherever their count or output asks for them";
     case 36: return "wide decoder: 0..10 embedding frequencies and at most 128 first-layer inputs (2 num_levels + 3 + 6 n_freq)";
     default: return code >= 1000 ? "HIP launch error (code - 1000 = hipError_t)" : "unknown error";
   }

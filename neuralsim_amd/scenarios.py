@@ -281,9 +281,13 @@ def street_models(device, precision: str = "fp16", seed: int = 42, small: bool =
 
 
 @torch.no_grad()
-def street_lidar(world: AnalyticWorld, n_ego: int = 10, beams: int = 16384, x_range=(-60.0, 60.0), device=None, seed: int = 9):
+def street_lidar(world: AnalyticWorld, n_ego: int = 10, beams: int = 16384, x_range=(-60.0, 60.0), device=None, seed: int = 9,
+                 filter_kwargs: Optional[dict] = None, rig=None):
     """A roof lidar on the ego vehicle (``lidar_TOP``): per ego pose ``beams`` rays, azimuth uniform, elevation in
-    [-22, +2.5] degrees; ranges by tracing the analytic world (0 = no return).  -> rays_o, rays_d [F,M,3], ranges [F,M]."""
+    [-22, +2.5] degrees; ranges by tracing the analytic world (0 = no return).  -> rays_o, rays_d [F,M,3], ranges [F,M].
+    ``filter_kwargs`` (the configs' ``filter_kwargs`` block: ``filter_valid``, ``filter_in_cams`` against ``rig`` = (intr, c2w, WH)
+    of ``street_rig`` with the same ``n_ego``, ``filter_in_aabb`` f32 [2,3], ``boxes`` + ``box_offsets``, ``near_clip``): the beams
+    go through ``lidar_filter.filter_lidar_bank`` on ``device`` and come back as one flat bank, [1,T,3], [1,T,3], [1,T]."""
     g = torch.Generator().manual_seed(seed)
     o_l, d_l, r_l = [], [], []
     for e in range(n_ego):
@@ -297,14 +301,49 @@ def street_lidar(world: AnalyticWorld, n_ego: int = 10, beams: int = 16384, x_ra
         d_l.append(d)
         r_l.append(torch.where(tr["hit"], tr["t"], torch.zeros_like(tr["t"])))
     out = torch.stack(o_l), torch.stack(d_l), torch.stack(r_l)
+    if filter_kwargs is not None:
+        if device is None:
+            raise ValueError("street_lidar: filter_kwargs needs a device (the filter has no CPU path)")
+        return _filter_street_lidar(*(t.to(device) for t in out), rig, filter_kwargs)
     return tuple(t.to(device) for t in out) if device is not None else out
+
+
+def _filter_street_lidar(o: torch.Tensor, d: torch.Tensor, r: torch.Tensor, rig, filter_kwargs: dict):
+    """the beams of ``street_lidar`` (already in the world: identity poses) through the fused filter, frame = ego pose"""
+    from . import lidar_filter as lf
+    kw = dict(filter_kwargs)
+    F_, M_ = r.shape
+    dev = r.device
+    cams = None
+    if kw.pop("filter_in_cams", False):
+        if rig is None:
+            raise ValueError("street_lidar: filter_in_cams needs rig = (intr, c2w, WH)")
+        intr, c2w, WH = rig
+        if c2w.shape[0] % F_:
+            raise ValueError(f"street_lidar: a rig of {c2w.shape[0]} views does not divide into {F_} ego poses")
+        C = c2w.shape[0] // F_
+        hw = torch.stack([WH[:, 1], WH[:, 0]], dim=-1).view(F_, C, 2)
+        cams = lf.CameraSet(c2w.to(dev).float().view(F_, C, 4, 4).contiguous(), intr.to(dev).float().view(F_, C, 3, 3).contiguous(), hw)
+    aabb = kw.pop("filter_in_aabb", None)
+    args = dict(filter_valid=kw.pop("filter_valid", True), cams=cams, near_clip=kw.pop("near_clip", 1e-4),
+                aabb=aabb.to(dev).float().contiguous() if aabb is not None else None, boxes=kw.pop("boxes", None),
+                box_offsets=kw.pop("box_offsets", None))
+    if kw:
+        raise ValueError(f"street_lidar: unknown filter_kwargs {sorted(kw)}")
+    fi = torch.arange(F_, dtype=torch.long).repeat_interleave(M_).to(dev)
+    eye = torch.eye(4, dtype=torch.float32)[:3].expand(F_, 3, 4).contiguous().to(dev)
+    bank = lf.filter_lidar_bank(dict(rays_o=o.reshape(-1, 3).contiguous(), rays_d=d.reshape(-1, 3).contiguous(),
+                                     ranges=r.reshape(-1).contiguous()), eye, frame_inds=fi, **args)
+    return bank["rays_o"].unsqueeze(0), bank["rays_d"].unsqueeze(0), bank["ranges"].unsqueeze(0)
 
 
 def build_street_trainer(device, rank: int = 0, world_size: int = 1, precision: str = "fp16", rays_per_gpu: int = 16384,
                          seed: int = 42, small: bool = False, num_uniform: Optional[int] = None, n_ego: int = None,
-                         lidar_rays: int = 0, loss_cfg: Optional[dict] = None):
+                         lidar_rays: int = 0, loss_cfg: Optional[dict] = None, lidar_filter_kwargs: Optional[dict] = None):
     """``loss_cfg``: the yaml's remaining loss blocks (``RenderTrainer(loss_cfg=)``; ``STREET_LOSS_CFG`` is the config's own);
-    with one the dataset also carries the occupancy masks.  None: the trainer as it always was."""
+    with one the dataset also carries the occupancy masks.  None: the trainer as it always was.
+    ``lidar_filter_kwargs``: the configs' ``filter_kwargs`` (``street_lidar``): the lidar beams are filtered against the camera rig
+    once, up front, and the trainer draws its lidar batches from the flat filtered bank.  None: every beam, as before."""
     from . import distributed as ndist
     from .trainer import RenderTrainer
     world = street_world()
@@ -319,7 +358,8 @@ def build_street_trainer(device, rank: int = 0, world_size: int = 1, precision: 
         num_uniform = 256 if small else 2 ** 16                                         # ``num_uniform 2^16`` (yaml:38)
     lidar = None
     if lidar_rays:          # the reference's street iteration: a pixel batch AND a lidar batch (yaml:7-8: 8192 + 8192)
-        lo, ld, lr_ = street_lidar(world, n_ego=n_ego or (2 if small else 10), beams=512 if small else 16384, device=device)
+        lo, ld, lr_ = street_lidar(world, n_ego=n_ego or (2 if small else 10), beams=512 if small else 16384, device=device,
+                                   filter_kwargs=lidar_filter_kwargs, rig=(intr, c2w, WH))
         lidar = dict(rays_o=lo, rays_d=ld, ranges=lr_, num_rays=int(lidar_rays), w_depth=0.02, w_los=0.1, epsilon=1.5,
                      discard_toofar=80.0, near=0.1, far=200.0)
     return RenderTrainer(m, intr, c2w, WH, num_rays=rays_per_gpu, lr=1e-3, w_eikonal=0.01, num_uniform=num_uniform,

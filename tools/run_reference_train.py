@@ -10,6 +10,9 @@ its dataset is ``neuralsim_amd.dataio.SyntheticObjectDataset`` (``--dataset_cfg.
 On a machine without a HIP device (the authoring container) pass ``--emulate``: the kernels run on the test-only host
 emulator (tests/emu) and every ``cuda`` device the trainer asks for is mapped to the CPU -- the trainer hard-codes
 ``torch.device('cuda', local_rank)`` (train.py:1204).  Nothing of this is needed on a GPU box.
+
+``NSIM_LIDAR_FILTER=hip`` replaces the loader's ``_filter_lidar_gts`` (the configs' ``filter_kwargs``) by
+``neuralsim_amd.lidar_filter.reference_filter_adapter``: one fused pass instead of four masks and gathers.  Default: the reference's.
 """
 import os
 import runpy
@@ -152,6 +155,18 @@ def _remember_ddp_modules():
     return seen
 
 
+def torch_no_grad_method(fn):
+    """``fn(self, ...)`` as a method under ``torch.no_grad()`` (as the loader's own filter methods are decorated)"""
+    import functools
+    import torch
+
+    @functools.wraps(fn)
+    def method(self, *a, **k):
+        with torch.no_grad():
+            return fn(self, *a, **k)
+    return method
+
+
 def main(argv):
     emulate = "--emulate" in argv
     argv = [a for a in argv if a != "--emulate"]
@@ -171,6 +186,12 @@ def main(argv):
         # to autograd's device thread costs 0.28 ms per step on the Python-side backward functions (neuralsim_amd/__init__.py)
         import torch
         torch.autograd.set_multithreading_enabled(False)
+    if os.environ.get("NSIM_LIDAR_FILTER", "") == "hip":
+        # the loader's four sequential LiDAR filters (base_loader.py:732-844) as ONE fused count / scan / emit pass
+        # (neuralsim_amd/lidar_filter.py); the default stays the reference's own method
+        from dataio.data_loader.base_loader import SceneDataLoader
+        from neuralsim_amd.lidar_filter import reference_filter_adapter
+        SceneDataLoader._filter_lidar_gts = torch_no_grad_method(reference_filter_adapter)
     rel = "code_single/tools/train.py"
     if "--script" in argv:                 # another entry point of the reference (code_multi/tools/train.py), also unchanged
         i = argv.index("--script")

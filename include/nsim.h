@@ -629,7 +629,7 @@ int nsim_ngp_fwd(const NsimNgpMeta* meta, const void* wpack, const float* h_plan
                  int64_t S, float step, float* sigma, float* alpha, float* rgb, void* stream);
 /* Backward on the saved planes and forward outputs: dsigma / dalpha [S], drgb [S,3] (each may be NULL; drgb == NULL skips the
  * radiance decoder, drad_w / drad_b are then untouched).  Accumulates dden_w / dden_b / drad_w / drad_b (layouts above; through
- * the replicas of nsim_set_grad_scratch when a scratch of 16 x 12288 floats is registered), dh_appear [R,4] (may be NULL)
+ * the replicas of nsim_set_grad_scratch when a scratch of 16 x 16384 floats is registered), dh_appear [R,4] (may be NULL)
  * and writes dh_planes [16][S][2] (may be NULL) for nsim_lotd_scatter (g_planes = gn = NULL).  trunc_exp: d sigma / d raw =
  * exp(min(raw - 1, 15)).  The rays get no gradient. */
 int nsim_ngp_bwd(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* x,
@@ -648,6 +648,60 @@ int nsim_occ_collect_density(float* val, const float* x, const float* rays_o, co
                              const int64_t* ridx, const float* sigma, int64_t n, const NsimOccMeta* meta, void* stream);
 int nsim_occ_pack_bits_mean(const float* val, int64_t nvox, float occ_thre, int consider_mean, float* workspace,
                             uint32_t* bits, void* stream);
+
+/* ------------------------------------------------ dynamic-only EmerNeRF (EmerNerfStreetOnlyDynamic: EmerNeRFOnlyDynamicModel) */
+/* A density NeRF over (x, y, z, time) (code_multi/configs/exps/fg_neus=permuto_emernerf/with_gtbox.240212.yaml:277-360; wrapper
+ * app/models/single/dynamic_nerf.py).  The implementation is in the absent nr3d_lib: semantics fixed in DESIGN sec. 7.
+ *   dynamic_encoding_cfg{type: permuto} (yaml :290-300): a 4-D permutohedral lattice, <= 16 levels x 2 features, gathered
+ *     LEVEL-MAJOR by nsim_permuto_gather_pts from the lattice points of nsim_dyn_points into h_planes [16][P][2] f32.  The meta is
+ *     NsimNgpMeta: lotd.num_levels / lotd.n_active_levels give the level count and the hardmask (the pyramid itself is not read).
+ *   dynamic_decoder_cfg{D: 1, W: 64, relu} + n_geometry_feat: 64 (yaml :281, :301-305): h (2 num_levels) -> 64 (relu) -> 65
+ *     (linear); output 0 = raw, sigma = softplus(raw) = log1p(exp(raw)) (``trunc_softplus``: d sigma / d raw =
+ *     sigmoid(min(raw, 15))), outputs 1..64 = geometry feature.  den_w = [W1 (64 x 2 num_levels), W2 (65 x 64)] row-major,
+ *     den_b = [64, 65].
+ *   radiance_cfg{use_pos: false, use_view_dirs: true, use_nablas: false, dir_embed_cfg{spherical, 4}, D: 2, W: 64} (yaml
+ *     :329-338): [geo (64) | SH-4 of the normalised rays_d (16) | h_appear (n_appear = 0 | 4)] -> 64 -> 64 (relu) -> 3 (sigmoid).
+ *     rad_w = [Q1 (64 x (80 + n_appear)), Q2 (64 x 64), Q3 (3 x 64)], rad_b = [64, 64, 3]. */
+int64_t nsim_dyn_wpack_bytes(const NsimNgpMeta* meta);
+int nsim_dyn_pack_weights(const NsimNgpMeta* meta, const float* den_w, const float* den_b, const float* rad_w,
+                          const float* rad_b, void* wpack, void* stream);
+/* Fused decoders over the feature planes (pitch plane_pitch; 0 = S, the pitch nsim_permuto_gather_pts writes) of S samples.
+ * Writes sigma [S], alpha [S] = 1 - exp(-sigma step) (may be NULL) and rgb [S,3] from rays_d [R,3], ridx [S] and h_appear [R,4].
+ * rgb == NULL: the density decoder alone (occupancy refresh, forward_density); rays_d / ridx are then not read. */
+int nsim_dyn_fwd(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* rays_d,
+                 const int64_t* ridx, const float* h_appear, int64_t S, float step, float* sigma, float* alpha, float* rgb,
+                 void* stream);
+/* Backward on the saved planes and forward outputs: dsigma / dalpha [S], drgb [S,3] (each may be NULL; drgb == NULL skips the
+ * radiance decoder and the geometry rows, drad_w / drad_b are then untouched).  Accumulates dden_w / dden_b / drad_w / drad_b
+ * (layouts above; through the replicas of nsim_set_grad_scratch when the registered scratch holds them), dh_appear [R,4] (may
+ * be NULL) and writes dh_planes [16][S][2] (may be NULL) for nsim_permuto_scatter_pts.  Neither rays nor times get a gradient. */
+int nsim_dyn_bwd(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* rays_d,
+                 const int64_t* ridx, const float* h_appear, int64_t S, float step, const float* sigma_fwd, const float* rgb_fwd,
+                 const float* dsigma, const float* dalpha, const float* drgb, float* dh_planes, float* dden_w, float* dden_b,
+                 float* drad_w, float* drad_b, float* dh_appear, void* stream);
+/* The time input.  keyframes [T] ascending (the model's ``ts_keyframes`` for w, the accelerator's for the slices), ts [n]:
+ *   w [n] (may be NULL) = SeqEmbedding(keyframes, codes)(ts, 'interp') for codes [T] (``time_embedding_cfg{dim: 1}``):
+ *     v[i-1] + f (v[i] - v[i-1]) on the interval that holds ts, f clamped to [0,1] (the ends clamp), v[0] when T == 1;
+ *   slice [n] (may be NULL) = the index of the nearest keyframe, a tie to the lower index, times outside the range to the
+ *     first / last; word_off [n] (may be NULL) = slice * words_per_slice, the ray_word_off of nsim_march_count / _emit. */
+int nsim_dyn_time(const float* keyframes, const float* codes, int T, const float* ts, int64_t n, int64_t words_per_slice,
+                  float* w, int64_t* slice, int64_t* word_off, void* stream);
+/* Lattice points x4 [S,4] = (position, time coordinate): x [S,3] with w [S], or rays_o[ridx] + t rays_d[ridx] with w [R]. */
+int nsim_dyn_points(const float* x, const float* rays_o, const float* rays_d, const float* t, const int64_t* ridx,
+                    const float* w, int64_t S, float* x4, void* stream);
+/* ``accel_cfg{type: occ_grid_dynamic}`` (yaml :339-354): K value grids of nvox voxels, slice_stride floats apart, one per
+ * accelerator keyframe.  slice: the grid of every point (pts / x: [n]) or of every ray (rays + t + ridx: [R]); an index outside
+ * [0, K) drops the point.  update: ALL slices decay once, then every point is max-folded into its own slice; collect: the
+ * max-fold alone; pack_bits_mean: slice k's bits (ceil(nvox / 32) words each, padding bits clear) from slice k's own mean.
+ * workspace: 65 K floats, contents irrelevant; workspace[65 k + 64] receives slice k's threshold. */
+int nsim_occ_update_density_sliced(float* val, int64_t nvox, int64_t slice_stride, int K, float decay, const float* pts,
+                                   const float* sigma, const int64_t* slice, int64_t n, const NsimOccMeta* meta,
+                                   void* stream);
+int nsim_occ_collect_density_sliced(float* val, int64_t slice_stride, int K, const float* x, const float* rays_o,
+                                    const float* rays_d, const float* t, const int64_t* ridx, const int64_t* slice,
+                                    const float* sigma, int64_t n, const NsimOccMeta* meta, void* stream);
+int nsim_occ_pack_bits_mean_sliced(const float* val, int64_t nvox, int64_t slice_stride, int K, float occ_thre,
+                                   int consider_mean, float* workspace, uint32_t* bits, void* stream);
 
 /* ------------------------------------------------------------------------------- sky MLP (row a16) */
 /* ``SimpleSky`` (app/models/env/sky.py:16-51) as configured by the street configs

@@ -200,6 +200,14 @@ SIGNATURES = {
     "nsim_occ_update_density": [_P, _I64, _F, _P, _P, _I64, C.POINTER(OccMeta)],
     "nsim_occ_collect_density": [_P, _P, _P, _P, _P, _P, _P, _I64, C.POINTER(OccMeta)],
     "nsim_occ_pack_bits_mean": [_P, _I64, _F, _I, _P, _P],
+    "nsim_dyn_pack_weights": [C.POINTER(NgpMeta), _P, _P, _P, _P, _P],
+    "nsim_dyn_fwd": [C.POINTER(NgpMeta), _P, _P, _I64, _P, _P, _P, _I64, _F, _P, _P, _P],
+    "nsim_dyn_bwd": [C.POINTER(NgpMeta), _P, _P, _I64, _P, _P, _P, _I64, _F] + [_P] * 11,
+    "nsim_dyn_time": [_P, _P, _I, _P, _I64, _I64, _P, _P, _P],
+    "nsim_dyn_points": [_P, _P, _P, _P, _P, _P, _I64, _P],
+    "nsim_occ_update_density_sliced": [_P, _I64, _I64, _I, _F, _P, _P, _P, _I64, C.POINTER(OccMeta)],
+    "nsim_occ_collect_density_sliced": [_P, _I64, _I, _P, _P, _P, _P, _P, _P, _P, _I64, C.POINTER(OccMeta)],
+    "nsim_occ_pack_bits_mean_sliced": [_P, _I64, _I64, _I, _F, _I, _P, _P],
     "nsim_sky_pack_weights": [C.POINTER(SkyMeta), _P, _P, _P],
     "nsim_sky_fwd": [C.POINTER(SkyMeta), _P, _P, _P, _I64, _P, _P],
     "nsim_sky_bwd": [C.POINTER(SkyMeta), _P, _P, _P, _I64, _P, _P, _P, _P, _P],
@@ -285,6 +293,7 @@ NOSTREAM = {
     "nsim_sphere_trace_workspace_bytes": ([], _I64),
     "nsim_distant_wpack_bytes": ([C.POINTER(DistantMeta)], _I64),
     "nsim_ngp_wpack_bytes": ([C.POINTER(NgpMeta)], _I64),
+    "nsim_dyn_wpack_bytes": ([C.POINTER(NgpMeta)], _I64),
     "nsim_sky_wpack_bytes": ([C.POINTER(SkyMeta)], _I64),
     "nsim_sky_plane_pitch": ([_I64], _I64),
 }
@@ -417,8 +426,8 @@ def _marshal(args):
 
 
 _GRAD_SCRATCH = {}
-_GRAD_SCRATCH_USERS = ("nsim_field_bwd_rad", "nsim_field_bwd_sdf", "nsim_ngp_bwd")
-GRAD_SCRATCH_FLOATS = 16 * 12288      # 16 replicas of the largest decoder gradient (nsim_ngp_bwd: both decoders, 12067 floats)
+_GRAD_SCRATCH_USERS = ("nsim_field_bwd_rad", "nsim_field_bwd_sdf", "nsim_ngp_bwd", "nsim_dyn_bwd")
+GRAD_SCRATCH_FLOATS = 16 * 16384      # 16 replicas of the largest decoder gradient (nsim_dyn_bwd: both decoders, 16132 floats)
 
 
 def ensure_grad_scratch(device):

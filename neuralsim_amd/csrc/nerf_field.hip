@@ -1288,6 +1288,553 @@ __global__ void __launch_bounds__(256) k_occ_pack_bits_mean(const float* __restr
   bits[w] = b;
 }
 
+// ================================================================================== dynamic-only EmerNeRF
+// ``EmerNeRFOnlyDynamicModel`` (app/models/single/dynamic_nerf.py EmerNerfStreetOnlyDynamic; config
+// code_multi/configs/exps/fg_neus=permuto_emernerf/with_gtbox.240212.yaml:277-360): features of a 4-D permutohedral lattice
+// over (x, y, z, time) (gathered level-major by permuto.hip: nsim_permuto_gather_pts) -> dynamic decoder h (F = 2 L <= 32) ->
+// 64 (relu) -> 1 + 64 (linear): output 0 = raw density (sigma = softplus(raw)), outputs 1..64 = geometry feature ->
+// radiance decoder [geo (64) | SH-4 (16) | h_appear (0 | 4)] -> 64 -> 64 (relu) -> 3 (sigmoid).
+// Tiling on the 32-unit tiles of mfma_mlp.h: the density row of the second layer is a 64-long dot product on the VALU in
+// f32 (a per-lane vector of the pack, as the head of k_nerf) and never enters an MFMA chunk, so the geometry feature is
+// exactly two M-tiles; the first radiance layer takes three input tiles (geo 0..63 | SH 64..79 | appearance 80..83 | zero
+// padding to 96).  Its weight gradient is two products (geo block, tail block): the staging arrays hold 64 rows.
+enum { Y_D1 = 0, Y_D2, Y_Q1, Y_Q2, Y_Q3, Y_D1T, Y_D2T, Y_Q3T, Y_Q2T, Y_Q1T, Y_MCOUNT };
+enum { YV_DB1 = 0, YV_DWH, YV_DB2, YV_RB1, YV_RB2, YV_RB3, YV_SCAL, YV_COUNT };
+static_assert(Y_MCOUNT <= PACK_MAX_MATS && Y_MCOUNT == G_MCOUNT && YV_COUNT <= GV_COUNT, "the dynamic model's pack fits NgpLayout");
+static const int kYUo[Y_MCOUNT] = {64, 64, 64, 64, 32, 32, 64, 64, 64, 96};
+static const int kYUi[Y_MCOUNT] = {32, 64, 96, 64, 64, 64, 64, 32, 64, 64};
+
+// pack: [vectors | forward matrices | transposed matrices], as the NGP model's
+static inline NgpLayout dyn_layout(int precision) {
+  NgpLayout L;
+  L.elt = precision == 0 ? 2 : 4;
+  int64_t off = 0;
+  for (int v = 0; v < GV_COUNT; ++v) {
+    L.vec[v] = off;
+    if (v < YV_COUNT) off += 64 * 4;
+  }
+  L.fwd_end = 0;
+  for (int m = 0; m < Y_MCOUNT; ++m) {
+    L.mat[m] = off;
+    off += (int64_t)kYUo[m] * kYUi[m] * L.elt;
+    if (m == Y_Q3) L.fwd_end = off;
+  }
+  L.total = off;
+  return L;
+}
+
+// radiance input slot (0..95) -> column of the [64 x (80 + NA)] first radiance layer, or -1 (padding)
+__host__ __device__ inline int dyn_q1_col(int slot, int NA) { return slot < 80 + NA ? slot : -1; }
+
+__device__ __forceinline__ float dyn_src(int mat, int row, int col, int F, int NA, const float* den_w, const float* rad_w) {
+  const int K1 = 80 + NA;
+  const int d2 = 64 * F + 64, q2 = 64 * K1, q3 = q2 + 4096;      // d2: row 1 of the [65 x 64] second density layer
+  switch (mat) {
+    case Y_D1: return col < F ? den_w[row * F + col] : 0.f;
+    case Y_D1T: return row < F ? den_w[col * F + row] : 0.f;
+    case Y_D2: return den_w[d2 + row * 64 + col];
+    case Y_D2T: return den_w[d2 + col * 64 + row];
+    case Y_Q1: { const int c = dyn_q1_col(col, NA); return c >= 0 ? rad_w[row * K1 + c] : 0.f; }
+    case Y_Q1T: { const int c = dyn_q1_col(row, NA); return c >= 0 ? rad_w[col * K1 + c] : 0.f; }
+    case Y_Q2: return rad_w[q2 + row * 64 + col];
+    case Y_Q2T: return rad_w[q2 + col * 64 + row];
+    case Y_Q3: return row < 3 ? rad_w[q3 + row * 64 + col] : 0.f;
+    case Y_Q3T: return col < 3 ? rad_w[q3 + col * 64 + row] : 0.f;
+  }
+  return 0.f;
+}
+
+__global__ void __launch_bounds__(256) k_dyn_pack(NgpLayout L, PackShape sh, int F, int NA, const float* __restrict__ den_w,
+                                                   const float* __restrict__ den_b, const float* __restrict__ rad_w,
+                                                   const float* __restrict__ rad_b, char* __restrict__ wpack) {
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const auto src = [&](int m, int row, int col) { return dyn_src(m, row, col, F, NA, den_w, rad_w); };
+  if (pack_matrices(sh, Y_MCOUNT, L.mat, pack_form(L.elt), wpack, tid, src)) return;
+  if (tid < (int64_t)YV_COUNT * 64) {
+    const int v = (int)(tid >> 6), k = (int)(tid & 63), u = vec_unit(k, 64);
+    float val = 0.f;
+    switch (v) {
+      case YV_DB1: val = den_b[u]; break;
+      case YV_DWH: val = den_w[64 * F + u]; break;
+      case YV_DB2: val = den_b[65 + u]; break;
+      case YV_RB1: val = rad_b[u]; break;
+      case YV_RB2: val = rad_b[64 + u]; break;
+      case YV_RB3: val = u < 3 ? rad_b[128 + u] : 0.f; break;
+      case YV_SCAL: val = (k == 0) ? den_b[64] : 0.f; break;
+    }
+    ((float*)(wpack + L.vec[v]))[k] = val;
+  }
+}
+
+struct DynArgs {
+  NgpLayout lay;
+  int F, NL, n_active, NA;                // features = 2 NL; levels >= n_active are masked
+  const char* wpack;
+  const float* rays_d;                    // [R,3] (radiance only)
+  const int64_t* ridx;                    // [S] (radiance only)
+  const float* h_appear;                  // [R,4] or NULL
+  int64_t S, PS;                          // points; pitch of h_pl
+  float step;                             // alpha = 1 - exp(-sigma step)
+  const float* h_pl;                      // [16][PS][2] gathered features
+  float *sigma, *alpha, *rgb;             // forward outputs (rgb NULL: density only)
+  const float *sigma_fwd, *rgb_fwd;       // saved forward outputs
+  const float *dsigma, *dalpha, *drgb;    // upstream (each may be NULL)
+  float* dh_pl;                           // [16][S][2] hand-off to nsim_permuto_scatter_pts (may be NULL)
+  float* dst[4];                          // dden_w, dden_b, drad_w, drad_b -- or replica 0 of the registered scratch
+  int64_t rep_stride;
+  int rep_mask;
+  float* dh_appear;
+};
+
+#define DYN_WAVES 4
+#define DYN_WAVES_BWD 2       // the weight-gradient accumulators are 67.6 KB per private copy: two fit next to the staging
+
+// sigma = softplus(raw) = log1p(exp(raw)); past 30 the difference to raw is below half an ulp
+__device__ __forceinline__ float dyn_softplus(float raw) { return raw > 30.f ? raw : log1pf(expf(raw)); }
+
+// radiance input, third M-tile (slots 64..95): SH-4 of the view direction, appearance code, zero padding
+__device__ __forceinline__ void dyn_rin_tail(float (&tail)[16], const float vd[3], const float ha[4], int hi) {
+  float sh[16];
+  sh4_eval(vd, sh);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int slot = unit_of(0, r, hi);
+    float v = 0.f;
+    if (slot < 16) v = sh[slot];
+    else if (slot < 20) v = ha[slot - 16];
+    tail[r] = v;
+  }
+}
+
+// BWD = 0: sigma / alpha / rgb.  BWD = 1: recomputes the activations from the saved feature planes and accumulates the weight
+// gradients (per-wave private LDS accumulators in fp16 mode, as k_ngp), dh planes, dh_appear.
+template <int PREC, int BWD>
+__global__ void __launch_bounds__(64 * (BWD ? DYN_WAVES_BWD : DYN_WAVES)) k_dyn(DynArgs a) {
+  NSIM_DYN_SMEM(smem);
+  constexpr bool PRIV = (PREC == 0 && BWD);
+  constexpr int NW = BWD ? DYN_WAVES_BWD : DYN_WAVES;
+  const int lane = nsim_lane(), j = lane & 31, hi = lane >> 5;
+  const int wave = (int)(threadIdx.x >> 6);
+  const NgpLayout& L = a.lay;
+  const bool with_rad = BWD ? (a.drgb != nullptr) : (a.rgb != nullptr);
+  const char* W = a.wpack;
+  const char* WM = a.wpack;
+  int wbytes = 0;
+  if constexpr (PREC == 0) {
+    const int64_t nbytes = BWD ? L.mat[0] : L.fwd_end;
+    const int n16 = (int)((nbytes + 15) >> 4);
+    const f16x8* src = reinterpret_cast<const f16x8*>(a.wpack);
+    f16x8* dst = reinterpret_cast<f16x8*>(smem);
+    for (int i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
+    wbytes = n16 << 4;
+    __syncthreads();
+    W = smem;
+    if constexpr (!BWD) WM = smem;
+  }
+  constexpr int A_D1 = 0, A_DWH = 2048, A_DB1 = A_DWH + 64, A_BD = A_DB1 + 64, A_D2 = A_BD + 4, A_DB2 = A_D2 + 4096,
+                A_Q1 = A_DB2 + 64, A_Q2 = A_Q1 + 6144, A_Q3 = A_Q2 + 4096, A_RB1 = A_Q3 + 192, A_RB2 = A_RB1 + 64,
+                A_RB3 = A_RB2 + 64, A_TOTAL = A_RB3 + 4;
+  static_assert(A_TOTAL == 16904, "nsim_dyn_bwd sizes the LDS from this count");
+  constexpr int ACC_BYTES = (A_TOTAL * 4 + 15) & ~15;
+  float* accum = nullptr;
+  char* stA = nullptr;
+  char* stB = nullptr;
+  if constexpr (BWD) {
+    accum = reinterpret_cast<float*>(smem + wbytes + (PRIV ? wave * ACC_BYTES : 0));
+    char* stbase = smem + wbytes + (PRIV ? NW : 1) * ACC_BYTES + wave * stage_bytes_per_wave<PREC>();
+    stA = stbase;
+    stB = stbase + stage_bytes_per_wave<PREC>() / 2;
+    if constexpr (PRIV) {
+      for (int i = lane; i < A_TOTAL; i += 64) accum[i] = 0.f;
+    } else {
+      for (int i = threadIdx.x; i < A_TOTAL; i += blockDim.x) accum[i] = 0.f;
+    }
+    __syncthreads();
+  }
+  const float b_d = reinterpret_cast<const float*>(W + L.vec[YV_SCAL])[0];
+  const int64_t ntiles = (a.S + 31) / 32;
+  const int64_t wstride = (int64_t)gridDim.x * NW;
+  for (int64_t tile = (int64_t)blockIdx.x * NW + wave; tile < ntiles; tile += wstride) {
+    const int64_t s = tile * 32 + j;
+    const bool valid = s < a.S;
+    int64_t ray = 0;
+    float vd[3] = {0.f, 0.f, 1.f}, ha[4] = {0.f, 0.f, 0.f, 0.f};
+    if (valid && with_rad) {
+      ray = a.ridx[s];
+      float d[3], n2 = 0.f;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        d[c] = a.rays_d[3 * ray + c];
+        n2 = n2 + d[c] * d[c];
+      }
+      const float inv = n2 > 0.f ? 1.0f / sqrtf(n2) : 0.f;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) vd[c] = d[c] * inv;
+      if (a.h_appear && a.NA == 4) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) ha[c] = a.h_appear[4 * ray + c];
+      }
+    }
+    // -------------------------------------------------------------- features from the level-major planes
+    float h[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int l = 4 * q + 2 * hi + b;
+        float f0 = 0.f, f1 = 0.f;
+        if (valid && l < a.n_active) {      // (masked and padding levels: zero features, their planes are never read)
+          const float* hp = a.h_pl + ((int64_t)l * a.PS + s) * 2;
+          f0 = hp[0];
+          f1 = hp[1];
+        }
+        h[4 * q + 2 * b] = f0;
+        h[4 * q + 2 * b + 1] = f1;
+      }
+    }
+    // -------------------------------------------------------------- dynamic (density) decoder
+    float a1[32];
+    dense<PREC, 2, 1>(a1, WM + L.mat[Y_D1], h, true);
+#pragma unroll
+    for (int k = 0; k < 32; ++k) a1[k] = fmaxf(a1[k] + ngp_vec(W, L, YV_DB1, hi, k), 0.f);
+    float raw = 0.f;
+#pragma unroll
+    for (int k = 0; k < 32; ++k) raw = raw + ngp_vec(W, L, YV_DWH, hi, k) * a1[k];
+    raw = raw + wave_shfl_xor(raw, 32) + b_d;
+    if constexpr (!BWD) {
+      const float sg = dyn_softplus(raw);
+      if (valid && hi == 0) {
+        a.sigma[s] = sg;
+        if (a.alpha) a.alpha[s] = 1.0f - expf(-sg * a.step);
+      }
+    }
+    float geo[32], tail[16], r1[32], r2[32];
+    if (with_rad) {
+      dense<PREC, 2, 2>(geo, WM + L.mat[Y_D2], a1, true);
+      float rin[48];
+#pragma unroll
+      for (int k = 0; k < 32; ++k) {
+        geo[k] = geo[k] + ngp_vec(W, L, YV_DB2, hi, k);
+        rin[k] = geo[k];
+      }
+      dyn_rin_tail(tail, vd, ha, hi);
+#pragma unroll
+      for (int k = 0; k < 16; ++k) rin[32 + k] = tail[k];
+      dense<PREC, 2, 3>(r1, WM + L.mat[Y_Q1], rin, true);
+#pragma unroll
+      for (int k = 0; k < 32; ++k) r1[k] = fmaxf(r1[k] + ngp_vec(W, L, YV_RB1, hi, k), 0.f);
+      dense<PREC, 2, 2>(r2, WM + L.mat[Y_Q2], r1, false);
+#pragma unroll
+      for (int k = 0; k < 32; ++k) r2[k] = fmaxf(r2[k] + ngp_vec(W, L, YV_RB2, hi, k), 0.f);
+    }
+    if constexpr (!BWD) {
+      if (with_rad) {
+        float o3[16];
+        dense<PREC, 1, 2>(o3, WM + L.mat[Y_Q3], r2, false);
+        if (valid && hi == 0) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) a.rgb[3 * s + c] = 1.0f / (1.0f + nsim_fast_exp(-(o3[c] + ngp_vec(W, L, YV_RB3, hi, c))));
+        }
+      }
+    }
+    if constexpr (BWD) {
+      float da[32];
+#pragma unroll
+      for (int k = 0; k < 32; ++k) da[k] = 0.f;
+      if (with_rad) {
+        float gr[3] = {0.f, 0.f, 0.f}, rgbv[3] = {0.f, 0.f, 0.f};
+        if (valid) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            gr[c] = a.drgb[3 * s + c];
+            rgbv[c] = a.rgb_fwd[3 * s + c];
+          }
+        }
+        float dout[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dout[r] = 0.f;
+        if (hi == 0) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) dout[c] = gr[c] * rgbv[c] * (1.0f - rgbv[c]);
+        }
+        dw_product<PREC, 1, 2, PRIV>(stA, stB, dout, r2, accum + A_Q3, 64, 3, 64, accum + A_RB3);
+        float dr2[32];
+        dense<PREC, 2, 1>(dr2, WM + L.mat[Y_Q3T], dout, true);
+#pragma unroll
+        for (int k = 0; k < 32; ++k) dr2[k] = r2[k] > 0.f ? dr2[k] : 0.f;
+        dw_product<PREC, 2, 2, PRIV>(stA, stB, dr2, r1, accum + A_Q2, 64, 64, 64, accum + A_RB2);
+        float dr1[32];
+        dense<PREC, 2, 2>(dr1, WM + L.mat[Y_Q2T], dr2, true);
+#pragma unroll
+        for (int k = 0; k < 32; ++k) dr1[k] = r1[k] > 0.f ? dr1[k] : 0.f;
+        // the first radiance layer's gradient [64 x 96] in two products: columns 0..63 (geo), 64..95 (SH | appearance | padding)
+        dw_product<PREC, 2, 2, PRIV>(stA, stB, dr1, geo, accum + A_Q1, 96, 64, 64, accum + A_RB1);
+        dw_product<PREC, 2, 1, PRIV>(stA, stB, dr1, tail, accum + A_Q1 + 64, 96, 64, 32, nullptr);
+        float din[48];
+        dense<PREC, 3, 2>(din, WM + L.mat[Y_Q1T], dr1, true);
+        // appearance slots 80..83 = third M-tile local 16..19 (lower half-wave, registers 8..11); one atomic per ray and channel
+        if (a.dh_appear && a.NA == 4) {
+          float c0 = din[32 + 8], c1 = din[32 + 9], c2 = din[32 + 10], c3 = din[32 + 11];
+          const bool v = valid && hi == 0;
+          const bool last = halfwave_run_sum2(ray, v, c0, c1);
+          halfwave_run_sum2(ray, v, c2, c3);
+          if (last) {
+            float* dst = a.dh_appear + 4 * ray;
+            atomicAdd(dst, c0);
+            atomicAdd(dst + 1, c1);
+            atomicAdd(dst + 2, c2);
+            atomicAdd(dst + 3, c3);
+          }
+        }
+        float dgeo[32];
+#pragma unroll
+        for (int k = 0; k < 32; ++k) dgeo[k] = valid ? din[k] : 0.f;
+        dw_product<PREC, 2, 2, PRIV>(stA, stB, dgeo, a1, accum + A_D2, 64, 64, 64, accum + A_DB2);
+        dense<PREC, 2, 2>(da, WM + L.mat[Y_D2T], dgeo, true);
+      }
+      // ---- sigma = softplus(raw): d raw = (d sigma + d alpha step exp(-sigma step)) sigmoid(min(raw, 15))
+      float draw = 0.f;
+      if (valid) {
+        const float sg = a.sigma_fwd[s];
+        if (a.dsigma) draw = draw + a.dsigma[s];
+        if (a.dalpha) draw = draw + a.dalpha[s] * (a.step * expf(-sg * a.step));
+        draw = draw * (1.0f / (1.0f + expf(-fminf(raw, 15.0f))));
+      }
+      float whv[32];
+#pragma unroll
+      for (int k = 0; k < 32; ++k) {
+        whv[k] = draw * a1[k];
+        da[k] = a1[k] > 0.f ? da[k] + draw * ngp_vec(W, L, YV_DWH, hi, k) : 0.f;
+      }
+      rowsum_acc<PREC, 2, PRIV>(stA, whv, accum + A_DWH, 64);
+      {
+        float v = (hi == 0) ? draw : 0.f;
+        v = wave_sum(v);
+        if (lane == 0 && v != 0.f) {
+          if constexpr (PRIV) accum[A_BD] = accum[A_BD] + v;
+          else atomicAdd(&accum[A_BD], v);
+        }
+      }
+      dw_product<PREC, 2, 1, PRIV>(stA, stB, da, h, accum + A_D1, 32, 64, 32, accum + A_DB1);
+      if (a.dh_pl) {
+        float dh[16];
+        dense<PREC, 1, 2>(dh, WM + L.mat[Y_D1T], da, true);
+        if (valid) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+              const int l = 4 * q + 2 * hi + b;
+              if (l >= a.NL) continue;                      // (the scatter reads the lattice's own levels only)
+              const bool on = l < a.n_active;
+              float* dp = a.dh_pl + ((int64_t)l * a.S + s) * 2;
+              dp[0] = on ? dh[4 * q + 2 * b] : 0.f;
+              dp[1] = on ? dh[4 * q + 2 * b + 1] : 0.f;
+            }
+          }
+        }
+      }
+    }
+  }
+  if constexpr (BWD) {
+    __syncthreads();
+    const int F = a.F, K1 = 80 + a.NA;
+    const int64_t rep = (int64_t)(blockIdx.x & (unsigned)a.rep_mask) * a.rep_stride;
+    for (int i = threadIdx.x; i < A_TOTAL; i += blockDim.x) {
+      float v;
+      if constexpr (PRIV) {
+        constexpr int ACC_FLOATS = ACC_BYTES / 4;
+        const float* a0 = reinterpret_cast<const float*>(smem + wbytes);
+        v = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) v += a0[w * ACC_FLOATS + i];
+      } else {
+        v = accum[i];
+      }
+      if (v == 0.f) continue;
+      int d = -1;
+      int64_t off = 0;
+      if (i < A_DWH) {
+        const int row = i >> 5, col = i & 31;
+        if (col < F) { d = 0; off = row * F + col; }
+      } else if (i < A_DB1) { d = 0; off = 64 * F + (i - A_DWH); }
+      else if (i < A_BD) { d = 1; off = i - A_DB1; }
+      else if (i < A_D2) { if (i == A_BD) { d = 1; off = 64; } }
+      else if (i < A_DB2) { d = 0; off = 64 * F + 64 + (i - A_D2); }
+      else if (i < A_Q1) { d = 1; off = 65 + (i - A_DB2); }
+      else if (i < A_Q2) {
+        const int row = (i - A_Q1) / 96, c = dyn_q1_col((i - A_Q1) % 96, a.NA);
+        if (c >= 0) { d = 2; off = row * K1 + c; }
+      } else if (i < A_Q3) { d = 2; off = 64 * K1 + (i - A_Q2); }
+      else if (i < A_RB1) { d = 2; off = 64 * K1 + 4096 + (i - A_Q3); }
+      else if (i < A_RB2) { d = 3; off = i - A_RB1; }
+      else if (i < A_RB3) { d = 3; off = 64 + (i - A_RB2); }
+      else if (i - A_RB3 < 3) { d = 3; off = 128 + (i - A_RB3); }
+      if (d >= 0) atomicAdd(a.dst[d] + rep + off, v);
+    }
+  }
+}
+
+// ----------------------------------------------------------------------------------------- time input
+// w = SeqEmbedding(tk, v)(ts, 'interp') (piecewise linear, the ends clamp, T == 1: v[0]) and the slice of a time: the nearest of
+// the T keyframes tk, a tie to the lower index, times outside the range clamp.
+__global__ void __launch_bounds__(256) k_dyn_time(const float* __restrict__ tk, const float* __restrict__ v, int T,
+                                                   const float* __restrict__ ts, int64_t n, int64_t words_per_slice,
+                                                   float* __restrict__ w_out, int64_t* __restrict__ slice_out,
+                                                   int64_t* __restrict__ word_off_out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float t = ts[i];
+  if (w_out) {
+    float w = v[0];
+    if (T > 1) {
+      int lo = 0, hi = T;                   // first index with tk[idx] > t (searchsorted right), clamped to [1, T - 1]
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (tk[mid] > t) hi = mid;
+        else lo = mid + 1;
+      }
+      const int idx = lo < 1 ? 1 : (lo > T - 1 ? T - 1 : lo);
+      const float t0 = tk[idx - 1], t1 = tk[idx];
+      float f = (t - t0) / fmaxf(t1 - t0, 1e-12f);
+      f = fminf(fmaxf(f, 0.f), 1.f);
+      w = v[idx - 1] + f * (v[idx] - v[idx - 1]);
+    }
+    w_out[i] = w;
+  }
+  if (slice_out || word_off_out) {
+    int lo = 0, hi = T;                     // first keyframe >= t
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (tk[mid] >= t) hi = mid;
+      else lo = mid + 1;
+    }
+    int k = lo;
+    if (k >= T) k = T - 1;
+    else if (k > 0 && !(tk[k] - t < t - tk[k - 1])) k = k - 1;      // tie: lower index
+    if (slice_out) slice_out[i] = k;
+    if (word_off_out) word_off_out[i] = (int64_t)k * words_per_slice;
+  }
+}
+
+// lattice points [S,4] = (position, time coordinate): position x [S,3] with w per point, or rays_o[ridx] + t rays_d[ridx] with w
+// per ray
+__global__ void __launch_bounds__(256) k_dyn_points(const float* __restrict__ x, const float* __restrict__ rays_o,
+                                                     const float* __restrict__ rays_d, const float* __restrict__ t,
+                                                     const int64_t* __restrict__ ridx, const float* __restrict__ w, int64_t S,
+                                                     float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= S) return;
+  float p[4];
+  if (x) {
+    p[0] = x[3 * i]; p[1] = x[3 * i + 1]; p[2] = x[3 * i + 2];
+    p[3] = w[i];
+  } else {
+    const int64_t r = ridx[i];
+    const float tt = t[i];
+    p[0] = rays_o[3 * r] + tt * rays_d[3 * r];
+    p[1] = rays_o[3 * r + 1] + tt * rays_d[3 * r + 1];
+    p[2] = rays_o[3 * r + 2] + tt * rays_d[3 * r + 2];
+    p[3] = w[r];
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) out[4 * i + c] = p[c];
+}
+
+// ----------------------------------------------------------------------------------------- time-sliced density occupancy
+// ``accel_cfg{type: occ_grid_dynamic}``: K value grids of one resolution, ``stride`` floats apart; every point is folded into
+// the grid of ITS slice (per point with x, per ray with rays).  occ_max_wave with the slice in the run key: equal voxels of
+// neighbouring lanes merge only inside one slice.
+__global__ void __launch_bounds__(256) k_occ_max_density_sliced(float* __restrict__ val, int64_t stride, int K,
+                                                                 const float* __restrict__ x, const float* __restrict__ rays_o,
+                                                                 const float* __restrict__ rays_d, const float* __restrict__ t,
+                                                                 const int64_t* __restrict__ ridx,
+                                                                 const int64_t* __restrict__ slice, const float* __restrict__ sigma,
+                                                                 int64_t n, OccDev m) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = nsim_lane();
+  bool ok = i < n;
+  float px = 0.f, py = 0.f, pz = 0.f, v = 0.f;
+  int64_t k = 0;
+  if (ok) {
+    if (x) {
+      px = x[3 * i]; py = x[3 * i + 1]; pz = x[3 * i + 2];
+      k = slice[i];
+    } else {
+      const int64_t r = ridx[i];
+      const float tt = t[i];
+      px = rays_o[3 * r] + tt * rays_d[3 * r];
+      py = rays_o[3 * r + 1] + tt * rays_d[3 * r + 1];
+      pz = rays_o[3 * r + 2] + tt * rays_d[3 * r + 2];
+      k = slice[r];
+    }
+    v = fmaxf(sigma[i], 0.f);
+    if (!(v == v)) v = 0.f;
+    ok = k >= 0 && k < K;               // (a slice outside the grids is dropped, never written)
+  }
+  int64_t flat = -1 - lane;
+  if (ok) {
+    int64_t f;
+    ok = occ_voxel(m, px, py, pz, f);
+    if (ok) flat = k * stride + f;
+  }
+  if (!ok) v = 0.f;
+  const int64_t pk = wave_shfl(flat, lane - 1);
+  const unsigned long long heads = wave_ballot(lane == 0 || pk != flat);
+  const unsigned long long below = heads & ((2ull << lane) - 1ull);
+  const int run_start = 63 - __builtin_clzll(below);
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const float o = wave_shfl(v, lane - d);
+    if (lane - d >= run_start) v = fmaxf(v, o);
+  }
+  const bool last = lane == 63 || ((heads >> (lane + 1)) & 1ull);
+  if (!ok || !last) return;
+  if (val[flat] >= v) return;
+  int iv;
+  memcpy(&iv, &v, 4);
+  atomicMax((int*)val + flat, iv);
+}
+
+// k_occ_partial_sum / k_occ_pack_bits_mean for all K slices in one launch each (blockIdx.y = slice): the same sums in the same
+// order, so a slice's threshold equals that of a single grid holding its values.  Slice k: values val + k stride, words
+// bits + k ceil(nvox / 32), workspace ws + 65 k (64 partial sums, then the threshold used).
+__global__ void __launch_bounds__(256) k_occ_partial_sum_sliced(const float* __restrict__ val, int64_t stride, int64_t nvox,
+                                                                 float* __restrict__ ws) {
+  __shared__ float sh[4];
+  const float* vk = val + (int64_t)blockIdx.y * stride;
+  float s = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvox; i += (int64_t)gridDim.x * blockDim.x) s += vk[i];
+  s = wave_sum(s);
+  if (nsim_lane() == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) ws[(int64_t)blockIdx.y * (OCC_MEAN_BLOCKS + 1) + blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+__global__ void __launch_bounds__(256) k_occ_pack_bits_mean_sliced(const float* __restrict__ val, int64_t stride, int64_t nvox,
+                                                                    float occ_thre, int consider_mean, float* __restrict__ ws,
+                                                                    uint32_t* __restrict__ bits) {
+  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t k = blockIdx.y;
+  const float* vk = val + k * stride;
+  float* wk = ws + k * (OCC_MEAN_BLOCKS + 1);
+  float thre = occ_thre;
+  if (consider_mean) {
+    float s = 0.f;
+    for (int b = 0; b < OCC_MEAN_BLOCKS; ++b) s += wk[b];
+    thre = fminf(occ_thre, s / (float)nvox);
+  }
+  const int64_t nwords = (nvox + 31) / 32;
+  if (w == 0) wk[OCC_MEAN_BLOCKS] = thre;      // (word 64 of the slice's workspace: no thread reads it)
+  if (w >= nwords) return;
+  uint32_t b = 0;
+  for (int q = 0; q < 32; ++q) {
+    const int64_t vx = w * 32 + q;
+    if (vx < nvox && vk[vx] > thre) b |= (1u << q);      // (padding bits of the last word are never set)
+  }
+  bits[k * nwords + w] = b;
+}
+
 // ================================================================================== C ABI
 static int nerf_meta_check(const NsimDistantMeta* m) {
   if (!m) return 20;
@@ -1643,6 +2190,185 @@ int nsim_occ_pack_bits_mean(const float* val, int64_t nvox, float occ_thre, int 
   }
   hipLaunchKernelGGL(k_occ_pack_bits_mean, dim3(nsim_blocks((nvox + 31) / 32, 256)), dim3(256), 0, (hipStream_t)stream, val,
                      nvox, occ_thre, consider_mean, workspace, bits, workspace + OCC_MEAN_BLOCKS);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------ dynamic-only EmerNeRF
+static DynArgs dyn_args(const NsimNgpMeta* meta) {
+  DynArgs a = DynArgs();
+  a.lay = dyn_layout(meta->precision);
+  a.NL = meta->lotd.num_levels;
+  a.F = 2 * a.NL;
+  a.n_active = (meta->lotd.n_active_levels > 0 && meta->lotd.n_active_levels < a.NL) ? meta->lotd.n_active_levels : a.NL;
+  a.NA = meta->n_appear;
+  return a;
+}
+
+int64_t nsim_dyn_wpack_bytes(const NsimNgpMeta* meta) {
+  if (ngp_meta_check(meta)) return -1;
+  return dyn_layout(meta->precision).total;
+}
+
+int nsim_dyn_pack_weights(const NsimNgpMeta* meta, const float* den_w, const float* den_b, const float* rad_w,
+                          const float* rad_b, void* wpack, void* stream) {
+  const int rc = ngp_meta_check(meta);
+  if (rc) return rc;
+  if (!den_w || !den_b || !rad_w || !rad_b || !wpack) return 4;
+  const NgpLayout L = dyn_layout(meta->precision);
+  const PackShape sh = pack_shape(Y_MCOUNT, kYUo, kYUi);
+  const int64_t total = pack_elems(sh, Y_MCOUNT, (int64_t)YV_COUNT * 64);
+  hipLaunchKernelGGL(k_dyn_pack, dim3(nsim_blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, L, sh,
+                     2 * meta->lotd.num_levels, meta->n_appear, den_w, den_b, rad_w, rad_b, (char*)wpack);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_dyn_fwd(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* rays_d,
+                 const int64_t* ridx, const float* h_appear, int64_t S, float step, float* sigma, float* alpha, float* rgb,
+                 void* stream) {
+  const int rc = ngp_meta_check(meta);
+  if (rc) return rc;
+  if (S <= 0) return 0;
+  if (!wpack || !sigma) return 4;
+  if (!h_planes) return 28;
+  if (rgb && !(rays_d && ridx)) return 25;
+  DynArgs a = dyn_args(meta);
+  a.wpack = (const char*)wpack;
+  a.h_pl = h_planes;
+  a.PS = plane_pitch > 0 ? plane_pitch : S;
+  a.rays_d = rays_d; a.ridx = ridx; a.h_appear = h_appear;
+  a.S = S; a.step = step;
+  a.sigma = sigma; a.alpha = alpha; a.rgb = rgb;
+  const size_t shmem = meta->precision == 0 ? (size_t)((a.lay.fwd_end + 15) & ~15) : 0;
+  const int64_t tiles = (S + 31) / 32;
+  int64_t nb = (tiles + DYN_WAVES - 1) / DYN_WAVES;
+  nb = nb > 512 ? 512 : (nb < 1 ? 1 : nb);       // persistent workgroups: 38 KB of LDS each, two per CU
+  const dim3 grid((unsigned)nb), block(64 * DYN_WAVES);
+  if (meta->precision == 0) hipLaunchKernelGGL((k_dyn<0, 0>), grid, block, shmem, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((k_dyn<1, 0>), grid, block, shmem, (hipStream_t)stream, a);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_dyn_bwd(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* rays_d,
+                 const int64_t* ridx, const float* h_appear, int64_t S, float step, const float* sigma_fwd, const float* rgb_fwd,
+                 const float* dsigma, const float* dalpha, const float* drgb, float* dh_planes, float* dden_w, float* dden_b,
+                 float* drad_w, float* drad_b, float* dh_appear, void* stream) {
+  const int rc = ngp_meta_check(meta);
+  if (rc) return rc;
+  if (S <= 0) return 0;
+  if (!wpack || !h_planes || !sigma_fwd) return 28;
+  if (drgb && !(rays_d && ridx && rgb_fwd)) return 25;
+  if (!dden_w || !dden_b || (drgb && (!drad_w || !drad_b))) return 26;
+  DynArgs a = dyn_args(meta);
+  a.wpack = (const char*)wpack;
+  a.h_pl = h_planes;
+  a.PS = plane_pitch > 0 ? plane_pitch : S;
+  a.rays_d = rays_d; a.ridx = ridx; a.h_appear = h_appear;
+  a.S = S; a.step = step;
+  a.sigma_fwd = sigma_fwd; a.rgb_fwd = rgb_fwd;
+  a.dsigma = dsigma; a.dalpha = dalpha; a.drgb = drgb;
+  a.dh_pl = dh_planes;
+  a.dh_appear = dh_appear;
+  const bool priv = meta->precision == 0;
+  const size_t st = priv ? stage_bytes_per_wave<0>() : stage_bytes_per_wave<1>();
+  const size_t acc = (16904 * 4 + 15) & ~15;
+  const size_t vec_bytes = (size_t)((a.lay.mat[0] + 15) & ~15);
+  const size_t shmem = priv ? vec_bytes + DYN_WAVES_BWD * acc + DYN_WAVES_BWD * st : acc + DYN_WAVES_BWD * st;
+  const int64_t tiles = (S + 31) / 32;
+  int64_t nb = (tiles + DYN_WAVES_BWD - 1) / DYN_WAVES_BWD;
+  nb = nb > 256 ? 256 : (nb < 1 ? 1 : nb);       // one workgroup per CU (154 KB of LDS in fp16 mode)
+  const int F = 2 * meta->lotd.num_levels, K1 = 80 + meta->n_appear;
+  const int64_t n[4] = {64 * F + 65 * 64, 129, drgb ? 64 * K1 + 4096 + 192 : 0, drgb ? 131 : 0};
+  const int64_t n_all = n[0] + n[1] + n[2] + n[3];
+  int R = 1;
+  float* sc = nsim_grad_scratch_acquire(stream, n_all, nb, &R);
+  if (sc) {        // workgroup b adds into replica b % R of the registered scratch, folded below
+    a.dst[0] = sc; a.dst[1] = sc + n[0]; a.dst[2] = sc + n[0] + n[1]; a.dst[3] = sc + n[0] + n[1] + n[2];
+    a.rep_stride = n_all;
+    a.rep_mask = R - 1;
+  } else {
+    a.dst[0] = dden_w; a.dst[1] = dden_b; a.dst[2] = drad_w; a.dst[3] = drad_b;
+    a.rep_stride = 0;
+    a.rep_mask = 0;
+  }
+  const dim3 grid((unsigned)nb), block(64 * DYN_WAVES_BWD);
+  if (priv) hipLaunchKernelGGL((k_dyn<0, 1>), grid, block, shmem, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((k_dyn<1, 1>), grid, block, shmem, (hipStream_t)stream, a);
+  NSIM_CHECK_LAUNCH();
+  if (sc) {
+    nsim_grad_scratch_fold(sc, R, n_all, n[0], n[1], dden_w, dden_b, stream);
+    if (drgb) nsim_grad_scratch_fold(sc + n[0] + n[1], R, n_all, n[2], n[3], drad_w, drad_b, stream);
+    NSIM_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+int nsim_dyn_time(const float* keyframes, const float* codes, int T, const float* ts, int64_t n, int64_t words_per_slice,
+                  float* w, int64_t* slice, int64_t* word_off, void* stream) {
+  if (n <= 0) return 0;
+  if (!keyframes || !ts || T < 1) return 4;
+  if (w && !codes) return 4;
+  hipLaunchKernelGGL(k_dyn_time, dim3(nsim_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, keyframes, codes, T, ts, n,
+                     words_per_slice, w, slice, word_off);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_dyn_points(const float* x, const float* rays_o, const float* rays_d, const float* t, const int64_t* ridx,
+                    const float* w, int64_t S, float* x4, void* stream) {
+  if (S <= 0) return 0;
+  if (!w || !x4) return 4;
+  if (!x && !(rays_o && rays_d && t && ridx)) return 24;
+  hipLaunchKernelGGL(k_dyn_points, dim3(nsim_blocks(S, 256)), dim3(256), 0, (hipStream_t)stream, x, rays_o, rays_d, t, ridx, w,
+                     S, x4);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_occ_update_density_sliced(float* val, int64_t nvox, int64_t slice_stride, int K, float decay, const float* pts,
+                                   const float* sigma, const int64_t* slice, int64_t n, const NsimOccMeta* meta,
+                                   void* stream) {
+  if (nvox <= 0 || K <= 0) return 0;
+  if (!meta || !val || slice_stride < nvox) return 5;
+  // (one decay of all K slices: the padding between slices, if any, is scaled too and never read)
+  const int64_t span = (int64_t)(K - 1) * slice_stride + nvox;
+  hipLaunchKernelGGL(k_occ_scale, dim3(nsim_blocks(span, 256)), dim3(256), 0, (hipStream_t)stream, val, span, decay);
+  NSIM_CHECK_LAUNCH();
+  if (n <= 0) return 0;
+  if (!pts || !sigma || !slice) return 4;
+  hipLaunchKernelGGL(k_occ_max_density_sliced, dim3(nsim_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, val,
+                     slice_stride, K, pts, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
+                     (const int64_t*)nullptr, slice, sigma, n, occ_dev(meta));
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_occ_collect_density_sliced(float* val, int64_t slice_stride, int K, const float* x, const float* rays_o,
+                                    const float* rays_d, const float* t, const int64_t* ridx, const int64_t* slice,
+                                    const float* sigma, int64_t n, const NsimOccMeta* meta, void* stream) {
+  if (n <= 0 || K <= 0) return 0;
+  if (!meta || !val) return 5;
+  if (!sigma || !slice) return 4;
+  if (!x && !(rays_o && rays_d && t && ridx)) return 24;
+  hipLaunchKernelGGL(k_occ_max_density_sliced, dim3(nsim_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, val,
+                     slice_stride, K, x, rays_o, rays_d, t, ridx, slice, sigma, n, occ_dev(meta));
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_occ_pack_bits_mean_sliced(const float* val, int64_t nvox, int64_t slice_stride, int K, float occ_thre,
+                                   int consider_mean, float* workspace, uint32_t* bits, void* stream) {
+  if (nvox <= 0 || K <= 0) return 0;
+  if (!val || !bits || !workspace || slice_stride < nvox) return 4;
+  if (consider_mean) {
+    hipLaunchKernelGGL(k_occ_partial_sum_sliced, dim3(OCC_MEAN_BLOCKS, K), dim3(256), 0, (hipStream_t)stream, val,
+                       slice_stride, nvox, workspace);
+    NSIM_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(k_occ_pack_bits_mean_sliced, dim3(nsim_blocks((nvox + 31) / 32, 256), K), dim3(256), 0,
+                     (hipStream_t)stream, val, slice_stride, nvox, occ_thre, consider_mean, workspace, bits);
   NSIM_CHECK_LAUNCH();
   return 0;
 }

@@ -1,0 +1,544 @@
+"""Dynamic-only EmerNeRF street model -- host side of csrc/nerf_field.hip's ``k_dyn`` kernels.
+
+Mirrors ``nr3d_lib.models.fields_dynamic.nerf.EmerNeRFOnlyDynamicModel`` as the reference wraps and drives it
+(``EmerNerfStreetOnlyDynamic``, app/models/single/dynamic_nerf.py:93-160; config
+code_multi/configs/exps/fg_neus=permuto_emernerf/with_gtbox.240212.yaml:277-370): a density NeRF over (x, y, z, time) on a 4-D
+permutohedral lattice with a time-sliced occupancy grid.  The implementation lives in the absent nr3d_lib: the semantics are
+this package's reading of the yaml, recorded in DESIGN.md sec. 7; tests/dynamic_nerf_ref.py is the executable spec.
+
+All arithmetic runs in HIP kernels: the lattice gather / scatter of csrc/permuto.hip (``nsim_permuto_gather_pts`` /
+``_scatter_pts``), the occupancy marcher of csrc/sampling.hip with a per-ray word offset, and the fused decoders, the time
+input and the time-sliced occupancy folds of csrc/nerf_field.hip.  This file allocates tensors, sequences launches and defines
+the autograd boundary.
+"""
+from typing import Dict, Optional
+
+import torch
+import torch.nn as nn
+
+from .. import _lib
+from ..graphics import pack_ops as po
+from ..grid_encodings.permuto import PermutoConfig
+from ..model_base import ModelMixin
+from ..spatial import aabb_ray_test
+from .nerf import DensityOccGridAccel
+from .neus import _QueryCfg
+from .permuto_neus import _PermutoFieldEncoding
+
+
+class DynamicDensityOccGridAccel(DensityOccGridAccel):
+    """``accel_cfg{type: occ_grid_dynamic, vox_size | resolution, occ_thre, occ_thre_consider_mean, ema_decay, init_cfg{mode:
+    constant, constant_value}, update_from_net_cfg, update_from_samples_cfg: {}, n_steps_between_update, n_steps_warmup,
+    ts_keyframes}`` (with_gtbox.240212.yaml:339-354): K = len(ts_keyframes) density value grids of one resolution over the
+    model's AABB, one per accelerator keyframe.  ``occ_val`` is [K * n_voxels], ``occ_bits`` [K * ceil(n_voxels / 32)]; a ray
+    marches the slice whose keyframe is nearest to its time (``ray_word_off``).  Slice by slice it behaves as K independent
+    ``DensityOccGridAccel``s, each fed that slice's points."""
+
+    def __init__(self, aabb, ts_keyframes, **kw):
+        dev = kw.pop("device", None)
+        super().__init__(aabb, **kw)
+        ts = torch.as_tensor(ts_keyframes, dtype=torch.float32).detach().reshape(-1).clone()
+        assert ts.numel() >= 1 and bool((ts[1:] > ts[:-1]).all()), "accelerator keyframes must ascend"
+        self.K = int(ts.numel())
+        self.nvox = self.resolution[0] * self.resolution[1] * self.resolution[2]
+        self.words_per_slice = (self.nvox + 31) // 32
+        self.register_buffer("ts_keyframes", ts)
+        self.register_buffer("occ_val", torch.zeros(self.K * self.nvox, dtype=torch.float32))
+        self.register_buffer("occ_bits", torch.full([self.K * self.words_per_slice], -1, dtype=torch.int32))
+        self.register_buffer("occ_thre_dev", torch.full([self.K], self.occ_thre, dtype=torch.float32))
+        self.register_buffer("_mean_ws", torch.zeros([65 * self.K], dtype=torch.float32), persistent=False)
+        if dev is not None:
+            self.to(dev)
+
+    # ------------------------------------------------------------------ slices
+    def _time_call(self, ts, slice_out, off_out):
+        ts = ts.detach().float().reshape(-1).contiguous()
+        _lib.call("nsim_dyn_time", _lib.ptr(self.ts_keyframes), None, self.K, _lib.ptr(ts), ts.shape[0],
+                  self.words_per_slice, None, _lib.ptr(slice_out), _lib.ptr(off_out))
+
+    def slice_of(self, ts: torch.Tensor) -> torch.Tensor:
+        """int64 [n]: the accelerator keyframe nearest to each time (a tie to the lower index, the ends clamp)."""
+        out = torch.empty([ts.numel()], dtype=torch.long, device=self.occ_val.device)
+        self._time_call(ts, out, None)
+        return out
+
+    def ray_word_off(self, ts: torch.Tensor) -> torch.Tensor:
+        """int64 [n]: ``slice_of(ts) * words_per_slice``, the marcher's per-ray word offset into ``occ_bits``."""
+        out = torch.empty([ts.numel()], dtype=torch.long, device=self.occ_val.device)
+        self._time_call(ts, None, out)
+        return out
+
+    def _occupied(self) -> torch.Tensor:
+        """bool [K, n_voxels] in storage order: the bits the marcher reads."""
+        sh = torch.arange(32, dtype=torch.int32, device=self.occ_bits.device)
+        b = ((self.occ_bits.view(self.K, -1, 1) >> sh) & 1).bool()
+        return b.reshape(self.K, -1)[:, :self.nvox]
+
+    @property
+    def occ_grid(self) -> torch.Tensor:
+        r = self.resolution
+        return self._occupied().view(self.K, r[2], r[1], r[0]).permute(0, 3, 2, 1)
+
+    def frac_occupied(self, per_slice: bool = False):
+        f = self._occupied().float().mean(dim=1)
+        return f if per_slice else float(f.mean())
+
+    def set_all_occupied(self):
+        self.occ_val.fill_(max(self.constant_value, 2.0 * self.occ_thre, 1e-30))
+        self.occ_bits.fill_(-1)
+        self._clear_padding()
+
+    def _clear_padding(self):
+        """``fill_(-1)`` sets the padding bits of a slice's last word as well: they are never set."""
+        tail = self.nvox & 31
+        if tail:
+            self.occ_bits.view(self.K, -1)[:, -1] = (1 << tail) - 1
+
+    def pack_bits(self):
+        _lib.call("nsim_occ_pack_bits_mean_sliced", _lib.ptr(self.occ_val), self.nvox, self.nvox, self.K, self.occ_thre,
+                  int(self.occ_thre_consider_mean), _lib.ptr(self._mean_ws), _lib.ptr(self.occ_bits))
+        self.occ_thre_dev = self._mean_ws.view(self.K, 65)[:, 64].clone()
+
+    @torch.no_grad()
+    def update_from_samples(self, pts, sigma, slices, pack=True):
+        """Every slice decays once (val * ema_decay); point i is max-folded into slice ``slices[i]``."""
+        pts = pts.detach().float().contiguous()
+        sigma = sigma.detach().float().contiguous()
+        slices = slices.detach().long().contiguous()
+        _lib.call("nsim_occ_update_density_sliced", _lib.ptr(self.occ_val), self.nvox, self.nvox, self.K, self.ema_decay,
+                  _lib.ptr(pts), _lib.ptr(sigma), _lib.ptr(slices), pts.shape[0], self.meta)
+        if pack:
+            self.pack_bits()
+
+    def update_from_net(self, query_density, num_steps=None, num_pts=None, generator=None):
+        """``update_from_net_cfg{num_steps, num_pts}``: per step ``draw_points(num_pts)`` and a random slice per point from
+        the same generator; the density is queried at (pts, ts_keyframes[slice])."""
+        if self.update_from_samples_cfg is not None and self.sync_values is not None:
+            self.sync_values(self.occ_val)
+        dev = self.occ_val.device
+        for _ in range(num_steps or self.num_steps):
+            n = num_pts or self.num_pts
+            pts = self.draw_points(n, generator)
+            k = torch.randint(self.K, [n], device=dev, generator=generator)
+            self.update_from_samples(pts, query_density(pts, self.ts_keyframes[k]), k, pack=False)
+        self.pack_bits()
+
+    @torch.no_grad()
+    def collect(self, sigma, slices, pts=None, rays=None):
+        """Max-fold the densities of a training step's own samples into their slices (no decay, bits untouched): ``pts``
+        [n,3] with ``slices`` [n], or ``rays`` = (rays_o, rays_d, t, ridx) with ``slices`` per ray."""
+        o, d, t, ridx = rays if rays is not None else (None, None, None, None)
+        _lib.call("nsim_occ_collect_density_sliced", _lib.ptr(self.occ_val), self.nvox, self.K, _lib.ptr(pts), _lib.ptr(o),
+                  _lib.ptr(d), _lib.ptr(t), _lib.ptr(ridx), _lib.ptr(slices.detach().long().contiguous()),
+                  _lib.ptr(sigma.detach().float().contiguous()), sigma.shape[0], self.meta)
+
+    def init(self, query_density=None, logger=None, **kw):
+        """``init_cfg{mode: constant, constant_value}``: every slice holds the constant and is fully occupied."""
+        self.occ_val.fill_(self.constant_value)
+        self.occ_bits.fill_(-1)
+        self._clear_padding()
+        self.occ_thre_dev = torch.full_like(self.occ_thre_dev, min(self.occ_thre, self.constant_value)
+                                            if self.occ_thre_consider_mean else self.occ_thre)
+
+
+class _DynFn(torch.autograd.Function):
+    """(table, den_w, den_b, rad_w, rad_b, h_appear) -> (sigma [S], alpha [S] [, rgb [S,3]]) at the lattice points x4 [S,4]:
+    level-major lattice gather, then the fused decoders on the planes."""
+
+    @staticmethod
+    def forward(ctx, model, grid, den_w, den_b, rad_w, rad_b, h_appear, x4, rays_d, ridx, step, with_rgb):
+        dev = grid.device
+        S = x4.shape[0]
+        grid16, wpack = model._shadow()
+        need_bwd = any(ctx.needs_input_grad)
+        h_pl = torch.empty([16, S, 2], dtype=torch.float32, device=dev)
+        _lib.call("nsim_permuto_gather_pts", model.encoding.cfg.pmeta, _lib.ptr(grid16), _lib.ptr(x4), S, _lib.ptr(h_pl))
+        sigma = torch.empty([S], dtype=torch.float32, device=dev)
+        alpha = torch.empty([S], dtype=torch.float32, device=dev)
+        rgb = torch.empty([S, 3], dtype=torch.float32, device=dev) if with_rgb else None
+        ha = h_appear.detach().float().contiguous() if (h_appear is not None and with_rgb and model.n_appear) else None
+        _lib.call("nsim_dyn_fwd", model.meta, _lib.ptr(wpack), _lib.ptr(h_pl), S, _lib.ptr(rays_d if with_rgb else None),
+                  _lib.ptr(ridx if with_rgb else None), _lib.ptr(ha), S, float(step), _lib.ptr(sigma), _lib.ptr(alpha),
+                  _lib.ptr(rgb))
+        if _lib.TIMER is not None:
+            _lib.TIMER.note_units("nsim_dyn_fwd", S)
+        ctx.model, ctx.S, ctx.step, ctx.with_rgb = model, S, float(step), with_rgb
+        ctx.n_active = int(model.meta.lotd.n_active_levels)
+        ctx.ha_shape = h_appear.shape if ha is not None else None
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x4, rays_d, ridx, ha, h_pl if need_bwd else None, sigma, rgb)
+        return (sigma, alpha, rgb) if with_rgb else (sigma, alpha)
+
+    @staticmethod
+    def backward(ctx, g_sigma, g_alpha, g_rgb=None):
+        model = ctx.model
+        x4, rays_d, ridx, ha, h_pl, sigma, rgb = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        n_out = 12
+        if g_sigma is None and g_alpha is None and g_rgb is None:
+            return (None,) * n_out
+        dev, S = sigma.device, ctx.S
+        wpack = model._shadow()[1]
+        F, NA = model.encoding.cfg.out_features, model.n_appear
+        n_dw, n_db, n_rw, n_rb = 64 * F + 65 * 64, 129, 64 * (80 + NA) + 4096 + 192, 131
+        dden_w, dden_b, drad_w, drad_b = _lib.zeros([n_dw + n_db + n_rw + n_rb], device=dev).split([n_dw, n_db, n_rw, n_rb])
+        gs = g_sigma.float().contiguous() if g_sigma is not None else None
+        ga = g_alpha.float().contiguous() if g_alpha is not None else None
+        gr = g_rgb.float().contiguous() if (ctx.with_rgb and g_rgb is not None) else None
+        dha = _lib.zeros(list(ctx.ha_shape), device=dev) if (ha is not None and need[6] and gr is not None) else None
+        dgrid = _lib.zeros([model.encoding.cfg.n_params], device=dev) if need[1] else None
+        dh_pl = torch.empty([16, S, 2], dtype=torch.float32, device=dev) if dgrid is not None else None
+        prev = model._active_levels()           # the backward of a query uses the level mask the query was made with
+        model._set_active_raw(ctx.n_active)
+        try:
+            _lib.call("nsim_dyn_bwd", model.meta, _lib.ptr(wpack), _lib.ptr(h_pl), S, _lib.ptr(rays_d if gr is not None else None),
+                      _lib.ptr(ridx if gr is not None else None), _lib.ptr(ha), S, ctx.step, _lib.ptr(sigma.detach()),
+                      _lib.ptr(rgb.detach()) if rgb is not None else None, _lib.ptr(gs), _lib.ptr(ga), _lib.ptr(gr),
+                      _lib.ptr(dh_pl), _lib.ptr(dden_w), _lib.ptr(dden_b), _lib.ptr(drad_w), _lib.ptr(drad_b), _lib.ptr(dha))
+            if dgrid is not None:
+                valid = torch.ones([S], dtype=torch.uint8, device=dev)
+                _lib.call("nsim_permuto_scatter_pts", model.encoding.cfg.pmeta, _lib.ptr(x4), _lib.ptr(valid), S,
+                          _lib.ptr(dh_pl), _lib.ptr(dgrid))
+        finally:
+            model._set_active_raw(prev)
+        if _lib.TIMER is not None:
+            _lib.TIMER.note_units("nsim_dyn_bwd", S)
+            if dgrid is not None:
+                _lib.TIMER.note_units("nsim_permuto_scatter_pts", S)
+        if gr is None:      # no consumer of the colour: the radiance network is not part of the graph (None, not zeros)
+            drad_w = drad_b = dha = None
+        return (None, dgrid, dden_w, dden_b, drad_w, drad_b, dha) + (None,) * 5
+
+
+class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
+    is_ray_query_supported = True
+    use_ts = True
+    use_view_dirs = True
+
+    @property
+    def ray_query_cfg(self):
+        return self._ray_query_cfg
+
+    @ray_query_cfg.setter
+    def ray_query_cfg(self, cfg):
+        object.__setattr__(self, "_ray_query_cfg", _QueryCfg(cfg or {}))
+
+    def __init__(self, aabb: torch.Tensor = None, ts_keyframes: torch.Tensor = None, seed: int = 42, device=None,
+                 accel_n_jump_frames: int = None, **model_params):
+        """``model_params``: the reference's yaml block verbatim (with_gtbox.240212.yaml:279-360; fields/ref_config.py
+        ``validate_emernerf_params`` names every option the kernels do not cover).  The lattice normalisation, the keyframe
+        codes and the time-sliced occupancy grid need the AABB and the keyframe times: built by ``populate(aabb=,
+        ts_keyframes=)`` (app/models/single/dynamic_nerf.py:153)."""
+        super().__init__()
+        from . import ref_config
+        self._params, self._seed = dict(model_params), int(seed)
+        self._pending_device = device
+        self.cfgd = ref_config.validate_emernerf_params(self._params)
+        self.accel_cfg = _QueryCfg(self.cfgd["accel_cfg"])     # (the asset's populate adds ``ts_keyframes`` here, :150)
+        self.ray_query_cfg = self.cfgd["ray_query_cfg"]
+        self.n_appear = self.cfgd["n_appear"]
+        self._n_jump = accel_n_jump_frames
+        self._built = False
+        if aabb is not None and ts_keyframes is not None:
+            self.populate(aabb=aabb, ts_keyframes=ts_keyframes, device=device)
+
+    def _build(self, aabb: torch.Tensor, ts: torch.Tensor, ts_accel: torch.Tensor):
+        from . import ref_config
+        c = self.cfgd
+        pcfg = PermutoConfig(in_dim=4, **c["permuto_auto_compute_cfg"])
+        self.encoding = _PermutoFieldEncoding(pcfg, c["param_bound"], self._seed)
+        self.encoding.cfg.set_aabb(aabb)        # (x, y, z) normalised by the AABB; the 4th input (time code) as it stands
+        F, NA = self.encoding.cfg.out_features, self.n_appear
+        g = torch.Generator().manual_seed(self._seed + 1)
+
+        def lin(o, i):
+            b = 1.0 / (i ** 0.5)
+            return (torch.rand(o, i, generator=g) * 2 - 1) * b, (torch.rand(o, generator=g) * 2 - 1) * b
+        dw1, db1 = lin(64, F)
+        dw2, db2 = lin(65, 64)
+        rw1, rb1 = lin(64, 80 + NA)
+        rw2, rb2 = lin(64, 64)
+        rw3, rb3 = lin(3, 64)
+        self.den_w = nn.Parameter(torch.cat([dw1.reshape(-1), dw2.reshape(-1)]))
+        self.den_b = nn.Parameter(torch.cat([db1, db2]))
+        self.rad_w = nn.Parameter(torch.cat([rw1.reshape(-1), rw2.reshape(-1), rw3.reshape(-1)]))
+        self.rad_b = nn.Parameter(torch.cat([rb1, rb2, rb3]))
+        T = int(ts.numel())
+        self.register_buffer("ts_keyframes", ts.clone())
+        lo, hi = c["time_range"]
+        self.register_buffer("time_codes", torch.linspace(lo, hi, T, dtype=torch.float32), persistent=False)
+        acc = dict(self.accel_cfg)
+        acc.pop("ts_keyframes", None)
+        ufn = acc.get("update_from_net_cfg") or {}
+        self.accel = DynamicDensityOccGridAccel(
+            aabb, ts_accel, resolution=ref_config.occ_resolution(acc, aabb), occ_thre=float(acc.get("occ_thre", 0.01)),
+            ema_decay=float(acc.get("ema_decay", 0.95)), num_steps=int(ufn.get("num_steps", 4)),
+            num_pts=int(ufn.get("num_pts", 2 ** 20)), n_steps_between_update=int(acc.get("n_steps_between_update", 16)),
+            n_steps_warmup=int(acc.get("n_steps_warmup", 256)), update_from_samples_cfg=acc.get("update_from_samples_cfg", None),
+            init_cfg=acc.get("init_cfg"), occ_thre_consider_mean=bool(acc.get("occ_thre_consider_mean", False)),
+            constant_value=float((acc.get("init_cfg") or {}).get("constant_value", 1.0)))
+        self.accel.init()
+        m = _lib.NgpMeta()
+        m.lotd = self.encoding.cfg.meta         # level count and hardmask of the decoder launches (a stub pyramid)
+        m.precision = {"fp16": 0, "f32": 1}[c["precision"]]
+        m.n_appear = NA
+        self.meta = m
+        self._wpack, self._wpack_versions = None, None
+        self._built = True
+
+    # ------------------------------------------------------------------ reference life cycle
+    def populate(self, aabb: torch.Tensor = None, ts_keyframes: torch.Tensor = None, device=None,
+                 accel_n_jump_frames: int = None, **unused):
+        """``populate(aabb=, ts_keyframes=, device=)`` (app/models/single/dynamic_nerf.py:153).  The accelerator's keyframes are
+        ``accel_cfg['ts_keyframes']`` when the caller put them there (:150), else ``ts_keyframes[::accel_n_jump_frames]``
+        (``populate_cfg.accel_n_jump_frames``, default 2)."""
+        device = device if device is not None else self._pending_device
+        if aabb is not None or ts_keyframes is not None:
+            if aabb is None or ts_keyframes is None:
+                raise AssertionError("the dynamic model is sized from the AABB and the keyframe times: populate(aabb=, ts_keyframes=)")
+            a = torch.as_tensor(aabb, dtype=torch.float32).reshape(2, 3).detach().cpu()
+            ts = torch.as_tensor(ts_keyframes, dtype=torch.float32).reshape(-1).detach().cpu()
+            assert ts.numel() >= 1 and bool((ts[1:] > ts[:-1]).all()), "ts_keyframes must ascend"
+            tsa = self.accel_cfg.get("ts_keyframes", None)
+            if tsa is None:
+                nj = accel_n_jump_frames if accel_n_jump_frames is not None else (self._n_jump if self._n_jump is not None else 2)
+                tsa = ts[::int(nj)]
+            tsa = torch.as_tensor(tsa, dtype=torch.float32).reshape(-1).detach().cpu().contiguous()
+            same = self._built and torch.equal(a, self.accel.aabb.cpu()) and torch.equal(ts, self.ts_keyframes.cpu()) and \
+                torch.equal(tsa, self.accel.ts_keyframes.cpu())
+            if not same:
+                self._build(a, ts, tsa)
+        elif not self._built:
+            raise AssertionError("the dynamic model is sized from the AABB and the keyframe times: populate(aabb=, ts_keyframes=)")
+        if device is not None:
+            self.to(device)
+        return self
+
+    @torch.no_grad()
+    def training_initialize(self, config=None, logger=None, log_prefix=None) -> bool:
+        """No pre-training: the occupancy grid's ``init`` (constant, every slice fully occupied)."""
+        self.accel.init()
+        return False
+
+    def _param_groups(self, cfg: dict):
+        enc = self.encoding
+        enc.shadow()
+        return [dict(name="encoding", params=[enc.flattened_params], shadow16=lambda: enc.shadow()),
+                dict(name="dynamic_decoder", params=[self.den_w, self.den_b]),
+                dict(name="radiance_decoder", params=[self.rad_w, self.rad_b])]
+
+    def _after_optimizer_step(self):
+        self._wpack_versions = None
+
+    def _weight_reg_tensors(self):
+        return [self.den_w, self.rad_w]
+
+    def set_active_levels(self, n: Optional[int]):
+        """Hardmask over the lattice levels: levels >= n give zero features, get no gradient, and their tables are not read."""
+        self.encoding.cfg.set_active_levels(n)
+        self.meta.lotd.n_active_levels = self.encoding.cfg.meta.n_active_levels
+
+    def _active_levels(self) -> int:
+        return int(self.meta.lotd.n_active_levels)
+
+    def _set_active_raw(self, n: int):
+        self.meta.lotd.n_active_levels = n
+        self.encoding.cfg.meta.n_active_levels = n
+        self.encoding.cfg.pmeta.n_active_levels = n
+
+    def training_before_per_step(self, it: int, logger=None):
+        """The occupancy refresh on the ``n_steps_*`` schedule, arming of the sample collection."""
+        if self.accel.update_from_samples_cfg is not None:
+            self.accel.collect_armed = True
+        self.accel.cur_batch__step(int(it), self.query_density, generator=getattr(self, "refresh_generator", None))
+
+    def training_after_per_step(self, it: int, logger=None):
+        pass
+
+    def model_setup(self):
+        self._shadow()
+
+    @property
+    def device(self):
+        return self.den_w.device
+
+    @property
+    def space(self):
+        from ..spatial import AABBSpace
+        a = self.accel.aabb
+        key = (a.data_ptr(), a._version, str(a.device))
+        sp = getattr(self, "_space", None)
+        if sp is None or sp[0] != key:
+            sp = (key, AABBSpace(aabb=a.detach().clone(), device=a.device))
+            object.__setattr__(self, "_space", sp)
+        return sp[1]
+
+    # ------------------------------------------------------------------ kernels' inputs
+    def _shadow(self):
+        """(fp16 table shadow, MFMA-fragment weight pack), refreshed lazily when a parameter changed in place."""
+        grid16 = self.encoding.shadow()
+        vers = (self.den_w._version, self.den_b._version, self.rad_w._version, self.rad_b._version, self.meta.precision,
+                str(self.den_w.device), self.den_w.data_ptr())
+        if self._wpack is None or self._wpack_versions != vers:
+            nbytes = int(_lib.get_lib().nsim_dyn_wpack_bytes(self.meta))
+            if self._wpack is None or self._wpack.numel() != nbytes or self._wpack.device != self.den_w.device:
+                self._wpack = torch.zeros([nbytes], dtype=torch.uint8, device=self.den_w.device)
+            _lib.call("nsim_dyn_pack_weights", self.meta, _lib.ptr(self.den_w.detach()), _lib.ptr(self.den_b.detach()),
+                      _lib.ptr(self.rad_w.detach()), _lib.ptr(self.rad_b.detach()), _lib.ptr(self._wpack))
+            self._wpack_versions = vers
+        return grid16, self._wpack
+
+    def time_coord(self, ts: torch.Tensor) -> torch.Tensor:
+        """w = SeqEmbedding(ts_keyframes, time_codes)(ts, 'interp'): the 4th lattice input of each time (no gradient)."""
+        t = ts.detach().float().reshape(-1).contiguous()
+        w = torch.empty([t.shape[0]], dtype=torch.float32, device=t.device)
+        _lib.call("nsim_dyn_time", _lib.ptr(self.ts_keyframes), _lib.ptr(self.time_codes), int(self.ts_keyframes.shape[0]),
+                  _lib.ptr(t), t.shape[0], 0, _lib.ptr(w), None, None)
+        return w.reshape(ts.shape)
+
+    def _points(self, w, S, x=None, rays=None):
+        o, d, t, ridx = rays if rays is not None else (None, None, None, None)
+        x4 = torch.empty([S, 4], dtype=torch.float32, device=w.device)
+        _lib.call("nsim_dyn_points", _lib.ptr(x), _lib.ptr(o), _lib.ptr(d), _lib.ptr(t), _lib.ptr(ridx), _lib.ptr(w), S,
+                  _lib.ptr(x4))
+        return x4
+
+    def _step(self, cfg: dict = None) -> float:
+        qp = (cfg or {}).get("query_param", None) or self.ray_query_cfg.get("query_param", {})
+        return float((qp.get("march_cfg") or {}).get("step_size", 0.1))
+
+    # ------------------------------------------------------------------ point queries
+    def forward_density(self, x: torch.Tensor, ts: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """sigma at x [..., 3] (object coordinates) and times ts [...], with gradient to the table and the dynamic decoder."""
+        if x.requires_grad:
+            raise NotImplementedError("x.requires_grad: gradients to positions (pose refinement) are not built for this model")
+        if ts.requires_grad:
+            raise NotImplementedError("ts.requires_grad: gradients to the time input are not built for this model")
+        shape = x.shape[:-1]
+        xf = x.detach().float().reshape(-1, 3).contiguous()
+        S = xf.shape[0]
+        if S == 0:
+            return dict(sigma=torch.zeros(shape, dtype=torch.float32, device=xf.device))
+        w = self.time_coord(ts.expand(shape).reshape(-1))
+        x4 = self._points(w, S, x=xf)
+        sigma, _ = _DynFn.apply(self, self.encoding.flattened_params, self.den_w, self.den_b, self.rad_w, self.rad_b, None,
+                                x4, None, None, self._step(), False)
+        return dict(sigma=sigma.reshape(shape))
+
+    @torch.no_grad()
+    def query_density(self, x: torch.Tensor, ts: torch.Tensor) -> torch.Tensor:
+        return self.forward_density(x, ts)["sigma"]
+
+    def sample_pts_uniform(self, num_pts: int, generator=None) -> Dict[str, torch.Tensor]:
+        """Random points of the AABB at random keyframe times -> ``{'x', 'ts', 'sigma'}`` with gradient."""
+        lo, hi = self.accel.aabb[0], self.accel.aabb[1]
+        x = lo + torch.rand([num_pts, 3], device=self.device, generator=generator) * (hi - lo)
+        ts = self.ts_keyframes[torch.randint(int(self.ts_keyframes.shape[0]), [num_pts], device=self.device, generator=generator)]
+        ret = self.forward_density(x, ts)
+        ret["x"] = ret["net_x"] = x
+        ret["ts"] = ts
+        return ret
+
+    # ------------------------------------------------------------------ rays
+    def ray_test(self, rays_o, rays_d, near=None, far=None, rays_ts: torch.Tensor = None, **extra) -> Dict:
+        """The AABB test; ``rays_ts`` [N] travels through the compaction with the other per-ray inputs."""
+        if rays_ts is None:
+            raise ValueError("rays_ts is missing: a time-conditioned model (use_ts) needs the time of every ray")
+        if rays_ts.requires_grad:
+            raise NotImplementedError("rays_ts.requires_grad: gradients to the time input are not built for this model")
+        return aabb_ray_test(self.accel.aabb, self.accel.meta, rays_o, rays_d, near=near, far=far, rays_ts=rays_ts, **extra)
+
+    def ray_query(self, *, ray_input: dict = None, ray_tested: dict, config=None, return_buffer: bool = True,
+                  return_details: bool = False, render_per_obj_individual: bool = False, with_rgb: bool = None,
+                  with_normal: bool = None, **unused) -> Dict:
+        """``query_mode: march_occ``: the marcher's lattice t_k = near + (k + jitter) step inside the occupied voxels of the
+        slice of each ray's time; every sample's interval is ``step``."""
+        cfg = dict(config or {})
+        mode = cfg.get("query_mode", self.ray_query_cfg.get("query_mode", "march_occ"))
+        if mode != "march_occ":
+            raise NotImplementedError(f"ray_query_cfg.query_mode={mode!r}: march_occ is built")
+        if cfg.get("with_feature_dim", 0):
+            raise NotImplementedError("with_feature_dim > 0: the decoders of this model emit no extra feature channels")
+        with_rgb = cfg.get("with_rgb", True) if with_rgb is None else bool(with_rgb)
+        qp = dict(cfg.get("query_param", None) or self.ray_query_cfg.get("query_param", {}))
+        march = qp.get("march_cfg") or {}
+        step, max_steps = float(march.get("step_size", 0.1)), int(march.get("max_steps", 4096))
+        n_all = None
+        if render_per_obj_individual and ray_input is not None and ray_input.get("rays_o") is not None:
+            n_all = int(ray_input["rays_o"].shape[0])
+
+        def empty(details=None):
+            ret = dict(volume_buffer=dict(type="empty"))
+            if render_per_obj_individual:
+                dev_ = ray_tested["rays_inds"].device
+                z = lambda *sh: torch.zeros([n_all or 0, *sh], dtype=torch.float32, device=dev_)      # noqa: E731
+                ret["rendered"] = dict(mask_volume=z(), depth_volume=z())
+                if with_rgb:
+                    ret["rendered"]["rgb_volume"] = z(3)
+            if return_details:
+                ret["details"] = details or {}
+            return ret
+        R = int(ray_tested["num_rays"])
+        if R == 0:
+            return empty()
+        if ray_tested.get("rays_ts", None) is None:
+            raise ValueError("ray_tested['rays_ts'] is missing: a time-conditioned model (use_ts) needs the time of every ray")
+        for k in ("rays_o", "rays_d", "rays_ts"):
+            if ray_tested[k].requires_grad:
+                raise NotImplementedError(f"ray_tested[{k!r}].requires_grad: gradients to rays and times (pose refinement) are "
+                                          f"not built for this model")
+        o = ray_tested["rays_o"].detach().float().contiguous()
+        d = ray_tested["rays_d"].detach().float().contiguous()
+        ts = ray_tested["rays_ts"].detach().float().reshape(-1).contiguous()
+        near, far = ray_tested["near"].detach().float().contiguous(), ray_tested["far"].detach().float().contiguous()
+        dev = o.device
+        jitter = cfg.get("_jitter", None)
+        if jitter is None:
+            jitter = torch.rand([R], device=dev) if cfg.get("perturb", False) else torch.zeros([R], device=dev)
+        jitter = jitter.float().contiguous()
+        acc = self.accel
+        bits, occm = acc.occ_bits, acc.meta
+        with torch.no_grad():
+            slices = torch.empty([R], dtype=torch.long, device=dev)
+            woff = torch.empty([R], dtype=torch.long, device=dev)
+            acc._time_call(ts, slices, woff)
+            w = self.time_coord(ts)
+            counts = torch.empty([R], dtype=torch.long, device=dev)
+            _lib.call("nsim_march_count", _lib.ptr(o), _lib.ptr(d), _lib.ptr(near), _lib.ptr(far), _lib.ptr(jitter), R,
+                      _lib.ptr(bits), _lib.ptr(woff), occm, step, max_steps, _lib.ptr(counts))
+            pi, total = po.get_pack_infos_from_n(counts, return_total=True)
+            S = int(total.item())                    # host sync: size of the marched set
+            if S == 0:
+                acc.collect_armed = False
+                return empty(dict(march_counts=counts, slices=slices))
+            t = torch.empty([S], dtype=torch.float32, device=dev)
+            _lib.call("nsim_march_emit", _lib.ptr(o), _lib.ptr(d), _lib.ptr(near), _lib.ptr(far), _lib.ptr(jitter), R,
+                      _lib.ptr(bits), _lib.ptr(woff), occm, step, max_steps, _lib.ptr(pi), _lib.ptr(t))
+            ridx = torch.repeat_interleave(torch.arange(R, device=dev), counts, output_size=S)
+            sel = counts.nonzero()[:, 0]
+            x4 = self._points(w, S, rays=(o, d, t, ridx))
+        h_appear = ray_tested.get("rays_h_appear", None) if (with_rgb and self.n_appear) else None
+        if with_rgb and self.n_appear and h_appear is None:
+            raise ValueError("ray_tested['rays_h_appear'] is missing: radiance_cfg.n_appear_embedding is "
+                             f"{self.n_appear}, the radiance decoder reads a per-ray appearance code")
+        outs = _DynFn.apply(self, self.encoding.flattened_params, self.den_w, self.den_b, self.rad_w, self.rad_b, h_appear,
+                            x4, d, ridx, step, bool(with_rgb))
+        sigma, alpha = outs[0], outs[1]
+        if acc.collect_armed:
+            acc.collect(sigma, slices, rays=(o, d, t, ridx))
+            acc.collect_armed = False
+        vb = dict(type="packed", rays_inds_hit=ray_tested["rays_inds"][sel], pack_infos_hit=pi[sel], t=t, sigma=sigma,
+                  opacity_alpha=alpha)
+        if with_rgb:
+            vb["rgb"] = outs[2]
+        ret = dict(volume_buffer=vb)
+        if render_per_obj_individual or cfg.get("_render", False):
+            from .neus import volume_integration
+            ret["rendered"] = volume_integration(alpha, t, outs[2] if with_rgb else None, None, pi,
+                                                 cfg.get("depth_use_normalized_vw", True),
+                                                 rays_inds=ray_tested["rays_inds"] if n_all is not None else None, num_rays=n_all)
+            ret["rendered"].pop("vw", None)
+            ret["rendered"].pop("trans", None)
+        if return_details:
+            ret["details"] = dict(march_counts=counts, ridx=ridx, pack_infos=pi, slices=slices)
+        return ret

@@ -394,3 +394,100 @@ def validate_nerf_params(params: dict) -> Dict:
 def nerf_lod_res(cfgd: dict, aabb) -> Tuple[list, int]:
     """The 3-D pyramid of a validated NeRF block: ``lod_res_from_encoding_cfg`` on its (level-capped) auto-compute block."""
     return lod_res_from_encoding_cfg(dict(lotd_auto_compute_cfg=cfgd["auto"], lotd_use_cuboid=cfgd["cuboid"]), aabb)
+
+
+EMERNERF_REFERENCE_KEYS = {"dtype", "precision", "n_geometry_feat", "n_semantic_feat", "time_embedding_cfg", "dynamic_encoding_cfg",
+                           "dynamic_decoder_cfg", "use_flow_field", "use_flow_in_obj", "flow_encoding_cfg", "flow_decoder_cfg",
+                           "use_shadow", "shadow_cfg", "radiance_cfg", "density_activation", "accel_cfg", "ray_query_cfg",
+                           "use_tcnn_backend", "static_encoding_cfg", "static_decoder_cfg"}
+
+
+def validate_emernerf_params(params: dict) -> Dict:
+    """Reference ``model_params`` of ``EmerNeRFOnlyDynamicModel`` (fg_neus=permuto_emernerf/with_gtbox.240212.yaml:279-360) ->
+    the settings ``fields/dynamic_nerf.py`` builds from.  Every option the kernels of csrc/nerf_field.hip do not cover raises
+    ``NotImplementedError`` naming the key."""
+    p = dict(params)
+    unknown = set(p) - EMERNERF_REFERENCE_KEYS
+    if unknown:
+        raise TypeError(f"EmerNeRFOnlyDynamicModel: unexpected model_params {sorted(unknown)}")
+    if p.get("use_tcnn_backend", False):
+        _unsupported("use_tcnn_backend", True, "there is no tiny-cuda-nn here; the decoders are HIP MFMA kernels")
+    for k in ("static_encoding_cfg", "static_decoder_cfg"):
+        if p.get(k) is not None:
+            _unsupported(k, p[k], "the full EmerNeRFModel (static + dynamic branches) is not built; the dynamic-only model has no "
+                                  "static branch")
+    if p.get("use_flow_field", False):
+        _unsupported("use_flow_field", True, "the flow field (and the flow loss) is not built")
+    if p.get("use_shadow", False):
+        _unsupported("use_shadow", True, "the shadow head is not built")
+    if int(p.get("n_semantic_feat", 0) or 0) > 0:
+        _unsupported("n_semantic_feat", p.get("n_semantic_feat"), "the decoders emit no semantic channels")
+    if int(p.get("n_geometry_feat", 64)) != 64:
+        _unsupported("n_geometry_feat", p.get("n_geometry_feat"), "64 geometry features next to sigma")
+    out: Dict = dict(precision=p.get("precision") or _precision(p.get("dtype", "half")))
+    te = dict(p.get("time_embedding_cfg") or dict(dim=1, learnable=False, weight_init=dict(type="linspace", start=-1, end=1)))
+    if int(te.get("dim", 1)) != 1:
+        _unsupported("time_embedding_cfg.dim", te.get("dim"), "one time coordinate enters the 4-D lattice")
+    if te.get("learnable", False):
+        _unsupported("time_embedding_cfg.learnable", True, "the keyframe codes are a buffer: the time input gets no gradient")
+    wi = dict(te.get("weight_init") or dict(type="linspace", start=-1, end=1))
+    if wi.get("type", "linspace") != "linspace":
+        _unsupported("time_embedding_cfg.weight_init.type", wi.get("type"), "linspace")
+    out["time_range"] = (float(wi.get("start", -1.0)), float(wi.get("end", 1.0)))
+    enc = dict(p.get("dynamic_encoding_cfg") or {})
+    if enc.get("type", "permuto") != "permuto":
+        _unsupported("dynamic_encoding_cfg.type", enc.get("type"), "permuto (the 4-D permutohedral lattice)")
+    ac = _plain(dict((enc.get("param") or {}).get("permuto_auto_compute_cfg") or {}))
+    if ac.get("type", "multi_res") != "multi_res":
+        _unsupported("dynamic_encoding_cfg.param.permuto_auto_compute_cfg.type", ac.get("type"), "multi_res")
+    if int(ac.get("n_feats", 2)) != 2:
+        _unsupported("permuto_auto_compute_cfg.n_feats", ac.get("n_feats"), "2 features per level")
+    if not 1 <= int(ac.get("n_levels", 16)) <= 16:
+        _unsupported("permuto_auto_compute_cfg.n_levels", ac.get("n_levels"), "at most 16 levels (32 decoder input features)")
+    out["permuto_auto_compute_cfg"] = ac
+    out["param_bound"] = float(((enc.get("param") or {}).get("param_init_cfg") or {}).get("bound", 1e-4))
+    dd = dict(p.get("dynamic_decoder_cfg") or {})
+    _check_decoder("dynamic_decoder_cfg", dd, {1})
+    if dd.get("activation", "relu") not in ("relu", dict(type="relu")):
+        _unsupported("dynamic_decoder_cfg.activation", dd.get("activation"), "relu")
+    da = p.get("density_activation") or "trunc_softplus"
+    da = da.get("type") if isinstance(da, dict) else da
+    if da != "trunc_softplus":
+        _unsupported("density_activation", p.get("density_activation"), "trunc_softplus is what the kernels evaluate")
+    rd = dict(p.get("radiance_cfg") or {})
+    _check_decoder("radiance_cfg", rd, {2})
+    if rd.get("use_pos", False):
+        _unsupported("radiance_cfg.use_pos", True, "the radiance kernel has no position input")
+    if rd.get("use_nablas", False):
+        _unsupported("radiance_cfg.use_nablas", True, "a density field has no normals here")
+    de = dict(rd.get("dir_embed_cfg") or dict(type="spherical", degree=4))
+    if not rd.get("use_view_dirs", True) or de.get("type") != "spherical" or int(de.get("degree", 4)) != 4:
+        _unsupported("radiance_cfg.dir_embed_cfg", de, "view directions enter through spherical harmonics of degree 4")
+    out["n_appear"] = int(rd.get("n_appear_embedding", 0) or 0)
+    if out["n_appear"] not in (0, 4):
+        _unsupported("radiance_cfg.n_appear_embedding", rd.get("n_appear_embedding"), "0 or 4 appearance channels")
+    acc = _plain(dict(p.get("accel_cfg") or {}))
+    if acc.get("type", "occ_grid_dynamic") != "occ_grid_dynamic":
+        _unsupported("accel_cfg.type", acc.get("type"), "occ_grid_dynamic")
+    if acc.get("occ_val_fn_cfg") is not None:
+        _unsupported("accel_cfg.occ_val_fn_cfg", acc["occ_val_fn_cfg"], "the occupancy value of a density field is the density")
+    if (acc.get("init_cfg") or {}).get("mode", "constant") != "constant":
+        _unsupported("accel_cfg.init_cfg.mode", acc["init_cfg"].get("mode"), "constant")
+    if acc.get("update_from_samples_cfg"):
+        _unsupported("accel_cfg.update_from_samples_cfg", acc["update_from_samples_cfg"], "{} (every sample is used)")
+    out["accel_cfg"] = acc
+    rq = _plain(p.get("ray_query_cfg") or dict(query_mode="march_occ", query_param=dict(march_cfg=dict(step_size=0.1, max_steps=4096))))
+    if rq.get("query_mode", "march_occ") != "march_occ":
+        _unsupported("ray_query_cfg.query_mode", rq.get("query_mode"), "march_occ")
+    out["ray_query_cfg"] = rq
+    return out
+
+
+def occ_resolution(acc: dict, aabb) -> list:
+    """``accel_cfg.resolution``, or ``vox_size`` turned into one by the street model's rule (``neus_native_kwargs``)."""
+    if "resolution" in acc:
+        r = acc["resolution"]
+        return [int(r)] * 3 if not isinstance(r, (list, tuple)) else [int(v) for v in r]
+    if "vox_size" not in acc:
+        return [64, 64, 64]
+    return [max(1, int(math.ceil(float(aabb[1][i] - aabb[0][i]) / float(acc["vox_size"]) - 1e-6))) for i in range(3)]

@@ -94,7 +94,7 @@ class BufferComposeRenderer(nn.Module):
         return cfg
 
     def ray_query(self, rays_o: torch.Tensor, rays_d: torch.Tensor, *, drawables: List[Drawable],
-                  rays_h_appear: torch.Tensor = None, near=None, far=None, with_rgb: bool = None,
+                  rays_h_appear: torch.Tensor = None, rays_ts: torch.Tensor = None, near=None, far=None, with_rgb: bool = None,
                   with_normal: bool = None, sky_model=None, distant_model=None, distant_cr_id: str = None,
                   return_buffer=False, return_details=False,
                   bypass_ray_query_cfg: Dict[str, dict] = None, render_per_obj_in_scene: bool = False,
@@ -110,7 +110,9 @@ class BufferComposeRenderer(nn.Module):
         ``distant_model``: the 'Distant' class, queried LAST (reference :162-164) on ALL rays in the frame of its
         close-range object ``distant_cr_id`` (default: the first single-model drawable), ``near`` := that object's
         ``far`` on the rays that passed its ray test, rays detached (reference :506-531); its batched [N, K] buffer joins
-        the collect as one pack of K per ray (:598-606)."""
+        the collect as one pack of K per ray (:598-606).
+        ``rays_ts`` [N]: the time of every ray, handed to the ``ray_test`` of time-conditioned models (``model.use_ts``: the
+        'Dynamic' class) only; every other model is queried as without it."""
         assert rays_o.dim() == rays_d.dim() == 2
         cfgd = self.config
         with_rgb = cfgd.get("with_rgb", True) if with_rgb is None else with_rgb
@@ -178,7 +180,8 @@ class BufferComposeRenderer(nn.Module):
             else:
                 for dr in grp:
                     o_o, d_o = dr.rays_in_object(rays_o, rays_d)
-                    tested = model.ray_test(o_o, d_o, near=near, far=far, rays_h_appear=rays_h_appear)
+                    ts_kw = dict(rays_ts=rays_ts) if getattr(model, "use_ts", False) else {}
+                    tested = model.ray_test(o_o, d_o, near=near, far=far, rays_h_appear=rays_h_appear, **ts_kw)
                     ind_kw = dict(ray_input=dict(rays_o=o_o, rays_d=d_o), render_per_obj_individual=True) if individual else {}
                     raw = model.ray_query(ray_tested=tested, config=qcfg, return_buffer=True,
                                           return_details=return_details, **ind_kw)

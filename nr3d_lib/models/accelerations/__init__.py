@@ -2,25 +2,23 @@
 from neuralsim_amd.fields.neus import OccGridAccel  # noqa: F401
 OccGridEma = OccGridAccel
 from neuralsim_amd.fields.batched_neus import OccGridAccelBatched  # noqa: F401,E402  (``occ_grid_batched``)
+from neuralsim_amd.fields.dynamic_nerf import DynamicDensityOccGridAccel as OccGridAccelDynamic  # noqa: F401,E402  (``occ_grid_dynamic``)
 
 
 OccGridEmaBatched = OccGridAccelBatched_Ema = OccGridAccelBatched
 
 
 class _NotBuilt:
-    """Dynamic (time-dependent) occupancy grids: names the reference's class-membership tests mention
-    (``accel_cls in accel_types_dynamic``, app/models/single/dynamic_neus.py); never returned by ``get_accel_class`` here."""
-
-
-class OccGridAccelDynamic(_NotBuilt):
-    pass
+    """Batched dynamic occupancy grids: a name the reference's class-membership tests mention
+    (``accel_cls in accel_types_batched_dynamic``); never returned by ``get_accel_class`` here."""
 
 
 class OccGridAccelBatchedDynamic_Ema(_NotBuilt):
     pass
 
 
-# tuples of CLASSES: the reference tests ``get_accel_class(cfg.type) in accel_types_batched`` (batched_neus.py:111, 355)
+# tuples of CLASSES: the reference tests ``get_accel_class(cfg.type) in accel_types_batched`` (batched_neus.py:111, 355) and
+# ``... in accel_types_dynamic`` (app/models/single/dynamic_nerf.py:76-81, 145-150)
 accel_types_single = (OccGridAccel,)
 accel_types_batched = (OccGridAccelBatched,)
 accel_types_dynamic = (OccGridAccelDynamic,)
@@ -34,6 +32,8 @@ def get_accel_class(type: str):
         return OccGridAccel
     if type in _BATCHED_NAMES:
         return OccGridAccelBatched
+    if type == "occ_grid_dynamic":
+        return OccGridAccelDynamic
     raise NotImplementedError(f"accel type {type!r}")
 
 

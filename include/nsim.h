@@ -376,6 +376,15 @@ int nsim_permuto_gather_pts(const NsimPermutoMeta* meta, const void* grid_f16, c
  * points with valid[s] != 0 (the others are skipped before the simplex; their dh rows are never read). */
 int nsim_permuto_scatter_pts(const NsimPermutoMeta* meta, const float* x, const uint8_t* valid, int64_t S,
                              const float* dh_planes, float* dgrid, void* stream);
+/* ... and its backward to the POINTS, for callers whose lattice points are network outputs (positions warped by a predicted
+ * scene flow, EmerNeRF's flow field): dx[s][c] = sum over the active levels and the features of dh_planes[l][s][f] . dh[l][f] /
+ * dx_c for ALL in_dim inputs (inside a simplex the features are affine in x: the derivative of the barycentric weights times the
+ * vertex features).  dh_planes [16][plane_pitch][2] (plane_pitch 0 = S; a caller that gathered several point sets into one buffer
+ * passes the set's first row and the buffer's pitch), dx [S,in_dim] is WRITTEN (one writer per row, no atomics, need not be
+ * zeroed).  valid [S] or NULL (every point): a cleared point gets a zero row, none of its dh rows or table entries is read.
+ * Masked levels (n_active_levels) contribute nothing and their tables are not read. */
+int nsim_permuto_dx_pts(const NsimPermutoMeta* meta, const void* grid_f16, const float* x, const uint8_t* valid, int64_t S,
+                        const float* dh_planes, int64_t plane_pitch, float* dx, void* stream);
 
 /* ------------------------------------------------------- fused NeuS field (LoTD + MLPs, MFMA) */
 /* Network description (host struct).  LoTDNeuSModel = LoTDSDF + RadianceNet
@@ -679,6 +688,38 @@ int nsim_dyn_bwd(const NsimNgpMeta* meta, const void* wpack, const float* h_plan
                  const int64_t* ridx, const float* h_appear, int64_t S, float step, const float* sigma_fwd, const float* rgb_fwd,
                  const float* dsigma, const float* dalpha, const float* drgb, float* dh_planes, float* dden_w, float* dden_b,
                  float* drad_w, float* drad_b, float* dh_appear, void* stream);
+/* The aggregating variants of the with-flow model (EmerNeRF's 1/2, 1/4, 1/4 temporal aggregation): h_planes [16][3S][2] holds, per
+ * level, the features of the S samples, then of their forward-warped, then of their backward-warped neighbours (one
+ * nsim_permuto_gather_pts over the 3S lattice points).  The first density layer runs on each set, the hidden activations are
+ * blended a = 1/2 relu(.) + 1/4 relu(.) + 1/4 relu(.), everything after is nsim_dyn_fwd's.  bwd writes dh_planes [16][3S][2] in the
+ * same layout (for nsim_permuto_scatter_pts over the 3S points and nsim_permuto_dx_pts over the 2S warped ones). */
+int nsim_dyn_fwd_agg(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, const float* rays_d, const int64_t* ridx,
+                     const float* h_appear, int64_t S, float step, float* sigma, float* alpha, float* rgb, void* stream);
+int nsim_dyn_bwd_agg(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, const float* rays_d, const int64_t* ridx,
+                     const float* h_appear, int64_t S, float step, const float* sigma_fwd, const float* rgb_fwd,
+                     const float* dsigma, const float* dalpha, const float* drgb, float* dh_planes, float* dden_w, float* dden_b,
+                     float* drad_w, float* drad_b, float* dh_appear, void* stream);
+/* The scene-flow decoder of the with-flow EmerNeRF model (``flow_decoder_cfg{type: mlp, D: 2, W: 64}``, code_multi/configs/exps/
+ * fg_emernerf/no_gtbox_with_flow.240208.yaml): features of the flow lattice (num_levels <= 16 levels x 2, level-major planes
+ * [16][plane_pitch][2] of nsim_permuto_gather_pts, plane_pitch 0 = S) -> 64 (relu) -> 64 (relu) -> 6 (linear): flow6 [S,6] f32,
+ * columns 0..2 flow_fwd, 3..5 flow_bwd.  The hidden layers run on the MFMA tiles of csrc/mfma_mlp.h (precision 0: fp16 operands,
+ * 1: f32), the six output rows as f32 dot products.  Flat row-major parameters flow_w [64 x 2 num_levels | 64 x 64 | 6 x 64],
+ * flow_b [64 | 64 | 6]; wpack (nsim_flow_wpack_bytes) is written by nsim_flow_pack_weights.
+ * bwd: dflow6 [S,6] -> dflow_w / dflow_b ACCUMULATED (caller-zeroed; through the replicas of nsim_set_grad_scratch when
+ * registered) and dh_planes [16][plane_pitch][2] (rows of the lattice's own levels written; may be NULL) for
+ * nsim_permuto_scatter_pts / nsim_permuto_dx_pts. */
+int64_t nsim_flow_wpack_bytes(int precision);
+int nsim_flow_pack_weights(int num_levels, int precision, const float* flow_w, const float* flow_b, void* wpack, void* stream);
+int nsim_flow_fwd(int num_levels, int precision, const void* wpack, const float* h_planes, int64_t plane_pitch, int64_t S,
+                  float* flow6, void* stream);
+int nsim_flow_bwd(int num_levels, int precision, const void* wpack, const float* h_planes, int64_t plane_pitch, int64_t S,
+                  const float* dflow6, float* dh_planes, float* dflow_w, float* dflow_b, void* stream);
+/* The flow-warped lattice points: x4w [2S,4] = (x + flow_fwd, min(w + delta, code_hi)) | (x + flow_bwd, max(w - delta, code_lo))
+ * from x4 [S,4] (object coordinates and time code, nsim_dyn_points) and flow6 [S,6]; delta = the spacing of the keyframe codes.
+ * bwd: dflow6 [S,6] += the position parts of dx4w [2S,4] (nsim_permuto_dx_pts at the warped points). */
+int nsim_dyn_warp_fwd(const float* x4, const float* flow6, int64_t S, float delta, float code_lo, float code_hi, float* x4w,
+                      void* stream);
+int nsim_dyn_warp_bwd(const float* dx4w, int64_t S, float* dflow6, void* stream);
 /* The time input.  keyframes [T] ascending (the model's ``ts_keyframes`` for w, the accelerator's for the slices), ts [n]:
  *   w [n] (may be NULL) = SeqEmbedding(keyframes, codes)(ts, 'interp') for codes [T] (``time_embedding_cfg{dim: 1}``):
  *     v[i-1] + f (v[i] - v[i-1]) on the interval that holds ts, f clamped to [0,1] (the ends clamp), v[0] when T == 1;
@@ -907,6 +948,19 @@ int nsim_mono_pearson_bwd(const float* pred, const float* gt, const uint8_t* mas
 int nsim_mono_normal_fwd(const float* normals_pred, const float* normals_gt, const uint8_t* mask, const float* rot, int rot_mode,
                          int64_t N, double w_l1, double w_cos, double* ws, float* out, float* g_l1, float* g_cos, void* stream);
 int nsim_mono_scale2_bwd(const float* g0, const float* g1, int64_t n, const float* gout0, const float* gout1, float* d, void* stream);
+/* The scene-flow losses of a with-flow EmerNeRF query (app/loss/flow.py:35-55 FlowLoss.fn_cycle / fn_sparsity; the ``flow`` block of
+ * code_multi/configs/exps/fg_emernerf/no_gtbox_with_flow.240208.yaml) on the four [S,3] tensors flow_fwd, flow_fwd_pred_bwd,
+ * flow_bwd, flow_bwd_pred_fwd (S >= 1), both terms in one launch per direction:
+ *   out[0] = w_cycle 1/2 mean_{S 3}[(sg(flow_fwd) + flow_fwd_pred_bwd)^2 + (sg(flow_bwd) + flow_bwd_pred_fwd)^2]   (sg: stop-gradient)
+ *   out[1] = w_sparsity 1/4 mean_S[|flow_fwd| + |flow_fwd_pred_bwd| + |flow_bwd| + |flow_bwd_pred_fwd|]
+ * f64 sums (per thread, per workgroup, one f64 atomic per workgroup; ws [3] f64 zeroed by the caller, the last workgroup writes
+ * out [2] f32).  bwd recomputes from the inputs: d_* [S,3] written (a NULL d_* is skipped), gout_* the upstream gradients of out[0]
+ * / out[1] on the device (NULL = 0); the gradient of a norm at zero is zero. */
+int nsim_flow_loss_fwd(const float* flow_fwd, const float* flow_fwd_pred_bwd, const float* flow_bwd, const float* flow_bwd_pred_fwd,
+                       int64_t S, double w_cycle, double w_sparsity, double* ws, float* out, void* stream);
+int nsim_flow_loss_bwd(const float* flow_fwd, const float* flow_fwd_pred_bwd, const float* flow_bwd, const float* flow_bwd_pred_fwd,
+                       int64_t S, double w_cycle, double w_sparsity, const float* gout_cycle, const float* gout_sparsity,
+                       float* d_flow_fwd, float* d_flow_fwd_pred_bwd, float* d_flow_bwd, float* d_flow_bwd_pred_fwd, void* stream);
 /* One object's share of the joint rendering: replaces SingleVolumeRenderer._volume_integration_in_total
  * (app/renderers/single_volume_renderer.py:104-120; the ``cr_only`` depth of the mono losses reads it).  Per pack r of the object's
  * buffer (pack_infos [P,2] = begin, count; rays_inds [P]; samples vw_in_total, t [S], rgb / nablas [S,3] or NULL):

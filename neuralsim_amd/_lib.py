@@ -181,6 +181,7 @@ SIGNATURES = {
     "nsim_permuto_dz": [C.POINTER(PermutoMeta), _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P],
     "nsim_permuto_gather_pts": [C.POINTER(PermutoMeta), _P, _P, _I64, _P],
     "nsim_permuto_scatter_pts": [C.POINTER(PermutoMeta), _P, _P, _I64, _P, _P],
+    "nsim_permuto_dx_pts": [C.POINTER(PermutoMeta), _P, _P, _P, _I64, _P, _I64, _P],
     "nsim_field_bwd_rad": [C.POINTER(FieldMeta), _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P],
     "nsim_field_bwd_sdf": [C.POINTER(FieldMeta), _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I64],
     "nsim_lotd_hess_dx": [C.POINTER(LotdMeta), _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P],
@@ -203,6 +204,8 @@ SIGNATURES = {
     "nsim_dyn_pack_weights": [C.POINTER(NgpMeta), _P, _P, _P, _P, _P],
     "nsim_dyn_fwd": [C.POINTER(NgpMeta), _P, _P, _I64, _P, _P, _P, _I64, _F, _P, _P, _P],
     "nsim_dyn_bwd": [C.POINTER(NgpMeta), _P, _P, _I64, _P, _P, _P, _I64, _F] + [_P] * 11,
+    "nsim_dyn_fwd_agg": [C.POINTER(NgpMeta), _P, _P, _P, _P, _P, _I64, _F, _P, _P, _P],
+    "nsim_dyn_bwd_agg": [C.POINTER(NgpMeta), _P, _P, _P, _P, _P, _I64, _F] + [_P] * 11,
     "nsim_dyn_time": [_P, _P, _I, _P, _I64, _I64, _P, _P, _P],
     "nsim_dyn_points": [_P, _P, _P, _P, _P, _P, _I64, _P],
     "nsim_occ_update_density_sliced": [_P, _I64, _I64, _I, _F, _P, _P, _P, _I64, C.POINTER(OccMeta)],
@@ -239,6 +242,13 @@ SIGNATURES = {
     "nsim_mono_pearson_bwd": [_P, _P, _P, _I64, _I64, _D, _I, _D, _P, _P, _P, _P],
     "nsim_mono_normal_fwd": [_P, _P, _P, _P, _I, _I64, _D, _D, _P, _P, _P, _P],
     "nsim_mono_scale2_bwd": [_P, _P, _I64, _P, _P, _P],
+    "nsim_flow_pack_weights": [_I, _I, _P, _P, _P],
+    "nsim_flow_fwd": [_I, _I, _P, _P, _I64, _I64, _P],
+    "nsim_flow_bwd": [_I, _I, _P, _P, _I64, _I64, _P, _P, _P, _P],
+    "nsim_dyn_warp_fwd": [_P, _P, _I64, _F, _F, _F, _P],
+    "nsim_dyn_warp_bwd": [_P, _I64, _P],
+    "nsim_flow_loss_fwd": [_P, _P, _P, _P, _I64, _D, _D, _P, _P],
+    "nsim_flow_loss_bwd": [_P, _P, _P, _P, _I64, _D, _D, _P, _P, _P, _P, _P, _P],
     "nsim_packed_share_fwd": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I, _I, _P, _P, _P, _P],
     "nsim_packed_share_bwd": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "nsim_mse_loss_fwd": [_P, _P, _I64, _P],
@@ -294,6 +304,7 @@ NOSTREAM = {
     "nsim_distant_wpack_bytes": ([C.POINTER(DistantMeta)], _I64),
     "nsim_ngp_wpack_bytes": ([C.POINTER(NgpMeta)], _I64),
     "nsim_dyn_wpack_bytes": ([C.POINTER(NgpMeta)], _I64),
+    "nsim_flow_wpack_bytes": ([_I], _I64),
     "nsim_sky_wpack_bytes": ([C.POINTER(SkyMeta)], _I64),
     "nsim_sky_plane_pitch": ([_I64], _I64),
 }
@@ -426,7 +437,7 @@ def _marshal(args):
 
 
 _GRAD_SCRATCH = {}
-_GRAD_SCRATCH_USERS = ("nsim_field_bwd_rad", "nsim_field_bwd_sdf", "nsim_ngp_bwd", "nsim_dyn_bwd")
+_GRAD_SCRATCH_USERS = ("nsim_field_bwd_rad", "nsim_field_bwd_sdf", "nsim_ngp_bwd", "nsim_dyn_bwd", "nsim_dyn_bwd_agg", "nsim_flow_bwd")
 GRAD_SCRATCH_FLOATS = 16 * 16384      # 16 replicas of the largest decoder gradient (nsim_dyn_bwd: both decoders, 16132 floats)
 
 

@@ -1822,6 +1822,66 @@ __global__ void __launch_bounds__(MONO_BLOCK) k_packed_share_bwd(ShareArgs a, co
   }
 }
 
+// ---------------------------------------------------------------------------------------------- scene-flow losses
+// FlowLoss.fn_cycle / fn_sparsity (app/loss/flow.py:35-55) on the four [S,3] flow tensors of a with-flow EmerNeRF query, both terms
+// in one launch per direction:
+//   cycle    = w_cycle 1/2 mean over S 3 of (sg(flow_fwd) + flow_fwd_pred_bwd)^2 + (sg(flow_bwd) + flow_bwd_pred_fwd)^2
+//   sparsity = w_sparsity 1/4 mean over S of |flow_fwd| + |flow_fwd_pred_bwd| + |flow_bwd| + |flow_bwd_pred_fwd|
+// sg = stop-gradient: the cycle term differentiates the two predictions only.  The gradient of a norm at zero is zero (as torch's).
+// workspace (f64, zero on entry): the two sums, the ticket.
+#define FLOW_WS 3
+struct FlowLossArgs {
+  const float *ff, *fpb, *fb, *bpf;      // flow_fwd, flow_fwd_pred_bwd, flow_bwd, flow_bwd_pred_fwd
+  int64_t S;
+  double s_cycle, s_sparsity;            // w_cycle / (2 S 3), w_sparsity / (4 S)
+};
+
+__device__ __forceinline__ double flow_row(const float* p, int64_t i, double v[3]) {
+  v[0] = (double)p[3 * i], v[1] = (double)p[3 * i + 1], v[2] = (double)p[3 * i + 2];
+  return sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+}
+
+__global__ void __launch_bounds__(MONO_BLOCK) k_flow_loss_fwd(FlowLossArgs a, double* __restrict__ ws, float* __restrict__ out) {
+  double acc[2] = {0.0, 0.0};
+  for (int64_t i = (int64_t)blockIdx.x * MONO_BLOCK + threadIdx.x; i < a.S; i += (int64_t)gridDim.x * MONO_BLOCK) {
+    double ff[3], fpb[3], fb[3], bpf[3];
+    const double n = flow_row(a.ff, i, ff) + flow_row(a.fpb, i, fpb) + flow_row(a.fb, i, fb) + flow_row(a.bpf, i, bpf);
+    double c = 0.0;
+    for (int q = 0; q < 3; ++q) {
+      const double u = ff[q] + fpb[q], v = fb[q] + bpf[q];
+      c += u * u + v * v;
+    }
+    acc[0] += c, acc[1] += n;
+  }
+  acc[0] *= a.s_cycle, acc[1] *= a.s_sparsity;
+  mono_block_sums<2>(acc, ws);
+  if (mono_last_block(reinterpret_cast<unsigned*>(ws + 2))) {
+    out[0] = (float)mono_read(ws);
+    out[1] = (float)mono_read(ws + 1);
+  }
+}
+
+// d_* [S,3] are written (a NULL upstream gradient is 0; a NULL d_* is not wanted)
+__global__ void __launch_bounds__(MONO_BLOCK) k_flow_loss_bwd(FlowLossArgs a, const float* __restrict__ gout_cycle,
+                                                              const float* __restrict__ gout_sparsity, float* __restrict__ d_ff,
+                                                              float* __restrict__ d_fpb, float* __restrict__ d_fb,
+                                                              float* __restrict__ d_bpf) {
+  const double gc = gout_cycle ? 2.0 * a.s_cycle * (double)gout_cycle[0] : 0.0;
+  const double gs = gout_sparsity ? a.s_sparsity * (double)gout_sparsity[0] : 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * MONO_BLOCK + threadIdx.x; i < a.S; i += (int64_t)gridDim.x * MONO_BLOCK) {
+    double ff[3], fpb[3], fb[3], bpf[3];
+    const double nff = flow_row(a.ff, i, ff), nfpb = flow_row(a.fpb, i, fpb), nfb = flow_row(a.fb, i, fb), nbpf = flow_row(a.bpf, i, bpf);
+    const double rff = nff > 0.0 ? gs / nff : 0.0, rfpb = nfpb > 0.0 ? gs / nfpb : 0.0;
+    const double rfb = nfb > 0.0 ? gs / nfb : 0.0, rbpf = nbpf > 0.0 ? gs / nbpf : 0.0;
+    for (int q = 0; q < 3; ++q) {
+      if (d_ff) d_ff[3 * i + q] = (float)(rff * ff[q]);
+      if (d_fpb) d_fpb[3 * i + q] = (float)(gc * (ff[q] + fpb[q]) + rfpb * fpb[q]);
+      if (d_fb) d_fb[3 * i + q] = (float)(rfb * fb[q]);
+      if (d_bpf) d_bpf[3 * i + q] = (float)(gc * (fb[q] + bpf[q]) + rbpf * bpf[q]);
+    }
+  }
+}
+
 extern "C" {
 
 int nsim_mono_sum_f64(const float* x, int64_t n, double* out, void* stream) {
@@ -1994,6 +2054,36 @@ int nsim_packed_share_bwd(const float* vw_in_total, const float* t, const float*
   if (!mask || !depth) return 4;
   hipLaunchKernelGGL(k_packed_share_bwd, dim3(nsim_blocks(P, MONO_BLOCK / 64, 2048)), dim3(MONO_BLOCK), 0, (hipStream_t)stream, a, mask,
                      depth, g_mask, g_depth, g_rgb, g_normals, d_vw, d_rgb, d_nablas);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+static inline int flow_loss_args(FlowLossArgs* a, const float* flow_fwd, const float* flow_fwd_pred_bwd, const float* flow_bwd,
+                                 const float* flow_bwd_pred_fwd, int64_t S, double w_cycle, double w_sparsity) {
+  if (S < 1 || S > ((int64_t)1 << 40)) return 2;
+  if (!flow_fwd || !flow_fwd_pred_bwd || !flow_bwd || !flow_bwd_pred_fwd) return 4;
+  a->ff = flow_fwd, a->fpb = flow_fwd_pred_bwd, a->fb = flow_bwd, a->bpf = flow_bwd_pred_fwd, a->S = S;
+  a->s_cycle = w_cycle / (6.0 * (double)S), a->s_sparsity = w_sparsity / (4.0 * (double)S);
+  return 0;
+}
+
+int nsim_flow_loss_fwd(const float* flow_fwd, const float* flow_fwd_pred_bwd, const float* flow_bwd, const float* flow_bwd_pred_fwd,
+                       int64_t S, double w_cycle, double w_sparsity, double* ws, float* out, void* stream) {
+  FlowLossArgs a;
+  if (int rc = flow_loss_args(&a, flow_fwd, flow_fwd_pred_bwd, flow_bwd, flow_bwd_pred_fwd, S, w_cycle, w_sparsity)) return rc;
+  if (!ws || !out) return 4;
+  hipLaunchKernelGGL(k_flow_loss_fwd, mono_grid(S), dim3(MONO_BLOCK), 0, (hipStream_t)stream, a, ws, out);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_flow_loss_bwd(const float* flow_fwd, const float* flow_fwd_pred_bwd, const float* flow_bwd, const float* flow_bwd_pred_fwd,
+                       int64_t S, double w_cycle, double w_sparsity, const float* gout_cycle, const float* gout_sparsity,
+                       float* d_flow_fwd, float* d_flow_fwd_pred_bwd, float* d_flow_bwd, float* d_flow_bwd_pred_fwd, void* stream) {
+  FlowLossArgs a;
+  if (int rc = flow_loss_args(&a, flow_fwd, flow_fwd_pred_bwd, flow_bwd, flow_bwd_pred_fwd, S, w_cycle, w_sparsity)) return rc;
+  hipLaunchKernelGGL(k_flow_loss_bwd, mono_grid(S), dim3(MONO_BLOCK), 0, (hipStream_t)stream, a, gout_cycle, gout_sparsity, d_flow_fwd,
+                     d_flow_fwd_pred_bwd, d_flow_bwd, d_flow_bwd_pred_fwd);
   NSIM_CHECK_LAUNCH();
   return 0;
 }

@@ -1406,9 +1406,36 @@ __device__ __forceinline__ void dyn_rin_tail(float (&tail)[16], const float vd[3
   }
 }
 
+// features of sample s from the level-major planes (masked and padding levels: zero features, their planes are never read)
+__device__ __forceinline__ void dyn_load_h(const DynArgs& a, int64_t row, bool valid, int hi, float (&h)[16]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int l = 4 * q + 2 * hi + b;
+      float f0 = 0.f, f1 = 0.f;
+      if (valid && l < a.n_active) {
+        const float* hp = a.h_pl + ((int64_t)l * a.PS + row) * 2;
+        f0 = hp[0];
+        f1 = hp[1];
+      }
+      h[4 * q + 2 * b] = f0;
+      h[4 * q + 2 * b + 1] = f1;
+    }
+  }
+}
+
+// EmerNeRF's temporal aggregation (the with-flow model): the hidden layer of the density decoder is blended over the sample and
+// its two flow-warped neighbours, a = 1/2 relu(W1 h(x, w) + b1) + 1/4 relu(W1 h(x+, w+) + b1) + 1/4 relu(W1 h(x-, w-) + b1); the
+// second layer is affine and the weights sum to 1, so this is the weighted mean of the three decoder outputs.
+__device__ __forceinline__ float dyn_agg_weight(int p) { return p == 0 ? 0.5f : 0.25f; }
+
 // BWD = 0: sigma / alpha / rgb.  BWD = 1: recomputes the activations from the saved feature planes and accumulates the weight
 // gradients (per-wave private LDS accumulators in fp16 mode, as k_ngp), dh planes, dh_appear.
-template <int PREC, int BWD>
+// AGG: the three plane sets of a sample lie at rows s, s + S, s + 2S of ONE buffer of pitch PS = 3S; the first layer runs three
+// times, one after the other over the same registers and staging (no LDS beyond the plain kernel's), the backward writes three dh
+// plane sets (pitch 3S).  AGG = false is the kernel as it was: every AGG branch is an ``if constexpr``.
+template <int PREC, int BWD, bool AGG = false>
 __global__ void __launch_bounds__(64 * (BWD ? DYN_WAVES_BWD : DYN_WAVES)) k_dyn(DynArgs a) {
   NSIM_DYN_SMEM(smem);
   constexpr bool PRIV = (PREC == 0 && BWD);
@@ -1494,9 +1521,23 @@ __global__ void __launch_bounds__(64 * (BWD ? DYN_WAVES_BWD : DYN_WAVES)) k_dyn(
     }
     // -------------------------------------------------------------- dynamic (density) decoder
     float a1[32];
-    dense<PREC, 2, 1>(a1, WM + L.mat[Y_D1], h, true);
+    if constexpr (!AGG) {
+      dense<PREC, 2, 1>(a1, WM + L.mat[Y_D1], h, true);
 #pragma unroll
-    for (int k = 0; k < 32; ++k) a1[k] = fmaxf(a1[k] + ngp_vec(W, L, YV_DB1, hi, k), 0.f);
+      for (int k = 0; k < 32; ++k) a1[k] = fmaxf(a1[k] + ngp_vec(W, L, YV_DB1, hi, k), 0.f);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 32; ++k) a1[k] = 0.f;
+#pragma unroll 1
+      for (int p = 0; p < 3; ++p) {
+        float hp_[16], t1[32];
+        dyn_load_h(a, s + p * a.S, valid, hi, hp_);
+        dense<PREC, 2, 1>(t1, WM + L.mat[Y_D1], hp_, true);
+        const float wp = dyn_agg_weight(p);
+#pragma unroll
+        for (int k = 0; k < 32; ++k) a1[k] = a1[k] + wp * fmaxf(t1[k] + ngp_vec(W, L, YV_DB1, hi, k), 0.f);
+      }
+    }
     float raw = 0.f;
 #pragma unroll
     for (int k = 0; k < 32; ++k) raw = raw + ngp_vec(W, L, YV_DWH, hi, k) * a1[k];
@@ -1604,7 +1645,8 @@ __global__ void __launch_bounds__(64 * (BWD ? DYN_WAVES_BWD : DYN_WAVES)) k_dyn(
 #pragma unroll
       for (int k = 0; k < 32; ++k) {
         whv[k] = draw * a1[k];
-        da[k] = a1[k] > 0.f ? da[k] + draw * ngp_vec(W, L, YV_DWH, hi, k) : 0.f;
+        if constexpr (!AGG) da[k] = a1[k] > 0.f ? da[k] + draw * ngp_vec(W, L, YV_DWH, hi, k) : 0.f;
+        else da[k] = da[k] + draw * ngp_vec(W, L, YV_DWH, hi, k);      // (d a: the relu masks are the three passes' own)
       }
       rowsum_acc<PREC, 2, PRIV>(stA, whv, accum + A_DWH, 64);
       {
@@ -1615,6 +1657,7 @@ __global__ void __launch_bounds__(64 * (BWD ? DYN_WAVES_BWD : DYN_WAVES)) k_dyn(
           else atomicAdd(&accum[A_BD], v);
         }
       }
+      if constexpr (!AGG) {
       dw_product<PREC, 2, 1, PRIV>(stA, stB, da, h, accum + A_D1, 32, 64, 32, accum + A_DB1);
       if (a.dh_pl) {
         float dh[16];
@@ -1630,6 +1673,38 @@ __global__ void __launch_bounds__(64 * (BWD ? DYN_WAVES_BWD : DYN_WAVES)) k_dyn(
               float* dp = a.dh_pl + ((int64_t)l * a.S + s) * 2;
               dp[0] = on ? dh[4 * q + 2 * b] : 0.f;
               dp[1] = on ? dh[4 * q + 2 * b + 1] : 0.f;
+            }
+          }
+        }
+      }
+      } else {
+        // the three first-layer passes again, one after the other: pre-activation, its relu mask on the weighted d a, the
+        // weight-gradient product and the pass's dh plane set (row s + p S of pitch 3S)
+#pragma unroll 1
+        for (int p = 0; p < 3; ++p) {
+          float hp_[16], t1[32];
+          dyn_load_h(a, s + p * a.S, valid, hi, hp_);
+          dense<PREC, 2, 1>(t1, WM + L.mat[Y_D1], hp_, true);
+          const float wp = dyn_agg_weight(p);
+#pragma unroll
+          for (int k = 0; k < 32; ++k) t1[k] = (t1[k] + ngp_vec(W, L, YV_DB1, hi, k)) > 0.f ? wp * da[k] : 0.f;
+          dw_product<PREC, 2, 1, PRIV>(stA, stB, t1, hp_, accum + A_D1, 32, 64, 32, accum + A_DB1);
+          if (a.dh_pl) {
+            float dh[16];
+            dense<PREC, 1, 2>(dh, WM + L.mat[Y_D1T], t1, true);
+            if (valid) {
+#pragma unroll
+              for (int q = 0; q < 4; ++q) {
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                  const int l = 4 * q + 2 * hi + b;
+                  if (l >= a.NL) continue;
+                  const bool on = l < a.n_active;
+                  float* dp = a.dh_pl + ((int64_t)l * a.PS + s + p * a.S) * 2;
+                  dp[0] = on ? dh[4 * q + 2 * b] : 0.f;
+                  dp[1] = on ? dh[4 * q + 2 * b + 1] : 0.f;
+                }
+              }
             }
           }
         }
@@ -1672,6 +1747,275 @@ __global__ void __launch_bounds__(64 * (BWD ? DYN_WAVES_BWD : DYN_WAVES)) k_dyn(
       else if (i - A_RB3 < 3) { d = 3; off = 128 + (i - A_RB3); }
       if (d >= 0) atomicAdd(a.dst[d] + rep + off, v);
     }
+  }
+}
+
+// ----------------------------------------------------------------------------------------- scene-flow decoder
+// ``flow_decoder_cfg{type: mlp, D: 2, W: 64}`` of the with-flow EmerNeRF model (code_multi/configs/exps/fg_emernerf/
+// no_gtbox_with_flow.240208.yaml): features of the flow lattice h_f (F = 2 L_f <= 32, level-major planes of
+// nsim_permuto_gather_pts) -> 64 (relu) -> 64 (relu) -> 6 (linear): outputs 0..2 = flow_fwd, 3..5 = flow_bwd.  The two hidden
+// layers run on the 32-unit tiles of mfma_mlp.h; the six output rows are 64-long dot products on the VALU in f32 (per-lane
+// vectors of the pack, as the density row of k_dyn), so the displacements are not rounded to fp16 on the way out.  Flat
+// parameters: flow_w = [W1 64 x F | W2 64 x 64 | W3 6 x 64], flow_b = [b1 64 | b2 64 | b3 6], row-major.
+enum { F_W1 = 0, F_W2, F_W3T, F_W2T, F_W1T, F_MCOUNT };
+enum { FV_B1 = 0, FV_B2, FV_W3, FV_SCAL = FV_W3 + 6, FV_COUNT };
+static_assert(F_MCOUNT <= PACK_MAX_MATS, "PackShape holds the flow decoder's matrices");
+static const int kFUo[F_MCOUNT] = {64, 64, 64, 64, 32};
+static const int kFUi[F_MCOUNT] = {32, 64, 32, 64, 64};
+
+// pack: [vectors | forward matrices (W1, W2) | backward matrices (W3^T padded to 32 inputs, W2^T, W1^T)]
+struct FlowLayout {
+  int64_t mat[F_MCOUNT], vec[FV_COUNT], fwd_end, total;
+  int elt;
+};
+static inline FlowLayout flow_layout(int precision) {
+  FlowLayout L;
+  L.elt = precision == 0 ? 2 : 4;
+  int64_t off = 0;
+  for (int v = 0; v < FV_COUNT; ++v) {
+    L.vec[v] = off;
+    off += 64 * 4;
+  }
+  L.fwd_end = 0;
+  for (int m = 0; m < F_MCOUNT; ++m) {
+    L.mat[m] = off;
+    off += (int64_t)kFUo[m] * kFUi[m] * L.elt;
+    if (m == F_W2) L.fwd_end = off;
+  }
+  L.total = off;
+  return L;
+}
+
+__device__ __forceinline__ float flow_src(int mat, int row, int col, int F, const float* w) {
+  const int w2 = 64 * F, w3 = w2 + 4096;
+  switch (mat) {
+    case F_W1: return col < F ? w[row * F + col] : 0.f;
+    case F_W1T: return row < F ? w[col * F + row] : 0.f;
+    case F_W2: return w[w2 + row * 64 + col];
+    case F_W2T: return w[w2 + col * 64 + row];
+    case F_W3T: return col < 6 ? w[w3 + col * 64 + row] : 0.f;
+  }
+  return 0.f;
+}
+
+__global__ void __launch_bounds__(256) k_flow_pack(FlowLayout L, PackShape sh, int F, const float* __restrict__ flow_w,
+                                                    const float* __restrict__ flow_b, char* __restrict__ wpack) {
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const auto src = [&](int m, int row, int col) { return flow_src(m, row, col, F, flow_w); };
+  if (pack_matrices(sh, F_MCOUNT, L.mat, pack_form(L.elt), wpack, tid, src)) return;
+  if (tid < (int64_t)FV_COUNT * 64) {
+    const int v = (int)(tid >> 6), k = (int)(tid & 63), u = vec_unit(k, 64);
+    float val = 0.f;
+    if (v == FV_B1) val = flow_b[u];
+    else if (v == FV_B2) val = flow_b[64 + u];
+    else if (v < FV_SCAL) val = flow_w[64 * F + 4096 + (v - FV_W3) * 64 + u];
+    else val = k < 6 ? flow_b[128 + k] : 0.f;
+    ((float*)(wpack + L.vec[v]))[k] = val;
+  }
+}
+
+struct FlowArgs {
+  FlowLayout lay;
+  int F, NL, n_active;
+  const char* wpack;
+  int64_t S, PS;                          // points; pitch of h_pl and dh_pl
+  const float* h_pl;                      // [16][PS][2] gathered flow features
+  float* flow6;                           // [S,6] forward output
+  const float* dflow6;                    // [S,6] upstream
+  float* dh_pl;                           // [16][PS][2] hand-off to nsim_permuto_scatter_pts / _dx_pts (may be NULL)
+  float* dst[2];                          // dflow_w, dflow_b -- or replica 0 of the registered scratch
+  int64_t rep_stride;
+  int rep_mask;
+};
+
+#define FLOW_WAVES 4
+#define FLOW_WAVES_BWD 2      // the weight-gradient accumulators are 26.7 KB per private copy
+
+__device__ __forceinline__ float flow_vec(const char* WV, const FlowLayout& L, int v, int hi, int k) {
+  return reinterpret_cast<const float*>(WV + L.vec[v])[hi * 32 + k];
+}
+
+template <int PREC, int BWD>
+__global__ void __launch_bounds__(64 * (BWD ? FLOW_WAVES_BWD : FLOW_WAVES)) k_flow(FlowArgs a) {
+  NSIM_DYN_SMEM(smem);
+  constexpr bool PRIV = (PREC == 0 && BWD);
+  constexpr int NW = BWD ? FLOW_WAVES_BWD : FLOW_WAVES;
+  const int lane = nsim_lane(), j = lane & 31, hi = lane >> 5;
+  const int wave = (int)(threadIdx.x >> 6);
+  const FlowLayout& L = a.lay;
+  const char* W = a.wpack;
+  const char* WM = a.wpack;
+  int wbytes = 0;
+  if constexpr (PREC == 0) {
+    const int64_t nbytes = BWD ? L.mat[0] : L.fwd_end;
+    const int n16 = (int)((nbytes + 15) >> 4);
+    const f16x8* src = reinterpret_cast<const f16x8*>(a.wpack);
+    f16x8* dst = reinterpret_cast<f16x8*>(smem);
+    for (int i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
+    wbytes = n16 << 4;
+    __syncthreads();
+    W = smem;
+    if constexpr (!BWD) WM = smem;
+  }
+  constexpr int A_W1 = 0, A_B1 = 2048, A_W2 = A_B1 + 64, A_B2 = A_W2 + 4096, A_W3 = A_B2 + 64, A_B3 = A_W3 + 384,
+                A_TOTAL = A_B3 + 8;
+  static_assert(A_TOTAL == 6664, "nsim_flow_bwd sizes the LDS from this count");
+  constexpr int ACC_BYTES = (A_TOTAL * 4 + 15) & ~15;
+  float* accum = nullptr;
+  char* stA = nullptr;
+  char* stB = nullptr;
+  if constexpr (BWD) {
+    accum = reinterpret_cast<float*>(smem + wbytes + (PRIV ? wave * ACC_BYTES : 0));
+    char* stbase = smem + wbytes + (PRIV ? NW : 1) * ACC_BYTES + wave * stage_bytes_per_wave<PREC>();
+    stA = stbase;
+    stB = stbase + stage_bytes_per_wave<PREC>() / 2;
+    if constexpr (PRIV) {
+      for (int i = lane; i < A_TOTAL; i += 64) accum[i] = 0.f;
+    } else {
+      for (int i = threadIdx.x; i < A_TOTAL; i += blockDim.x) accum[i] = 0.f;
+    }
+    __syncthreads();
+  }
+  const int64_t ntiles = (a.S + 31) / 32;
+  const int64_t wstride = (int64_t)gridDim.x * NW;
+  for (int64_t tile = (int64_t)blockIdx.x * NW + wave; tile < ntiles; tile += wstride) {
+    const int64_t s = tile * 32 + j;
+    const bool valid = s < a.S;
+    float h[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int l = 4 * q + 2 * hi + b;
+        float f0 = 0.f, f1 = 0.f;
+        if (valid && l < a.n_active) {      // (masked and padding levels: zero features, their planes are never read)
+          const float* hp = a.h_pl + ((int64_t)l * a.PS + s) * 2;
+          f0 = hp[0];
+          f1 = hp[1];
+        }
+        h[4 * q + 2 * b] = f0;
+        h[4 * q + 2 * b + 1] = f1;
+      }
+    }
+    float a1[32], a2[32];
+    dense<PREC, 2, 1>(a1, WM + L.mat[F_W1], h, true);
+#pragma unroll
+    for (int k = 0; k < 32; ++k) a1[k] = fmaxf(a1[k] + flow_vec(W, L, FV_B1, hi, k), 0.f);
+    dense<PREC, 2, 2>(a2, WM + L.mat[F_W2], a1, true);
+#pragma unroll
+    for (int k = 0; k < 32; ++k) a2[k] = fmaxf(a2[k] + flow_vec(W, L, FV_B2, hi, k), 0.f);
+    if constexpr (!BWD) {
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        float o = 0.f;
+#pragma unroll
+        for (int k = 0; k < 32; ++k) o = o + flow_vec(W, L, FV_W3 + c, hi, k) * a2[k];
+        o = o + wave_shfl_xor(o, 32) + reinterpret_cast<const float*>(W + L.vec[FV_SCAL])[c];
+        if (valid && hi == 0) a.flow6[6 * s + c] = o;
+      }
+    } else {
+      // upstream gradient as the first M-tile's units 0..5: unit u < 4 is register u of the lower half-wave, 4 and 5 are
+      // registers 0 and 1 of the upper one (unit_of)
+      float dout[16], g6[6];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dout[r] = 0.f;
+#pragma unroll
+      for (int c = 0; c < 6; ++c) g6[c] = valid ? a.dflow6[6 * s + c] : 0.f;
+      if (hi == 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) dout[c] = g6[c];
+      } else {
+        dout[0] = g6[4];
+        dout[1] = g6[5];
+      }
+      dw_product<PREC, 1, 2, PRIV>(stA, stB, dout, a2, accum + A_W3, 64, 6, 64, accum + A_B3);
+      float da2[32];
+      dense<PREC, 2, 1>(da2, WM + L.mat[F_W3T], dout, true);
+#pragma unroll
+      for (int k = 0; k < 32; ++k) da2[k] = a2[k] > 0.f ? da2[k] : 0.f;
+      dw_product<PREC, 2, 2, PRIV>(stA, stB, da2, a1, accum + A_W2, 64, 64, 64, accum + A_B2);
+      float da1[32];
+      dense<PREC, 2, 2>(da1, WM + L.mat[F_W2T], da2, true);
+#pragma unroll
+      for (int k = 0; k < 32; ++k) da1[k] = a1[k] > 0.f ? da1[k] : 0.f;
+      dw_product<PREC, 2, 1, PRIV>(stA, stB, da1, h, accum + A_W1, 32, 64, 32, accum + A_B1);
+      if (a.dh_pl) {
+        float dh[16];
+        dense<PREC, 1, 2>(dh, WM + L.mat[F_W1T], da1, true);
+        if (valid) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+              const int l = 4 * q + 2 * hi + b;
+              if (l >= a.NL) continue;                      // (the scatter reads the lattice's own levels only)
+              const bool on = l < a.n_active;
+              float* dp = a.dh_pl + ((int64_t)l * a.PS + s) * 2;
+              dp[0] = on ? dh[4 * q + 2 * b] : 0.f;
+              dp[1] = on ? dh[4 * q + 2 * b + 1] : 0.f;
+            }
+          }
+        }
+      }
+    }
+  }
+  if constexpr (BWD) {
+    __syncthreads();
+    const int F = a.F;
+    const int64_t rep = (int64_t)(blockIdx.x & (unsigned)a.rep_mask) * a.rep_stride;
+    for (int i = threadIdx.x; i < A_TOTAL; i += blockDim.x) {
+      float v;
+      if constexpr (PRIV) {
+        constexpr int ACC_FLOATS = ACC_BYTES / 4;
+        const float* a0 = reinterpret_cast<const float*>(smem + wbytes);
+        v = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) v += a0[w * ACC_FLOATS + i];
+      } else {
+        v = accum[i];
+      }
+      if (v == 0.f) continue;
+      int d = -1;
+      int64_t off = 0;
+      if (i < A_B1) {
+        const int row = i >> 5, col = i & 31;
+        if (col < F) { d = 0; off = row * F + col; }
+      } else if (i < A_W2) { d = 1; off = i - A_B1; }
+      else if (i < A_B2) { d = 0; off = 64 * F + (i - A_W2); }
+      else if (i < A_W3) { d = 1; off = 64 + (i - A_B2); }
+      else if (i < A_B3) { d = 0; off = 64 * F + 4096 + (i - A_W3); }
+      else if (i - A_B3 < 6) { d = 1; off = 128 + (i - A_B3); }
+      if (d >= 0) atomicAdd(a.dst[d] + rep + off, v);
+    }
+  }
+}
+
+// warped lattice points of the flow field: x4w [2S,4] = (x + flow_fwd, w+) | (x + flow_bwd, w-) from the lattice points x4 [S,4]
+// (object coordinates: the AABB normalisation is part of the lattice's scale, so a displacement in object coordinates moves the
+// normalised position by flow / half-extent), w+ = min(w + delta, hi), w- = max(w - delta, lo) (the ends clamp, as k_dyn_time does)
+__global__ void __launch_bounds__(256) k_dyn_warp_fwd(const float* __restrict__ x4, const float* __restrict__ flow6, int64_t S,
+                                                       float delta, float lo, float hi, float* __restrict__ x4w) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S) return;
+  const float w = x4[4 * s + 3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float x = x4[4 * s + c];
+    x4w[4 * s + c] = x + flow6[6 * s + c];
+    x4w[4 * (S + s) + c] = x + flow6[6 * s + 3 + c];
+  }
+  x4w[4 * s + 3] = fminf(w + delta, hi);
+  x4w[4 * (S + s) + 3] = fmaxf(w - delta, lo);
+}
+
+// dflow6[s][0..2] += dx4w[s][0..2], dflow6[s][3..5] += dx4w[S + s][0..2] (the time parts carry no gradient)
+__global__ void __launch_bounds__(256) k_dyn_warp_bwd(const float* __restrict__ dx4w, int64_t S, float* __restrict__ dflow6) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S) return;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    dflow6[6 * s + c] = dflow6[6 * s + c] + dx4w[4 * s + c];
+    dflow6[6 * s + 3 + c] = dflow6[6 * s + 3 + c] + dx4w[4 * (S + s) + c];
   }
 }
 
@@ -2302,6 +2646,213 @@ int nsim_dyn_bwd(const NsimNgpMeta* meta, const void* wpack, const float* h_plan
     if (drgb) nsim_grad_scratch_fold(sc + n[0] + n[1], R, n_all, n[2], n[3], drad_w, drad_b, stream);
     NSIM_CHECK_LAUNCH();
   }
+  return 0;
+}
+
+// the aggregating variants (the with-flow model): h_planes [16][3S][2] holds the plane sets of the samples (rows 0..S), of their
+// forward-warped (S..2S) and backward-warped (2S..3S) neighbours; dh_planes is written in the same layout
+int nsim_dyn_fwd_agg(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, const float* rays_d, const int64_t* ridx,
+                     const float* h_appear, int64_t S, float step, float* sigma, float* alpha, float* rgb, void* stream) {
+  const int rc = ngp_meta_check(meta);
+  if (rc) return rc;
+  if (S <= 0) return 0;
+  if (!wpack || !sigma) return 4;
+  if (!h_planes) return 28;
+  if (rgb && !(rays_d && ridx)) return 25;
+  DynArgs a = dyn_args(meta);
+  a.wpack = (const char*)wpack;
+  a.h_pl = h_planes;
+  a.PS = 3 * S;
+  a.rays_d = rays_d; a.ridx = ridx; a.h_appear = h_appear;
+  a.S = S; a.step = step;
+  a.sigma = sigma; a.alpha = alpha; a.rgb = rgb;
+  const size_t shmem = meta->precision == 0 ? (size_t)((a.lay.fwd_end + 15) & ~15) : 0;
+  const int64_t tiles = (S + 31) / 32;
+  int64_t nb = (tiles + DYN_WAVES - 1) / DYN_WAVES;
+  nb = nb > 512 ? 512 : (nb < 1 ? 1 : nb);
+  const dim3 grid((unsigned)nb), block(64 * DYN_WAVES);
+  if (meta->precision == 0) hipLaunchKernelGGL((k_dyn<0, 0, true>), grid, block, shmem, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((k_dyn<1, 0, true>), grid, block, shmem, (hipStream_t)stream, a);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_dyn_bwd_agg(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, const float* rays_d, const int64_t* ridx,
+                     const float* h_appear, int64_t S, float step, const float* sigma_fwd, const float* rgb_fwd,
+                     const float* dsigma, const float* dalpha, const float* drgb, float* dh_planes, float* dden_w, float* dden_b,
+                     float* drad_w, float* drad_b, float* dh_appear, void* stream) {
+  const int rc = ngp_meta_check(meta);
+  if (rc) return rc;
+  if (S <= 0) return 0;
+  if (!wpack || !h_planes || !sigma_fwd) return 28;
+  if (drgb && !(rays_d && ridx && rgb_fwd)) return 25;
+  if (!dden_w || !dden_b || (drgb && (!drad_w || !drad_b))) return 26;
+  DynArgs a = dyn_args(meta);
+  a.wpack = (const char*)wpack;
+  a.h_pl = h_planes;
+  a.PS = 3 * S;
+  a.rays_d = rays_d; a.ridx = ridx; a.h_appear = h_appear;
+  a.S = S; a.step = step;
+  a.sigma_fwd = sigma_fwd; a.rgb_fwd = rgb_fwd;
+  a.dsigma = dsigma; a.dalpha = dalpha; a.drgb = drgb;
+  a.dh_pl = dh_planes;
+  a.dh_appear = dh_appear;
+  const bool priv = meta->precision == 0;
+  const size_t st = priv ? stage_bytes_per_wave<0>() : stage_bytes_per_wave<1>();
+  const size_t acc = (16904 * 4 + 15) & ~15;
+  const size_t vec_bytes = (size_t)((a.lay.mat[0] + 15) & ~15);
+  const size_t shmem = priv ? vec_bytes + DYN_WAVES_BWD * acc + DYN_WAVES_BWD * st : acc + DYN_WAVES_BWD * st;      // (as nsim_dyn_bwd)
+  const int64_t tiles = (S + 31) / 32;
+  int64_t nb = (tiles + DYN_WAVES_BWD - 1) / DYN_WAVES_BWD;
+  nb = nb > 256 ? 256 : (nb < 1 ? 1 : nb);
+  const int F = 2 * meta->lotd.num_levels, K1 = 80 + meta->n_appear;
+  const int64_t n[4] = {64 * F + 65 * 64, 129, drgb ? 64 * K1 + 4096 + 192 : 0, drgb ? 131 : 0};
+  const int64_t n_all = n[0] + n[1] + n[2] + n[3];
+  int R = 1;
+  float* sc = nsim_grad_scratch_acquire(stream, n_all, nb, &R);
+  if (sc) {
+    a.dst[0] = sc; a.dst[1] = sc + n[0]; a.dst[2] = sc + n[0] + n[1]; a.dst[3] = sc + n[0] + n[1] + n[2];
+    a.rep_stride = n_all;
+    a.rep_mask = R - 1;
+  } else {
+    a.dst[0] = dden_w; a.dst[1] = dden_b; a.dst[2] = drad_w; a.dst[3] = drad_b;
+    a.rep_stride = 0;
+    a.rep_mask = 0;
+  }
+  const dim3 grid((unsigned)nb), block(64 * DYN_WAVES_BWD);
+  if (priv) hipLaunchKernelGGL((k_dyn<0, 1, true>), grid, block, shmem, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((k_dyn<1, 1, true>), grid, block, shmem, (hipStream_t)stream, a);
+  NSIM_CHECK_LAUNCH();
+  if (sc) {
+    nsim_grad_scratch_fold(sc, R, n_all, n[0], n[1], dden_w, dden_b, stream);
+    if (drgb) nsim_grad_scratch_fold(sc + n[0] + n[1], R, n_all, n[2], n[3], drad_w, drad_b, stream);
+    NSIM_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------ scene-flow decoder, warp
+static int flow_check(int num_levels, int precision) {
+  if (num_levels < 1 || num_levels > 16) return 42;
+  if (precision != 0 && precision != 1) return 21;
+  return 0;
+}
+
+static FlowArgs flow_args(int num_levels, int precision) {
+  FlowArgs a = FlowArgs();
+  a.lay = flow_layout(precision);
+  a.NL = num_levels;
+  a.F = 2 * num_levels;
+  a.n_active = num_levels;
+  return a;
+}
+
+int64_t nsim_flow_wpack_bytes(int precision) {
+  if (precision != 0 && precision != 1) return -1;
+  return flow_layout(precision).total;
+}
+
+int nsim_flow_pack_weights(int num_levels, int precision, const float* flow_w, const float* flow_b, void* wpack, void* stream) {
+  const int rc = flow_check(num_levels, precision);
+  if (rc) return rc;
+  if (!flow_w || !flow_b || !wpack) return 4;
+  const FlowLayout L = flow_layout(precision);
+  const PackShape sh = pack_shape(F_MCOUNT, kFUo, kFUi);
+  const int64_t total = pack_elems(sh, F_MCOUNT, (int64_t)FV_COUNT * 64);
+  hipLaunchKernelGGL(k_flow_pack, dim3(nsim_blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, L, sh, 2 * num_levels, flow_w,
+                     flow_b, (char*)wpack);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_flow_fwd(int num_levels, int precision, const void* wpack, const float* h_planes, int64_t plane_pitch, int64_t S,
+                  float* flow6, void* stream) {
+  const int rc = flow_check(num_levels, precision);
+  if (rc) return rc;
+  if (S <= 0) return 0;
+  if (!wpack || !flow6) return 4;
+  if (!h_planes) return 28;
+  if (plane_pitch != 0 && plane_pitch < S) return 2;
+  FlowArgs a = flow_args(num_levels, precision);
+  a.wpack = (const char*)wpack;
+  a.h_pl = h_planes;
+  a.PS = plane_pitch > 0 ? plane_pitch : S;
+  a.S = S;
+  a.flow6 = flow6;
+  const size_t shmem = precision == 0 ? (size_t)((a.lay.fwd_end + 15) & ~15) : 0;
+  const int64_t tiles = (S + 31) / 32;
+  int64_t nb = (tiles + FLOW_WAVES - 1) / FLOW_WAVES;
+  nb = nb > 1024 ? 1024 : (nb < 1 ? 1 : nb);     // persistent workgroups: 15 KB of LDS each
+  const dim3 grid((unsigned)nb), block(64 * FLOW_WAVES);
+  if (precision == 0) hipLaunchKernelGGL((k_flow<0, 0>), grid, block, shmem, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((k_flow<1, 0>), grid, block, shmem, (hipStream_t)stream, a);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_flow_bwd(int num_levels, int precision, const void* wpack, const float* h_planes, int64_t plane_pitch, int64_t S,
+                  const float* dflow6, float* dh_planes, float* dflow_w, float* dflow_b, void* stream) {
+  const int rc = flow_check(num_levels, precision);
+  if (rc) return rc;
+  if (S <= 0) return 0;
+  if (!wpack || !h_planes || !dflow6) return 28;
+  if (!dflow_w || !dflow_b) return 26;
+  if (plane_pitch != 0 && plane_pitch < S) return 2;
+  FlowArgs a = flow_args(num_levels, precision);
+  a.wpack = (const char*)wpack;
+  a.h_pl = h_planes;
+  a.PS = plane_pitch > 0 ? plane_pitch : S;
+  a.S = S;
+  a.dflow6 = dflow6;
+  a.dh_pl = dh_planes;
+  const bool priv = precision == 0;
+  const size_t st = priv ? stage_bytes_per_wave<0>() : stage_bytes_per_wave<1>();
+  const size_t acc = (6664 * 4 + 15) & ~15;
+  const size_t vec_bytes = (size_t)((a.lay.mat[0] + 15) & ~15);
+  const size_t shmem = priv ? vec_bytes + FLOW_WAVES_BWD * acc + FLOW_WAVES_BWD * st : acc + FLOW_WAVES_BWD * st;
+  const int64_t tiles = (S + 31) / 32;
+  int64_t nb = (tiles + FLOW_WAVES_BWD - 1) / FLOW_WAVES_BWD;
+  nb = nb > 512 ? 512 : (nb < 1 ? 1 : nb);       // two workgroups per CU (76 KB of LDS in fp16 mode)
+  const int F = 2 * num_levels;
+  const int64_t n[2] = {64 * F + 4096 + 384, 134};
+  const int64_t n_all = n[0] + n[1];
+  int R = 1;
+  float* sc = nsim_grad_scratch_acquire(stream, n_all, nb, &R);
+  if (sc) {        // workgroup b adds into replica b % R of the registered scratch, folded below
+    a.dst[0] = sc; a.dst[1] = sc + n[0];
+    a.rep_stride = n_all;
+    a.rep_mask = R - 1;
+  } else {
+    a.dst[0] = dflow_w; a.dst[1] = dflow_b;
+    a.rep_stride = 0;
+    a.rep_mask = 0;
+  }
+  const dim3 grid((unsigned)nb), block(64 * FLOW_WAVES_BWD);
+  if (priv) hipLaunchKernelGGL((k_flow<0, 1>), grid, block, shmem, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((k_flow<1, 1>), grid, block, shmem, (hipStream_t)stream, a);
+  NSIM_CHECK_LAUNCH();
+  if (sc) {
+    nsim_grad_scratch_fold(sc, R, n_all, n[0], n[1], dflow_w, dflow_b, stream);
+    NSIM_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+int nsim_dyn_warp_fwd(const float* x4, const float* flow6, int64_t S, float delta, float code_lo, float code_hi, float* x4w,
+                      void* stream) {
+  if (S <= 0) return 0;
+  if (!x4 || !flow6 || !x4w) return 4;
+  hipLaunchKernelGGL(k_dyn_warp_fwd, dim3(nsim_blocks(S, 256)), dim3(256), 0, (hipStream_t)stream, x4, flow6, S, delta, code_lo,
+                     code_hi, x4w);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_dyn_warp_bwd(const float* dx4w, int64_t S, float* dflow6, void* stream) {
+  if (S <= 0) return 0;
+  if (!dx4w || !dflow6) return 4;
+  hipLaunchKernelGGL(k_dyn_warp_bwd, dim3(nsim_blocks(S, 256)), dim3(256), 0, (hipStream_t)stream, dx4w, S, dflow6);
+  NSIM_CHECK_LAUNCH();
   return 0;
 }
 

@@ -511,6 +511,43 @@ __global__ void __launch_bounds__(256) k_permuto_dz(PermutoArgs a, float* __rest
   }
 }
 
+// d L / d x of the point-mode planes (nsim_permuto_gather_pts) for callers whose lattice points are themselves network outputs
+// (positions warped by a predicted scene flow): dx[s][c] = sum_levels sum_f dL/dh[l][s][f] . d h[l][f] / d x_c over ALL D inputs,
+// d h / d x_c = sum_r (d bary_r / d x_c) table[v_r] -- the simplex walk of k_permuto_dz with C0 = 0.  One lane per point, the
+// levels in a loop: every dx row has one writer, so nothing is accumulated in memory (no atomics, dx need not be zeroed).  Masked
+// levels (>= n_active) are not visited: their features are zeros whatever x is, their tables are not read.  A point the valid
+// mask clears gets a zero row before any plane or table read.  dh planes [16][PS][2] (PS = the pitch of the caller's buffer).
+template <int D>
+__global__ void __launch_bounds__(256) k_permuto_dx_pts(PermutoArgs a, float* __restrict__ dx) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= a.S) return;
+  float acc[D];
+#pragma unroll
+  for (int c = 0; c < D; ++c) acc[c] = 0.f;
+  if (!a.valid || a.valid[s] != 0) {
+    float x[D];
+    permuto_point<D, false>(a, s, x);
+    for (int l = 0; l < a.pm.n_active; ++l) {
+      Simplex<D> sp;
+      float dB[D + 1][D];
+      permuto_simplex<D, D, true>(x, a.pm.scale[l], a.pm.shift[l], sp, dB);
+      const float* dp = a.dh_pl + ((int64_t)l * a.PS + s) * 2;
+      const float d0 = dp[0], d1 = dp[1];
+      const int64_t base = (int64_t)l * a.pm.T * 2;
+#pragma unroll
+      for (int r = 0; r <= D; ++r) {
+        float g0, g1;
+        permuto_load2(a.grid, base, permuto_vertex<D>(sp, r, a.pm.T), g0, g1);
+        const float w = d0 * g0 + d1 * g1;
+#pragma unroll
+        for (int c = 0; c < D; ++c) acc[c] = acc[c] + dB[r][c] * w;
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < D; ++c) dx[(int64_t)D * s + c] = acc[c];
+}
+
 // ================================================================================== C ABI
 template <int MODE>
 static int permuto_launch_fwd(const NsimPermutoMeta* meta, const PermutoArgs& a, hipStream_t stream) {
@@ -677,6 +714,35 @@ int nsim_permuto_scatter_pts(const NsimPermutoMeta* meta, const float* x, const 
   a.x = x; a.valid = valid; a.S = S;
   a.dh_pl = dh_planes; a.dgrid = dgrid;
   return permuto_launch_bwd<2>(meta, a, (hipStream_t)stream);
+}
+
+int nsim_permuto_dx_pts(const NsimPermutoMeta* meta, const void* grid_f16, const float* x, const uint8_t* valid, int64_t S,
+                        const float* dh_planes, int64_t plane_pitch, float* dx, void* stream) {
+  const int rc = permuto_meta_check(meta);
+  if (rc) return rc;
+  if (meta->num_levels > 16) return 42;
+  if (S <= 0) return 0;
+  if (!grid_f16 || !x || !dh_planes || !dx) return 28;
+  if (plane_pitch != 0 && plane_pitch < S) return 2;
+  PermutoArgs a = PermutoArgs();
+  a.pm = permuto_dev(meta);
+  a.grid = (const f16*)grid_f16;
+  a.x = x; a.valid = valid; a.S = S; a.PS = plane_pitch ? plane_pitch : S;
+  a.dh_pl = dh_planes;
+  const dim3 grid((unsigned)nsim_blocks(S, 256)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  switch (meta->in_dim) {
+    case 2: hipLaunchKernelGGL((k_permuto_dx_pts<2>), grid, block, 0, st, a, dx); break;
+    case 3: hipLaunchKernelGGL((k_permuto_dx_pts<3>), grid, block, 0, st, a, dx); break;
+    case 4: hipLaunchKernelGGL((k_permuto_dx_pts<4>), grid, block, 0, st, a, dx); break;
+    case 5: hipLaunchKernelGGL((k_permuto_dx_pts<5>), grid, block, 0, st, a, dx); break;
+    case 6: hipLaunchKernelGGL((k_permuto_dx_pts<6>), grid, block, 0, st, a, dx); break;
+    case 7: hipLaunchKernelGGL((k_permuto_dx_pts<7>), grid, block, 0, st, a, dx); break;
+    case 8: hipLaunchKernelGGL((k_permuto_dx_pts<8>), grid, block, 0, st, a, dx); break;
+    default: return 41;
+  }
+  NSIM_CHECK_LAUNCH();
+  return 0;
 }
 
 }  // extern "C"

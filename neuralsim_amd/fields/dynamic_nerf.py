@@ -10,6 +10,12 @@ All arithmetic runs in HIP kernels: the lattice gather / scatter of csrc/permuto
 ``_scatter_pts``), the occupancy marcher of csrc/sampling.hip with a per-ray word offset, and the fused decoders, the time
 input and the time-sliced occupancy folds of csrc/nerf_field.hip.  This file allocates tensors, sequences launches and defines
 the autograd boundary.
+
+``use_flow_field: true`` (code_multi/configs/exps/fg_emernerf/no_gtbox_with_flow.240208.yaml:353-371): a second 4-D lattice and a
+flow decoder (``nsim_flow_fwd`` / ``_bwd``) predict the forward / backward scene flow; the density decoder aggregates its hidden
+features over the sample and its two flow-warped neighbours (``nsim_dyn_fwd_agg`` / ``_bwd_agg``), and the gradient reaches the
+flow through the warped lattice points (``nsim_permuto_dx_pts``, ``nsim_dyn_warp_bwd``).  tests/dynamic_flow_ref.py is that
+variant's executable spec.
 """
 from typing import Dict, Optional
 
@@ -210,6 +216,124 @@ class _DynFn(torch.autograd.Function):
         return (None, dgrid, dden_w, dden_b, drad_w, drad_b, dha) + (None,) * 5
 
 
+FLOW_KEYS = ("flow_fwd", "flow_fwd_pred_bwd", "flow_bwd", "flow_bwd_pred_fwd")
+
+
+def _all_valid(n, dev):
+    return torch.ones([n], dtype=torch.uint8, device=dev)
+
+
+class _DynFlowFn(torch.autograd.Function):
+    """The with-flow query (``use_flow_field``): (table, den_w, den_b, rad_w, rad_b, h_appear, flow table, flow_w, flow_b) ->
+    (sigma [S], alpha [S], rgb [S,3] | None, flow6 [S,6], pred6 [2S,6]) at the lattice points x4 [S,4].  Flow at x -> warp -> flow at
+    the 2S warped points -> dynamic gather at the 3S points -> aggregating decoder.  flow6 = (flow_fwd | flow_bwd) at x; pred6 rows
+    0..S are the flow at (x+, w+), rows S..2S at (x-, w-).  The backward carries d loss / d x+- from both lattices into the flow at
+    x (``nsim_permuto_dx_pts`` -> ``nsim_dyn_warp_bwd``); x itself, rays and times get no gradient."""
+
+    @staticmethod
+    def forward(ctx, model, grid, den_w, den_b, rad_w, rad_b, h_appear, fgrid, flow_w, flow_b, x4, rays_d, ridx, step, with_rgb):
+        dev, S = grid.device, x4.shape[0]
+        grid16, wpack = model._shadow()
+        fgrid16, fwpack = model._flow_shadow()
+        fm, dm = model.flow_encoding.cfg.pmeta, model.encoding.cfg.pmeta
+        Lf, prec = int(fm.num_levels), int(model.meta.precision)
+        lo, hi = model.cfgd["time_range"]
+        hf = torch.empty([16, S, 2], dtype=torch.float32, device=dev)
+        _lib.call("nsim_permuto_gather_pts", fm, _lib.ptr(fgrid16), _lib.ptr(x4), S, _lib.ptr(hf))
+        flow6 = torch.empty([S, 6], dtype=torch.float32, device=dev)
+        _lib.call("nsim_flow_fwd", Lf, prec, _lib.ptr(fwpack), _lib.ptr(hf), 0, S, _lib.ptr(flow6))
+        x4all = torch.empty([3 * S, 4], dtype=torch.float32, device=dev)
+        x4all[:S] = x4
+        x4w = x4all[S:]
+        _lib.call("nsim_dyn_warp_fwd", _lib.ptr(x4), _lib.ptr(flow6), S, float(model.time_delta), float(lo), float(hi), _lib.ptr(x4w))
+        hfw = torch.empty([16, 2 * S, 2], dtype=torch.float32, device=dev)
+        _lib.call("nsim_permuto_gather_pts", fm, _lib.ptr(fgrid16), _lib.ptr(x4w), 2 * S, _lib.ptr(hfw))
+        pred6 = torch.empty([2 * S, 6], dtype=torch.float32, device=dev)
+        _lib.call("nsim_flow_fwd", Lf, prec, _lib.ptr(fwpack), _lib.ptr(hfw), 0, 2 * S, _lib.ptr(pred6))
+        h_pl = torch.empty([16, 3 * S, 2], dtype=torch.float32, device=dev)
+        _lib.call("nsim_permuto_gather_pts", dm, _lib.ptr(grid16), _lib.ptr(x4all), 3 * S, _lib.ptr(h_pl))
+        sigma = torch.empty([S], dtype=torch.float32, device=dev)
+        alpha = torch.empty([S], dtype=torch.float32, device=dev)
+        rgb = torch.empty([S, 3], dtype=torch.float32, device=dev) if with_rgb else None
+        ha = h_appear.detach().float().contiguous() if (h_appear is not None and with_rgb and model.n_appear) else None
+        _lib.call("nsim_dyn_fwd_agg", model.meta, _lib.ptr(wpack), _lib.ptr(h_pl), _lib.ptr(rays_d if with_rgb else None),
+                  _lib.ptr(ridx if with_rgb else None), _lib.ptr(ha), S, float(step), _lib.ptr(sigma), _lib.ptr(alpha), _lib.ptr(rgb))
+        if _lib.TIMER is not None:
+            _lib.TIMER.note_units("nsim_dyn_fwd_agg", S)
+        ctx.model, ctx.S, ctx.step, ctx.with_rgb = model, S, float(step), with_rgb
+        ctx.n_active = int(model.meta.lotd.n_active_levels)
+        ctx.ha_shape = h_appear.shape if ha is not None else None
+        ctx.set_materialize_grads(False)
+        need_bwd = any(ctx.needs_input_grad)
+        ctx.save_for_backward(x4all, rays_d, ridx, ha, sigma, rgb, *((h_pl, hf, hfw, grid16, fgrid16) if need_bwd else ()))
+        if with_rgb:
+            return sigma, alpha, rgb, flow6, pred6
+        return sigma, alpha, flow6, pred6
+
+    @staticmethod
+    def backward(ctx, g_sigma, g_alpha, *rest):
+        model, S = ctx.model, ctx.S
+        g_rgb, g_flow6, g_pred6 = (rest if ctx.with_rgb else (None,) + tuple(rest))
+        n_out = 15
+        if all(g is None for g in (g_sigma, g_alpha, g_rgb, g_flow6, g_pred6)):
+            return (None,) * n_out
+        x4all, rays_d, ridx, ha, sigma, rgb, h_pl, hf, hfw, grid16, fgrid16 = ctx.saved_tensors
+        dev = sigma.device
+        x4, x4w = x4all[:S], x4all[S:]
+        wpack, fwpack = model._shadow()[1], model._flow_shadow()[1]
+        fm, dm = model.flow_encoding.cfg.pmeta, model.encoding.cfg.pmeta
+        Lf, prec = int(fm.num_levels), int(model.meta.precision)
+        F, NA = model.encoding.cfg.out_features, model.n_appear
+        n_dw, n_db, n_rw, n_rb = 64 * F + 65 * 64, 129, 64 * (80 + NA) + 4096 + 192, 131
+        dden_w, dden_b, drad_w, drad_b = _lib.zeros([n_dw + n_db + n_rw + n_rb], device=dev).split([n_dw, n_db, n_rw, n_rb])
+        dflow_w, dflow_b = _lib.zeros([model.flow_w.numel() + model.flow_b.numel()], device=dev).split(
+            [model.flow_w.numel(), model.flow_b.numel()])
+        dgrid = _lib.zeros([model.encoding.cfg.n_params], device=dev)
+        dfgrid = _lib.zeros([model.flow_encoding.cfg.n_params], device=dev)
+        dflow6 = g_flow6.float().contiguous().clone() if g_flow6 is not None else _lib.zeros([S, 6], device=dev)
+        gr = g_rgb.float().contiguous() if (ctx.with_rgb and g_rgb is not None) else None
+        dha = _lib.zeros(list(ctx.ha_shape), device=dev) if (ha is not None and ctx.needs_input_grad[6] and gr is not None) else None
+        dense_grad = not (g_sigma is None and g_alpha is None and gr is None)
+        if dense_grad:
+            gs = g_sigma.float().contiguous() if g_sigma is not None else None
+            ga = g_alpha.float().contiguous() if g_alpha is not None else None
+            dh_pl = torch.empty([16, 3 * S, 2], dtype=torch.float32, device=dev)
+            dx_dyn = torch.empty([2 * S, 4], dtype=torch.float32, device=dev)
+            prev = model._active_levels()       # the backward of a query uses the level mask the query was made with
+            model._set_active_raw(ctx.n_active)
+            try:
+                _lib.call("nsim_dyn_bwd_agg", model.meta, _lib.ptr(wpack), _lib.ptr(h_pl), _lib.ptr(rays_d if gr is not None else None),
+                          _lib.ptr(ridx if gr is not None else None), _lib.ptr(ha), S, ctx.step, _lib.ptr(sigma.detach()),
+                          _lib.ptr(rgb.detach()) if rgb is not None else None, _lib.ptr(gs), _lib.ptr(ga), _lib.ptr(gr),
+                          _lib.ptr(dh_pl), _lib.ptr(dden_w), _lib.ptr(dden_b), _lib.ptr(drad_w), _lib.ptr(drad_b), _lib.ptr(dha))
+                _lib.call("nsim_permuto_scatter_pts", dm, _lib.ptr(x4all), _lib.ptr(_all_valid(3 * S, dev)), 3 * S, _lib.ptr(dh_pl),
+                          _lib.ptr(dgrid))
+                # the plane sets of the warped points start S rows into every level of the [16][3S][2] buffer
+                _lib.call("nsim_permuto_dx_pts", dm, _lib.ptr(grid16), _lib.ptr(x4w), None, 2 * S, _lib.ptr(dh_pl.view(-1)[2 * S:]),
+                          3 * S, _lib.ptr(dx_dyn))
+            finally:
+                model._set_active_raw(prev)
+            _lib.call("nsim_dyn_warp_bwd", _lib.ptr(dx_dyn), S, _lib.ptr(dflow6))
+            if _lib.TIMER is not None:
+                _lib.TIMER.note_units("nsim_dyn_bwd_agg", S)
+        if g_pred6 is not None:
+            dh_fw = torch.empty([16, 2 * S, 2], dtype=torch.float32, device=dev)
+            _lib.call("nsim_flow_bwd", Lf, prec, _lib.ptr(fwpack), _lib.ptr(hfw), 0, 2 * S, _lib.ptr(g_pred6.float().contiguous()),
+                      _lib.ptr(dh_fw), _lib.ptr(dflow_w), _lib.ptr(dflow_b))
+            _lib.call("nsim_permuto_scatter_pts", fm, _lib.ptr(x4w), _lib.ptr(_all_valid(2 * S, dev)), 2 * S, _lib.ptr(dh_fw),
+                      _lib.ptr(dfgrid))
+            dx_flow = torch.empty([2 * S, 4], dtype=torch.float32, device=dev)
+            _lib.call("nsim_permuto_dx_pts", fm, _lib.ptr(fgrid16), _lib.ptr(x4w), None, 2 * S, _lib.ptr(dh_fw), 0, _lib.ptr(dx_flow))
+            _lib.call("nsim_dyn_warp_bwd", _lib.ptr(dx_flow), S, _lib.ptr(dflow6))
+        dh_f = torch.empty([16, S, 2], dtype=torch.float32, device=dev)
+        _lib.call("nsim_flow_bwd", Lf, prec, _lib.ptr(fwpack), _lib.ptr(hf), 0, S, _lib.ptr(dflow6), _lib.ptr(dh_f), _lib.ptr(dflow_w),
+                  _lib.ptr(dflow_b))
+        _lib.call("nsim_permuto_scatter_pts", fm, _lib.ptr(x4), _lib.ptr(_all_valid(S, dev)), S, _lib.ptr(dh_f), _lib.ptr(dfgrid))
+        if gr is None:      # no consumer of the colour: the radiance network is not part of the graph (None, not zeros)
+            drad_w = drad_b = dha = None
+        return (None, dgrid, dden_w, dden_b, drad_w, drad_b, dha, dfgrid, dflow_w, dflow_b) + (None,) * 5
+
+
 class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
     is_ray_query_supported = True
     use_ts = True
@@ -263,9 +387,24 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
         self.den_b = nn.Parameter(torch.cat([db1, db2]))
         self.rad_w = nn.Parameter(torch.cat([rw1.reshape(-1), rw2.reshape(-1), rw3.reshape(-1)]))
         self.rad_b = nn.Parameter(torch.cat([rb1, rb2, rb3]))
+        self.use_flow = c.get("flow") is not None
+        if self.use_flow:
+            # (use_flow_field, no_gtbox_with_flow.240208.yaml:353-371) a second 4-D lattice with its own seed, shifts, table and
+            # fp16 shadow, and the [F_f -> 64 -> 64 -> 6] decoder of the forward / backward scene flow
+            fl = c["flow"]
+            fac = dict(fl["permuto_auto_compute_cfg"])
+            fac.setdefault("seed", 1)
+            self.flow_encoding = _PermutoFieldEncoding(PermutoConfig(in_dim=4, **fac), fl["param_bound"], self._seed + 2)
+            self.flow_encoding.cfg.set_aabb(aabb)
+            fw1, fb1 = lin(64, self.flow_encoding.cfg.out_features)
+            fw2, fb2 = lin(64, 64)
+            fw3, fb3 = lin(6, 64)
+            self.flow_w = nn.Parameter(torch.cat([fw1.reshape(-1), fw2.reshape(-1), fw3.reshape(-1)]))
+            self.flow_b = nn.Parameter(torch.cat([fb1, fb2, fb3]))
         T = int(ts.numel())
         self.register_buffer("ts_keyframes", ts.clone())
         lo, hi = c["time_range"]
+        self.time_delta = (hi - lo) / (T - 1) if T > 1 else 0.0        # spacing of the keyframe codes: the flow's time step
         self.register_buffer("time_codes", torch.linspace(lo, hi, T, dtype=torch.float32), persistent=False)
         acc = dict(self.accel_cfg)
         acc.pop("ts_keyframes", None)
@@ -284,6 +423,7 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
         m.n_appear = NA
         self.meta = m
         self._wpack, self._wpack_versions = None, None
+        self._fwpack, self._fwpack_versions = None, None
         self._built = True
 
     # ------------------------------------------------------------------ reference life cycle
@@ -323,15 +463,22 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
     def _param_groups(self, cfg: dict):
         enc = self.encoding
         enc.shadow()
-        return [dict(name="encoding", params=[enc.flattened_params], shadow16=lambda: enc.shadow()),
-                dict(name="dynamic_decoder", params=[self.den_w, self.den_b]),
-                dict(name="radiance_decoder", params=[self.rad_w, self.rad_b])]
+        groups = [dict(name="encoding", params=[enc.flattened_params], shadow16=lambda: enc.shadow()),
+                  dict(name="dynamic_decoder", params=[self.den_w, self.den_b]),
+                  dict(name="radiance_decoder", params=[self.rad_w, self.rad_b])]
+        if self.use_flow:
+            fenc = self.flow_encoding
+            fenc.shadow()
+            groups += [dict(name="flow_encoding", params=[fenc.flattened_params], shadow16=lambda: fenc.shadow()),
+                       dict(name="flow_decoder", params=[self.flow_w, self.flow_b])]
+        return groups
 
     def _after_optimizer_step(self):
         self._wpack_versions = None
+        self._fwpack_versions = None
 
     def _weight_reg_tensors(self):
-        return [self.den_w, self.rad_w]
+        return [self.den_w, self.rad_w] + ([self.flow_w] if self.use_flow else [])
 
     def set_active_levels(self, n: Optional[int]):
         """Hardmask over the lattice levels: levels >= n give zero features, get no gradient, and their tables are not read."""
@@ -388,6 +535,34 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
             self._wpack_versions = vers
         return grid16, self._wpack
 
+    def _flow_shadow(self):
+        """(fp16 shadow of the flow table, weight pack of the flow decoder), refreshed lazily like ``_shadow``"""
+        fgrid16 = self.flow_encoding.shadow()
+        vers = (self.flow_w._version, self.flow_b._version, self.meta.precision, str(self.flow_w.device), self.flow_w.data_ptr())
+        if self._fwpack is None or self._fwpack_versions != vers:
+            prec = int(self.meta.precision)
+            nbytes = int(_lib.get_lib().nsim_flow_wpack_bytes(prec))
+            if self._fwpack is None or self._fwpack.numel() != nbytes or self._fwpack.device != self.flow_w.device:
+                self._fwpack = torch.zeros([nbytes], dtype=torch.uint8, device=self.flow_w.device)
+            _lib.call("nsim_flow_pack_weights", int(self.flow_encoding.cfg.pmeta.num_levels), prec, _lib.ptr(self.flow_w.detach()),
+                      _lib.ptr(self.flow_b.detach()), _lib.ptr(self._fwpack))
+            self._fwpack_versions = vers
+        return fgrid16, self._fwpack
+
+    def _query(self, h_appear, x4, rays_d, ridx, step, with_rgb):
+        """-> (sigma, alpha, rgb | None, flow dict | None): the plain decoder, or the flow-aggregated one with its four flow
+        tensors ([S,3] each: the keys app/loss/flow.py reads)"""
+        if not self.use_flow:
+            outs = _DynFn.apply(self, self.encoding.flattened_params, self.den_w, self.den_b, self.rad_w, self.rad_b, h_appear,
+                                x4, rays_d, ridx, step, with_rgb)
+            return outs[0], outs[1], (outs[2] if with_rgb else None), None
+        outs = _DynFlowFn.apply(self, self.encoding.flattened_params, self.den_w, self.den_b, self.rad_w, self.rad_b, h_appear,
+                                self.flow_encoding.flattened_params, self.flow_w, self.flow_b, x4, rays_d, ridx, step, with_rgb)
+        flow6, pred6 = outs[-2], outs[-1]
+        S = x4.shape[0]
+        flow = dict(flow_fwd=flow6[:, :3], flow_fwd_pred_bwd=pred6[:S, 3:], flow_bwd=flow6[:, 3:], flow_bwd_pred_fwd=pred6[S:, :3])
+        return outs[0], outs[1], (outs[2] if with_rgb else None), flow
+
     def time_coord(self, ts: torch.Tensor) -> torch.Tensor:
         """w = SeqEmbedding(ts_keyframes, time_codes)(ts, 'interp'): the 4th lattice input of each time (no gradient)."""
         t = ts.detach().float().reshape(-1).contiguous()
@@ -418,19 +593,25 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
         xf = x.detach().float().reshape(-1, 3).contiguous()
         S = xf.shape[0]
         if S == 0:
-            return dict(sigma=torch.zeros(shape, dtype=torch.float32, device=xf.device))
+            ret = dict(sigma=torch.zeros(shape, dtype=torch.float32, device=xf.device))
+            if self.use_flow:
+                ret.update({k: torch.zeros([*shape, 3], dtype=torch.float32, device=xf.device) for k in FLOW_KEYS})
+            return ret
         w = self.time_coord(ts.expand(shape).reshape(-1))
         x4 = self._points(w, S, x=xf)
-        sigma, _ = _DynFn.apply(self, self.encoding.flattened_params, self.den_w, self.den_b, self.rad_w, self.rad_b, None,
-                                x4, None, None, self._step(), False)
-        return dict(sigma=sigma.reshape(shape))
+        sigma, _, _, flow = self._query(None, x4, None, None, self._step(), False)
+        ret = dict(sigma=sigma.reshape(shape))
+        if flow is not None:
+            ret.update({k: v.reshape(*shape, 3) for k, v in flow.items()})
+        return ret
 
     @torch.no_grad()
     def query_density(self, x: torch.Tensor, ts: torch.Tensor) -> torch.Tensor:
         return self.forward_density(x, ts)["sigma"]
 
     def sample_pts_uniform(self, num_pts: int, generator=None) -> Dict[str, torch.Tensor]:
-        """Random points of the AABB at random keyframe times -> ``{'x', 'ts', 'sigma'}`` with gradient."""
+        """Random points of the AABB at random keyframe times -> ``{'x', 'ts', 'sigma'}`` with gradient (and the four flow
+        tensors of a with-flow model)."""
         lo, hi = self.accel.aabb[0], self.accel.aabb[1]
         x = lo + torch.rand([num_pts, 3], device=self.device, generator=generator) * (hi - lo)
         ts = self.ts_keyframes[torch.randint(int(self.ts_keyframes.shape[0]), [num_pts], device=self.device, generator=generator)]
@@ -521,9 +702,8 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
         if with_rgb and self.n_appear and h_appear is None:
             raise ValueError("ray_tested['rays_h_appear'] is missing: radiance_cfg.n_appear_embedding is "
                              f"{self.n_appear}, the radiance decoder reads a per-ray appearance code")
-        outs = _DynFn.apply(self, self.encoding.flattened_params, self.den_w, self.den_b, self.rad_w, self.rad_b, h_appear,
-                            x4, d, ridx, step, bool(with_rgb))
-        sigma, alpha = outs[0], outs[1]
+        sigma, alpha, rgb, flow = self._query(h_appear, x4, d, ridx, step, bool(with_rgb))
+        outs = (sigma, alpha, rgb)
         if acc.collect_armed:
             acc.collect(sigma, slices, rays=(o, d, t, ridx))
             acc.collect_armed = False
@@ -531,6 +711,8 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
                   opacity_alpha=alpha)
         if with_rgb:
             vb["rgb"] = outs[2]
+        if flow is not None:
+            vb.update(flow)
         ret = dict(volume_buffer=vb)
         if render_per_obj_individual or cfg.get("_render", False):
             from .neus import volume_integration

@@ -416,15 +416,47 @@ def validate_emernerf_params(params: dict) -> Dict:
         if p.get(k) is not None:
             _unsupported(k, p[k], "the full EmerNeRFModel (static + dynamic branches) is not built; the dynamic-only model has no "
                                   "static branch")
+    flow = None
     if p.get("use_flow_field", False):
-        _unsupported("use_flow_field", True, "the flow field (and the flow loss) is not built")
+        # (no_gtbox_with_flow.240208.yaml:353-371) the flow lattice and decoder; the absent library's defaults are unknown
+        if p.get("flow_encoding_cfg") is None or p.get("flow_decoder_cfg") is None:
+            _unsupported("use_flow_field", True, "needs both a flow_encoding_cfg and a flow_decoder_cfg (the defaults of the absent "
+                                                 "nr3d_lib are unknown)")
+        if not p.get("use_flow_in_obj", True):
+            _unsupported("use_flow_in_obj", False, "the flow is a displacement in object coordinates")
+        fe = dict(p["flow_encoding_cfg"])
+        if fe.get("type", "permuto") != "permuto":
+            _unsupported("flow_encoding_cfg.type", fe.get("type"), "permuto (a second 4-D permutohedral lattice)")
+        fac = _plain(dict((fe.get("param") or {}).get("permuto_auto_compute_cfg") or {}))
+        if fac.get("type", "multi_res") != "multi_res":
+            _unsupported("flow_encoding_cfg.param.permuto_auto_compute_cfg.type", fac.get("type"), "multi_res")
+        if int(fac.get("n_feats", 2)) != 2:
+            _unsupported("flow_encoding_cfg.param.permuto_auto_compute_cfg.n_feats", fac.get("n_feats"), "2 features per level")
+        if not 1 <= int(fac.get("n_levels", 16)) <= 16:
+            _unsupported("flow_encoding_cfg.param.permuto_auto_compute_cfg.n_levels", fac.get("n_levels"),
+                         "at most 16 levels (32 decoder input features)")
+        fd = dict(p["flow_decoder_cfg"])
+        if fd.get("type", "mlp") != "mlp":
+            _unsupported("flow_decoder_cfg.type", fd.get("type"), "only the fused MLP decoder is built")
+        if int(fd.get("D", 2)) != 2:
+            _unsupported("flow_decoder_cfg.D", fd.get("D"), "two hidden layers")
+        if int(fd.get("W", 64)) != 64:
+            _unsupported("flow_decoder_cfg.W", fd.get("W"), "the fused MFMA decoders are 64 wide")
+        if fd.get("output_activation") is not None:
+            _unsupported("flow_decoder_cfg.output_activation", fd["output_activation"], "the six outputs are linear")
+        if not fd.get("last_bias", True):
+            _unsupported("flow_decoder_cfg.last_bias", False, "the output layer has a bias")
+        if fd.get("activation", "relu") not in ("relu", dict(type="relu")):
+            _unsupported("flow_decoder_cfg.activation", fd.get("activation"), "relu")
+        flow = dict(permuto_auto_compute_cfg=fac,
+                    param_bound=float(((fe.get("param") or {}).get("param_init_cfg") or {}).get("bound", 1e-4)))
     if p.get("use_shadow", False):
         _unsupported("use_shadow", True, "the shadow head is not built")
     if int(p.get("n_semantic_feat", 0) or 0) > 0:
         _unsupported("n_semantic_feat", p.get("n_semantic_feat"), "the decoders emit no semantic channels")
     if int(p.get("n_geometry_feat", 64)) != 64:
         _unsupported("n_geometry_feat", p.get("n_geometry_feat"), "64 geometry features next to sigma")
-    out: Dict = dict(precision=p.get("precision") or _precision(p.get("dtype", "half")))
+    out: Dict = dict(precision=p.get("precision") or _precision(p.get("dtype", "half")), flow=flow)
     te = dict(p.get("time_embedding_cfg") or dict(dim=1, learnable=False, weight_init=dict(type="linspace", start=-1, end=1)))
     if int(te.get("dim", 1)) != 1:
         _unsupported("time_embedding_cfg.dim", te.get("dim"), "one time coordinate enters the 4-D lattice")

@@ -68,6 +68,42 @@ class _PermutoFn(torch.autograd.Function):
         return None, dgrid, None, None, None
 
 
+class _PermutoPlanesFn(torch.autograd.Function):
+    """x [S,in_dim], table -> level-major feature planes [16][S][2] (``nsim_permuto_gather_pts``), with gradient to the table
+    (``nsim_permuto_scatter_pts``) and to the POINTS (``nsim_permuto_dx_pts``: the points may be network outputs).  The backward
+    runs under the level mask the forward was made with."""
+
+    @staticmethod
+    def forward(ctx, x, grid32, grid16, cfg: PermutoConfig):
+        xd = x.detach().float().contiguous()
+        S = xd.shape[0]
+        h_pl = torch.empty([16, S, 2], dtype=torch.float32, device=xd.device)
+        _lib.call("nsim_permuto_gather_pts", cfg.meta, _lib.ptr(grid16), _lib.ptr(xd), S, _lib.ptr(h_pl))
+        ctx.save_for_backward(xd, grid16)
+        ctx.cfg, ctx.n, ctx.n_active = cfg, grid32.shape[0], int(cfg.meta.n_active_levels)
+        return h_pl
+
+    @staticmethod
+    def backward(ctx, g_pl):
+        xd, grid16 = ctx.saved_tensors
+        cfg, S = ctx.cfg, xd.shape[0]
+        g_pl = g_pl.float().contiguous()
+        dgrid = dx = None
+        prev = int(cfg.meta.n_active_levels)
+        cfg.meta.n_active_levels = ctx.n_active
+        try:
+            if ctx.needs_input_grad[1]:
+                dgrid = torch.zeros([ctx.n], dtype=torch.float32, device=xd.device)
+                valid = torch.ones([S], dtype=torch.uint8, device=xd.device)
+                _lib.call("nsim_permuto_scatter_pts", cfg.meta, _lib.ptr(xd), _lib.ptr(valid), S, _lib.ptr(g_pl), _lib.ptr(dgrid))
+            if ctx.needs_input_grad[0]:
+                dx = torch.empty_like(xd)
+                _lib.call("nsim_permuto_dx_pts", cfg.meta, _lib.ptr(grid16), _lib.ptr(xd), None, S, _lib.ptr(g_pl), 0, _lib.ptr(dx))
+        finally:
+            cfg.meta.n_active_levels = prev
+        return dx, dgrid, None, None
+
+
 class PermutoEncoding(nn.Module):
     """f32 master parameters + fp16 shadow (what the kernels gather: (in_dim + 1) x 4 B per level and point).
 
@@ -103,6 +139,17 @@ class PermutoEncoding(nn.Module):
         shape = x.shape[:-1]
         out, dydx = _PermutoFn.apply(x.reshape(-1, self.cfg.in_dim), self.flattened_params, self.shadow(), self.cfg, True)
         return out.reshape(*shape, self.cfg.out_features), dydx.reshape(*shape, self.cfg.out_features, self.cfg.in_dim)
+
+    def forward_planes(self, x: torch.Tensor) -> torch.Tensor:
+        """x [S, in_dim] -> the level-major feature planes [16][S][2] the point-mode decoders read (rows past the pyramid and
+        masked levels are zeros; at most 16 levels), differentiable w.r.t. the table AND x: inside a simplex the features are
+        affine in x, so d h / d x is the derivative of the barycentric weights times the vertex features (not defined on a
+        simplex face, where the kernel takes the side its simplex walk lands on)."""
+        if x.dim() != 2 or x.shape[1] != self.cfg.in_dim:
+            raise ValueError(f"forward_planes takes x [S, {self.cfg.in_dim}], got {tuple(x.shape)}")
+        if self.cfg.num_levels > 16:
+            raise ValueError("the point-mode planes hold at most 16 levels")
+        return _PermutoPlanesFn.apply(x, self.flattened_params, self.shadow(), self.cfg)
 
     @staticmethod
     def backward_dydx(dl_dh: torch.Tensor, dydx: torch.Tensor) -> torch.Tensor:

@@ -938,6 +938,111 @@ def mono_normal_cue_loss(normals_pred: torch.Tensor, normals_gt: torch.Tensor, m
     return _MonoNormalFn.apply(normals_pred, normals_gt, m, r, mode, float(w_l1), float(w_cos))
 
 
+# The scene-flow losses (app/loss/flow.py; the ``flow`` block of fg_emernerf/no_gtbox_with_flow.240208.yaml) on the four flow tensors
+# of a with-flow EmerNeRF query (``volume_buffer`` / ``uniform_samples`` keys flow_fwd, flow_fwd_pred_bwd, flow_bwd,
+# flow_bwd_pred_fwd): one launch forward and one backward for both terms.
+class _FlowLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ff, fpb, fb, bpf, w_cycle, w_sparsity):
+        rows = [_rows3(t, n) for t, n in zip((ff, fpb, fb, bpf), _FLOW_KEYS)]
+        S = rows[0].shape[0]
+        ws = torch.zeros([3], dtype=torch.float64, device=rows[0].device)
+        out = torch.empty([2], dtype=torch.float32, device=rows[0].device)
+        _lib.call("nsim_flow_loss_fwd", *[_lib.ptr(r) for r in rows], S, w_cycle, w_sparsity, _lib.ptr(ws), _lib.ptr(out))
+        ctx.save_for_backward(*rows)
+        ctx.shapes = [t.shape for t in (ff, fpb, fb, bpf)]
+        ctx.w = (w_cycle, w_sparsity)
+        ctx.set_materialize_grads(False)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_cycle, g_sparsity):
+        rows = ctx.saved_tensors
+        if g_cycle is None and g_sparsity is None:
+            return (None,) * 6
+        go = [None if g is None else g.float().reshape(1).contiguous() for g in (g_cycle, g_sparsity)]
+        d = [torch.empty_like(r) if need else None for r, need in zip(rows, ctx.needs_input_grad[:4])]
+        _lib.call("nsim_flow_loss_bwd", *[_lib.ptr(r) for r in rows], rows[0].shape[0], ctx.w[0], ctx.w[1], _lib.ptr(go[0]),
+                  _lib.ptr(go[1]), *[_lib.ptr(t) for t in d])
+        return tuple(None if t is None else t.reshape(sh) for t, sh in zip(d, ctx.shapes)) + (None, None)
+
+
+_FLOW_KEYS = ("flow_fwd", "flow_fwd_pred_bwd", "flow_bwd", "flow_bwd_pred_fwd")
+
+
+def flow_loss(flow_fwd: torch.Tensor, flow_fwd_pred_bwd: torch.Tensor, flow_bwd: torch.Tensor, flow_bwd_pred_fwd: torch.Tensor,
+              w_cycle: float = 1.0, w_sparsity: float = 1.0):
+    """``FlowLoss.fn_cycle`` / ``fn_sparsity`` (app/loss/flow.py:35-55) -> (w_cycle cycle, w_sparsity sparsity) on four [..., 3]
+    tensors of one shape (S rows):
+      cycle    = 1/2 mean over S 3 of (flow_fwd.detach() + flow_fwd_pred_bwd)^2 + (flow_bwd.detach() + flow_bwd_pred_fwd)^2
+      sparsity = 1/4 mean over S of |flow_fwd| + |flow_fwd_pred_bwd| + |flow_bwd| + |flow_bwd_pred_fwd|
+    Gradient to all four; ``flow_fwd`` / ``flow_bwd`` get none from the cycle term (the reference detaches them), and a row that is
+    exactly zero gets a zero gradient from its norm.  f64 sums; one launch per direction.  S == 0 returns zeros without a launch."""
+    ts = (flow_fwd, flow_fwd_pred_bwd, flow_bwd, flow_bwd_pred_fwd)
+    if any(t.shape != flow_fwd.shape for t in ts) or flow_fwd.dim() < 1 or flow_fwd.shape[-1] != 3:
+        raise ValueError("neuralsim_amd: flow_loss takes four [..., 3] tensors of one shape, got " +
+                         ", ".join(str(tuple(t.shape)) for t in ts))
+    if flow_fwd.numel() == 0:
+        return tuple(torch.zeros([], dtype=torch.float32, device=flow_fwd.device) for _ in range(2))
+    return _FlowLossFn.apply(*ts, float(w_cycle), float(w_sparsity))
+
+
+def flow_block_terms(block: dict, raw_per_obj_model: dict, uniform_samples: dict, it: int) -> dict:
+    """``FlowLoss.forward`` (app/loss/flow.py:57-123) on a ``flow`` block in the yaml's own form -- ``class_name_cfgs: {Dynamic:
+    {cycle: {w | anneal, on_render_ratio}, sparsity: {...}, on_render_ratio}}``, ``on_uniform_samples`` (default true),
+    ``on_render_ratio`` (default 1) -- -> the weighted terms ``loss_flow_cycle.{class}.uniform`` / ``.render`` and
+    ``loss_flow_sparsity.{class}.uniform`` / ``.render``.  ``raw_per_obj_model``: {id: {class_name, volume_buffer}}; an ``empty``
+    buffer and a class without an entry are skipped.  A term's render ratio is its own ``on_render_ratio``, else the class's, else the
+    block's.  Weights and annealed values are resolved on the host and folded into the kernels' scales: one ``flow_loss`` launch per
+    direction and sample set, whatever the number of terms."""
+    import copy
+    from nr3d_lib.models.annealers import get_anneal_val
+    blk = dict(block)
+    classes = blk.get("class_name_cfgs", {})
+    on_uniform, ratio = bool(blk.get("on_uniform_samples", True)), blk.get("on_render_ratio", 1.0)
+    out = {}
+
+    def weight(config, term, cname):
+        if term not in config:
+            return 0, {}
+        c = dict(config.pop(term))
+        w = c.pop("w", None)
+        if c.get("anneal", None) is not None:
+            w = get_anneal_val(it=it, **c["anneal"])
+        if w is None:
+            raise ValueError(f"neuralsim_amd: loss_cfg flow.class_name_cfgs.{cname}.{term} has neither w nor anneal")
+        return w, c
+
+    def emit(inputs, cname, where, w_cycle, w_sparsity):
+        cyc, spa = flow_loss(*inputs, w_cycle=w_cycle or 0.0, w_sparsity=w_sparsity or 0.0)
+        if w_cycle is not None:
+            out[f"loss_flow_cycle.{cname}.{where}"] = cyc
+        if w_sparsity is not None:
+            out[f"loss_flow_sparsity.{cname}.{where}"] = spa
+    for obj in raw_per_obj_model.values():
+        vb = obj["volume_buffer"]
+        cname = obj["class_name"]
+        if vb["type"] == "empty" or cname not in classes:
+            continue
+        config = copy.deepcopy(dict(classes[cname]))
+        w_cycle, cfg_cycle = weight(config, "cycle", cname)
+        w_sparsity, cfg_sparsity = weight(config, "sparsity", cname)
+        on = lambda w, s=1.0: (w * s) if w > 0 else None         # noqa: E731  (a term of weight 0 is not emitted)
+        if on_uniform:
+            if cname not in uniform_samples:
+                raise ValueError(f"neuralsim_amd: uniform_samples should contain {cname}")
+            missing = [k for k in _FLOW_KEYS if k not in uniform_samples[cname]]
+            if missing:
+                raise ValueError(f"neuralsim_amd: uniform_samples[{cname}] should contain {missing[0]!r}")
+            if w_cycle > 0 or w_sparsity > 0:
+                emit([uniform_samples[cname][k] for k in _FLOW_KEYS], cname, "uniform", on(w_cycle), on(w_sparsity))
+        alpha_render = config.pop("on_render_ratio", ratio)
+        if alpha_render > 0 and (w_cycle > 0 or w_sparsity > 0):
+            emit([vb[k] for k in _FLOW_KEYS], cname, "render", on(w_cycle, cfg_cycle.get("on_render_ratio", alpha_render)),
+                 on(w_sparsity, cfg_sparsity.get("on_render_ratio", alpha_render)))
+    return out
+
+
 class _PackedShareFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, vw, rgb, nablas, t, pack_infos, rays_inds, N, normalized_depth, normalize_nablas):

@@ -646,6 +646,30 @@ int nsim_ngp_bwd(const NsimNgpMeta* meta, const void* wpack, const float* h_plan
                  int64_t S, float step, const float* sigma_fwd, const float* rgb_fwd, const float* dsigma,
                  const float* dalpha, const float* drgb, float* dh_planes, float* dden_w, float* dden_b, float* drad_w,
                  float* drad_b, float* dh_appear, void* stream);
+/* Pose refinement (``LearnableParams{refine_ego_motion, enable_after}``: the rays, or the points x, carry gradients; the model
+ * opts in with ``ray_query_cfg.query_param.rays_has_grad``).  The sample depths t are constants of the step:
+ * x_s = o_r + t_s d_r, v_s = d_r.  nsim_ngp_bwd_pose is nsim_ngp_bwd (same arguments, same weight / table / appearance
+ * gradients; dh_planes is required) that also WRITES, one row per sample,
+ *   dx [S,3] (required): the share of the first density layer's direct position input, W1[:, F:]^T da1 . 2 x_scale (object
+ *     coordinates) -- the table's share is added by nsim_lotd_dx_lm below;
+ *   dv [S,3] (NULL, or with drgb != NULL): the gradient to the UN-NORMALISED rays_d[ridx]: the SH-4 slots of the radiance
+ *     input gradient through d sh4 / d n and n = d / |d|, i.e. (I - n n^T) g / |d|.
+ * Launch order of a backward with ray gradients: (1) nsim_ngp_bwd_pose, (2) nsim_lotd_dx_lm (dx_add = dx, in place),
+ * (3) nsim_ray_grad_reduce (or dx is the gradient to x), (4) nsim_lotd_scatter. */
+int nsim_ngp_bwd_pose(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* x,
+                      const float* rays_o, const float* rays_d, const float* t, const int64_t* ridx, const float* h_appear,
+                      int64_t S, float step, const float* sigma_fwd, const float* rgb_fwd, const float* dsigma,
+                      const float* dalpha, const float* drgb, float* dh_planes, float* dden_w, float* dden_b, float* drad_w,
+                      float* drad_b, float* dh_appear, float* dx, float* dv, void* stream);
+/* Position gradient of the level-major 3-D gather (the LoTD counterpart of nsim_permuto_dx_pts), at x [S,3] or
+ * rays_o[ridx] + t rays_d[ridx]:  dx[s][c] = dx_add[s][c] + sum_{l < n_active} sum_f dh_planes[l][s][f] d h[l][f] / d x_c,
+ * the derivative of the trilinear weights times the eight vertex entries of the fp16 table (Dense and Hash levels), scaled
+ * by x_scale (R - 1): object coordinates.  dh_planes [16][plane_pitch][2] (0 = S: what nsim_ngp_bwd writes); dx_add [S,3]
+ * may be NULL or dx itself.  Every row of dx [S,3] is written by one lane: no atomics, no zero-fill; masked levels'
+ * tables and planes are not read.  At most 16 levels. */
+int nsim_lotd_dx_lm(const NsimLotdMeta* meta, const void* grid_f16, const float* x, const float* rays_o, const float* rays_d,
+                    const float* t, const int64_t* ridx, int64_t S, const float* dh_planes, int64_t plane_pitch,
+                    const float* dx_add, float* dx, void* stream);
 /* ``accel_cfg{type: occ_grid, occ_thre, occ_thre_consider_mean, ema_decay, update_from_net_cfg, update_from_samples_cfg: {}}``
  * of a density field (yaml :138-152): the value grid holds densities.  update: val = max(val * decay, sigma(p)) over pts [n,3];
  * collect (a training step's own samples: x [n,3] or rays + t + ridx): the max-fold without decay; pack_bits_mean: a voxel is
@@ -699,6 +723,27 @@ int nsim_dyn_bwd_agg(const NsimNgpMeta* meta, const void* wpack, const float* h_
                      const float* h_appear, int64_t S, float step, const float* sigma_fwd, const float* rgb_fwd,
                      const float* dsigma, const float* dalpha, const float* drgb, float* dh_planes, float* dden_w, float* dden_b,
                      float* drad_w, float* drad_b, float* dh_appear, void* stream);
+/* Pose refinement (the rays carry gradients; ``ray_query_cfg.query_param.rays_has_grad``): nsim_dyn_bwd / nsim_dyn_bwd_agg with a
+ * colour gradient (drgb, dh_planes and dv required) that also WRITE dv [S,3], one row per sample: the gradient to the
+ * UN-NORMALISED rays_d[ridx] -- the SH-4 slots of the radiance input gradient through d sh4 / d n and n = d / |d|, i.e.
+ * (I - n n^T) g / |d|.  The model has no direct position input: the position gradient of a sample is nsim_permuto_dx_pts on the
+ * dh planes (components 0..2; the time component is dropped -- times get no gradient); with flow, plus the position parts of
+ * dx4w at the two warped points (both lattices) and nsim_permuto_dx_pts on the flow lattice at x with the dh planes nsim_flow_bwd
+ * leaves for the total dflow6.  Without a colour gradient there is no dv: the plain entry points serve.  Then
+ * nsim_ray_grad_reduce. */
+int nsim_dyn_bwd_pose(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* rays_d,
+                      const int64_t* ridx, const float* h_appear, int64_t S, float step, const float* sigma_fwd,
+                      const float* rgb_fwd, const float* dsigma, const float* dalpha, const float* drgb, float* dh_planes,
+                      float* dden_w, float* dden_b, float* drad_w, float* drad_b, float* dh_appear, float* dv, void* stream);
+int nsim_dyn_bwd_agg_pose(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, const float* rays_d,
+                          const int64_t* ridx, const float* h_appear, int64_t S, float step, const float* sigma_fwd,
+                          const float* rgb_fwd, const float* dsigma, const float* dalpha, const float* drgb, float* dh_planes,
+                          float* dden_w, float* dden_b, float* drad_w, float* drad_b, float* dh_appear, float* dv, void* stream);
+/* dx [S,3] (every row written) = the position parts of dx4_dyn[s] + dx4_flow[s] (nsim_permuto_dx_pts at the samples on the dynamic
+ * / the flow lattice, [S,4]) + dx4w_dyn[s] + dx4w_dyn[S + s] + dx4w_flow[s] + dx4w_flow[S + s] (at the 2S warped points, [2S,4]:
+ * x+- = x +- flow, so d x+- / d x = I).  Each input may be NULL.  The time components are dropped. */
+int nsim_dyn_pose_dx(const float* dx4_dyn, const float* dx4_flow, const float* dx4w_dyn, const float* dx4w_flow, int64_t S,
+                     float* dx, void* stream);
 /* The scene-flow decoder of the with-flow EmerNeRF model (``flow_decoder_cfg{type: mlp, D: 2, W: 64}``, code_multi/configs/exps/
  * fg_emernerf/no_gtbox_with_flow.240208.yaml): features of the flow lattice (num_levels <= 16 levels x 2, level-major planes
  * [16][plane_pitch][2] of nsim_permuto_gather_pts, plane_pitch 0 = S) -> 64 (relu) -> 64 (relu) -> 6 (linear): flow6 [S,6] f32,

@@ -198,6 +198,8 @@ SIGNATURES = {
     "nsim_ngp_pack_weights": [C.POINTER(NgpMeta), _P, _P, _P, _P, _P],
     "nsim_ngp_fwd": [C.POINTER(NgpMeta), _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _F, _P, _P, _P],
     "nsim_ngp_bwd": [C.POINTER(NgpMeta), _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _F] + [_P] * 11,
+    "nsim_ngp_bwd_pose": [C.POINTER(NgpMeta), _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _F] + [_P] * 13,
+    "nsim_lotd_dx_lm": [C.POINTER(LotdMeta), _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P],
     "nsim_occ_update_density": [_P, _I64, _F, _P, _P, _I64, C.POINTER(OccMeta)],
     "nsim_occ_collect_density": [_P, _P, _P, _P, _P, _P, _P, _I64, C.POINTER(OccMeta)],
     "nsim_occ_pack_bits_mean": [_P, _I64, _F, _I, _P, _P],
@@ -206,6 +208,9 @@ SIGNATURES = {
     "nsim_dyn_bwd": [C.POINTER(NgpMeta), _P, _P, _I64, _P, _P, _P, _I64, _F] + [_P] * 11,
     "nsim_dyn_fwd_agg": [C.POINTER(NgpMeta), _P, _P, _P, _P, _P, _I64, _F, _P, _P, _P],
     "nsim_dyn_bwd_agg": [C.POINTER(NgpMeta), _P, _P, _P, _P, _P, _I64, _F] + [_P] * 11,
+    "nsim_dyn_pose_dx": [_P, _P, _P, _P, _I64, _P],
+    "nsim_dyn_bwd_pose": [C.POINTER(NgpMeta), _P, _P, _I64, _P, _P, _P, _I64, _F] + [_P] * 12,
+    "nsim_dyn_bwd_agg_pose": [C.POINTER(NgpMeta), _P, _P, _P, _P, _P, _I64, _F] + [_P] * 12,
     "nsim_dyn_time": [_P, _P, _I, _P, _I64, _I64, _P, _P, _P],
     "nsim_dyn_points": [_P, _P, _P, _P, _P, _P, _I64, _P],
     "nsim_occ_update_density_sliced": [_P, _I64, _I64, _I, _F, _P, _P, _P, _I64, C.POINTER(OccMeta)],
@@ -437,7 +442,8 @@ def _marshal(args):
 
 
 _GRAD_SCRATCH = {}
-_GRAD_SCRATCH_USERS = ("nsim_field_bwd_rad", "nsim_field_bwd_sdf", "nsim_ngp_bwd", "nsim_dyn_bwd", "nsim_dyn_bwd_agg", "nsim_flow_bwd")
+_GRAD_SCRATCH_USERS = ("nsim_field_bwd_rad", "nsim_field_bwd_sdf", "nsim_ngp_bwd", "nsim_ngp_bwd_pose", "nsim_dyn_bwd", "nsim_dyn_bwd_agg",
+                       "nsim_dyn_bwd_pose", "nsim_dyn_bwd_agg_pose", "nsim_flow_bwd")
 GRAD_SCRATCH_FLOATS = 16 * 16384      # 16 replicas of the largest decoder gradient (nsim_dyn_bwd: both decoders, 16132 floats)
 
 

@@ -919,6 +919,7 @@ struct NgpArgs {
   int64_t rep_stride;                     // floats between replicas (workgroup b adds into replica b & rep_mask)
   int rep_mask;
   float* dh_appear;
+  float *dx, *dv;                         // POSE: per-sample gradients to the position / the un-normalised ray direction
 };
 
 #define NGP_WAVES 4
@@ -976,8 +977,13 @@ __device__ __forceinline__ NgpPoint ngp_point(const NgpArgs& a, int64_t tile, in
 
 // BWD = 0: sigma / alpha / rgb.  BWD = 1: recomputes the activations from the saved feature planes and accumulates the
 // weight gradients (per-wave private LDS accumulators in fp16 mode, as k_nerf), dh planes, dh_appear.
-template <int PREC, int BWD>
+// POSE (backward only; pose refinement, the rays or points carry gradients): also dx [S,3], the first density layer's
+// direct position input pulled back to object coordinates (W1[:, F:]^T da1 . 2 xs -- the table's share is added by
+// k_lotd_dx_lm from the dh planes), and dv [S,3] (NULL without a colour gradient), the SH-4 slots of the radiance input
+// gradient through sh4_grad and the normalisation n = d / |d|: dv = (I - n n^T) g / |d|.
+template <int PREC, int BWD, bool POSE = false>
 __global__ void __launch_bounds__(64 * (BWD ? NGP_WAVES_BWD : NGP_WAVES)) k_ngp(NgpArgs a) {
+  static_assert(!POSE || BWD, "the ray gradients are outputs of the backward");
   NSIM_DYN_SMEM(smem);
   constexpr bool PRIV = (PREC == 0 && BWD);
   constexpr int NW = BWD ? NGP_WAVES_BWD : NGP_WAVES;
@@ -1136,6 +1142,30 @@ __global__ void __launch_bounds__(64 * (BWD ? NGP_WAVES_BWD : NGP_WAVES)) k_ngp(
             atomicAdd(dst + 3, c3);
           }
         }
+        if constexpr (POSE) {
+          if (a.dv) {     // SH slot k of the second M-tile: half-wave (k >> 2) & 1, register (k & 3) + 4 (k >> 3)
+            float gsh[16];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+              const float v = (hi == ((k >> 2) & 1)) ? din[16 + (k & 3) + 4 * (k >> 3)] : 0.f;
+              gsh[k] = v + wave_shfl_xor(v, 32);
+            }
+            float gv[3];
+            sh4_grad(p.vd, gsh, gv);
+            if (p.valid && hi == 0) {
+              float n2 = 0.f;
+#pragma unroll
+              for (int c = 0; c < 3; ++c) {
+                const float dc = a.rays_d[3 * p.ray + c];
+                n2 = n2 + dc * dc;
+              }
+              const float inv = n2 > 0.f ? 1.0f / sqrtf(n2) : 0.f;
+              const float ng = p.vd[0] * gv[0] + p.vd[1] * gv[1] + p.vd[2] * gv[2];
+#pragma unroll
+              for (int c = 0; c < 3; ++c) a.dv[3 * s + c] = (gv[c] - p.vd[c] * ng) * inv;
+            }
+          }
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) dO[r] = din[r];      // geometry feature (slot 0: the packed row is zero)
       }
@@ -1161,6 +1191,21 @@ __global__ void __launch_bounds__(64 * (BWD ? NGP_WAVES_BWD : NGP_WAVES)) k_ngp(
 #pragma unroll
         for (int r = 0; r < 16; ++r) xt[r] = (hi == 0 && r < 3) ? p.xn[r < 3 ? r : 0] : 0.f;
         dw_product<PREC, 2, 1, PRIV>(stA, stB, da, xt, accum + A_DX, 3, 64, 3, nullptr);
+      }
+      if constexpr (POSE) {     // x_n = 2 (x xs + xb) - 1: d x_c = 2 xs_c sum_u W1[u][F + c] da[u]
+        float gx[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 32; ++k) {
+          gx[0] = gx[0] + ngp_vec(W, L, GV_DX0, hi, k) * da[k];
+          gx[1] = gx[1] + ngp_vec(W, L, GV_DX1, hi, k) * da[k];
+          gx[2] = gx[2] + ngp_vec(W, L, GV_DX2, hi, k) * da[k];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gx[c] = gx[c] + wave_shfl_xor(gx[c], 32);
+        if (p.valid && hi == 0) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) a.dx[3 * s + c] = gx[c] * (2.0f * a.xs[c]);
+        }
       }
       if (a.dh_pl) {
         float dh[16];
@@ -1220,6 +1265,67 @@ __global__ void __launch_bounds__(64 * (BWD ? NGP_WAVES_BWD : NGP_WAVES)) k_ngp(
       if (d >= 0) atomicAdd(a.dst[d] + rep + off, v);
     }
   }
+}
+
+// ----------------------------------------------------------------------------------------- pose refinement
+// The position gradient of the level-major 3-D gather (the LoTD counterpart of permuto.hip's k_permuto_dx_pts):
+//   dx[s][c] = dx_add[s][c] + sum_{l < n_active} dscale_l,c sum_slot (d w_slot / d pos_c) (dh[l][s][0] g0 + dh[l][s][1] g1)
+// with dh the planes [16][pitch][2] the decoder backward leaves for the scatter, (g0, g1) the fp16 table entry of the slot's
+// vertex (lotd_dev.h: the parity enumeration of every gather) and dscale = xs (R - 1), so dx is in object coordinates.  The
+// model saves no dh/dx planes in the forward (they are 6 floats per level and sample and only this launch would read them):
+// the eight vertices are fetched again.  One lane per sample over all active levels: every dx row has one writer; masked
+// levels touch neither their table nor their plane.
+struct LotdDxArgs {
+  LotdDev lotd;
+  const f16* grid;
+  const float *x, *rays_o, *rays_d, *t;
+  const int64_t* ridx;
+  int64_t S, PS;
+  const float *dh_pl, *dx_add;
+  float* dx;
+};
+
+__global__ void __launch_bounds__(256) k_lotd_dx_lm(LotdDxArgs a) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= a.S) return;
+  float xx[3];
+  if (a.x) {
+    xx[0] = a.x[3 * s]; xx[1] = a.x[3 * s + 1]; xx[2] = a.x[3 * s + 2];
+  } else {
+    const int64_t ray = a.ridx[s];
+    const float tt = a.t[s];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) xx[c] = a.rays_o[3 * ray + c] + tt * a.rays_d[3 * ray + c];
+  }
+  const GridRef gref = grid_ref(a.grid);
+  float acc[3] = {0.f, 0.f, 0.f};
+  if (a.dx_add) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c] = a.dx_add[3 * s + c];
+  }
+  for (int l = 0; l < a.lotd.n_active; ++l) {
+    const LotdRes R = a.lotd.res[l];
+    const int type = a.lotd.type[l];
+    const uint32_t T = a.lotd.size[l], off = (uint32_t)a.lotd.offset[l];
+    const LotdCell c = lotd_cell(xx, R, a.lotd);
+    const LotdSlots SL = lotd_slots(c);
+    const float* dp = a.dh_pl + ((int64_t)l * a.PS + s) * 2;
+    const float d0 = dp[0], d1 = dp[1];
+    float j[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int slot = 0; slot < 8; ++slot) {
+      float w, dw[3], g0, g1;
+      lotd_slot_w(SL, slot, w, dw);
+      lotd_load2(gref, off + 2u * lotd_slot_index(SL, slot, R, type, T), g0, g1);
+      const float v = d0 * g0 + d1 * g1;
+#pragma unroll
+      for (int c3 = 0; c3 < 3; ++c3) j[c3] = j[c3] + dw[c3] * v;
+    }
+#pragma unroll
+    for (int c3 = 0; c3 < 3; ++c3) acc[c3] = acc[c3] + j[c3] * c.dscale[c3];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) a.dx[3 * s + c] = acc[c];
 }
 
 // ----------------------------------------------------------------------------------------- density occupancy
@@ -1384,6 +1490,7 @@ struct DynArgs {
   int64_t rep_stride;
   int rep_mask;
   float* dh_appear;
+  float* dv;                              // POSE: per-sample gradient to the un-normalised ray direction (radiance only)
 };
 
 #define DYN_WAVES 4
@@ -1435,8 +1542,12 @@ __device__ __forceinline__ float dyn_agg_weight(int p) { return p == 0 ? 0.5f : 
 // AGG: the three plane sets of a sample lie at rows s, s + S, s + 2S of ONE buffer of pitch PS = 3S; the first layer runs three
 // times, one after the other over the same registers and staging (no LDS beyond the plain kernel's), the backward writes three dh
 // plane sets (pitch 3S).  AGG = false is the kernel as it was: every AGG branch is an ``if constexpr``.
-template <int PREC, int BWD, bool AGG = false>
+// POSE (backward with a colour gradient only; pose refinement): also dv [S,3], the SH-4 slots of the radiance input gradient
+// through sh4_grad and n = d / |d|: dv = (I - n n^T) g / |d|.  This model has no direct position input: the position gradient
+// comes from the lattice alone (nsim_permuto_dx_pts on the dh planes).  Every POSE branch is an ``if constexpr``.
+template <int PREC, int BWD, bool AGG = false, bool POSE = false>
 __global__ void __launch_bounds__(64 * (BWD ? DYN_WAVES_BWD : DYN_WAVES)) k_dyn(DynArgs a) {
+  static_assert(!POSE || BWD, "the ray gradients are outputs of the backward");
   NSIM_DYN_SMEM(smem);
   constexpr bool PRIV = (PREC == 0 && BWD);
   constexpr int NW = BWD ? DYN_WAVES_BWD : DYN_WAVES;
@@ -1625,6 +1736,28 @@ __global__ void __launch_bounds__(64 * (BWD ? DYN_WAVES_BWD : DYN_WAVES)) k_dyn(
             atomicAdd(dst + 1, c1);
             atomicAdd(dst + 2, c2);
             atomicAdd(dst + 3, c3);
+          }
+        }
+        if constexpr (POSE) {     // SH slot k of the third M-tile: half-wave (k >> 2) & 1, register (k & 3) + 4 (k >> 3)
+          float gsh[16];
+#pragma unroll
+          for (int k = 0; k < 16; ++k) {
+            const float v = (hi == ((k >> 2) & 1)) ? din[32 + (k & 3) + 4 * (k >> 3)] : 0.f;
+            gsh[k] = v + wave_shfl_xor(v, 32);
+          }
+          float gv[3];
+          sh4_grad(vd, gsh, gv);
+          if (valid && hi == 0) {
+            float n2 = 0.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+              const float dc = a.rays_d[3 * ray + c];
+              n2 = n2 + dc * dc;
+            }
+            const float inv = n2 > 0.f ? 1.0f / sqrtf(n2) : 0.f;
+            const float ng = vd[0] * gv[0] + vd[1] * gv[1] + vd[2] * gv[2];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) a.dv[3 * s + c] = (gv[c] - vd[c] * ng) * inv;
           }
         }
         float dgeo[32];
@@ -2016,6 +2149,26 @@ __global__ void __launch_bounds__(256) k_dyn_warp_bwd(const float* __restrict__ 
   for (int c = 0; c < 3; ++c) {
     dflow6[6 * s + c] = dflow6[6 * s + c] + dx4w[4 * s + c];
     dflow6[6 * s + 3 + c] = dflow6[6 * s + 3 + c] + dx4w[4 * (S + s) + c];
+  }
+}
+
+// Pose refinement: the position gradient of sample s from the lattice launches' [.,4] outputs -- dx[s][c] = the position parts of
+// dx4_dyn[s] + dx4_flow[s] (nsim_permuto_dx_pts at the sample, dynamic / flow lattice) + dx4w_dyn[s] + dx4w_dyn[S + s] + dx4w_flow[s]
+// + dx4w_flow[S + s] (at its two warped points: x+- = x +- flow, d x+- / d x = I); the time components are dropped.  Each input
+// may be NULL; every dx row is written.
+__global__ void __launch_bounds__(256) k_dyn_pose_dx(const float* __restrict__ dx4_dyn, const float* __restrict__ dx4_flow,
+                                                      const float* __restrict__ dx4w_dyn, const float* __restrict__ dx4w_flow,
+                                                      int64_t S, float* __restrict__ dx) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S) return;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float v = 0.f;
+    if (dx4_dyn) v = v + dx4_dyn[4 * s + c];
+    if (dx4w_dyn) v = v + dx4w_dyn[4 * s + c] + dx4w_dyn[4 * (S + s) + c];
+    if (dx4w_flow) v = v + dx4w_flow[4 * s + c] + dx4w_flow[4 * (S + s) + c];
+    if (dx4_flow) v = v + dx4_flow[4 * s + c];
+    dx[3 * s + c] = v;
   }
 }
 
@@ -2441,15 +2594,18 @@ int nsim_ngp_fwd(const NsimNgpMeta* meta, const void* wpack, const float* h_plan
   return 0;
 }
 
-int nsim_ngp_bwd(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* x,
-                 const float* rays_o, const float* rays_d, const float* t, const int64_t* ridx, const float* h_appear,
-                 int64_t S, float step, const float* sigma_fwd, const float* rgb_fwd, const float* dsigma,
-                 const float* dalpha, const float* drgb, float* dh_planes, float* dden_w, float* dden_b, float* drad_w,
-                 float* drad_b, float* dh_appear, void* stream) {
+// nsim_ngp_bwd (pose == false) | nsim_ngp_bwd_pose (pose: dx [S,3] and, with a colour gradient, dv [S,3] as well)
+static int ngp_bwd(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* x,
+                   const float* rays_o, const float* rays_d, const float* t, const int64_t* ridx, const float* h_appear,
+                   int64_t S, float step, const float* sigma_fwd, const float* rgb_fwd, const float* dsigma,
+                   const float* dalpha, const float* drgb, float* dh_planes, float* dden_w, float* dden_b, float* drad_w,
+                   float* drad_b, float* dh_appear, bool pose, float* dx, float* dv, void* stream) {
   const int rc = ngp_meta_check(meta);
   if (rc) return rc;
   if (S <= 0) return 0;
   if (!wpack || !h_planes || !sigma_fwd) return 28;
+  if (pose && (!dx || (dv && !drgb))) return 4;
+  if (pose && !dh_planes) return 28;          // the next launch (nsim_lotd_dx_lm) reads them
   if (!x && !(rays_o && rays_d && t && ridx)) return 24;
   if (drgb && !(rays_d && ridx && rgb_fwd)) return 25;
   if (!dden_w || !dden_b || (drgb && (!drad_w || !drad_b))) return 26;
@@ -2463,6 +2619,7 @@ int nsim_ngp_bwd(const NsimNgpMeta* meta, const void* wpack, const float* h_plan
   a.dsigma = dsigma; a.dalpha = dalpha; a.drgb = drgb;
   a.dh_pl = dh_planes;
   a.dh_appear = dh_appear;
+  a.dx = dx; a.dv = dv;
   const bool priv = meta->precision == 0;
   const size_t st = priv ? stage_bytes_per_wave<0>() : stage_bytes_per_wave<1>();
   const size_t acc = (12900 * 4 + 15) & ~15;
@@ -2486,14 +2643,59 @@ int nsim_ngp_bwd(const NsimNgpMeta* meta, const void* wpack, const float* h_plan
     a.rep_mask = 0;
   }
   const dim3 grid((unsigned)nb), block(64 * NGP_WAVES_BWD);
-  if (priv) hipLaunchKernelGGL((k_ngp<0, 1>), grid, block, shmem, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((k_ngp<1, 1>), grid, block, shmem, (hipStream_t)stream, a);
+  if (pose) {
+    if (priv) hipLaunchKernelGGL((k_ngp<0, 1, true>), grid, block, shmem, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((k_ngp<1, 1, true>), grid, block, shmem, (hipStream_t)stream, a);
+  } else {
+    if (priv) hipLaunchKernelGGL((k_ngp<0, 1>), grid, block, shmem, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((k_ngp<1, 1>), grid, block, shmem, (hipStream_t)stream, a);
+  }
   NSIM_CHECK_LAUNCH();
   if (sc) {      // the replicas of [den_w | den_b] and of [rad_w | rad_b] folded by field.hip's reduction (which zeroes them again)
     nsim_grad_scratch_fold(sc, R, n_all, n[0], n[1], dden_w, dden_b, stream);
     if (drgb) nsim_grad_scratch_fold(sc + n[0] + n[1], R, n_all, n[2], n[3], drad_w, drad_b, stream);
     NSIM_CHECK_LAUNCH();
   }
+  return 0;
+}
+
+int nsim_ngp_bwd(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* x,
+                 const float* rays_o, const float* rays_d, const float* t, const int64_t* ridx, const float* h_appear,
+                 int64_t S, float step, const float* sigma_fwd, const float* rgb_fwd, const float* dsigma,
+                 const float* dalpha, const float* drgb, float* dh_planes, float* dden_w, float* dden_b, float* drad_w,
+                 float* drad_b, float* dh_appear, void* stream) {
+  return ngp_bwd(meta, wpack, h_planes, plane_pitch, x, rays_o, rays_d, t, ridx, h_appear, S, step, sigma_fwd, rgb_fwd, dsigma,
+                 dalpha, drgb, dh_planes, dden_w, dden_b, drad_w, drad_b, dh_appear, false, nullptr, nullptr, stream);
+}
+
+int nsim_ngp_bwd_pose(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* x,
+                      const float* rays_o, const float* rays_d, const float* t, const int64_t* ridx, const float* h_appear,
+                      int64_t S, float step, const float* sigma_fwd, const float* rgb_fwd, const float* dsigma,
+                      const float* dalpha, const float* drgb, float* dh_planes, float* dden_w, float* dden_b, float* drad_w,
+                      float* drad_b, float* dh_appear, float* dx, float* dv, void* stream) {
+  return ngp_bwd(meta, wpack, h_planes, plane_pitch, x, rays_o, rays_d, t, ridx, h_appear, S, step, sigma_fwd, rgb_fwd, dsigma,
+                 dalpha, drgb, dh_planes, dden_w, dden_b, drad_w, drad_b, dh_appear, true, dx, dv, stream);
+}
+
+int nsim_lotd_dx_lm(const NsimLotdMeta* meta, const void* grid_f16, const float* x, const float* rays_o, const float* rays_d,
+                    const float* t, const int64_t* ridx, int64_t S, const float* dh_planes, int64_t plane_pitch,
+                    const float* dx_add, float* dx, void* stream) {
+  const int rc = lotd_meta_check(meta);
+  if (rc) return rc;
+  if (meta->num_levels > 16) return 38;           // the planes hold 16 levels
+  if (S <= 0) return 0;
+  if (!x && !(rays_o && rays_d && t && ridx)) return 24;
+  if (!grid_f16 || !dx) return 4;
+  if (!dh_planes || (plane_pitch != 0 && plane_pitch < S)) return 28;
+  LotdDxArgs a;
+  a.lotd = lotd_dev(meta);
+  a.grid = (const f16*)grid_f16;
+  a.x = x; a.rays_o = rays_o; a.rays_d = rays_d; a.t = t; a.ridx = ridx;
+  a.S = S;
+  a.PS = plane_pitch ? plane_pitch : S;
+  a.dh_pl = dh_planes; a.dx_add = dx_add; a.dx = dx;
+  hipLaunchKernelGGL(k_lotd_dx_lm, dim3(nsim_blocks(S, 256)), dim3(256), 0, (hipStream_t)stream, a);
+  NSIM_CHECK_LAUNCH();
   return 0;
 }
 
@@ -2595,26 +2797,30 @@ int nsim_dyn_fwd(const NsimNgpMeta* meta, const void* wpack, const float* h_plan
   return 0;
 }
 
-int nsim_dyn_bwd(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* rays_d,
-                 const int64_t* ridx, const float* h_appear, int64_t S, float step, const float* sigma_fwd, const float* rgb_fwd,
-                 const float* dsigma, const float* dalpha, const float* drgb, float* dh_planes, float* dden_w, float* dden_b,
-                 float* drad_w, float* drad_b, float* dh_appear, void* stream) {
+// nsim_dyn_bwd | nsim_dyn_bwd_agg (agg: the three plane sets at pitch 3S) | their _pose forms (dv [S,3]; needs drgb)
+static int dyn_bwd(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* rays_d,
+                   const int64_t* ridx, const float* h_appear, int64_t S, float step, const float* sigma_fwd, const float* rgb_fwd,
+                   const float* dsigma, const float* dalpha, const float* drgb, float* dh_planes, float* dden_w, float* dden_b,
+                   float* drad_w, float* drad_b, float* dh_appear, bool agg, float* dv, void* stream) {
   const int rc = ngp_meta_check(meta);
   if (rc) return rc;
   if (S <= 0) return 0;
   if (!wpack || !h_planes || !sigma_fwd) return 28;
   if (drgb && !(rays_d && ridx && rgb_fwd)) return 25;
   if (!dden_w || !dden_b || (drgb && (!drad_w || !drad_b))) return 26;
+  if (dv && !drgb) return 25;
+  if (dv && !dh_planes) return 28;            // the pose forms hand the planes to nsim_permuto_dx_pts
   DynArgs a = dyn_args(meta);
   a.wpack = (const char*)wpack;
   a.h_pl = h_planes;
-  a.PS = plane_pitch > 0 ? plane_pitch : S;
+  a.PS = agg ? 3 * S : (plane_pitch > 0 ? plane_pitch : S);
   a.rays_d = rays_d; a.ridx = ridx; a.h_appear = h_appear;
   a.S = S; a.step = step;
   a.sigma_fwd = sigma_fwd; a.rgb_fwd = rgb_fwd;
   a.dsigma = dsigma; a.dalpha = dalpha; a.drgb = drgb;
   a.dh_pl = dh_planes;
   a.dh_appear = dh_appear;
+  a.dv = dv;
   const bool priv = meta->precision == 0;
   const size_t st = priv ? stage_bytes_per_wave<0>() : stage_bytes_per_wave<1>();
   const size_t acc = (16904 * 4 + 15) & ~15;
@@ -2638,8 +2844,16 @@ int nsim_dyn_bwd(const NsimNgpMeta* meta, const void* wpack, const float* h_plan
     a.rep_mask = 0;
   }
   const dim3 grid((unsigned)nb), block(64 * DYN_WAVES_BWD);
-  if (priv) hipLaunchKernelGGL((k_dyn<0, 1>), grid, block, shmem, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((k_dyn<1, 1>), grid, block, shmem, (hipStream_t)stream, a);
+  switch ((dv ? 4 : 0) + (agg ? 2 : 0) + (priv ? 0 : 1)) {
+    case 0: hipLaunchKernelGGL((k_dyn<0, 1>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 1: hipLaunchKernelGGL((k_dyn<1, 1>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 2: hipLaunchKernelGGL((k_dyn<0, 1, true>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 3: hipLaunchKernelGGL((k_dyn<1, 1, true>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 4: hipLaunchKernelGGL((k_dyn<0, 1, false, true>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 5: hipLaunchKernelGGL((k_dyn<1, 1, false, true>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 6: hipLaunchKernelGGL((k_dyn<0, 1, true, true>), grid, block, shmem, (hipStream_t)stream, a); break;
+    case 7: hipLaunchKernelGGL((k_dyn<1, 1, true, true>), grid, block, shmem, (hipStream_t)stream, a); break;
+  }
   NSIM_CHECK_LAUNCH();
   if (sc) {
     nsim_grad_scratch_fold(sc, R, n_all, n[0], n[1], dden_w, dden_b, stream);
@@ -2647,6 +2861,23 @@ int nsim_dyn_bwd(const NsimNgpMeta* meta, const void* wpack, const float* h_plan
     NSIM_CHECK_LAUNCH();
   }
   return 0;
+}
+
+int nsim_dyn_bwd(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* rays_d,
+                 const int64_t* ridx, const float* h_appear, int64_t S, float step, const float* sigma_fwd, const float* rgb_fwd,
+                 const float* dsigma, const float* dalpha, const float* drgb, float* dh_planes, float* dden_w, float* dden_b,
+                 float* drad_w, float* drad_b, float* dh_appear, void* stream) {
+  return dyn_bwd(meta, wpack, h_planes, plane_pitch, rays_d, ridx, h_appear, S, step, sigma_fwd, rgb_fwd, dsigma, dalpha, drgb,
+                 dh_planes, dden_w, dden_b, drad_w, drad_b, dh_appear, false, nullptr, stream);
+}
+
+int nsim_dyn_bwd_pose(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, int64_t plane_pitch, const float* rays_d,
+                      const int64_t* ridx, const float* h_appear, int64_t S, float step, const float* sigma_fwd,
+                      const float* rgb_fwd, const float* dsigma, const float* dalpha, const float* drgb, float* dh_planes,
+                      float* dden_w, float* dden_b, float* drad_w, float* drad_b, float* dh_appear, float* dv, void* stream) {
+  if (S > 0 && !dv) return 4;
+  return dyn_bwd(meta, wpack, h_planes, plane_pitch, rays_d, ridx, h_appear, S, step, sigma_fwd, rgb_fwd, dsigma, dalpha, drgb,
+                 dh_planes, dden_w, dden_b, drad_w, drad_b, dh_appear, false, dv, stream);
 }
 
 // the aggregating variants (the with-flow model): h_planes [16][3S][2] holds the plane sets of the samples (rows 0..S), of their
@@ -2681,54 +2912,17 @@ int nsim_dyn_bwd_agg(const NsimNgpMeta* meta, const void* wpack, const float* h_
                      const float* h_appear, int64_t S, float step, const float* sigma_fwd, const float* rgb_fwd,
                      const float* dsigma, const float* dalpha, const float* drgb, float* dh_planes, float* dden_w, float* dden_b,
                      float* drad_w, float* drad_b, float* dh_appear, void* stream) {
-  const int rc = ngp_meta_check(meta);
-  if (rc) return rc;
-  if (S <= 0) return 0;
-  if (!wpack || !h_planes || !sigma_fwd) return 28;
-  if (drgb && !(rays_d && ridx && rgb_fwd)) return 25;
-  if (!dden_w || !dden_b || (drgb && (!drad_w || !drad_b))) return 26;
-  DynArgs a = dyn_args(meta);
-  a.wpack = (const char*)wpack;
-  a.h_pl = h_planes;
-  a.PS = 3 * S;
-  a.rays_d = rays_d; a.ridx = ridx; a.h_appear = h_appear;
-  a.S = S; a.step = step;
-  a.sigma_fwd = sigma_fwd; a.rgb_fwd = rgb_fwd;
-  a.dsigma = dsigma; a.dalpha = dalpha; a.drgb = drgb;
-  a.dh_pl = dh_planes;
-  a.dh_appear = dh_appear;
-  const bool priv = meta->precision == 0;
-  const size_t st = priv ? stage_bytes_per_wave<0>() : stage_bytes_per_wave<1>();
-  const size_t acc = (16904 * 4 + 15) & ~15;
-  const size_t vec_bytes = (size_t)((a.lay.mat[0] + 15) & ~15);
-  const size_t shmem = priv ? vec_bytes + DYN_WAVES_BWD * acc + DYN_WAVES_BWD * st : acc + DYN_WAVES_BWD * st;      // (as nsim_dyn_bwd)
-  const int64_t tiles = (S + 31) / 32;
-  int64_t nb = (tiles + DYN_WAVES_BWD - 1) / DYN_WAVES_BWD;
-  nb = nb > 256 ? 256 : (nb < 1 ? 1 : nb);
-  const int F = 2 * meta->lotd.num_levels, K1 = 80 + meta->n_appear;
-  const int64_t n[4] = {64 * F + 65 * 64, 129, drgb ? 64 * K1 + 4096 + 192 : 0, drgb ? 131 : 0};
-  const int64_t n_all = n[0] + n[1] + n[2] + n[3];
-  int R = 1;
-  float* sc = nsim_grad_scratch_acquire(stream, n_all, nb, &R);
-  if (sc) {
-    a.dst[0] = sc; a.dst[1] = sc + n[0]; a.dst[2] = sc + n[0] + n[1]; a.dst[3] = sc + n[0] + n[1] + n[2];
-    a.rep_stride = n_all;
-    a.rep_mask = R - 1;
-  } else {
-    a.dst[0] = dden_w; a.dst[1] = dden_b; a.dst[2] = drad_w; a.dst[3] = drad_b;
-    a.rep_stride = 0;
-    a.rep_mask = 0;
-  }
-  const dim3 grid((unsigned)nb), block(64 * DYN_WAVES_BWD);
-  if (priv) hipLaunchKernelGGL((k_dyn<0, 1, true>), grid, block, shmem, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((k_dyn<1, 1, true>), grid, block, shmem, (hipStream_t)stream, a);
-  NSIM_CHECK_LAUNCH();
-  if (sc) {
-    nsim_grad_scratch_fold(sc, R, n_all, n[0], n[1], dden_w, dden_b, stream);
-    if (drgb) nsim_grad_scratch_fold(sc + n[0] + n[1], R, n_all, n[2], n[3], drad_w, drad_b, stream);
-    NSIM_CHECK_LAUNCH();
-  }
-  return 0;
+  return dyn_bwd(meta, wpack, h_planes, 0, rays_d, ridx, h_appear, S, step, sigma_fwd, rgb_fwd, dsigma, dalpha, drgb, dh_planes,
+                 dden_w, dden_b, drad_w, drad_b, dh_appear, true, nullptr, stream);
+}
+
+int nsim_dyn_bwd_agg_pose(const NsimNgpMeta* meta, const void* wpack, const float* h_planes, const float* rays_d,
+                          const int64_t* ridx, const float* h_appear, int64_t S, float step, const float* sigma_fwd,
+                          const float* rgb_fwd, const float* dsigma, const float* dalpha, const float* drgb, float* dh_planes,
+                          float* dden_w, float* dden_b, float* drad_w, float* drad_b, float* dh_appear, float* dv, void* stream) {
+  if (S > 0 && !dv) return 4;
+  return dyn_bwd(meta, wpack, h_planes, 0, rays_d, ridx, h_appear, S, step, sigma_fwd, rgb_fwd, dsigma, dalpha, drgb, dh_planes,
+                 dden_w, dden_b, drad_w, drad_b, dh_appear, true, dv, stream);
 }
 
 // ------------------------------------------------------------------------------ scene-flow decoder, warp
@@ -2852,6 +3046,16 @@ int nsim_dyn_warp_bwd(const float* dx4w, int64_t S, float* dflow6, void* stream)
   if (S <= 0) return 0;
   if (!dx4w || !dflow6) return 4;
   hipLaunchKernelGGL(k_dyn_warp_bwd, dim3(nsim_blocks(S, 256)), dim3(256), 0, (hipStream_t)stream, dx4w, S, dflow6);
+  NSIM_CHECK_LAUNCH();
+  return 0;
+}
+
+int nsim_dyn_pose_dx(const float* dx4_dyn, const float* dx4_flow, const float* dx4w_dyn, const float* dx4w_flow, int64_t S,
+                     float* dx, void* stream) {
+  if (S <= 0) return 0;
+  if (!dx) return 4;
+  hipLaunchKernelGGL(k_dyn_pose_dx, dim3(nsim_blocks(S, 256)), dim3(256), 0, (hipStream_t)stream, dx4_dyn, dx4_flow, dx4w_dyn,
+                     dx4w_flow, S, dx);
   NSIM_CHECK_LAUNCH();
   return 0;
 }

@@ -28,7 +28,7 @@ from ..grid_encodings.permuto import PermutoConfig
 from ..model_base import ModelMixin
 from ..spatial import aabb_ray_test
 from .nerf import DensityOccGridAccel
-from .neus import _QueryCfg
+from .neus import _QueryCfg, rays_has_grad
 from .permuto_neus import _PermutoFieldEncoding
 
 
@@ -149,10 +149,13 @@ class DynamicDensityOccGridAccel(DensityOccGridAccel):
 
 class _DynFn(torch.autograd.Function):
     """(table, den_w, den_b, rad_w, rad_b, h_appear) -> (sigma [S], alpha [S] [, rgb [S,3]]) at the lattice points x4 [S,4]:
-    level-major lattice gather, then the fused decoders on the planes."""
+    level-major lattice gather, then the fused decoders on the planes.  ``p_x`` [S,3] | ``p_o``, ``p_d`` [R,3] with ``p_t`` [S]: the
+    points or rays x4 was made of, given only when they carry gradients (pose refinement, ``rays_has_grad``): the backward then
+    returns theirs -- ``nsim_dyn_bwd_pose`` (dv) -> ``nsim_permuto_dx_pts`` -> ``nsim_dyn_pose_dx`` -> ``nsim_ray_grad_reduce``."""
 
     @staticmethod
-    def forward(ctx, model, grid, den_w, den_b, rad_w, rad_b, h_appear, x4, rays_d, ridx, step, with_rgb):
+    def forward(ctx, model, grid, den_w, den_b, rad_w, rad_b, h_appear, x4, rays_d, ridx, step, with_rgb, p_x=None, p_o=None,
+                p_d=None, p_t=None):
         dev = grid.device
         S = x4.shape[0]
         grid16, wpack = model._shadow()
@@ -171,16 +174,18 @@ class _DynFn(torch.autograd.Function):
         ctx.model, ctx.S, ctx.step, ctx.with_rgb = model, S, float(step), with_rgb
         ctx.n_active = int(model.meta.lotd.n_active_levels)
         ctx.ha_shape = h_appear.shape if ha is not None else None
+        ctx.ray_shape = p_o.shape if p_o is not None else (p_d.shape if p_d is not None else None)
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(x4, rays_d, ridx, ha, h_pl if need_bwd else None, sigma, rgb)
+        pose_in = p_x is not None or p_o is not None or p_d is not None       # (the table the forward read: the backward's dx_pts)
+        ctx.save_for_backward(x4, rays_d, ridx, ha, h_pl if need_bwd else None, sigma, rgb, p_t, grid16 if pose_in else None)
         return (sigma, alpha, rgb) if with_rgb else (sigma, alpha)
 
     @staticmethod
     def backward(ctx, g_sigma, g_alpha, g_rgb=None):
         model = ctx.model
-        x4, rays_d, ridx, ha, h_pl, sigma, rgb = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        n_out = 12
+        x4, rays_d, ridx, ha, h_pl, sigma, rgb, p_t, grid16 = ctx.saved_tensors
+        n_out = len(ctx.needs_input_grad)       # 12, or 16 with the pose inputs
+        need = tuple(ctx.needs_input_grad) + (False,) * (16 - n_out)
         if g_sigma is None and g_alpha is None and g_rgb is None:
             return (None,) * n_out
         dev, S = sigma.device, ctx.S
@@ -193,14 +198,29 @@ class _DynFn(torch.autograd.Function):
         gr = g_rgb.float().contiguous() if (ctx.with_rgb and g_rgb is not None) else None
         dha = _lib.zeros(list(ctx.ha_shape), device=dev) if (ha is not None and need[6] and gr is not None) else None
         dgrid = _lib.zeros([model.encoding.cfg.n_params], device=dev) if need[1] else None
-        dh_pl = torch.empty([16, S, 2], dtype=torch.float32, device=dev) if dgrid is not None else None
+        need_x, need_o, need_d = need[12], need[13], need[14]
+        pose = need_x or need_o or need_d
+        dh_pl = torch.empty([16, S, 2], dtype=torch.float32, device=dev) if (dgrid is not None or pose) else None
+        dv = torch.empty([S, 3], dtype=torch.float32, device=dev) if (need_d and gr is not None) else None
+        d_x = d_o = d_d = None
         prev = model._active_levels()           # the backward of a query uses the level mask the query was made with
         model._set_active_raw(ctx.n_active)
         try:
-            _lib.call("nsim_dyn_bwd", model.meta, _lib.ptr(wpack), _lib.ptr(h_pl), S, _lib.ptr(rays_d if gr is not None else None),
-                      _lib.ptr(ridx if gr is not None else None), _lib.ptr(ha), S, ctx.step, _lib.ptr(sigma.detach()),
-                      _lib.ptr(rgb.detach()) if rgb is not None else None, _lib.ptr(gs), _lib.ptr(ga), _lib.ptr(gr),
-                      _lib.ptr(dh_pl), _lib.ptr(dden_w), _lib.ptr(dden_b), _lib.ptr(drad_w), _lib.ptr(drad_b), _lib.ptr(dha))
+            args = (model.meta, _lib.ptr(wpack), _lib.ptr(h_pl), S, _lib.ptr(rays_d if gr is not None else None),
+                    _lib.ptr(ridx if gr is not None else None), _lib.ptr(ha), S, ctx.step, _lib.ptr(sigma.detach()),
+                    _lib.ptr(rgb.detach()) if rgb is not None else None, _lib.ptr(gs), _lib.ptr(ga), _lib.ptr(gr),
+                    _lib.ptr(dh_pl), _lib.ptr(dden_w), _lib.ptr(dden_b), _lib.ptr(drad_w), _lib.ptr(drad_b), _lib.ptr(dha))
+            if dv is not None:
+                _lib.call("nsim_dyn_bwd_pose", *args, _lib.ptr(dv))
+            else:
+                _lib.call("nsim_dyn_bwd", *args)
+            if pose:
+                dx4 = torch.empty([S, 4], dtype=torch.float32, device=dev)
+                _lib.call("nsim_permuto_dx_pts", model.encoding.cfg.pmeta, _lib.ptr(grid16), _lib.ptr(x4), None, S,
+                          _lib.ptr(dh_pl), 0, _lib.ptr(dx4))
+                dx = torch.empty([S, 3], dtype=torch.float32, device=dev)
+                _lib.call("nsim_dyn_pose_dx", _lib.ptr(dx4), None, None, None, S, _lib.ptr(dx))
+                d_x, d_o, d_d = model._reduce_ray_grads(dx, dv, p_t, ridx, ctx.ray_shape, need_x, need_o, need_d)
             if dgrid is not None:
                 valid = torch.ones([S], dtype=torch.uint8, device=dev)
                 _lib.call("nsim_permuto_scatter_pts", model.encoding.cfg.pmeta, _lib.ptr(x4), _lib.ptr(valid), S,
@@ -213,7 +233,7 @@ class _DynFn(torch.autograd.Function):
                 _lib.TIMER.note_units("nsim_permuto_scatter_pts", S)
         if gr is None:      # no consumer of the colour: the radiance network is not part of the graph (None, not zeros)
             drad_w = drad_b = dha = None
-        return (None, dgrid, dden_w, dden_b, drad_w, drad_b, dha) + (None,) * 5
+        return ((None, dgrid, dden_w, dden_b, drad_w, drad_b, dha) + (None,) * 5 + (d_x, d_o, d_d, None))[:n_out]
 
 
 FLOW_KEYS = ("flow_fwd", "flow_fwd_pred_bwd", "flow_bwd", "flow_bwd_pred_fwd")
@@ -228,10 +248,14 @@ class _DynFlowFn(torch.autograd.Function):
     (sigma [S], alpha [S], rgb [S,3] | None, flow6 [S,6], pred6 [2S,6]) at the lattice points x4 [S,4].  Flow at x -> warp -> flow at
     the 2S warped points -> dynamic gather at the 3S points -> aggregating decoder.  flow6 = (flow_fwd | flow_bwd) at x; pred6 rows
     0..S are the flow at (x+, w+), rows S..2S at (x-, w-).  The backward carries d loss / d x+- from both lattices into the flow at
-    x (``nsim_permuto_dx_pts`` -> ``nsim_dyn_warp_bwd``); x itself, rays and times get no gradient."""
+    x (``nsim_permuto_dx_pts`` -> ``nsim_dyn_warp_bwd``); times get no gradient.  ``p_x`` | ``p_o``, ``p_d``, ``p_t`` as in
+    ``_DynFn``: with them the backward also returns the gradient to the points or rays -- per sample the position parts of the
+    dynamic lattice's gradient at x, of both lattices' at x+ and x- (d x+- / d x = I) and of the flow lattice's at x under the
+    total dflow6 (``nsim_dyn_pose_dx``), dv from ``nsim_dyn_bwd_agg_pose``; then ``nsim_ray_grad_reduce``."""
 
     @staticmethod
-    def forward(ctx, model, grid, den_w, den_b, rad_w, rad_b, h_appear, fgrid, flow_w, flow_b, x4, rays_d, ridx, step, with_rgb):
+    def forward(ctx, model, grid, den_w, den_b, rad_w, rad_b, h_appear, fgrid, flow_w, flow_b, x4, rays_d, ridx, step, with_rgb,
+                p_x=None, p_o=None, p_d=None, p_t=None):
         dev, S = grid.device, x4.shape[0]
         grid16, wpack = model._shadow()
         fgrid16, fwpack = model._flow_shadow()
@@ -265,7 +289,8 @@ class _DynFlowFn(torch.autograd.Function):
         ctx.ha_shape = h_appear.shape if ha is not None else None
         ctx.set_materialize_grads(False)
         need_bwd = any(ctx.needs_input_grad)
-        ctx.save_for_backward(x4all, rays_d, ridx, ha, sigma, rgb, *((h_pl, hf, hfw, grid16, fgrid16) if need_bwd else ()))
+        ctx.ray_shape = p_o.shape if p_o is not None else (p_d.shape if p_d is not None else None)
+        ctx.save_for_backward(x4all, rays_d, ridx, ha, sigma, rgb, p_t, *((h_pl, hf, hfw, grid16, fgrid16) if need_bwd else ()))
         if with_rgb:
             return sigma, alpha, rgb, flow6, pred6
         return sigma, alpha, flow6, pred6
@@ -274,11 +299,14 @@ class _DynFlowFn(torch.autograd.Function):
     def backward(ctx, g_sigma, g_alpha, *rest):
         model, S = ctx.model, ctx.S
         g_rgb, g_flow6, g_pred6 = (rest if ctx.with_rgb else (None,) + tuple(rest))
-        n_out = 15
+        n_out = len(ctx.needs_input_grad)       # 15, or 19 with the pose inputs
         if all(g is None for g in (g_sigma, g_alpha, g_rgb, g_flow6, g_pred6)):
             return (None,) * n_out
-        x4all, rays_d, ridx, ha, sigma, rgb, h_pl, hf, hfw, grid16, fgrid16 = ctx.saved_tensors
+        x4all, rays_d, ridx, ha, sigma, rgb, p_t, h_pl, hf, hfw, grid16, fgrid16 = ctx.saved_tensors
         dev = sigma.device
+        need_x, need_o, need_d = (tuple(ctx.needs_input_grad) + (False,) * 4)[15:18]
+        pose = need_x or need_o or need_d
+        dv = dx_a = dx_dyn = dx_flow = None
         x4, x4w = x4all[:S], x4all[S:]
         wpack, fwpack = model._shadow()[1], model._flow_shadow()[1]
         fm, dm = model.flow_encoding.cfg.pmeta, model.encoding.cfg.pmeta
@@ -302,10 +330,18 @@ class _DynFlowFn(torch.autograd.Function):
             prev = model._active_levels()       # the backward of a query uses the level mask the query was made with
             model._set_active_raw(ctx.n_active)
             try:
-                _lib.call("nsim_dyn_bwd_agg", model.meta, _lib.ptr(wpack), _lib.ptr(h_pl), _lib.ptr(rays_d if gr is not None else None),
-                          _lib.ptr(ridx if gr is not None else None), _lib.ptr(ha), S, ctx.step, _lib.ptr(sigma.detach()),
-                          _lib.ptr(rgb.detach()) if rgb is not None else None, _lib.ptr(gs), _lib.ptr(ga), _lib.ptr(gr),
-                          _lib.ptr(dh_pl), _lib.ptr(dden_w), _lib.ptr(dden_b), _lib.ptr(drad_w), _lib.ptr(drad_b), _lib.ptr(dha))
+                args = (model.meta, _lib.ptr(wpack), _lib.ptr(h_pl), _lib.ptr(rays_d if gr is not None else None),
+                        _lib.ptr(ridx if gr is not None else None), _lib.ptr(ha), S, ctx.step, _lib.ptr(sigma.detach()),
+                        _lib.ptr(rgb.detach()) if rgb is not None else None, _lib.ptr(gs), _lib.ptr(ga), _lib.ptr(gr),
+                        _lib.ptr(dh_pl), _lib.ptr(dden_w), _lib.ptr(dden_b), _lib.ptr(drad_w), _lib.ptr(drad_b), _lib.ptr(dha))
+                if need_d and gr is not None:
+                    dv = torch.empty([S, 3], dtype=torch.float32, device=dev)
+                    _lib.call("nsim_dyn_bwd_agg_pose", *args, _lib.ptr(dv))
+                else:
+                    _lib.call("nsim_dyn_bwd_agg", *args)
+                if pose:        # the un-warped rows of the same planes
+                    dx_a = torch.empty([S, 4], dtype=torch.float32, device=dev)
+                    _lib.call("nsim_permuto_dx_pts", dm, _lib.ptr(grid16), _lib.ptr(x4), None, S, _lib.ptr(dh_pl), 3 * S, _lib.ptr(dx_a))
                 _lib.call("nsim_permuto_scatter_pts", dm, _lib.ptr(x4all), _lib.ptr(_all_valid(3 * S, dev)), 3 * S, _lib.ptr(dh_pl),
                           _lib.ptr(dgrid))
                 # the plane sets of the warped points start S rows into every level of the [16][3S][2] buffer
@@ -329,9 +365,16 @@ class _DynFlowFn(torch.autograd.Function):
         _lib.call("nsim_flow_bwd", Lf, prec, _lib.ptr(fwpack), _lib.ptr(hf), 0, S, _lib.ptr(dflow6), _lib.ptr(dh_f), _lib.ptr(dflow_w),
                   _lib.ptr(dflow_b))
         _lib.call("nsim_permuto_scatter_pts", fm, _lib.ptr(x4), _lib.ptr(_all_valid(S, dev)), S, _lib.ptr(dh_f), _lib.ptr(dfgrid))
+        d_x = d_o = d_d = None
+        if pose:            # the total dflow6 pulled back through the flow field at x, and the sum of the position parts
+            dx_f = torch.empty([S, 4], dtype=torch.float32, device=dev)
+            _lib.call("nsim_permuto_dx_pts", fm, _lib.ptr(fgrid16), _lib.ptr(x4), None, S, _lib.ptr(dh_f), 0, _lib.ptr(dx_f))
+            dx = torch.empty([S, 3], dtype=torch.float32, device=dev)
+            _lib.call("nsim_dyn_pose_dx", _lib.ptr(dx_a), _lib.ptr(dx_f), _lib.ptr(dx_dyn), _lib.ptr(dx_flow), S, _lib.ptr(dx))
+            d_x, d_o, d_d = model._reduce_ray_grads(dx, dv, p_t, ridx, ctx.ray_shape, need_x, need_o, need_d)
         if gr is None:      # no consumer of the colour: the radiance network is not part of the graph (None, not zeros)
             drad_w = drad_b = dha = None
-        return (None, dgrid, dden_w, dden_b, drad_w, drad_b, dha, dfgrid, dflow_w, dflow_b) + (None,) * 5
+        return ((None, dgrid, dden_w, dden_b, drad_w, drad_b, dha, dfgrid, dflow_w, dflow_b) + (None,) * 5 + (d_x, d_o, d_d, None))[:n_out]
 
 
 class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
@@ -549,15 +592,29 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
             self._fwpack_versions = vers
         return fgrid16, self._fwpack
 
-    def _query(self, h_appear, x4, rays_d, ridx, step, with_rgb):
+    @staticmethod
+    def _reduce_ray_grads(dx, dv, t, ridx, ray_shape, need_x, need_o, need_d):
+        """per-sample dx [S,3] (and dv) -> (d_x, d_o, d_d): dx itself for points, else the per-ray sums of
+        ``nsim_ray_grad_reduce`` into zero-filled rows (a ray without samples gets an exact zero row)"""
+        if need_x:
+            return dx, None, None
+        d_o = torch.zeros(list(ray_shape), dtype=torch.float32, device=dx.device) if need_o else None
+        d_d = torch.zeros(list(ray_shape), dtype=torch.float32, device=dx.device) if need_d else None
+        _lib.call("nsim_ray_grad_reduce", _lib.ptr(dx), _lib.ptr(dv), _lib.ptr(t), _lib.ptr(ridx), dx.shape[0], _lib.ptr(d_o),
+                  _lib.ptr(d_d))
+        return None, d_o, d_d
+
+    def _query(self, h_appear, x4, rays_d, ridx, step, with_rgb, pose=(None, None, None, None)):
         """-> (sigma, alpha, rgb | None, flow dict | None): the plain decoder, or the flow-aggregated one with its four flow
-        tensors ([S,3] each: the keys app/loss/flow.py reads)"""
+        tensors ([S,3] each: the keys app/loss/flow.py reads).  ``pose`` = (x, rays_o, rays_d, t): the points or rays x4 was made
+        of where they carry gradients."""
         if not self.use_flow:
             outs = _DynFn.apply(self, self.encoding.flattened_params, self.den_w, self.den_b, self.rad_w, self.rad_b, h_appear,
-                                x4, rays_d, ridx, step, with_rgb)
+                                x4, rays_d, ridx, step, with_rgb, *pose)
             return outs[0], outs[1], (outs[2] if with_rgb else None), None
         outs = _DynFlowFn.apply(self, self.encoding.flattened_params, self.den_w, self.den_b, self.rad_w, self.rad_b, h_appear,
-                                self.flow_encoding.flattened_params, self.flow_w, self.flow_b, x4, rays_d, ridx, step, with_rgb)
+                                self.flow_encoding.flattened_params, self.flow_w, self.flow_b, x4, rays_d, ridx, step, with_rgb,
+                                *pose)
         flow6, pred6 = outs[-2], outs[-1]
         S = x4.shape[0]
         flow = dict(flow_fwd=flow6[:, :3], flow_fwd_pred_bwd=pred6[:S, 3:], flow_bwd=flow6[:, 3:], flow_bwd_pred_fwd=pred6[S:, :3])
@@ -583,10 +640,12 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
         return float((qp.get("march_cfg") or {}).get("step_size", 0.1))
 
     # ------------------------------------------------------------------ point queries
-    def forward_density(self, x: torch.Tensor, ts: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """sigma at x [..., 3] (object coordinates) and times ts [...], with gradient to the table and the dynamic decoder."""
-        if x.requires_grad:
-            raise NotImplementedError("x.requires_grad: gradients to positions (pose refinement) are not built for this model")
+    def forward_density(self, x: torch.Tensor, ts: torch.Tensor, x_has_grad: bool = False) -> Dict[str, torch.Tensor]:
+        """sigma at x [..., 3] (object coordinates) and times ts [...], with gradient to the table and the dynamic decoder -- and,
+        with ``x_has_grad=True``, to x (pose refinement)."""
+        if x.requires_grad and not x_has_grad:
+            raise NotImplementedError("x.requires_grad: gradients to positions (pose refinement) are not built for this model "
+                                      "unless asked for: forward_density(x, ts, x_has_grad=True)")
         if ts.requires_grad:
             raise NotImplementedError("ts.requires_grad: gradients to the time input are not built for this model")
         shape = x.shape[:-1]
@@ -599,7 +658,8 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
             return ret
         w = self.time_coord(ts.expand(shape).reshape(-1))
         x4 = self._points(w, S, x=xf)
-        sigma, _, _, flow = self._query(None, x4, None, None, self._step(), False)
+        pose = (x.float().reshape(-1, 3), None, None, None) if x.requires_grad else (None,) * 4
+        sigma, _, _, flow = self._query(None, x4, None, None, self._step(), False, pose)
         ret = dict(sigma=sigma.reshape(shape))
         if flow is not None:
             ret.update({k: v.reshape(*shape, 3) for k, v in flow.items()})
@@ -664,10 +724,12 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
             return empty()
         if ray_tested.get("rays_ts", None) is None:
             raise ValueError("ray_tested['rays_ts'] is missing: a time-conditioned model (use_ts) needs the time of every ray")
+        has_grad = rays_has_grad(self.ray_query_cfg, cfg)
         for k in ("rays_o", "rays_d", "rays_ts"):
-            if ray_tested[k].requires_grad:
+            if ray_tested[k].requires_grad and not (has_grad and k != "rays_ts"):
                 raise NotImplementedError(f"ray_tested[{k!r}].requires_grad: gradients to rays and times (pose refinement) are "
-                                          f"not built for this model")
+                                          f"not built for this model" + (" unless ray_query_cfg.query_param.rays_has_grad is set"
+                                                                         if k != "rays_ts" else ""))
         o = ray_tested["rays_o"].detach().float().contiguous()
         d = ray_tested["rays_d"].detach().float().contiguous()
         ts = ray_tested["rays_ts"].detach().float().reshape(-1).contiguous()
@@ -702,7 +764,11 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
         if with_rgb and self.n_appear and h_appear is None:
             raise ValueError("ray_tested['rays_h_appear'] is missing: radiance_cfg.n_appear_embedding is "
                              f"{self.n_appear}, the radiance decoder reads a per-ray appearance code")
-        sigma, alpha, rgb, flow = self._query(h_appear, x4, d, ridx, step, bool(with_rgb))
+        # (marching, the occupancy grid, the slice choice and the sample depths saw detached rays; the samples o + t d carry the graph)
+        ro, rd = ray_tested["rays_o"], ray_tested["rays_d"]
+        pose = (None, ro.float() if ro.requires_grad else None, rd.float() if rd.requires_grad else None, t) \
+            if (ro.requires_grad or rd.requires_grad) else (None,) * 4
+        sigma, alpha, rgb, flow = self._query(h_appear, x4, d, ridx, step, bool(with_rgb), pose)
         outs = (sigma, alpha, rgb)
         if acc.collect_armed:
             acc.collect(sigma, slices, rays=(o, d, t, ridx))

@@ -19,7 +19,7 @@ from ..graphics import pack_ops as po
 from ..grid_encodings.lotd import LoTDConfig, LoTDEncoding
 from ..model_base import ModelMixin
 from ..spatial import aabb_ray_test
-from .neus import OccGridAccel, _QueryCfg
+from .neus import OccGridAccel, _QueryCfg, rays_has_grad
 
 
 class DensityOccGridAccel(OccGridAccel):
@@ -90,7 +90,9 @@ class DensityOccGridAccel(OccGridAccel):
 
 class _NgpFn(torch.autograd.Function):
     """(table, den_w, den_b, rad_w, rad_b, h_appear) -> (sigma [S], alpha [S] [, rgb [S,3]]) at x [S,3] or at
-    rays_o[ridx] + t rays_d[ridx]: level-major gather, then the fused decoders on the planes."""
+    rays_o[ridx] + t rays_d[ridx]: level-major gather, then the fused decoders on the planes.  When x, or rays_o / rays_d,
+    require grad (pose refinement; the model opts in with ``rays_has_grad``) the backward also returns their gradients:
+    ``nsim_ngp_bwd_pose`` -> ``nsim_lotd_dx_lm`` -> ``nsim_ray_grad_reduce``; t is a constant of the step."""
 
     @staticmethod
     def forward(ctx, model, grid, den_w, den_b, rad_w, rad_b, h_appear, x, rays_o, rays_d, t, ridx, step, with_rgb):
@@ -113,13 +115,14 @@ class _NgpFn(torch.autograd.Function):
         ctx.n_active = int(model.meta.lotd.n_active_levels)
         ctx.ha_shape = h_appear.shape if ha is not None else None
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(x, rays_o, rays_d, t, ridx, ha, h_pl if need_bwd else None, sigma, rgb)
+        pose_in = any(ctx.needs_input_grad[7:10])       # (the table the forward read: the backward's nsim_lotd_dx_lm)
+        ctx.save_for_backward(x, rays_o, rays_d, t, ridx, ha, h_pl if need_bwd else None, sigma, rgb, grid16 if pose_in else None)
         return (sigma, alpha, rgb) if with_rgb else (sigma, alpha)
 
     @staticmethod
     def backward(ctx, g_sigma, g_alpha, g_rgb=None):
         model = ctx.model
-        x, rays_o, rays_d, t, ridx, ha, h_pl, sigma, rgb = ctx.saved_tensors
+        x, rays_o, rays_d, t, ridx, ha, h_pl, sigma, rgb, grid16 = ctx.saved_tensors
         need = ctx.needs_input_grad
         n_out = 14
         if g_sigma is None and g_alpha is None and g_rgb is None:
@@ -134,15 +137,33 @@ class _NgpFn(torch.autograd.Function):
         gr = g_rgb.float().contiguous() if (ctx.with_rgb and g_rgb is not None) else None
         dha = _lib.zeros(list(ctx.ha_shape), device=dev) if (ha is not None and need[6] and gr is not None) else None
         dgrid = _lib.zeros([model.encoding.cfg.n_params], device=dev) if need[1] else None
-        dh_pl = torch.empty([16, S, 2], dtype=torch.float32, device=dev) if dgrid is not None else None
+        need_x, need_o, need_d = need[7] and x is not None, need[8] and x is None, need[9] and x is None
+        pose = need_x or need_o or need_d
+        dh_pl = torch.empty([16, S, 2], dtype=torch.float32, device=dev) if (dgrid is not None or pose) else None
+        dx = torch.empty([S, 3], dtype=torch.float32, device=dev) if pose else None
+        dv = torch.empty([S, 3], dtype=torch.float32, device=dev) if (need_d and gr is not None) else None
+        d_x = d_o = d_d = None
         meta = model.meta
         prev = int(meta.lotd.n_active_levels)       # the backward of a query uses the level mask the query was made with
         meta.lotd.n_active_levels = ctx.n_active
         try:
-            _lib.call("nsim_ngp_bwd", meta, _lib.ptr(wpack), _lib.ptr(h_pl), ctx.PS, _lib.ptr(x), _lib.ptr(rays_o),
-                      _lib.ptr(rays_d), _lib.ptr(t), _lib.ptr(ridx), _lib.ptr(ha), S, ctx.step, _lib.ptr(sigma.detach()),
-                      _lib.ptr(rgb.detach()) if rgb is not None else None, _lib.ptr(gs), _lib.ptr(ga), _lib.ptr(gr),
-                      _lib.ptr(dh_pl), _lib.ptr(dden_w), _lib.ptr(dden_b), _lib.ptr(drad_w), _lib.ptr(drad_b), _lib.ptr(dha))
+            args = (meta, _lib.ptr(wpack), _lib.ptr(h_pl), ctx.PS, _lib.ptr(x), _lib.ptr(rays_o),
+                    _lib.ptr(rays_d), _lib.ptr(t), _lib.ptr(ridx), _lib.ptr(ha), S, ctx.step, _lib.ptr(sigma.detach()),
+                    _lib.ptr(rgb.detach()) if rgb is not None else None, _lib.ptr(gs), _lib.ptr(ga), _lib.ptr(gr),
+                    _lib.ptr(dh_pl), _lib.ptr(dden_w), _lib.ptr(dden_b), _lib.ptr(drad_w), _lib.ptr(drad_b), _lib.ptr(dha))
+            if pose:
+                _lib.call("nsim_ngp_bwd_pose", *args, _lib.ptr(dx), _lib.ptr(dv))
+                _lib.call("nsim_lotd_dx_lm", meta.lotd, _lib.ptr(grid16), _lib.ptr(x), _lib.ptr(rays_o),
+                          _lib.ptr(rays_d), _lib.ptr(t), _lib.ptr(ridx), S, _lib.ptr(dh_pl), S, _lib.ptr(dx), _lib.ptr(dx))
+                if need_x:
+                    d_x = dx
+                else:       # (zero-filled: a ray without samples gets an exact zero row)
+                    d_o = torch.zeros_like(rays_o) if need_o else None
+                    d_d = torch.zeros_like(rays_d) if need_d else None
+                    _lib.call("nsim_ray_grad_reduce", _lib.ptr(dx), _lib.ptr(dv), _lib.ptr(t), _lib.ptr(ridx), S,
+                              _lib.ptr(d_o), _lib.ptr(d_d))
+            else:
+                _lib.call("nsim_ngp_bwd", *args)
             if dgrid is not None:
                 _lib.call("nsim_lotd_scatter", meta.lotd, _lib.ptr(x), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t),
                           _lib.ptr(ridx), None, S, _lib.ptr(dh_pl), _lib.ptr(dh_pl), None, _lib.ptr(dgrid), 0, 0)
@@ -155,7 +176,7 @@ class _NgpFn(torch.autograd.Function):
                 _lib.TIMER.note_units("nsim_lotd_scatter", S)
         if gr is None:      # no consumer of the colour: the radiance network is not part of the graph (None, not zeros)
             drad_w = drad_b = dha = None
-        return (None, dgrid, dden_w, dden_b, drad_w, drad_b, dha) + (None,) * 7
+        return (None, dgrid, dden_w, dden_b, drad_w, drad_b, dha, d_x, d_o, d_d) + (None,) * 4
 
 
 class LoTDNeRFModel(ModelMixin, nn.Module):
@@ -344,12 +365,14 @@ class LoTDNeRFModel(ModelMixin, nn.Module):
         return float((qp.get("march_cfg") or {}).get("step_size", 0.1))
 
     # ------------------------------------------------------------------ point queries
-    def forward_density(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """sigma at x [..., 3] (object coordinates), with gradient to the table and the density decoder."""
-        if x.requires_grad:
-            raise NotImplementedError("x.requires_grad: gradients to positions (pose refinement) are not built for this model")
+    def forward_density(self, x: torch.Tensor, x_has_grad: bool = False) -> Dict[str, torch.Tensor]:
+        """sigma at x [..., 3] (object coordinates), with gradient to the table and the density decoder -- and, with
+        ``x_has_grad=True``, to x (pose refinement)."""
+        if x.requires_grad and not x_has_grad:
+            raise NotImplementedError("x.requires_grad: gradients to positions (pose refinement) are not built for this model "
+                                      "unless asked for: forward_density(x, x_has_grad=True)")
         shape = x.shape[:-1]
-        xf = x.detach().float().reshape(-1, 3).contiguous()
+        xf = x.float().reshape(-1, 3).contiguous() if (x_has_grad and x.requires_grad) else x.detach().float().reshape(-1, 3).contiguous()
         if xf.shape[0] == 0:
             return dict(sigma=torch.zeros(shape, dtype=torch.float32, device=xf.device))
         sigma, _ = _NgpFn.apply(self, self.encoding.flattened_params, self.den_w, self.den_b, self.rad_w, self.rad_b, None,
@@ -405,12 +428,16 @@ class LoTDNeRFModel(ModelMixin, nn.Module):
         R = int(ray_tested["num_rays"])
         if R == 0:
             return empty()
+        has_grad = rays_has_grad(self.ray_query_cfg, cfg)
         for k in ("rays_o", "rays_d"):
-            if ray_tested[k].requires_grad:
+            if ray_tested[k].requires_grad and not has_grad:
                 raise NotImplementedError(f"ray_tested[{k!r}].requires_grad: gradients to rays (pose refinement) are not built "
-                                          f"for this model")
+                                          f"for this model unless ray_query_cfg.query_param.rays_has_grad is set")
+        # marching, the occupancy grid and the sample depths see detached rays; the decoders' samples o + t d carry the graph
         o = ray_tested["rays_o"].detach().float().contiguous()
         d = ray_tested["rays_d"].detach().float().contiguous()
+        o_g = ray_tested["rays_o"].float().contiguous() if ray_tested["rays_o"].requires_grad else o
+        d_g = ray_tested["rays_d"].float().contiguous() if ray_tested["rays_d"].requires_grad else d
         near, far = ray_tested["near"].detach().float().contiguous(), ray_tested["far"].detach().float().contiguous()
         dev = o.device
         jitter = cfg.get("_jitter", None)
@@ -437,7 +464,7 @@ class LoTDNeRFModel(ModelMixin, nn.Module):
             raise ValueError("ray_tested['rays_h_appear'] is missing: radiance_decoder_cfg.n_appear_embedding is "
                              f"{self.n_appear}, the radiance decoder reads a per-ray appearance code")
         outs = _NgpFn.apply(self, self.encoding.flattened_params, self.den_w, self.den_b, self.rad_w, self.rad_b, h_appear,
-                            None, o, d, t, ridx, step, bool(with_rgb))
+                            None, o_g, d_g, t, ridx, step, bool(with_rgb))
         sigma, alpha = outs[0], outs[1]
         if self.accel.collect_armed:
             self.accel.collect(sigma=sigma, rays=(o, d, t, ridx))

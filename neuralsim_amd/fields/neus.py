@@ -524,6 +524,14 @@ class _QueryCfg(dict):
         self[k] = v
 
 
+def rays_has_grad(ray_query_cfg: dict, cfg: dict = None) -> bool:
+    """``ray_query_cfg.query_param.rays_has_grad`` of the density models (named after ``nablas_has_grad``): the rays of a query,
+    or the points of ``forward_density(x_has_grad=True)``, may carry gradients -- a config with ``LearnableParams`` sets it.  Read
+    per call from ``config``, else from the model's own ``ray_query_cfg``."""
+    qp = (cfg or {}).get("query_param", None) or (ray_query_cfg or {}).get("query_param", {})
+    return bool((qp or {}).get("rays_has_grad", False))
+
+
 class LoTDNeuSModel(ModelMixin, nn.Module):
     is_ray_query_supported = True
 

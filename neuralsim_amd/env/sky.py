@@ -102,14 +102,9 @@ class SimpleSky(ModelMixin, nn.Module):
 
     def _packed(self):
         vers = (self.w._version, self.b._version, self.meta.precision, str(self.w.device))
-        if self._wpack is None or self._wpack_versions != vers:
-            nbytes = int(_lib.get_lib().nsim_sky_wpack_bytes(self.meta))
-            if self._wpack is None or self._wpack.numel() != nbytes or self._wpack.device != self.w.device:
-                self._wpack = torch.zeros([nbytes], dtype=torch.uint8, device=self.w.device)
-            _lib.call("nsim_sky_pack_weights", self.meta, _lib.ptr(self.w.detach()), _lib.ptr(self.b.detach()),
-                      _lib.ptr(self._wpack))
-            self._wpack_versions = vers
-        return self._wpack
+        return self._weight_pack(
+            "_wpack", vers, self.w.device, lambda: _lib.get_lib().nsim_sky_wpack_bytes(self.meta),
+            lambda buf: _lib.call("nsim_sky_pack_weights", self.meta, _lib.ptr(self.w.detach()), _lib.ptr(self.b.detach()), _lib.ptr(buf)))
 
     def forward(self, v: torch.Tensor, *, h_appear: torch.Tensor = None) -> torch.Tensor:
         """v [..., 3] unit view directions, h_appear [..., n_appear] -> rgb [..., 3]."""

@@ -20,15 +20,13 @@ variant's executable spec.
 from typing import Dict, Optional
 
 import torch
-import torch.nn as nn
 
 from .. import _lib
-from ..graphics import pack_ops as po
 from ..grid_encodings.permuto import PermutoConfig
-from ..model_base import ModelMixin
 from ..spatial import aabb_ray_test
+from .density_base import MarchedDensityModel, f32c, reduce_ray_grads, zero_grads_like
 from .nerf import DensityOccGridAccel
-from .neus import _QueryCfg, rays_has_grad
+from .neus import _QueryCfg
 from .permuto_neus import _PermutoFieldEncoding
 
 
@@ -190,12 +188,8 @@ class _DynFn(torch.autograd.Function):
             return (None,) * n_out
         dev, S = sigma.device, ctx.S
         wpack = model._shadow()[1]
-        F, NA = model.encoding.cfg.out_features, model.n_appear
-        n_dw, n_db, n_rw, n_rb = 64 * F + 65 * 64, 129, 64 * (80 + NA) + 4096 + 192, 131
-        dden_w, dden_b, drad_w, drad_b = _lib.zeros([n_dw + n_db + n_rw + n_rb], device=dev).split([n_dw, n_db, n_rw, n_rb])
-        gs = g_sigma.float().contiguous() if g_sigma is not None else None
-        ga = g_alpha.float().contiguous() if g_alpha is not None else None
-        gr = g_rgb.float().contiguous() if (ctx.with_rgb and g_rgb is not None) else None
+        dden_w, dden_b, drad_w, drad_b = zero_grads_like(model.den_w, model.den_b, model.rad_w, model.rad_b)
+        gs, ga, gr = f32c(g_sigma), f32c(g_alpha), f32c(g_rgb if ctx.with_rgb else None)
         dha = _lib.zeros(list(ctx.ha_shape), device=dev) if (ha is not None and need[6] and gr is not None) else None
         dgrid = _lib.zeros([model.encoding.cfg.n_params], device=dev) if need[1] else None
         need_x, need_o, need_d = need[12], need[13], need[14]
@@ -203,9 +197,7 @@ class _DynFn(torch.autograd.Function):
         dh_pl = torch.empty([16, S, 2], dtype=torch.float32, device=dev) if (dgrid is not None or pose) else None
         dv = torch.empty([S, 3], dtype=torch.float32, device=dev) if (need_d and gr is not None) else None
         d_x = d_o = d_d = None
-        prev = model._active_levels()           # the backward of a query uses the level mask the query was made with
-        model._set_active_raw(ctx.n_active)
-        try:
+        with model._level_mask(ctx.n_active):
             args = (model.meta, _lib.ptr(wpack), _lib.ptr(h_pl), S, _lib.ptr(rays_d if gr is not None else None),
                     _lib.ptr(ridx if gr is not None else None), _lib.ptr(ha), S, ctx.step, _lib.ptr(sigma.detach()),
                     _lib.ptr(rgb.detach()) if rgb is not None else None, _lib.ptr(gs), _lib.ptr(ga), _lib.ptr(gr),
@@ -220,13 +212,10 @@ class _DynFn(torch.autograd.Function):
                           _lib.ptr(dh_pl), 0, _lib.ptr(dx4))
                 dx = torch.empty([S, 3], dtype=torch.float32, device=dev)
                 _lib.call("nsim_dyn_pose_dx", _lib.ptr(dx4), None, None, None, S, _lib.ptr(dx))
-                d_x, d_o, d_d = model._reduce_ray_grads(dx, dv, p_t, ridx, ctx.ray_shape, need_x, need_o, need_d)
+                d_x, d_o, d_d = reduce_ray_grads(dx, dv, p_t, ridx, ctx.ray_shape, need_x, need_o, need_d)
             if dgrid is not None:
-                valid = torch.ones([S], dtype=torch.uint8, device=dev)
-                _lib.call("nsim_permuto_scatter_pts", model.encoding.cfg.pmeta, _lib.ptr(x4), _lib.ptr(valid), S,
+                _lib.call("nsim_permuto_scatter_pts", model.encoding.cfg.pmeta, _lib.ptr(x4), _lib.ptr(_all_valid(S, dev)), S,
                           _lib.ptr(dh_pl), _lib.ptr(dgrid))
-        finally:
-            model._set_active_raw(prev)
         if _lib.TIMER is not None:
             _lib.TIMER.note_units("nsim_dyn_bwd", S)
             if dgrid is not None:
@@ -311,25 +300,19 @@ class _DynFlowFn(torch.autograd.Function):
         wpack, fwpack = model._shadow()[1], model._flow_shadow()[1]
         fm, dm = model.flow_encoding.cfg.pmeta, model.encoding.cfg.pmeta
         Lf, prec = int(fm.num_levels), int(model.meta.precision)
-        F, NA = model.encoding.cfg.out_features, model.n_appear
-        n_dw, n_db, n_rw, n_rb = 64 * F + 65 * 64, 129, 64 * (80 + NA) + 4096 + 192, 131
-        dden_w, dden_b, drad_w, drad_b = _lib.zeros([n_dw + n_db + n_rw + n_rb], device=dev).split([n_dw, n_db, n_rw, n_rb])
-        dflow_w, dflow_b = _lib.zeros([model.flow_w.numel() + model.flow_b.numel()], device=dev).split(
-            [model.flow_w.numel(), model.flow_b.numel()])
+        dden_w, dden_b, drad_w, drad_b = zero_grads_like(model.den_w, model.den_b, model.rad_w, model.rad_b)
+        dflow_w, dflow_b = zero_grads_like(model.flow_w, model.flow_b)
         dgrid = _lib.zeros([model.encoding.cfg.n_params], device=dev)
         dfgrid = _lib.zeros([model.flow_encoding.cfg.n_params], device=dev)
         dflow6 = g_flow6.float().contiguous().clone() if g_flow6 is not None else _lib.zeros([S, 6], device=dev)
-        gr = g_rgb.float().contiguous() if (ctx.with_rgb and g_rgb is not None) else None
+        gr = f32c(g_rgb if ctx.with_rgb else None)
         dha = _lib.zeros(list(ctx.ha_shape), device=dev) if (ha is not None and ctx.needs_input_grad[6] and gr is not None) else None
         dense_grad = not (g_sigma is None and g_alpha is None and gr is None)
         if dense_grad:
-            gs = g_sigma.float().contiguous() if g_sigma is not None else None
-            ga = g_alpha.float().contiguous() if g_alpha is not None else None
+            gs, ga = f32c(g_sigma), f32c(g_alpha)
             dh_pl = torch.empty([16, 3 * S, 2], dtype=torch.float32, device=dev)
             dx_dyn = torch.empty([2 * S, 4], dtype=torch.float32, device=dev)
-            prev = model._active_levels()       # the backward of a query uses the level mask the query was made with
-            model._set_active_raw(ctx.n_active)
-            try:
+            with model._level_mask(ctx.n_active):
                 args = (model.meta, _lib.ptr(wpack), _lib.ptr(h_pl), _lib.ptr(rays_d if gr is not None else None),
                         _lib.ptr(ridx if gr is not None else None), _lib.ptr(ha), S, ctx.step, _lib.ptr(sigma.detach()),
                         _lib.ptr(rgb.detach()) if rgb is not None else None, _lib.ptr(gs), _lib.ptr(ga), _lib.ptr(gr),
@@ -347,8 +330,6 @@ class _DynFlowFn(torch.autograd.Function):
                 # the plane sets of the warped points start S rows into every level of the [16][3S][2] buffer
                 _lib.call("nsim_permuto_dx_pts", dm, _lib.ptr(grid16), _lib.ptr(x4w), None, 2 * S, _lib.ptr(dh_pl.view(-1)[2 * S:]),
                           3 * S, _lib.ptr(dx_dyn))
-            finally:
-                model._set_active_raw(prev)
             _lib.call("nsim_dyn_warp_bwd", _lib.ptr(dx_dyn), S, _lib.ptr(dflow6))
             if _lib.TIMER is not None:
                 _lib.TIMER.note_units("nsim_dyn_bwd_agg", S)
@@ -371,24 +352,16 @@ class _DynFlowFn(torch.autograd.Function):
             _lib.call("nsim_permuto_dx_pts", fm, _lib.ptr(fgrid16), _lib.ptr(x4), None, S, _lib.ptr(dh_f), 0, _lib.ptr(dx_f))
             dx = torch.empty([S, 3], dtype=torch.float32, device=dev)
             _lib.call("nsim_dyn_pose_dx", _lib.ptr(dx_a), _lib.ptr(dx_f), _lib.ptr(dx_dyn), _lib.ptr(dx_flow), S, _lib.ptr(dx))
-            d_x, d_o, d_d = model._reduce_ray_grads(dx, dv, p_t, ridx, ctx.ray_shape, need_x, need_o, need_d)
+            d_x, d_o, d_d = reduce_ray_grads(dx, dv, p_t, ridx, ctx.ray_shape, need_x, need_o, need_d)
         if gr is None:      # no consumer of the colour: the radiance network is not part of the graph (None, not zeros)
             drad_w = drad_b = dha = None
         return ((None, dgrid, dden_w, dden_b, drad_w, drad_b, dha, dfgrid, dflow_w, dflow_b) + (None,) * 5 + (d_x, d_o, d_d, None))[:n_out]
 
 
-class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
-    is_ray_query_supported = True
+class EmerNeRFOnlyDynamicModel(MarchedDensityModel):
     use_ts = True
     use_view_dirs = True
-
-    @property
-    def ray_query_cfg(self):
-        return self._ray_query_cfg
-
-    @ray_query_cfg.setter
-    def ray_query_cfg(self, cfg):
-        object.__setattr__(self, "_ray_query_cfg", _QueryCfg(cfg or {}))
+    _appear_cfg = "radiance_cfg"
 
     def __init__(self, aabb: torch.Tensor = None, ts_keyframes: torch.Tensor = None, seed: int = 42, device=None,
                  accel_n_jump_frames: int = None, **model_params):
@@ -417,19 +390,8 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
         self.encoding.cfg.set_aabb(aabb)        # (x, y, z) normalised by the AABB; the 4th input (time code) as it stands
         F, NA = self.encoding.cfg.out_features, self.n_appear
         g = torch.Generator().manual_seed(self._seed + 1)
-
-        def lin(o, i):
-            b = 1.0 / (i ** 0.5)
-            return (torch.rand(o, i, generator=g) * 2 - 1) * b, (torch.rand(o, generator=g) * 2 - 1) * b
-        dw1, db1 = lin(64, F)
-        dw2, db2 = lin(65, 64)
-        rw1, rb1 = lin(64, 80 + NA)
-        rw2, rb2 = lin(64, 64)
-        rw3, rb3 = lin(3, 64)
-        self.den_w = nn.Parameter(torch.cat([dw1.reshape(-1), dw2.reshape(-1)]))
-        self.den_b = nn.Parameter(torch.cat([db1, db2]))
-        self.rad_w = nn.Parameter(torch.cat([rw1.reshape(-1), rw2.reshape(-1), rw3.reshape(-1)]))
-        self.rad_b = nn.Parameter(torch.cat([rb1, rb2, rb3]))
+        self._make_decoder("den", [(64, F), (65, 64)], g)
+        self._make_decoder("rad", [(64, 80 + NA), (64, 64), (3, 64)], g)
         self.use_flow = c.get("flow") is not None
         if self.use_flow:
             # (use_flow_field, no_gtbox_with_flow.240208.yaml:353-371) a second 4-D lattice with its own seed, shifts, table and
@@ -439,11 +401,7 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
             fac.setdefault("seed", 1)
             self.flow_encoding = _PermutoFieldEncoding(PermutoConfig(in_dim=4, **fac), fl["param_bound"], self._seed + 2)
             self.flow_encoding.cfg.set_aabb(aabb)
-            fw1, fb1 = lin(64, self.flow_encoding.cfg.out_features)
-            fw2, fb2 = lin(64, 64)
-            fw3, fb3 = lin(6, 64)
-            self.flow_w = nn.Parameter(torch.cat([fw1.reshape(-1), fw2.reshape(-1), fw3.reshape(-1)]))
-            self.flow_b = nn.Parameter(torch.cat([fb1, fb2, fb3]))
+            self._make_decoder("flow", [(64, self.flow_encoding.cfg.out_features), (64, 64), (6, 64)], g)
         T = int(ts.numel())
         self.register_buffer("ts_keyframes", ts.clone())
         lo, hi = c["time_range"]
@@ -451,15 +409,7 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
         self.register_buffer("time_codes", torch.linspace(lo, hi, T, dtype=torch.float32), persistent=False)
         acc = dict(self.accel_cfg)
         acc.pop("ts_keyframes", None)
-        ufn = acc.get("update_from_net_cfg") or {}
-        self.accel = DynamicDensityOccGridAccel(
-            aabb, ts_accel, resolution=ref_config.occ_resolution(acc, aabb), occ_thre=float(acc.get("occ_thre", 0.01)),
-            ema_decay=float(acc.get("ema_decay", 0.95)), num_steps=int(ufn.get("num_steps", 4)),
-            num_pts=int(ufn.get("num_pts", 2 ** 20)), n_steps_between_update=int(acc.get("n_steps_between_update", 16)),
-            n_steps_warmup=int(acc.get("n_steps_warmup", 256)), update_from_samples_cfg=acc.get("update_from_samples_cfg", None),
-            init_cfg=acc.get("init_cfg"), occ_thre_consider_mean=bool(acc.get("occ_thre_consider_mean", False)),
-            constant_value=float((acc.get("init_cfg") or {}).get("constant_value", 1.0)))
-        self.accel.init()
+        self._make_accel(DynamicDensityOccGridAccel, aabb, ts_accel, acc=acc, resolution=ref_config.occ_resolution(acc, aabb))
         m = _lib.NgpMeta()
         m.lotd = self.encoding.cfg.meta         # level count and hardmask of the decoder launches (a stub pyramid)
         m.precision = {"fp16": 0, "f32": 1}[c["precision"]]
@@ -528,40 +478,10 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
         self.encoding.cfg.set_active_levels(n)
         self.meta.lotd.n_active_levels = self.encoding.cfg.meta.n_active_levels
 
-    def _active_levels(self) -> int:
-        return int(self.meta.lotd.n_active_levels)
-
     def _set_active_raw(self, n: int):
         self.meta.lotd.n_active_levels = n
         self.encoding.cfg.meta.n_active_levels = n
         self.encoding.cfg.pmeta.n_active_levels = n
-
-    def training_before_per_step(self, it: int, logger=None):
-        """The occupancy refresh on the ``n_steps_*`` schedule, arming of the sample collection."""
-        if self.accel.update_from_samples_cfg is not None:
-            self.accel.collect_armed = True
-        self.accel.cur_batch__step(int(it), self.query_density, generator=getattr(self, "refresh_generator", None))
-
-    def training_after_per_step(self, it: int, logger=None):
-        pass
-
-    def model_setup(self):
-        self._shadow()
-
-    @property
-    def device(self):
-        return self.den_w.device
-
-    @property
-    def space(self):
-        from ..spatial import AABBSpace
-        a = self.accel.aabb
-        key = (a.data_ptr(), a._version, str(a.device))
-        sp = getattr(self, "_space", None)
-        if sp is None or sp[0] != key:
-            sp = (key, AABBSpace(aabb=a.detach().clone(), device=a.device))
-            object.__setattr__(self, "_space", sp)
-        return sp[1]
 
     # ------------------------------------------------------------------ kernels' inputs
     def _shadow(self):
@@ -569,40 +489,20 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
         grid16 = self.encoding.shadow()
         vers = (self.den_w._version, self.den_b._version, self.rad_w._version, self.rad_b._version, self.meta.precision,
                 str(self.den_w.device), self.den_w.data_ptr())
-        if self._wpack is None or self._wpack_versions != vers:
-            nbytes = int(_lib.get_lib().nsim_dyn_wpack_bytes(self.meta))
-            if self._wpack is None or self._wpack.numel() != nbytes or self._wpack.device != self.den_w.device:
-                self._wpack = torch.zeros([nbytes], dtype=torch.uint8, device=self.den_w.device)
-            _lib.call("nsim_dyn_pack_weights", self.meta, _lib.ptr(self.den_w.detach()), _lib.ptr(self.den_b.detach()),
-                      _lib.ptr(self.rad_w.detach()), _lib.ptr(self.rad_b.detach()), _lib.ptr(self._wpack))
-            self._wpack_versions = vers
-        return grid16, self._wpack
+        return grid16, self._weight_pack(
+            "_wpack", vers, self.den_w.device, lambda: _lib.get_lib().nsim_dyn_wpack_bytes(self.meta),
+            lambda buf: _lib.call("nsim_dyn_pack_weights", self.meta, _lib.ptr(self.den_w.detach()), _lib.ptr(self.den_b.detach()),
+                                  _lib.ptr(self.rad_w.detach()), _lib.ptr(self.rad_b.detach()), _lib.ptr(buf)))
 
     def _flow_shadow(self):
         """(fp16 shadow of the flow table, weight pack of the flow decoder), refreshed lazily like ``_shadow``"""
         fgrid16 = self.flow_encoding.shadow()
         vers = (self.flow_w._version, self.flow_b._version, self.meta.precision, str(self.flow_w.device), self.flow_w.data_ptr())
-        if self._fwpack is None or self._fwpack_versions != vers:
-            prec = int(self.meta.precision)
-            nbytes = int(_lib.get_lib().nsim_flow_wpack_bytes(prec))
-            if self._fwpack is None or self._fwpack.numel() != nbytes or self._fwpack.device != self.flow_w.device:
-                self._fwpack = torch.zeros([nbytes], dtype=torch.uint8, device=self.flow_w.device)
-            _lib.call("nsim_flow_pack_weights", int(self.flow_encoding.cfg.pmeta.num_levels), prec, _lib.ptr(self.flow_w.detach()),
-                      _lib.ptr(self.flow_b.detach()), _lib.ptr(self._fwpack))
-            self._fwpack_versions = vers
-        return fgrid16, self._fwpack
-
-    @staticmethod
-    def _reduce_ray_grads(dx, dv, t, ridx, ray_shape, need_x, need_o, need_d):
-        """per-sample dx [S,3] (and dv) -> (d_x, d_o, d_d): dx itself for points, else the per-ray sums of
-        ``nsim_ray_grad_reduce`` into zero-filled rows (a ray without samples gets an exact zero row)"""
-        if need_x:
-            return dx, None, None
-        d_o = torch.zeros(list(ray_shape), dtype=torch.float32, device=dx.device) if need_o else None
-        d_d = torch.zeros(list(ray_shape), dtype=torch.float32, device=dx.device) if need_d else None
-        _lib.call("nsim_ray_grad_reduce", _lib.ptr(dx), _lib.ptr(dv), _lib.ptr(t), _lib.ptr(ridx), dx.shape[0], _lib.ptr(d_o),
-                  _lib.ptr(d_d))
-        return None, d_o, d_d
+        prec = int(self.meta.precision)
+        return fgrid16, self._weight_pack(
+            "_fwpack", vers, self.flow_w.device, lambda: _lib.get_lib().nsim_flow_wpack_bytes(prec),
+            lambda buf: _lib.call("nsim_flow_pack_weights", int(self.flow_encoding.cfg.pmeta.num_levels), prec,
+                                  _lib.ptr(self.flow_w.detach()), _lib.ptr(self.flow_b.detach()), _lib.ptr(buf)))
 
     def _query(self, h_appear, x4, rays_d, ridx, step, with_rgb, pose=(None, None, None, None)):
         """-> (sigma, alpha, rgb | None, flow dict | None): the plain decoder, or the flow-aggregated one with its four flow
@@ -634,10 +534,6 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
         _lib.call("nsim_dyn_points", _lib.ptr(x), _lib.ptr(o), _lib.ptr(d), _lib.ptr(t), _lib.ptr(ridx), _lib.ptr(w), S,
                   _lib.ptr(x4))
         return x4
-
-    def _step(self, cfg: dict = None) -> float:
-        qp = (cfg or {}).get("query_param", None) or self.ray_query_cfg.get("query_param", {})
-        return float((qp.get("march_cfg") or {}).get("step_size", 0.1))
 
     # ------------------------------------------------------------------ point queries
     def forward_density(self, x: torch.Tensor, ts: torch.Tensor, x_has_grad: bool = False) -> Dict[str, torch.Tensor]:
@@ -689,104 +585,31 @@ class EmerNeRFOnlyDynamicModel(ModelMixin, nn.Module):
             raise NotImplementedError("rays_ts.requires_grad: gradients to the time input are not built for this model")
         return aabb_ray_test(self.accel.aabb, self.accel.meta, rays_o, rays_d, near=near, far=far, rays_ts=rays_ts, **extra)
 
-    def ray_query(self, *, ray_input: dict = None, ray_tested: dict, config=None, return_buffer: bool = True,
-                  return_details: bool = False, render_per_obj_individual: bool = False, with_rgb: bool = None,
-                  with_normal: bool = None, **unused) -> Dict:
-        """``query_mode: march_occ``: the marcher's lattice t_k = near + (k + jitter) step inside the occupied voxels of the
-        slice of each ray's time; every sample's interval is ``step``."""
-        cfg = dict(config or {})
-        mode = cfg.get("query_mode", self.ray_query_cfg.get("query_mode", "march_occ"))
-        if mode != "march_occ":
-            raise NotImplementedError(f"ray_query_cfg.query_mode={mode!r}: march_occ is built")
-        if cfg.get("with_feature_dim", 0):
-            raise NotImplementedError("with_feature_dim > 0: the decoders of this model emit no extra feature channels")
-        with_rgb = cfg.get("with_rgb", True) if with_rgb is None else bool(with_rgb)
-        qp = dict(cfg.get("query_param", None) or self.ray_query_cfg.get("query_param", {}))
-        march = qp.get("march_cfg") or {}
-        step, max_steps = float(march.get("step_size", 0.1)), int(march.get("max_steps", 4096))
-        n_all = None
-        if render_per_obj_individual and ray_input is not None and ray_input.get("rays_o") is not None:
-            n_all = int(ray_input["rays_o"].shape[0])
-
-        def empty(details=None):
-            ret = dict(volume_buffer=dict(type="empty"))
-            if render_per_obj_individual:
-                dev_ = ray_tested["rays_inds"].device
-                z = lambda *sh: torch.zeros([n_all or 0, *sh], dtype=torch.float32, device=dev_)      # noqa: E731
-                ret["rendered"] = dict(mask_volume=z(), depth_volume=z())
-                if with_rgb:
-                    ret["rendered"]["rgb_volume"] = z(3)
-            if return_details:
-                ret["details"] = details or {}
-            return ret
-        R = int(ray_tested["num_rays"])
-        if R == 0:
-            return empty()
+    def _check_rays(self, ray_tested, has_grad):
         if ray_tested.get("rays_ts", None) is None:
             raise ValueError("ray_tested['rays_ts'] is missing: a time-conditioned model (use_ts) needs the time of every ray")
-        has_grad = rays_has_grad(self.ray_query_cfg, cfg)
         for k in ("rays_o", "rays_d", "rays_ts"):
             if ray_tested[k].requires_grad and not (has_grad and k != "rays_ts"):
                 raise NotImplementedError(f"ray_tested[{k!r}].requires_grad: gradients to rays and times (pose refinement) are "
                                           f"not built for this model" + (" unless ray_query_cfg.query_param.rays_has_grad is set"
                                                                          if k != "rays_ts" else ""))
-        o = ray_tested["rays_o"].detach().float().contiguous()
-        d = ray_tested["rays_d"].detach().float().contiguous()
+
+    def _march_extras(self, ray_tested):
+        """The slice of each ray's time in the time-sliced accelerator, its word offset, and the rays' time coordinates."""
         ts = ray_tested["rays_ts"].detach().float().reshape(-1).contiguous()
-        near, far = ray_tested["near"].detach().float().contiguous(), ray_tested["far"].detach().float().contiguous()
-        dev = o.device
-        jitter = cfg.get("_jitter", None)
-        if jitter is None:
-            jitter = torch.rand([R], device=dev) if cfg.get("perturb", False) else torch.zeros([R], device=dev)
-        jitter = jitter.float().contiguous()
-        acc = self.accel
-        bits, occm = acc.occ_bits, acc.meta
-        with torch.no_grad():
-            slices = torch.empty([R], dtype=torch.long, device=dev)
-            woff = torch.empty([R], dtype=torch.long, device=dev)
-            acc._time_call(ts, slices, woff)
-            w = self.time_coord(ts)
-            counts = torch.empty([R], dtype=torch.long, device=dev)
-            _lib.call("nsim_march_count", _lib.ptr(o), _lib.ptr(d), _lib.ptr(near), _lib.ptr(far), _lib.ptr(jitter), R,
-                      _lib.ptr(bits), _lib.ptr(woff), occm, step, max_steps, _lib.ptr(counts))
-            pi, total = po.get_pack_infos_from_n(counts, return_total=True)
-            S = int(total.item())                    # host sync: size of the marched set
-            if S == 0:
-                acc.collect_armed = False
-                return empty(dict(march_counts=counts, slices=slices))
-            t = torch.empty([S], dtype=torch.float32, device=dev)
-            _lib.call("nsim_march_emit", _lib.ptr(o), _lib.ptr(d), _lib.ptr(near), _lib.ptr(far), _lib.ptr(jitter), R,
-                      _lib.ptr(bits), _lib.ptr(woff), occm, step, max_steps, _lib.ptr(pi), _lib.ptr(t))
-            ridx = torch.repeat_interleave(torch.arange(R, device=dev), counts, output_size=S)
-            sel = counts.nonzero()[:, 0]
-            x4 = self._points(w, S, rays=(o, d, t, ridx))
-        h_appear = ray_tested.get("rays_h_appear", None) if (with_rgb and self.n_appear) else None
-        if with_rgb and self.n_appear and h_appear is None:
-            raise ValueError("ray_tested['rays_h_appear'] is missing: radiance_cfg.n_appear_embedding is "
-                             f"{self.n_appear}, the radiance decoder reads a per-ray appearance code")
+        slices = torch.empty([ts.shape[0]], dtype=torch.long, device=ts.device)
+        woff = torch.empty([ts.shape[0]], dtype=torch.long, device=ts.device)
+        self.accel._time_call(ts, slices, woff)
+        return woff, self.time_coord(ts), dict(slices=slices)
+
+    def _decode(self, ray_tested, h_appear, o, d, t, ridx, w, step, with_rgb):
+        x4 = self._points(w, t.shape[0], rays=(o, d, t, ridx))
         # (marching, the occupancy grid, the slice choice and the sample depths saw detached rays; the samples o + t d carry the graph)
         ro, rd = ray_tested["rays_o"], ray_tested["rays_d"]
         pose = (None, ro.float() if ro.requires_grad else None, rd.float() if rd.requires_grad else None, t) \
             if (ro.requires_grad or rd.requires_grad) else (None,) * 4
-        sigma, alpha, rgb, flow = self._query(h_appear, x4, d, ridx, step, bool(with_rgb), pose)
-        outs = (sigma, alpha, rgb)
-        if acc.collect_armed:
-            acc.collect(sigma, slices, rays=(o, d, t, ridx))
-            acc.collect_armed = False
-        vb = dict(type="packed", rays_inds_hit=ray_tested["rays_inds"][sel], pack_infos_hit=pi[sel], t=t, sigma=sigma,
-                  opacity_alpha=alpha)
-        if with_rgb:
-            vb["rgb"] = outs[2]
-        if flow is not None:
-            vb.update(flow)
-        ret = dict(volume_buffer=vb)
-        if render_per_obj_individual or cfg.get("_render", False):
-            from .neus import volume_integration
-            ret["rendered"] = volume_integration(alpha, t, outs[2] if with_rgb else None, None, pi,
-                                                 cfg.get("depth_use_normalized_vw", True),
-                                                 rays_inds=ray_tested["rays_inds"] if n_all is not None else None, num_rays=n_all)
-            ret["rendered"].pop("vw", None)
-            ret["rendered"].pop("trans", None)
-        if return_details:
-            ret["details"] = dict(march_counts=counts, ridx=ridx, pack_infos=pi, slices=slices)
-        return ret
+        sigma, alpha, rgb, flow = self._query(h_appear, x4, d, ridx, step, with_rgb, pose)
+        return sigma, alpha, rgb, flow or {}
+
+    def _collect(self, sigma, rays, extras):
+        self.accel.collect(sigma, extras["slices"], rays=rays)

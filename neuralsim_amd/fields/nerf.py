@@ -12,14 +12,12 @@ csrc/nerf_field.hip.  This file allocates tensors, sequences launches and define
 from typing import Dict, Optional
 
 import torch
-import torch.nn as nn
 
 from .. import _lib
-from ..graphics import pack_ops as po
 from ..grid_encodings.lotd import LoTDConfig, LoTDEncoding
-from ..model_base import ModelMixin
 from ..spatial import aabb_ray_test
-from .neus import OccGridAccel, _QueryCfg, rays_has_grad
+from .density_base import MarchedDensityModel, f32c, reduce_ray_grads, zero_grads_like
+from .neus import OccGridAccel
 
 
 class DensityOccGridAccel(OccGridAccel):
@@ -129,12 +127,8 @@ class _NgpFn(torch.autograd.Function):
             return (None,) * n_out
         dev, S = sigma.device, ctx.S
         wpack = model._shadow()[1]
-        F, NA = model.encoding.cfg.out_features, model.n_appear
-        n_dw, n_db, n_rw, n_rb = 64 * (F + 3) + 2048, 96, 64 * (47 + NA) + 4096 + 192, 131
-        dden_w, dden_b, drad_w, drad_b = _lib.zeros([n_dw + n_db + n_rw + n_rb], device=dev).split([n_dw, n_db, n_rw, n_rb])
-        gs = g_sigma.float().contiguous() if g_sigma is not None else None
-        ga = g_alpha.float().contiguous() if g_alpha is not None else None
-        gr = g_rgb.float().contiguous() if (ctx.with_rgb and g_rgb is not None) else None
+        dden_w, dden_b, drad_w, drad_b = zero_grads_like(model.den_w, model.den_b, model.rad_w, model.rad_b)
+        gs, ga, gr = f32c(g_sigma), f32c(g_alpha), f32c(g_rgb if ctx.with_rgb else None)
         dha = _lib.zeros(list(ctx.ha_shape), device=dev) if (ha is not None and need[6] and gr is not None) else None
         dgrid = _lib.zeros([model.encoding.cfg.n_params], device=dev) if need[1] else None
         need_x, need_o, need_d = need[7] and x is not None, need[8] and x is None, need[9] and x is None
@@ -144,9 +138,7 @@ class _NgpFn(torch.autograd.Function):
         dv = torch.empty([S, 3], dtype=torch.float32, device=dev) if (need_d and gr is not None) else None
         d_x = d_o = d_d = None
         meta = model.meta
-        prev = int(meta.lotd.n_active_levels)       # the backward of a query uses the level mask the query was made with
-        meta.lotd.n_active_levels = ctx.n_active
-        try:
+        with model._level_mask(ctx.n_active):
             args = (meta, _lib.ptr(wpack), _lib.ptr(h_pl), ctx.PS, _lib.ptr(x), _lib.ptr(rays_o),
                     _lib.ptr(rays_d), _lib.ptr(t), _lib.ptr(ridx), _lib.ptr(ha), S, ctx.step, _lib.ptr(sigma.detach()),
                     _lib.ptr(rgb.detach()) if rgb is not None else None, _lib.ptr(gs), _lib.ptr(ga), _lib.ptr(gr),
@@ -155,21 +147,13 @@ class _NgpFn(torch.autograd.Function):
                 _lib.call("nsim_ngp_bwd_pose", *args, _lib.ptr(dx), _lib.ptr(dv))
                 _lib.call("nsim_lotd_dx_lm", meta.lotd, _lib.ptr(grid16), _lib.ptr(x), _lib.ptr(rays_o),
                           _lib.ptr(rays_d), _lib.ptr(t), _lib.ptr(ridx), S, _lib.ptr(dh_pl), S, _lib.ptr(dx), _lib.ptr(dx))
-                if need_x:
-                    d_x = dx
-                else:       # (zero-filled: a ray without samples gets an exact zero row)
-                    d_o = torch.zeros_like(rays_o) if need_o else None
-                    d_d = torch.zeros_like(rays_d) if need_d else None
-                    _lib.call("nsim_ray_grad_reduce", _lib.ptr(dx), _lib.ptr(dv), _lib.ptr(t), _lib.ptr(ridx), S,
-                              _lib.ptr(d_o), _lib.ptr(d_d))
+                d_x, d_o, d_d = reduce_ray_grads(dx, dv, t, ridx, None if need_x else rays_o.shape, need_x, need_o, need_d)
             else:
                 _lib.call("nsim_ngp_bwd", *args)
             if dgrid is not None:
                 _lib.call("nsim_lotd_scatter", meta.lotd, _lib.ptr(x), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t),
                           _lib.ptr(ridx), None, S, _lib.ptr(dh_pl), _lib.ptr(dh_pl), None, _lib.ptr(dgrid), 0, 0)
                 # (the scatter reads a g plane next to dh whatever gn is; with gn == NULL it is multiplied by zero: dh stands in)
-        finally:
-            meta.lotd.n_active_levels = prev
         if _lib.TIMER is not None:
             _lib.TIMER.note_units("nsim_ngp_bwd", S)
             if dgrid is not None:
@@ -179,16 +163,8 @@ class _NgpFn(torch.autograd.Function):
         return (None, dgrid, dden_w, dden_b, drad_w, drad_b, dha, d_x, d_o, d_d) + (None,) * 4
 
 
-class LoTDNeRFModel(ModelMixin, nn.Module):
-    is_ray_query_supported = True
-
-    @property
-    def ray_query_cfg(self):
-        return self._ray_query_cfg
-
-    @ray_query_cfg.setter
-    def ray_query_cfg(self, cfg):
-        object.__setattr__(self, "_ray_query_cfg", _QueryCfg(cfg or {}))
+class LoTDNeRFModel(MarchedDensityModel):
+    _appear_cfg = "radiance_decoder_cfg"
 
     def __init__(self, aabb: torch.Tensor = None, seed: int = 42, device=None, **model_params):
         """``model_params``: the reference's yaml block verbatim (ngp_withlidar.230814.yaml:101-158; fields/ref_config.py
@@ -217,29 +193,10 @@ class LoTDNeRFModel(ModelMixin, nn.Module):
         F, NA = self.encoding.cfg.out_features, c["n_appear"]
         self.n_appear = NA
         g = torch.Generator().manual_seed(self._seed + 1)
-
-        def lin(o, i):
-            b = 1.0 / (i ** 0.5)
-            return (torch.rand(o, i, generator=g) * 2 - 1) * b, (torch.rand(o, generator=g) * 2 - 1) * b
-        dw1, db1 = lin(64, F + 3)
-        dw2, db2 = lin(32, 64)
-        rw1, rb1 = lin(64, 47 + NA)
-        rw2, rb2 = lin(64, 64)
-        rw3, rb3 = lin(3, 64)
-        self.den_w = nn.Parameter(torch.cat([dw1.reshape(-1), dw2.reshape(-1)]))
-        self.den_b = nn.Parameter(torch.cat([db1, db2]))
-        self.rad_w = nn.Parameter(torch.cat([rw1.reshape(-1), rw2.reshape(-1), rw3.reshape(-1)]))
-        self.rad_b = nn.Parameter(torch.cat([rb1, rb2, rb3]))
+        self._make_decoder("den", [(64, F + 3), (32, 64)], g)
+        self._make_decoder("rad", [(64, 47 + NA), (64, 64), (3, 64)], g)
         acc = c["accel_cfg"]
-        ufn = acc.get("update_from_net_cfg") or {}
-        self.accel = DensityOccGridAccel(
-            aabb, resolution=acc.get("resolution", (64, 64, 64)), occ_thre=float(acc.get("occ_thre", 0.01)),
-            ema_decay=float(acc.get("ema_decay", 0.95)), num_steps=int(ufn.get("num_steps", 4)),
-            num_pts=int(ufn.get("num_pts", 2 ** 20)), n_steps_between_update=int(acc.get("n_steps_between_update", 16)),
-            n_steps_warmup=int(acc.get("n_steps_warmup", 256)), update_from_samples_cfg=acc.get("update_from_samples_cfg", None),
-            init_cfg=acc.get("init_cfg"), occ_thre_consider_mean=bool(acc.get("occ_thre_consider_mean", False)),
-            constant_value=float((acc.get("init_cfg") or {}).get("constant_value", 1.0)))
-        self.accel.init()
+        self._make_accel(DensityOccGridAccel, aabb, acc=acc, resolution=acc.get("resolution", (64, 64, 64)))
         self.ray_query_cfg = c["ray_query_cfg"]
         m = _lib.NgpMeta()
         m.lotd = self.encoding.cfg.meta
@@ -297,6 +254,9 @@ class LoTDNeRFModel(ModelMixin, nn.Module):
         self.meta.lotd.n_active_levels = n
         self._fm32.lotd.n_active_levels = n
 
+    def _set_active_raw(self, n: int):
+        self.meta.lotd.n_active_levels = n          # (the decoder launches' mask: all the backward reads)
+
     def _anneal(self, it: int):
         """``anneal_cfg{type: hardmask, start_level, start_it, stop_it}``, the NeuS model's rule (fields/neus.py
         ``anneal_levels``): level l is active once it >= start_it + (l - start_level) / (L - 1 - start_level) (stop_it - start_it)."""
@@ -312,30 +272,7 @@ class LoTDNeRFModel(ModelMixin, nn.Module):
     def training_before_per_step(self, it: int, logger=None):
         """Level annealing, the occupancy refresh on the ``n_steps_*`` schedule, arming of the sample collection."""
         self._anneal(int(it))
-        if self.accel.update_from_samples_cfg is not None:
-            self.accel.collect_armed = True
-        self.accel.cur_batch__step(int(it), self.query_density, generator=getattr(self, "refresh_generator", None))
-
-    def training_after_per_step(self, it: int, logger=None):
-        pass
-
-    def model_setup(self):
-        self._shadow()
-
-    @property
-    def device(self):
-        return self.den_w.device
-
-    @property
-    def space(self):
-        from ..spatial import AABBSpace
-        a = self.accel.aabb
-        key = (a.data_ptr(), a._version, str(a.device))
-        sp = getattr(self, "_space", None)
-        if sp is None or sp[0] != key:
-            sp = (key, AABBSpace(aabb=a.detach().clone(), device=a.device))
-            object.__setattr__(self, "_space", sp)
-        return sp[1]
+        super().training_before_per_step(it, logger)
 
     # ------------------------------------------------------------------ kernels' inputs
     def _shadow(self):
@@ -343,14 +280,10 @@ class LoTDNeRFModel(ModelMixin, nn.Module):
         grid16 = self.encoding.shadow()
         vers = (self.den_w._version, self.den_b._version, self.rad_w._version, self.rad_b._version, self.meta.precision,
                 str(self.den_w.device), self.den_w.data_ptr())
-        if self._wpack is None or self._wpack_versions != vers:
-            nbytes = int(_lib.get_lib().nsim_ngp_wpack_bytes(self.meta))
-            if self._wpack is None or self._wpack.numel() != nbytes or self._wpack.device != self.den_w.device:
-                self._wpack = torch.zeros([nbytes], dtype=torch.uint8, device=self.den_w.device)
-            _lib.call("nsim_ngp_pack_weights", self.meta, _lib.ptr(self.den_w.detach()), _lib.ptr(self.den_b.detach()),
-                      _lib.ptr(self.rad_w.detach()), _lib.ptr(self.rad_b.detach()), _lib.ptr(self._wpack))
-            self._wpack_versions = vers
-        return grid16, self._wpack
+        return grid16, self._weight_pack(
+            "_wpack", vers, self.den_w.device, lambda: _lib.get_lib().nsim_ngp_wpack_bytes(self.meta),
+            lambda buf: _lib.call("nsim_ngp_pack_weights", self.meta, _lib.ptr(self.den_w.detach()), _lib.ptr(self.den_b.detach()),
+                                  _lib.ptr(self.rad_w.detach()), _lib.ptr(self.rad_b.detach()), _lib.ptr(buf)))
 
     def _gather(self, grid16, x, rays_o, rays_d, t, ridx, S, dev):
         """Level-major f32 feature planes [16][P][2] of S points (``nsim_lotd_gather_lm`` on the f32 meta: features only,
@@ -359,10 +292,6 @@ class LoTDNeRFModel(ModelMixin, nn.Module):
         _lib.call("nsim_lotd_gather_lm", self._fm32, _lib.ptr(grid16), _lib.ptr(x), _lib.ptr(rays_o), _lib.ptr(rays_d),
                   _lib.ptr(t), _lib.ptr(ridx), None, S, None, 0, _lib.ptr(h_pl))
         return h_pl
-
-    def _step(self, cfg: dict = None) -> float:
-        qp = (cfg or {}).get("query_param", None) or self.ray_query_cfg.get("query_param", {})
-        return float((qp.get("march_cfg") or {}).get("step_size", 0.1))
 
     # ------------------------------------------------------------------ point queries
     def forward_density(self, x: torch.Tensor, x_has_grad: bool = False) -> Dict[str, torch.Tensor]:
@@ -395,92 +324,18 @@ class LoTDNeRFModel(ModelMixin, nn.Module):
     def ray_test(self, rays_o, rays_d, near=None, far=None, **extra) -> Dict:
         return aabb_ray_test(self.accel.aabb, self.accel.meta, rays_o, rays_d, near=near, far=far, **extra)
 
-    def ray_query(self, *, ray_input: dict = None, ray_tested: dict, config=None, return_buffer: bool = True,
-                  return_details: bool = False, render_per_obj_individual: bool = False, with_rgb: bool = None,
-                  with_normal: bool = None, **unused) -> Dict:
-        """``query_mode: march_occ``: the samples are the marcher's lattice t_k = near + (k + jitter) step inside occupied
-        voxels (jitter per ray when ``perturb``, else 0); every sample's interval is ``step``."""
-        cfg = dict(config or {})
-        mode = cfg.get("query_mode", self.ray_query_cfg.get("query_mode", "march_occ"))
-        if mode != "march_occ":
-            raise NotImplementedError(f"ray_query_cfg.query_mode={mode!r}: march_occ is built")
-        if cfg.get("with_feature_dim", 0):
-            raise NotImplementedError("with_feature_dim > 0: the decoders of this model emit no extra feature channels")
-        with_rgb = cfg.get("with_rgb", True) if with_rgb is None else bool(with_rgb)
-        qp = dict(cfg.get("query_param", None) or self.ray_query_cfg.get("query_param", {}))
-        march = qp.get("march_cfg") or {}
-        step, max_steps = float(march.get("step_size", 0.1)), int(march.get("max_steps", 4096))
-        n_all = None
-        if render_per_obj_individual and ray_input is not None and ray_input.get("rays_o") is not None:
-            n_all = int(ray_input["rays_o"].shape[0])
-
-        def empty(details=None):
-            ret = dict(volume_buffer=dict(type="empty"))
-            if render_per_obj_individual:
-                dev_ = ray_tested["rays_inds"].device
-                z = lambda *sh: torch.zeros([n_all or 0, *sh], dtype=torch.float32, device=dev_)      # noqa: E731
-                ret["rendered"] = dict(mask_volume=z(), depth_volume=z())
-                if with_rgb:
-                    ret["rendered"]["rgb_volume"] = z(3)
-            if return_details:
-                ret["details"] = details or {}
-            return ret
-        R = int(ray_tested["num_rays"])
-        if R == 0:
-            return empty()
-        has_grad = rays_has_grad(self.ray_query_cfg, cfg)
+    def _check_rays(self, ray_tested, has_grad):
         for k in ("rays_o", "rays_d"):
             if ray_tested[k].requires_grad and not has_grad:
                 raise NotImplementedError(f"ray_tested[{k!r}].requires_grad: gradients to rays (pose refinement) are not built "
                                           f"for this model unless ray_query_cfg.query_param.rays_has_grad is set")
-        # marching, the occupancy grid and the sample depths see detached rays; the decoders' samples o + t d carry the graph
-        o = ray_tested["rays_o"].detach().float().contiguous()
-        d = ray_tested["rays_d"].detach().float().contiguous()
-        o_g = ray_tested["rays_o"].float().contiguous() if ray_tested["rays_o"].requires_grad else o
-        d_g = ray_tested["rays_d"].float().contiguous() if ray_tested["rays_d"].requires_grad else d
-        near, far = ray_tested["near"].detach().float().contiguous(), ray_tested["far"].detach().float().contiguous()
-        dev = o.device
-        jitter = cfg.get("_jitter", None)
-        if jitter is None:
-            jitter = torch.rand([R], device=dev) if cfg.get("perturb", False) else torch.zeros([R], device=dev)
-        jitter = jitter.float().contiguous()
-        bits, occm = self.accel.occ_bits, self.accel.meta
-        with torch.no_grad():
-            counts = torch.empty([R], dtype=torch.long, device=dev)
-            _lib.call("nsim_march_count", _lib.ptr(o), _lib.ptr(d), _lib.ptr(near), _lib.ptr(far), _lib.ptr(jitter), R,
-                      _lib.ptr(bits), None, occm, step, max_steps, _lib.ptr(counts))
-            pi, total = po.get_pack_infos_from_n(counts, return_total=True)
-            S = int(total.item())                    # host sync: size of the marched set
-            if S == 0:
-                self.accel.collect_armed = False
-                return empty(dict(march_counts=counts))
-            t = torch.empty([S], dtype=torch.float32, device=dev)
-            _lib.call("nsim_march_emit", _lib.ptr(o), _lib.ptr(d), _lib.ptr(near), _lib.ptr(far), _lib.ptr(jitter), R,
-                      _lib.ptr(bits), None, occm, step, max_steps, _lib.ptr(pi), _lib.ptr(t))
-            ridx = torch.repeat_interleave(torch.arange(R, device=dev), counts, output_size=S)
-            sel = counts.nonzero()[:, 0]
-        h_appear = ray_tested.get("rays_h_appear", None) if (with_rgb and self.n_appear) else None
-        if with_rgb and self.n_appear and h_appear is None:
-            raise ValueError("ray_tested['rays_h_appear'] is missing: radiance_decoder_cfg.n_appear_embedding is "
-                             f"{self.n_appear}, the radiance decoder reads a per-ray appearance code")
-        outs = _NgpFn.apply(self, self.encoding.flattened_params, self.den_w, self.den_b, self.rad_w, self.rad_b, h_appear,
-                            None, o_g, d_g, t, ridx, step, bool(with_rgb))
-        sigma, alpha = outs[0], outs[1]
-        if self.accel.collect_armed:
-            self.accel.collect(sigma=sigma, rays=(o, d, t, ridx))
-            self.accel.collect_armed = False
-        vb = dict(type="packed", rays_inds_hit=ray_tested["rays_inds"][sel], pack_infos_hit=pi[sel], t=t, sigma=sigma,
-                  opacity_alpha=alpha)
-        if with_rgb:
-            vb["rgb"] = outs[2]
-        ret = dict(volume_buffer=vb)
-        if render_per_obj_individual or cfg.get("_render", False):
-            from .neus import volume_integration
-            ret["rendered"] = volume_integration(alpha, t, outs[2] if with_rgb else None, None, pi,
-                                                 cfg.get("depth_use_normalized_vw", True),
-                                                 rays_inds=ray_tested["rays_inds"] if n_all is not None else None, num_rays=n_all)
-            ret["rendered"].pop("vw", None)
-            ret["rendered"].pop("trans", None)
-        if return_details:
-            ret["details"] = dict(march_counts=counts, ridx=ridx, pack_infos=pi)
-        return ret
+
+    def _decode(self, ray_tested, h_appear, o, d, t, ridx, w, step, with_rgb):
+        ro, rd = ray_tested["rays_o"], ray_tested["rays_d"]
+        outs = _NgpFn.apply(self, self.encoding.flattened_params, self.den_w, self.den_b, self.rad_w, self.rad_b, h_appear, None,
+                            ro.float().contiguous() if ro.requires_grad else o, rd.float().contiguous() if rd.requires_grad else d,
+                            t, ridx, step, with_rgb)
+        return outs[0], outs[1], (outs[2] if with_rgb else None), {}
+
+    def _collect(self, sigma, rays, extras):
+        self.accel.collect(sigma=sigma, rays=rays)

@@ -21,6 +21,8 @@ import torch.nn as nn
 
 from .. import _lib
 from ..model_base import ModelMixin
+from ..spatial import cached_aabb_space
+from .density_base import f32c
 
 
 class LoTD4Config:
@@ -105,8 +107,7 @@ class _DistantFn(torch.autograd.Function):
         dha = torch.zeros(ctx.ha_shape, dtype=torch.float32, device=dev) if (ha is not None and need[6]) else None
         dgrid = z(model.cfg.n_params) if need[1] else None
         dh_pl = torch.empty([16, ctx.S, 2], dtype=torch.float32, device=dev) if dgrid is not None else None
-        gs = g_sigma.float().contiguous() if g_sigma is not None else None
-        gr = g_rgb.float().contiguous() if g_rgb is not None else None
+        gs, gr = f32c(g_sigma), f32c(g_rgb)
         if gs is None and gr is None:
             return (None,) * 12
         keep = ctx.holder.get("keep") if ctx.holder is not None else None
@@ -220,15 +221,7 @@ class _DistantBase(ModelMixin, nn.Module):
     def space(self):
         """The close-range object's box this model surrounds (``populate(aabb=cr_obj.model.space.aabb)``,
         app/models/single/nerf.py:170-177)."""
-        from ..spatial import AABBSpace
-        a = self.aabb
-        key = (a.data_ptr(), a._version, str(a.device))       # no value comparison: that would be a device->host sync
-        sp = getattr(self, "_space", None)
-        if sp is None or sp[0] != key:
-            from ..spatial import AABBSpace
-            sp = (key, AABBSpace(aabb=a.detach().clone(), device=a.device))
-            object.__setattr__(self, "_space", sp)          # a view of the model's box, not a registered sub-module
-        return sp[1]
+        return cached_aabb_space(self, self.aabb)
 
     def training_before_per_step(self, it: int, logger=None):
         pass
@@ -243,15 +236,10 @@ class _DistantBase(ModelMixin, nn.Module):
             self._shadow_version = p._version
         vers = (self.den_w._version, self.den_b._version, self.rad_w._version, self.rad_b._version, self.meta.precision,
                 str(self.den_w.device))
-        if self._wpack is None or self._wpack_versions != vers:
-            nbytes = int(_lib.get_lib().nsim_distant_wpack_bytes(self.meta))
-            if self._wpack is None or self._wpack.numel() != nbytes or self._wpack.device != self.den_w.device:
-                self._wpack = torch.zeros([nbytes], dtype=torch.uint8, device=self.den_w.device)
-            _lib.call("nsim_distant_pack_weights", self.meta, _lib.ptr(self.den_w.detach()), _lib.ptr(self.den_b.detach()),
-                      _lib.ptr(self._expand_rad_w(self.rad_w.detach())), _lib.ptr(self.rad_b.detach()),
-                      _lib.ptr(self._wpack))
-            self._wpack_versions = vers
-        return self.params16, self._wpack
+        return self.params16, self._weight_pack(
+            "_wpack", vers, self.den_w.device, lambda: _lib.get_lib().nsim_distant_wpack_bytes(self.meta),
+            lambda buf: _lib.call("nsim_distant_pack_weights", self.meta, _lib.ptr(self.den_w.detach()), _lib.ptr(self.den_b.detach()),
+                                  _lib.ptr(self._expand_rad_w(self.rad_w.detach())), _lib.ptr(self.rad_b.detach()), _lib.ptr(buf)))
 
     # The kernels' first radiance layer is [64 x (F + 16 SH + 4 appearance)]; without view directions the parameter is
     # [64 x (F + 4)] (the reference's shape) and the SH columns of the packed matrix are zeros.

@@ -28,7 +28,7 @@ from .. import _lib
 from ..grid_encodings.lotd import LoTDConfig, LoTDEncoding
 from ..graphics import pack_ops as po
 from ..model_base import ModelMixin
-from ..spatial import AABBSpace, aabb_ray_test
+from ..spatial import AABBSpace, aabb_ray_test, cached_aabb_space
 
 def C_memmove(dst, src):
     ctypes.memmove(ctypes.byref(dst), ctypes.byref(src), ctypes.sizeof(src))
@@ -770,16 +770,7 @@ class LoTDNeuSModel(ModelMixin, nn.Module):
 
     @property
     def space(self) -> AABBSpace:
-        """``model.space`` (``.aabb``, ``.get_bounding_volume()``, ``.ray_test``): app/resources/nodes.py:92-103,
-        app/models/single/nerf.py:175."""
-        a = self.accel.aabb
-        key = (a.data_ptr(), a._version, str(a.device))       # no value comparison: that would be a device->host sync
-        sp = getattr(self, "_space", None)
-        if sp is None or sp[0] != key:
-            from ..spatial import AABBSpace
-            sp = (key, AABBSpace(aabb=a.detach().clone(), device=a.device))
-            object.__setattr__(self, "_space", sp)          # a view of the model's box, not a registered sub-module
-        return sp[1]
+        return cached_aabb_space(self, self.accel.aabb)
 
     # ------------------------------------------------------------------ optimizer (model_base.ModelMixin)
     def _param_groups(self, cfg: dict):

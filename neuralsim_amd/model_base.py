@@ -107,6 +107,20 @@ class ModelMixin:
     def _after_optimizer_step(self):
         """Derived buffers that follow the parameters (packed MFMA weight fragments) refresh lazily from versions."""
 
+    def _weight_pack(self, slot: str, versions: tuple, device, nbytes, pack) -> torch.Tensor:
+        """The MFMA-fragment weight pack kept in ``self.<slot>`` (uint8), re-packed lazily: ``pack(buf)`` runs when
+        ``self.<slot>_versions`` differs from ``versions`` or is None (how callers invalidate a pack); the buffer is
+        reallocated only when ``nbytes()`` or ``device`` changed."""
+        buf = getattr(self, slot)
+        if buf is None or getattr(self, slot + "_versions") != versions:
+            n = int(nbytes())
+            if buf is None or buf.numel() != n or buf.device != device:
+                buf = torch.zeros([n], dtype=torch.uint8, device=device)
+                setattr(self, slot, buf)
+            pack(buf)
+            setattr(self, slot + "_versions", versions)
+        return buf
+
     # ------------------------------------------------------------------ reference life cycle
     def training_setup(self, training_cfg: dict = None, name_prefix: str = ""):
         cfg = dict(training_cfg or {})

@@ -97,3 +97,14 @@ class AABBSpace(nn.Module):
         if self._meta is None or self._meta[0] != self.aabb._version:
             self._meta = (self.aabb._version, make_occ_meta(self.aabb))
         return aabb_ray_test(self.aabb, self._meta[1], rays_o, rays_d, near=near, far=far, **extra)
+
+
+def cached_aabb_space(owner, aabb: torch.Tensor) -> AABBSpace:
+    """``model.space`` (``.aabb``, ``.get_bounding_volume()``, ``.ray_test``: app/resources/nodes.py:92-103,
+    app/models/single/nerf.py:175) of the box tensor ``aabb``, rebuilt when the tensor was replaced, written in place or moved."""
+    key = (aabb.data_ptr(), aabb._version, str(aabb.device))       # no value comparison: that would be a device->host sync
+    sp = getattr(owner, "_space", None)
+    if sp is None or sp[0] != key:
+        sp = (key, AABBSpace(aabb=aabb.detach().clone(), device=aabb.device))
+        object.__setattr__(owner, "_space", sp)          # a view of the model's box, not a registered sub-module
+    return sp[1]
